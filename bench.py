@@ -9,12 +9,16 @@ reference's tower rule (strong scaling: the configuration BASELINE.json's metric
 gradient buffer is all-reduced over RCCL inside the timed step; the same line also carries the
 weak-scaling number (64 questions per GPU) and BASELINE configs[3] (128 per GPU, p = 16).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (metric, value, roofline, cpu_baseline ...).  Inputs are resident in HBM
-before the timed region; nothing under /root/reference is read.
+A plain run sets up, runs W warmup steps and times exactly K steps of the metric's step (plain_run); --dump-outputs DIR
+writes what the last of them computed.  --full is the whole measurement: the wait for a quiet box, the eager leg, the metric
+as the median of METRIC_BLOCKS blocks, roofline probes and the side legs (the --no-* options leave parts of it out).
+
+Rank 0 prints ONE JSON line (metric, value, ms_per_step ...).  Inputs are resident in HBM before the timed region and
+the same in every run with the same arguments (fixed seeds); nothing outside the repository is read.
 """
 import argparse
 import ctypes as C
@@ -481,7 +485,10 @@ def make_step(macx, dev, dist, world, rank, global_batch, p, seed):
         torch.autograd.backward([state.memory], [gmem])
         if world > 1:
             bucket.allreduce_(bl, global_batch)
+        step.memory = state.memory.detach()        # the value only: keeping the step's autograd graph alive breaks the next backward
 
+    leaves = [("vecQuestions", vqd), ("words", wd), ("knowledgeBase", kbd)] + [(f, getattr(params, f)) for f in params.fields]
+    step.outputs = lambda: step_outputs(step.memory, leaves if world == 1 else leaves[:3], None if bucket is None else bucket.flat)
     step.bucket, step.slice = bucket, (lo, hi)
     return step, params, kbd, bl
 
@@ -524,6 +531,7 @@ def make_dp_graph_step(macx, dev, dist, params, bucket, kbd, lo, hi, global_batc
     def step(i):
         cap.step(iteration=i)
 
+    step.outputs = lambda: step_outputs(cap.memory, [], bucket.flat)
     return step, bool(flag.item() > 0.5), cap
 
 
@@ -540,7 +548,69 @@ def make_graph_step(macx, dev, params, kbd, bl, p, seed):
     def step(i):
         cap.replay(iteration=i)
 
+    # the eager step's names: after the self-check the leaves' .grad are the tensors the replays write
+    leaves = [("vecQuestions", cap.vecQuestions), ("words", cap.words), ("knowledgeBase", cap.knowledgeBase)]
+    step.outputs = lambda: step_outputs(cap.memory, leaves + [(f, getattr(params, f)) for f in params.fields])
     return step, cap
+
+
+def step_outputs(memory, leaves, flat=None):
+    """What one step hands its caller, as {name: float32 host array}: the final memory, the gradient of every leaf that has one
+    (grad_<leaf>) and, for N > 1, the all-reduced flat gradient buffer (grad_flat)."""
+    out = {"memory": memory}
+    out.update(("grad_" + name, t.grad) for name, t in leaves if t.grad is not None)
+    if flat is not None:
+        out["grad_flat"] = flat
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(outs, path, limit=64 * 1000 * 1000):
+    """path/<name>.npy per output.  Above `limit` bytes in all, the largest arrays give way, largest first, to a fixed seeded
+    sample of their elements (path/<name>_sample.npy: flat indices drawn without replacement by numpy's default_rng(0), sorted)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outs = dict(outs)
+    excess = sum(v.nbytes for v in outs.values()) - limit
+    for k in sorted(outs, key=lambda k: -outs[k].nbytes):
+        if excess <= 0:
+            break
+        v = outs.pop(k).reshape(-1)
+        keep = max(1, v.size - (excess + v.itemsize - 1) // v.itemsize)
+        outs[k + "_sample"] = v[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        excess -= (v.size - keep) * v.itemsize
+    for k, v in outs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    print("wrote %d arrays of the last timed step to %s" % (len(outs), path), file=sys.stderr, flush=True)
+    return sorted(outs)
+
+
+def plain_run(args, macx, L, dev, dist, world, rank, global_batch, p, seed, barrier):
+    """The headline alone: the metric's step as --full chooses it (the captured step where it reproduces the eager step bit for
+    bit), W warmup steps, then exactly K timed steps.  No settle, no eager leg, no probes, no side legs."""
+    step, params, kbd, bl = make_step(macx, dev, dist, world, rank, global_batch, p, seed)
+    metric, prime, launch = step, 16, "eager launches (one C-ABI call per unit)"
+    if world == 1 and not args.eager and mode_is_h2(L):
+        gstep, cap = make_graph_step(macx, dev, params, kbd, bl, p, seed)
+        if cap.captured:
+            metric, prime, launch = gstep, 4, "one captured HIP graph per step (macx.CapturedTrainStep, self-checked against the eager step)"
+    elif world > 1 and not args.eager and mode_is_h2(L):
+        try:
+            cstep, ok, _ = make_dp_graph_step(macx, dev, dist, params, step.bucket, kbd, *step.slice, global_batch, p, seed)
+        except Exception:               # (as in --full: every rank fails alike, the eager step is timed)
+            ok = False
+        if ok:
+            metric, prime, launch = cstep, 4, "two captured HIP graphs per rank and step (macx.CapturedDPTrainStep)"
+    dt = time_steps(metric, args.steps, args.warmup, prime, barrier, world, dev, dist)
+    if rank == 0:
+        if args.dump_outputs:
+            write_outputs(metric.outputs(), args.dump_outputs)
+        mode = L.macx_gemm_mode(-1)
+        print(json.dumps({"metric": "questions/sec fwd+bwd (B=64,d=512,p=12,KB=14x14x1024) at 1/2/4/8 MI355X",
+                          "value": round(global_batch * args.steps / dt, 2), "unit": "questions/s", "higher_is_better": True,
+                          "dtype": "f32 (3xfp16-split emulation)" if mode == 2 else ("f32 (6xbf16-split emulation)" if mode == 1 else "f32"),
+                          "ms_per_step": round(dt / args.steps * 1e3, 3), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                          "scaling": "weak" if args.per_gpu_batch else "strong", "data": "synthetic", "launch": launch,
+                          "full": False}), flush=True)
 
 
 def main():
@@ -548,6 +618,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="the whole measurement (settle, eager leg, median of several blocks, roofline "
+                    "probes, side legs; the --no-* options apply to it) instead of the K timed steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (final memory, every gradient) "
+                    "as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-model-level", action="store_true")
     ap.add_argument("--no-native", action="store_true", help="skip the comparison legs on the other two kernel families")
@@ -622,6 +696,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    if not args.full:
+        plain_run(args, macx, L, dev, dist, world, rank, global_batch, p, seed, barrier)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # untimed priming before the W requested warmup steps: the caching allocator settles on the saved/ws block sizes in the
     # first two, the rest (~0.1 s of work) lets the clocks of an idle GPU ramp before anything is timed
     PRIME = 16
@@ -645,6 +725,8 @@ def main():
             prev = cur
         settle_dp = {"n_blocks": n_blk, "last_block_ms_per_step": round(cur / 10 * 1e3, 3)}
     dts = time_blocks(step, args.steps, args.warmup, PRIME, barrier, world, dev, dist, blocks=METRIC_BLOCKS if world > 1 else 1)
+    keep = lambda st: st.outputs() if args.dump_outputs and rank == 0 else None      # noqa: E731 -- right after a metric timing
+    outputs = keep(step)
     # One GPU: the timed step is the product's captured training step (one HIP graph per step: the ~135 launches of a step
     # cost what the GPU needs, not what the host can issue -- boxes of the pool differ by 7x in host speed); the eager step
     # timed above stays in the line as `eager_step`.  N > 1 (and MACX_BENCH_EAGER=1) time the eager step: the exchange is not
@@ -665,6 +747,7 @@ def main():
                          "what": "the same step as eager launches, same process: median of 3 blocks of --steps steps.  This is the 1-GPU "
                                  "figure an N > 1 line (eager data-parallel steps) compares with"}
             dts = time_blocks(gstep, args.steps, args.warmup, 4, barrier, world, dev, dist)
+            outputs = keep(gstep)
             launch_mode = ("one captured HIP graph per step (macx.CapturedTrainStep: forward + full backward, self-checked bit for bit against "
                            "the eager step incl. every gradient; the run's mask word is rewritten before each replay: fresh dropout masks per step)")
         del gstep, cap
@@ -693,6 +776,7 @@ def main():
                 ok = False
         if ok:
             dts = cdts
+            outputs = keep(cstep)
             launch_mode = ("two captured HIP graphs per rank and step (macx.CapturedDPTrainStep: forward + backward phase 1 | backward phase 2), "
                            "the early bucket's all-reduce between them on a side stream, the late bucket behind them; self-checked bit for "
                            "bit against the eager data-parallel step on every rank; fresh dropout masks per step through the mask word")
@@ -700,6 +784,7 @@ def main():
             dp_graph_note = "the replayed step did not reproduce the eager data-parallel step on every rank: eager launches timed"
     if world == 1 and len(dts) == 1:          # the eager step IS the metric here (--eager, another kernel family, no capture): time the remaining blocks
         dts = dts + time_blocks(step, args.steps, 0, 0, barrier, world, dev, dist, blocks=METRIC_BLOCKS - 1)
+        outputs = keep(step)
     dt, timing = block_summary(dts, args.steps, global_batch)
     ms_per_step = dt / args.steps * 1e3
     qps = global_batch * args.steps / dt
@@ -719,6 +804,8 @@ def main():
         extra["model_level_dp"] = model_level_dp(macx, dev, dist, world, rank, global_batch, seed)
         torch.cuda.empty_cache()
 
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     if rank == 0 and args.no_probe:
         print(json.dumps({"metric": "questions/sec fwd+bwd (B=64,d=512,p=12,KB=14x14x1024) at 1/2/4/8 MI355X", "value": round(qps, 2),
                           "unit": "questions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

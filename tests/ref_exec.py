@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: executes the reference's OWN code -- /root/reference/{config,ops,mac_cell,model}.py,
+"""TEST INFRASTRUCTURE: executes the reference's OWN code -- the upstream project's {config,ops,mac_cell,model}.py,
 unmodified -- on the eager TF-1.x stand-in of tests/tf1_shim, and adapts its inputs/outputs so that
 oracle/mac_oracle.py can be compared with it on identical parameters, inputs and dropout draws.
 
@@ -8,23 +8,258 @@ classifier / addAnswerLossOp / addPredOp / stem (model.py:165-204, 428-489, 512-
 on a stand-in `self` that carries only the attributes those methods read.
 What does not: TensorFlow (replaced by the shim) -- and therefore TF's RNG stream; draws are injected.
 
-/root/reference exists only in the build container: callers must check `available()` first.
+Where the reference's code runs: MACX_REFERENCE_DIR names a checkout of the upstream project.  Without it, every call
+below is REPLAYED from tests/golden/reference_exec/ -- what the reference's code returned (parsed flags, states, logits,
+draws, variables, the exception it raised) for exactly these arguments, recorded by a live session with
+MACX_RECORD_REFERENCE=1.  A replayed result is built like a live one: its variables and inputs are leaf tensors, and a
+backward pass through its outputs must bring exactly the cotangents of the recorded session (checked) and receives the
+gradients the reference's graph produced for them.  A call that was never recorded fails.
 """
+import atexit
+import builtins
+import hashlib
 import importlib
+import json
 import os
 import sys
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
-REF = os.environ.get("MACX_REFERENCE_DIR", "/root/reference")
+REF = os.environ.get("MACX_REFERENCE_DIR", "")
 SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tf1_shim")
+FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_exec")
+RECORD = os.environ.get("MACX_RECORD_REFERENCE") == "1"
 
 _mods = {}
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# record / replay.  A result is stored as JSON with references: "rng" = the n-th draw of the stand-in's seeded generator
+# (variables and dropout draws: regenerated, not stored), "t" = a stored array, "leaf" / "out" = where autograd connects.
+# ---------------------------------------------------------------------------------------------------------------
+_store = {}                                        # replay: records and arrays of tests/golden/reference_exec
+_new = {"records": {}, "blobs": {}}                # record: this session's
+
+
+def _digest(a):
+    return hashlib.sha1(("%s%s" % (a.dtype, a.shape)).encode() + a.tobytes()).hexdigest()[:20]
+
+
+def _canon(x):
+    """JSON-able, value-based description of a call argument (tensors by content digest)"""
+    if isinstance(x, torch.Tensor):
+        return "T:" + _digest(x.detach().contiguous().numpy())
+    if isinstance(x, dict):
+        return {"d": [[str(k), _canon(v)] for k, v in sorted(x.items())]}
+    if isinstance(x, (list, tuple)):
+        return [_canon(v) for v in x]
+    if isinstance(x, float):
+        return repr(x)
+    if isinstance(x, torch.dtype):
+        return str(x)
+    if hasattr(x, "__dict__"):                     # the parsed config
+        return _canon(vars(x))
+    return x
+
+
+def _cfg_digest(cfg):
+    return None if cfg is None else hashlib.sha1(json.dumps(_canon(cfg), sort_keys=True).encode()).hexdigest()[:20]
+
+
+def _regenerate(rng):
+    """the stand-in's generator draws of one run, as tests/tf1_shim computes them"""
+    gen, dt, out = torch.Generator().manual_seed(rng["seed"]), getattr(torch, rng["dtype"]), []
+    for kind, shape, scale in rng["log"]:
+        if kind == "normal":
+            out.append((torch.randn(shape, generator=gen, dtype=torch.float64) * scale).to(dt))
+        else:
+            u = torch.rand(shape, generator=gen, dtype=torch.float64)
+            out.append((u if kind == "uniform" else (u * 2 - 1) * scale).to(dt))
+    return out
+
+
+def _encode(x, ctx):
+    if isinstance(x, torch.Tensor):
+        a = x.detach().contiguous().numpy()
+        h = _digest(a)
+        e = {"rng": ctx["rng"][h]} if h in ctx["rng"] else {"t": h}
+        _new["blobs"].setdefault(h, a) if "t" in e else None
+        if x.requires_grad and x.is_leaf:
+            if all(t is not x for t in ctx["leaves"]):
+                ctx["leaves"].append(x)
+            e["leaf"] = [i for i, t in enumerate(ctx["leaves"]) if t is x][0]
+        elif x.requires_grad:
+            ctx["outs"].append(x)
+            e["out"] = len(ctx["outs"]) - 1
+        return e
+    if isinstance(x, dict):
+        return {"d": [[k, _encode(v, ctx)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return {"l": [_encode(v, ctx) for v in x]}
+    if isinstance(x, (bool, int, float, str)) or x is None:
+        return {"v": x}
+    if all(hasattr(x, a) for a in CELL_ATTRS):     # the reference's MACCell: the histories the tests read
+        return {"cell": [[a, _encode(getattr(x, a), ctx)] for a in CELL_ATTRS]}
+    raise TypeError("cannot record a %r in a reference result" % type(x))
+
+
+CELL_ATTRS = ("controls", "memories", "infos", "attentions")
+
+
+class _Node(torch.autograd.Function):
+    """the recorded run as one autograd node: its leaves in, its differentiable outputs out"""
+
+    @staticmethod
+    def forward(ctx, backward, values, *leaves):
+        ctx.backward = backward
+        ctx.set_materialize_grads(False)
+        return tuple(v.clone() for v in values)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None, None) + tuple(ctx.backward(grads))
+
+
+def _decode(rec, blobs, backward):
+    """the result as the tests see it: fresh leaves, the differentiable outputs from one _Node"""
+    drawn = _regenerate(rec["rng"]) if "rng" in rec else []
+    value = lambda e: (drawn[e["rng"]] if "rng" in e else torch.from_numpy(blobs[e["t"]].copy()))    # noqa: E731
+    leaves, outs = {}, {}
+
+    def scan(e):
+        if "leaf" in e:
+            leaves[e["leaf"]] = value(e).requires_grad_(True)
+        elif "out" in e:
+            outs[e["out"]] = value(e)
+        for v in [v for _, v in e.get("d", []) + e.get("cell", [])] + e.get("l", []):
+            scan(v)
+
+    scan(rec["result"])
+    leaves = [leaves[i] for i in range(len(leaves))]
+    outs = _Node.apply(backward, [outs[i] for i in range(len(outs))], *leaves) if outs else ()
+
+    def build(e):
+        if "leaf" in e or "out" in e:
+            return leaves[e["leaf"]] if "leaf" in e else outs[e["out"]]
+        if "rng" in e or "t" in e:
+            return value(e)
+        if "d" in e or "cell" in e:
+            d = {k: build(v) for k, v in e.get("d", e.get("cell"))}
+            return SimpleNamespace(**d) if "cell" in e else d
+        return [build(v) for v in e["l"]] if "l" in e else e["v"]
+
+    return build(rec["result"])
+
+
+def _load_store():
+    if not _store:
+        _store.update(records={}, blobs={})
+        for f in sorted(os.listdir(FIXTURES)) if os.path.isdir(FIXTURES) else []:
+            with np.load(os.path.join(FIXTURES, f)) as z:
+                for k in z.files:
+                    if k == "records":
+                        _store["records"].update(json.loads(bytes(z[k]).decode()))
+                    else:
+                        _store["blobs"][k] = z[k]
+    return _store["records"], _store["blobs"]
+
+
+def _recorded(fn):
+    """live call (and, with MACX_RECORD_REFERENCE=1, its record) or the replay of the recorded one"""
+    flags = fn.__name__ == "parse_flags"
+    sets_answers = fn.__name__ in ("run_reference", "run_reference_training")      # they set cfg.answerWordsNum first thing
+
+    def call(*args, **kw):
+        key = hashlib.sha1(json.dumps([fn.__name__, _canon(args), _canon(kw)], sort_keys=True).encode()).hexdigest()
+        cfg = None if flags else args[0]
+        if available():
+            rec = {}
+            try:
+                res = fn(*args, **kw)
+            except Exception as e:              # noqa: BLE001 -- the reference's exception is part of its result
+                rec["raise"] = [type(e).__module__, type(e).__name__, str(e)]
+                raise
+            finally:
+                if RECORD:
+                    rec["cfg_after"] = _cfg_digest(cfg)
+                    _new["records"][key] = rec
+            if not RECORD or flags:             # (parse_flags hands out the reference's own config object: its code reads that one)
+                if RECORD:
+                    rec["result"] = _encode(dict(vars(res)), {"rng": {}, "leaves": [], "outs": []})
+                return res
+            st = load()["tf"].state
+            rec["rng"] = {"seed": st.seed, "dtype": str(st.dtype).split(".")[-1], "log": [list(ev) for ev in st.rng]}
+            ctx = {"rng": {_digest(v.numpy()): i for i, v in reversed(list(enumerate(_regenerate(rec["rng"]))))}, "leaves": [], "outs": []}
+            rec["result"] = _encode(res, ctx)
+
+            def backward(grads):
+                pairs = [(o, g) for o, g in zip(ctx["outs"], grads) if g is not None]
+                got = torch.autograd.grad([o for o, _ in pairs], ctx["leaves"], [g for _, g in pairs], allow_unused=True, retain_graph=True)
+                rec["backward"] = {k: [None if g is None else _encode(g.detach(), {"rng": {}})["t"] for g in v]
+                                   for k, v in (("cot", grads), ("grads", got))}
+                return got
+
+            return _decode(rec, _new["blobs"], backward)
+        recs, blobs = _load_store()
+        rec = recs.get(key)
+        if rec is None:
+            raise AssertionError("%s: no recorded reference run for these arguments in %s (record them with "
+                                 "MACX_REFERENCE_DIR=<upstream checkout> MACX_RECORD_REFERENCE=1)" % (fn.__name__, FIXTURES))
+        if sets_answers:
+            cfg.answerWordsNum = kw.get("answerWordsNum", 7)
+        if _cfg_digest(cfg) != rec["cfg_after"]:
+            raise AssertionError("%s: the config differs from the recorded run's after the call" % fn.__name__)
+        if "raise" in rec:
+            mod, name, msg = rec["raise"]
+            if mod != "builtins":
+                raise AssertionError("the recorded reference raised %s.%s, which a replay cannot raise" % (mod, name))
+            raise getattr(builtins, name)(msg)
+
+        def backward(grads):
+            if "backward" not in rec:
+                raise AssertionError("%s: the recorded session ran no backward pass through this result" % fn.__name__)
+            for i, (g, c) in enumerate(zip(grads, rec["backward"]["cot"])):
+                if (g is None) != (c is None) or (g is not None and not torch.equal(g.detach(), torch.from_numpy(blobs[c].copy()))):
+                    raise AssertionError("%s: output %d receives another cotangent than in the recorded session" % (fn.__name__, i))
+            return [None if g is None else torch.from_numpy(blobs[g].copy()) for g in rec["backward"]["grads"]]
+
+        res = _decode(rec, blobs, backward)
+        return SimpleNamespace(**res) if flags else res
+
+    call.__name__, call.__doc__ = fn.__name__, fn.__doc__
+    return call
+
+
+def write_records(path=FIXTURES, shard_bytes=900 * 1024):
+    """this session's records -> path/reference_exec_NN.npz (the records' JSON, 200 per file, then the arrays; each file small)"""
+    os.makedirs(path, exist_ok=True)
+    for f in os.listdir(path):
+        os.remove(os.path.join(path, f))
+    keys, shards = sorted(_new["records"]), []
+    for i in range(0, len(keys), 200):
+        part = json.dumps({k: _new["records"][k] for k in keys[i:i + 200]}, sort_keys=True, separators=(",", ":"))
+        shards.append({"records": np.frombuffer(part.encode(), dtype=np.uint8)})
+    size = shard_bytes
+    for h in sorted(_new["blobs"]):
+        a = _new["blobs"][h]
+        if size + a.nbytes > shard_bytes:
+            shards.append({})
+            size = 0
+        shards[-1][h], size = a, size + a.nbytes + 200
+    for i, z in enumerate(shards):
+        np.savez_compressed(os.path.join(path, "reference_exec_%02d.npz" % i), **z)
+
+
+if RECORD:
+    atexit.register(lambda: _new["records"] and write_records())
+
+
+
 def available():
-    return os.path.isfile(os.path.join(REF, "mac_cell.py"))
+    """the reference's code can run here (MACX_REFERENCE_DIR); otherwise its results are replayed"""
+    return bool(REF) and os.path.isfile(os.path.join(REF, "mac_cell.py"))
 
 
 def load():
@@ -46,6 +281,7 @@ def load():
     return _mods
 
 
+@_recorded
 def parse_flags(flag_file, *extra):
     """The reference's own parser (config.py:95-428) over one of its published flag files
     (configs/args*.txt) plus extra command-line flags; returns the `config` singleton."""
@@ -90,6 +326,7 @@ def snapshot(cfg):
     return {k: getattr(cfg, k) for k in CELL_FLAGS}
 
 
+@_recorded
 def run_reference(cfg, vecQ, questionWords, questionCntxWords, lengths, kb, train=False, keeps=(1.0, 1.0, 1.0),
                   output_keep=1.0, preset=None, seed=0, dtype=torch.float64, need_grad=False, answers=None,
                   with_output=True, answerWordsNum=7, draws=None):
@@ -156,6 +393,7 @@ def replay_mask_fn(draws, keeps, output_keep=1.0):
     return fn
 
 
+@_recorded
 def run_reference_stem(cfg, images_nhwc, keep=1.0, seed=0, dtype=torch.float64, need_grad=False, draws=None, out_dim=None):
     """MACnet.stem (model.py:165-204) exactly as the reference builds it: ops.CNNLayer -> ops.cnn (ops.py:380-438).
     images_nhwc [B,H,W,C] (the graph's layout after model.py:67-68).  Returns dict(kb [B,H*W,outDim], variables, draws, images)."""
@@ -172,6 +410,7 @@ def run_reference_stem(cfg, images_nhwc, keep=1.0, seed=0, dtype=torch.float64, 
     return dict(kb=kb, variables=dict(tf.state.variables), draws=[u for _, u in tf.state.draws], images=img)
 
 
+@_recorded
 def run_reference_encoder(cfg, questions, lengths, emb, keep_input=1.0, keep_question=1.0, seed=0, dtype=torch.float64,
                           need_grad=False, draws=None):
     """qEmbeddingsOp (model.py:207-219) + encoder (model.py:279-307 -> ops.RNNLayer / biRNNLayer, ops.py:859-950) as the
@@ -190,6 +429,7 @@ def run_reference_encoder(cfg, questions, lengths, emb, keep_input=1.0, keep_que
     return dict(words=words, vecQ=vecQ, variables=dict(tf.state.variables), draws=[u for _, u in tf.state.draws])
 
 
+@_recorded
 def run_reference_training(cfg, vecQ, questionWords, questionCntxWords, lengths, kb, answers, steps, lr, preset=None, seed=0,
                            dtype=torch.float64, answerWordsNum=7):
     """`steps` training steps exactly as model.py strings them: MACnetwork -> outputOp -> classifier -> addAnswerLossOp
@@ -224,4 +464,5 @@ def run_reference_training(cfg, vecQ, questionWords, questionCntxWords, lengths,
                         m={k: optimizer.m[k + ":0"].clone() for k in names if k + ":0" in optimizer.m},
                         v={k: optimizer.v[k + ":0"].clone() for k in names if k + ":0" in optimizer.v},
                         ema={k: tf.state.ema[k].clone() for k in names if k in tf.state.ema}))
-    return dict(steps=out, global_step=fake.globalStep.value, ema_names=sorted(fake.emaDict))
+    return dict(steps=out, global_step=fake.globalStep.value, ema_names=sorted(fake.emaDict),
+                initial={k: v.detach().clone() for k, v in tf.state.initial.items()})

@@ -310,6 +310,21 @@ def test_bench_metric_blocks_report_the_median_and_the_spread(monkeypatch):
     assert abs(info["spread"] - (9.0 - 4.0) / 4.2) < 1e-3
 
 
+def test_bench_dump_outputs_stay_under_the_limit(tmp_path):
+    """bench.write_outputs: every array as <name>.npy; over the byte limit the largest give way to a fixed seeded sample of their
+    elements (<name>_sample.npy), the same sample in every run"""
+    import numpy as np
+    import bench
+    outs = {"big": np.arange(1000, dtype=np.float32), "small": np.ones(10, dtype=np.float32)}
+    assert bench.write_outputs(outs, str(tmp_path / "all")) == ["big", "small"]
+    assert np.array_equal(np.load(tmp_path / "all" / "big.npy"), outs["big"])
+    assert bench.write_outputs(outs, str(tmp_path / "a"), limit=2000) == ["big_sample", "small"]
+    bench.write_outputs(outs, str(tmp_path / "b"), limit=2000)
+    a, b = np.load(tmp_path / "a" / "big_sample.npy"), np.load(tmp_path / "b" / "big_sample.npy")
+    assert a.dtype == np.float32 and a.nbytes + outs["small"].nbytes <= 2000 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(outs["big"].tolist())
+
+
 def test_product_code_never_touches_the_debug_knobs():
     """The A/B hooks travel per call in macx_opts.tune (ABI 5; the process-global macx_debug_set of ABI <= 4 is gone from the library),
     and what is left of process-wide state -- macx_gemm_mode's default kernel family, options.SESSION_TUNE on the Python side -- is

@@ -46,6 +46,8 @@ class _State:
     def reset(self, dtype=torch.float64, seed=0, preset=None, require_grad=False):
         self.dtype = dtype
         self.gen = torch.Generator().manual_seed(seed)
+        self.seed = seed
+        self.rng = []                # [(kind, shape, scale)]: every draw from `gen`, in order (tests/ref_exec.py regenerates them)
         self.variables = {}          # full name -> tensor, in creation order
         self.preset = dict(preset or {})   # values a "checkpoint restore" would put into the variables
         self.require_grad = require_grad
@@ -169,6 +171,7 @@ def uniform(shape):
         u = torch.as_tensor(state.uniform_hook(tuple(shape)), dtype=state.dtype)
     else:
         u = torch.rand(shape, generator=state.gen, dtype=torch.float64).to(state.dtype)
+        state.rng.append(("uniform", tuple(shape), 1.0))
     state.draws.append(("uniform", u))
     return _w(u)
 
@@ -238,6 +241,7 @@ class _Init:
         if self.kind == "constant":
             return torch.full(shape, float(self.value), dtype=state.dtype)
         if self.kind == "normal":
+            state.rng.append(("normal", tuple(shape), self.stddev))
             return (torch.randn(shape, generator=state.gen, dtype=torch.float64) * self.stddev).to(state.dtype)
         if self.kind == "xavier":
             # tf.contrib.layers.xavier_initializer(uniform=True) -> variance_scaling(1.0, FAN_AVG, uniform):
@@ -254,6 +258,7 @@ class _Init:
                     rf *= s
                 fan_in, fan_out = shape[-2] * rf, shape[-1] * rf
             lim = math.sqrt(6.0 / (fan_in + fan_out))
+            state.rng.append(("xavier", tuple(shape), lim))
             return ((torch.rand(shape, generator=state.gen, dtype=torch.float64) * 2 - 1) * lim).to(state.dtype)
         raise ValueError(self.kind)
 

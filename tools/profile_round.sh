@@ -16,5 +16,5 @@ rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTI
 python tools/pmc_summary.py $O/${TAG}_f/f_counter_collection.csv $O/${TAG}_w/w_counter_collection.csv > $O/${TAG}_pmc_hbm.txt 2>&1
 python tools/pmc_summary.py $O/${TAG}_s/s_counter_collection.csv > $O/${TAG}_pmc_sq.txt 2>&1
 python tools/pmc_summary.py $O/${TAG}_l/l_counter_collection.csv > $O/${TAG}_pmc_lds_valu.txt 2>&1
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 head -12 $O/${TAG}_kernel_stats.txt | cut -c1-170; head -6 $O/${TAG}_pmc_hbm.txt | cut -c1-140; cut -c1-300 $O/${TAG}_bench.json

@@ -10,7 +10,7 @@ python tools/step_timeline.py $O/c1e/r_results.db > $O/r06_start_timeline_eager.
 rocprofv3 --kernel-trace -d $O/c1g -o r -- $B --steps 5 --warmup 2 > $O/c1g.log 2>&1
 python tools/step_timeline.py $O/c1g/r_results.db > $O/r06_start_timeline_graph.txt
 rm -rf $O/c1e $O/c1g
-python bench.py --no-model-level --no-native --no-extra-legs > $O/r06_start_bench.json 2> $O/r06_start_bench.err
+python bench.py --full --no-model-level --no-native --no-extra-legs > $O/r06_start_bench.json 2> $O/r06_start_bench.err
 head -30 $O/r06_start_kernel_stats.txt | cut -c1-60,100-170
 tail -40 $O/r06_start_timeline_graph.txt
 cut -c1-400 $O/r06_start_bench.json

@@ -10,7 +10,7 @@ python tools/step_timeline.py $O/c4e/r_results.db --brief > $O/c4_timeline.txt
 rm -rf $O/c4e
 head -12 $O/c4_kernel_stats.txt | cut -c1-60,100-170
 head -3 $O/c4_timeline.txt
-python bench.py --no-model-level --no-native --no-extra-legs > $O/c4_bench.json 2> $O/c4_bench.err; echo "bench rc=$?"
+python bench.py --full --no-model-level --no-native --no-extra-legs > $O/c4_bench.json 2> $O/c4_bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/c4_bench.json").read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ python tools/step_timeline.py $O/c6e/r_results.db --brief > $O/c6_timeline.txt
 rm -rf $O/c6e
 head -32 $O/c6_kernel_stats.txt | cut -c1-60,100-170
 head -1 $O/c6_timeline.txt
-python bench.py --no-cpu-baseline --no-model-level --no-native --no-extra-legs > $O/c6_bench.json 2> $O/c6_bench.err; echo "bench rc=$?"
+python bench.py --full --no-cpu-baseline --no-model-level --no-native --no-extra-legs > $O/c6_bench.json 2> $O/c6_bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/c6_bench.json").read().strip().splitlines()[-1])
