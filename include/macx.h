@@ -307,6 +307,23 @@ int macx_stem_backward(const macx_stem_shapes*, int act, float keep, uint32_t se
                        const float* kb, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
                        const float* d_kb, const macx_stem_grads*, void* stream);
 
+/* ---- general convolution (the generic stem: any --stemNumLayers / --stemKernelSize(s) / --stemStrideSizes) ---------- */
+/* ops.cnn's tf.nn.conv2d(inp, kernel, strides = [1, s, s, 1], padding = "SAME") (ops.py:380-411) for any kernel size k >= 1
+ * and stride s >= 1, as implicit GEMMs on exact-fp32 MFMA (no im2col buffer):
+ *   Ho = ceil(H / s), pad_total = max((Ho - 1) s + k - H, 0), pad_top = pad_total / 2 (the odd row at the bottom); same along W.
+ *   macx_conv2d_fwd       y [B,Ho,Wo,Cout] = conv(x [B,H,W,Cin], w [k,k,Cin,Cout] (HWIO)) (+ bias [Cout] unless NULL)
+ *   macx_conv2d_bwd_data  dx [B,H,W,Cin] = d conv / dx applied to dy [B,Ho,Wo,Cout]
+ *   macx_conv2d_wgrad     dw [k,k,Cin,Cout] = d conv / dw applied to dy; ws >= macx_conv2d_ws_floats floats (may be 0 / NULL).
+ *                         Fixed-order split-K reduction: identical calls give identical bits.
+ * Cin and Cout multiples of 4, every pointer 16-byte aligned, B*H*W and B*Ho*Wo < 2^31; anything else is MACX_EINVAL and
+ * nothing is launched.  The bias gradient is a column sum of dy (macx_op_reduce ROWS). */
+typedef struct macx_conv_shapes { int32_t B, H, W, Cin, Cout, k, stride; } macx_conv_shapes;
+size_t macx_conv2d_ws_floats(const macx_conv_shapes*);
+int macx_conv2d_fwd(const macx_conv_shapes*, const float* x, const float* w, const float* bias, float* y, void* stream);
+int macx_conv2d_bwd_data(const macx_conv_shapes*, const float* dy, const float* w, float* dx, void* stream);
+int macx_conv2d_wgrad(const macx_conv_shapes*, const float* x, const float* dy, float* dw, float* ws, size_t ws_floats,
+                      void* stream);
+
 /* Feed-dict image layout (model.py:67-68): the h5 features are [B, C, H, W] (extract_features.py) and the graph
  * transposes them to NHWC before the stem.  nhwc[b][hw][c] = nchw[b][c][hw]. */
 int macx_images_to_nhwc(const float* nchw, int B, int C, int HW, float* nhwc, void* stream);

@@ -8,7 +8,7 @@ from .options import UnsupportedOptions, freeze     # noqa: F401
 from .params import MACCellParams                   # noqa: F401
 from .generic import GenericMACCell, GenericParams  # noqa: F401
 from .output import GenericOutputClassifier, OutputClassifier   # noqa: F401
-from .stem import Stem                              # noqa: F401
+from .stem import GenericStem, Stem                 # noqa: F401
 from .encoder import GenericQuestionEncoder, QuestionEncoder   # noqa: F401
 from .model import MACNet, MACNetCore               # noqa: F401
 from .graph import CapturedForward, CapturedTrainStep, CapturedDPTrainStep  # noqa: F401

@@ -94,6 +94,10 @@ class MacxStemGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in STEM_FIELDS]
 
 
+class MacxConvShapes(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "Cin", "Cout", "k", "stride")]
+
+
 class MacxEncShapes(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "S", "V", "E", "h", "b0")]
 
@@ -132,7 +136,8 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_kb_attend_bwd_ws_floats", "macx_answer_loss", "macx_workspace_bytes", "macx_embed_lookup", "macx_embed_lookup_bwd", "macx_control_attend_bwd",
            "macx_control_attend_bwd_ws_floats", "macx_read_fwd", "macx_read_bwd",
            "macx_write_fwd", "macx_write_bwd", "macx_read_chain_time", "macx_cell_forward_chain_time", "macx_saved_activation", "macx_ctrl_inputs_ws_floats",
-           "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd")
+           "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd", "macx_conv2d_ws_floats", "macx_conv2d_fwd", "macx_conv2d_bwd_data",
+           "macx_conv2d_wgrad")
 
 _lib = None
 
@@ -225,6 +230,10 @@ def lib():
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("macx_check",):
             f.restype = C.c_int
+    L.macx_conv2d_ws_floats.argtypes = [P(MacxConvShapes)]
+    L.macx_conv2d_fwd.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.macx_conv2d_bwd_data.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.macx_conv2d_wgrad.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.macx_images_to_nhwc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.macx_encoder_saved_floats.argtypes = [P(MacxEncShapes)]
     L.macx_encoder_ws_floats.argtypes = [P(MacxEncShapes)]

@@ -19,6 +19,7 @@
 #include "macx_wgrad_h2.hip.h"
 #include "macx_small.hip.h"
 #include "macx_ops.hip.h"
+#include "macx_conv.hip.h"
 
 using namespace macx;
 
@@ -2529,6 +2530,76 @@ int macx_images_to_nhwc(const float* nchw, int B, int C, int HW, float* nhwc, vo
   if (!nchw || !nhwc || B < 1 || C < 1 || HW < 1 || B > 65535) return MACX_EINVAL;
   hipLaunchKernelGGL(transpose_kernel, dim3((HW + 31) / 32, (C + 31) / 32, B), dim3(256), 0, (hipStream_t)stream, nchw, C, HW, nhwc);
   return (int)hipGetLastError();
+}
+
+// =================================================================================================
+// general convolution (the generic stem's layers, ops.cnn ops.py:380-411): macx_conv.hip.h
+// =================================================================================================
+namespace {
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the shapes the conv kernels take (sizes, 16-byte channel rows, 32-bit GEMM indices) -> geometry; false: MACX_EINVAL
+inline bool conv_ok(const macx_conv_shapes* s, macx::ConvGeom* g) {
+  if (!s || s->B < 1 || s->H < 1 || s->W < 1 || s->Cin < 4 || s->Cout < 4 || s->k < 1 || s->stride < 1) return false;
+  if (s->Cin % 4 || s->Cout % 4) return false;
+  if ((long long)s->B * s->H * s->W >= (1ll << 31)) return false;
+  if ((long long)s->k * s->k * (s->Cin > s->Cout ? s->Cin : s->Cout) >= (1ll << 31)) return false;
+  *g = macx::conv_geom(s->B, s->H, s->W, s->Cin, s->Cout, s->k, s->stride);
+  return true;
+}
+}  // namespace
+
+size_t macx_conv2d_ws_floats(const macx_conv_shapes* s) {
+  macx::ConvGeom g;
+  if (!conv_ok(s, &g)) return 0;
+  int slabs = 1, span = 0;
+  macx::conv_wgrad_split(g, &slabs, &span);
+  return slabs > 1 ? (size_t)slabs * g.k * g.k * g.Cin * g.Cout : 0;
+}
+
+int macx_conv2d_fwd(const macx_conv_shapes* s, const float* x, const float* w, const float* bias, float* y, void* stream) {
+  macx::ConvGeom g;
+  if (!conv_ok(s, &g) || !x || !w || !y || !al16(x) || !al16(w) || !al16(y)) return MACX_EINVAL;
+  macx::ConvArgs a{};
+  a.g = g; a.a = x; a.b = w; a.bias = bias; a.out = y;
+  a.M = g.B * g.Ho * g.Wo; a.N = g.Cout; a.K = g.k * g.k * g.Cin;
+  a.kspan = (a.K + macx::CV_BK - 1) / macx::CV_BK * macx::CV_BK;
+  CK(macx::conv_launch<macx::CV_FWD>(a, 1, (hipStream_t)stream));
+  return MACX_OK;
+}
+
+int macx_conv2d_bwd_data(const macx_conv_shapes* s, const float* dy, const float* w, float* dx, void* stream) {
+  macx::ConvGeom g;
+  if (!conv_ok(s, &g) || !dy || !w || !dx || !al16(dy) || !al16(w) || !al16(dx)) return MACX_EINVAL;
+  macx::ConvArgs a{};
+  a.g = g; a.a = dy; a.b = w; a.out = dx;
+  a.M = g.B * g.H * g.W; a.N = g.Cin; a.K = g.k * g.k * g.Cout;
+  a.kspan = (a.K + macx::CV_BK - 1) / macx::CV_BK * macx::CV_BK;
+  CK(macx::conv_launch<macx::CV_BWD>(a, 1, (hipStream_t)stream));
+  return MACX_OK;
+}
+
+int macx_conv2d_wgrad(const macx_conv_shapes* s, const float* x, const float* dy, float* dw, float* ws, size_t ws_floats,
+                      void* stream) {
+  macx::ConvGeom g;
+  if (!conv_ok(s, &g) || !x || !dy || !dw || !al16(x) || !al16(dy) || !al16(dw)) return MACX_EINVAL;
+  const size_t need = macx_conv2d_ws_floats(s);
+  if (need && (!ws || !al16(ws) || ws_floats < need)) return MACX_EINVAL;
+  int slabs = 1, span = 0;
+  macx::conv_wgrad_split(g, &slabs, &span);
+  macx::ConvArgs a{};
+  a.g = g; a.a = x; a.b = dy;
+  a.M = g.k * g.k * g.Cin; a.N = g.Cout; a.K = g.B * g.Ho * g.Wo;
+  a.kspan = span;
+  const size_t n = (size_t)a.M * a.N;
+  a.out = slabs > 1 ? ws : dw;
+  a.slab = slabs > 1 ? n : 0;
+  hipStream_t st = (hipStream_t)stream;
+  CK(macx::conv_launch<macx::CV_WGRAD>(a, slabs, st));
+  if (slabs > 1) {
+    hipLaunchKernelGGL(macx::conv_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, n, slabs, dw);
+    CK(hipGetLastError());
+  }
+  return MACX_OK;
 }
 
 // =================================================================================================

@@ -5,8 +5,9 @@ question encoder's outputs as inputs:
 
 `MACNetCore` takes the question encoder's outputs (vecQuestions / questionCntxWords / questionLengths) as inputs;
 `MACNet` adds `embeddingsOp` + `encoder` (model.py:208-307) in front, so its inputs are exactly
-the reference's feed dict: question word ids, question lengths, image features, (answers).  Out of this graph stay
-only the host side (preprocess.py / main.py) and the baseline / unused stem variants."""
+the reference's feed dict: question word ids, question lengths, image features, (answers).  Every stem option set the
+reference builds is covered (stem.Stem for the default CNN, stem.GenericStem for the others; the knowledge base then has
+stem.out_hw cells, e.g. 7 x 7 for --stemStrideSizes 2 1).  Out of this graph stays only the host side (preprocess.py / main.py)."""
 import torch
 
 from .cell import MACCell
