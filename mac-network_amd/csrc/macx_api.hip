@@ -428,8 +428,15 @@ LinP make_write_lin(const macx_opts* o, const macx_shapes* s, const macx_dropout
   return l;
 }
 
-// pre: bit 2 -- this launch's filler workgroups compute the step's y (ChainPreP::ylin); bit 0 -- stage 0 of this step was done by the previous step's launch (ChainFwdP::mode 2); bit 1 -- this launch's fillers do
-// stage 0 of step i + 1 (ChainPreP).  Both only where macx_cell_forward sequences the steps itself.
+// what a step's chain launch and its filler workgroups take over from the launches around it (ChainPreP); only where
+// macx_cell_forward sequences the steps itself
+enum {
+  PRE_STAGE0_DONE = 1,    // stage 0 of this step was done by the previous step's launch (ChainFwdP::mode 2)
+  PRE_STAGE0_NEXT = 2,    // this launch's fillers do stage 0 of step i + 1
+  PRE_YLIN = 4,           // this launch's fillers compute the step's y (ChainPreP::ylin)
+  PRE_WRITE_NEXT = 8,     // this step's write unit is left to the next launch
+  PRE_WRITE_PREV = 16,    // this launch's fillers run the previous step's write unit (ChainPreP::wlin)
+};
 ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
                          const macx_inputs* in, float* saved, const SavedLayout& L, int keep, int i, int ob, int pre = 0) {
   const int B = s->B, N = s->N, d = s->d;
@@ -472,22 +479,22 @@ ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dr
     c.I2 = h2_view(saved + L.I2 + (size_t)ob * L.act_stride, R, d);
   }
   c.logits = saved + L.logit_part;
-  if (rdrop && c.mode == 0 && (pre & 1)) c.mode = 2;
-  if (pre & 6) c.pre.nfill = pre_fill_count(d, (size_t)R, device_cu_count());
-  if ((pre & 4) && c.pre.nfill) {
-    // this step's y = md Wy + by on the filler workgroups (cell_step_impl then launches no linear for it)
+  if (rdrop && c.mode == 0 && (pre & PRE_STAGE0_DONE)) c.mode = 2;
+  if (pre & (PRE_STAGE0_NEXT | PRE_YLIN)) c.pre.nfill = pre_fill_count(d, (size_t)R, device_cu_count());
+  if ((pre & PRE_YLIN) && c.pre.nfill) {
+    // this step's y = md Wy + by on the filler workgroups (read_step then launches no linear for it)
     c.pre.ylin = lin_basic(saved + L.md + (size_t)i * Bd, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, saved + L.y + (size_t)i * Bd, d);
     c.pre.step = i;
     c.pre.yflag = reinterpret_cast<uint32_t*>(saved + L.sync) + i;
     c.pre.fail = reinterpret_cast<uint32_t*>(saved + L.sync) + 63;
-    if ((pre & 16) && i > 0) {
-      // ... after the previous step's write unit (cell_step_impl did not launch it)
+    if ((pre & PRE_WRITE_PREV) && i > 0) {
+      // ... after the previous step's write unit (cell_step did not launch it)
       c.pre.wlin = make_write_lin(o, s, dp, P, saved, L, i - 1, saved + L.seg[MACX_SEG_INFOS] + (size_t)(i - 1) * Bd,
                                   saved + L.seg[MACX_SEG_MEMORIES] + (size_t)i * Bd, true);
       c.pre.gflag = reinterpret_cast<uint32_t*>(saved + L.sync) + 64 + 16 * i;
     }
   }
-  if (rdrop && (pre & 2) && c.pre.nfill) {
+  if (rdrop && (pre & PRE_STAGE0_NEXT) && c.pre.nfill) {
     c.pre.key1 = make_drop(dp->keep_read, dp, SITE_READ_KB, i + 1).key;
     c.pre.key2 = make_drop(dp->keep_read, dp, SITE_READ_ATT, i + 1).key;
     c.pre.bits1 = reinterpret_cast<uint8_t*>(saved + L.kb_bits + (size_t)(ob + 1) * L.bits_stride);
@@ -757,56 +764,108 @@ int macx_saved_segment(const macx_opts* o, const macx_shapes* s, int keep, int s
 
 // -------------------------------------------------------------------------------------------------
 namespace {
-enum { U_CONTROL = 1, U_READ = 2, U_WRITE = 4, U_ALL = 7 };   // which units of a step an entry point runs
+// One call of the fused cell, forward or backward: its arguments, the layout of `saved`, the derived sizes and the kernel-family /
+// route decisions, taken once per call under the entry point's ModeScope
+struct CellRun {
+  const macx_opts* o; const macx_shapes* s; const macx_dropout* dp; const macx_params* P; const macx_inputs* in;
+  float* saved;
+  SavedLayout L;
+  hipStream_t st;
+  int B, N, d, p, keep;
+  size_t Bd, dd;
+  bool rdrop;     // read dropout
+  bool h2;        // the H2 kernel family
+  bool chain;     // ... and the read unit's products in the chain kernels
+  CellRun(const macx_opts* o_, const macx_shapes* s_, const macx_dropout* dp_, const macx_params* P_, const macx_inputs* in_,
+          float* saved_, int keep_, void* stream)
+      : o(o_), s(s_), dp(dp_), P(P_), in(in_), saved(saved_), L(make_saved(o_, s_, keep_)), st((hipStream_t)stream), B(s_->B),
+        N(s_->N), d(s_->d), p(s_->p), keep(keep_), Bd((size_t)s_->B * s_->d), dd((size_t)s_->d * s_->d),
+        rdrop(dp_->keep_read < 1.0f), h2(h2_mode()), chain(use_chain(s_->d, s_->N)) {}
+  WMaxRef mx(int k) const { return wmax_ref(saved, L.wmax, k, chain); }
+  float* controls() const { return saved + L.seg[MACX_SEG_CONTROLS]; }
+  float* memories() const { return saved + L.seg[MACX_SEG_MEMORIES]; }
+  // step i's information before the write dropout (mac_cell.py:461-463); self.infos keeps the dropped value (mac_cell.py:474)
+  float* info_raw(int i) const { return saved + (dp->keep_write < 1.0f ? L.info_raw : L.seg[MACX_SEG_INFOS]) + (size_t)i * Bd; }
+  GemmH2P h2_gemm_params() const;
+  // weight packs: the forward pass's, or with W the backward pass's transposes
+  hipError_t read_weight_maxima() const;
+  void add_read_packs(Packer& pk, const BwdLayout* W = nullptr) const;
+  void add_write_packs(Packer& pk, const BwdLayout* W = nullptr) const;
+  int add_control_packs(Packer& pk, const BwdLayout* W = nullptr) const;
+  // forward: the units of step i
+  int control_step(int i) const;
+  int read_products_chain(int i, int pre) const;
+  int read_products_h2(int i) const;
+  int read_products_f32(int i) const;
+  int read_step(int i, int pre, bool md_fused) const;
+  int write_step(int i, bool md_fused) const;
+  int cell_step(int i, int pre) const;
+};
 
-// weights -> MFMA operand layout  (memKbProj rows [0,d) multiply x*y, rows [d,2d) multiply x: ops.py:718)
-struct Packer;
-int add_bwd_packs(Packer& pk, const macx_opts* o, const macx_shapes* s, const macx_params* P, float* wT, const BwdLayout& W,
-                  const float* saved, const SavedLayout& L, int units, hipStream_t st);
-int pack_forward_weights(const macx_opts* o, const macx_shapes* s, const macx_params* P, float* saved, const SavedLayout& L,
-                         int keep, int units, hipStream_t st) {
-  const int B = s->B, d = s->d, p = s->p;
-  {
-    Packer pk;
-    if (h2_mode() && (units & U_READ)) {
-      // per-matrix maxima -> weight exponents (plain weights) and the bound of the question-mixed tile (W1a, W1b)
-      const size_t dd_ = (size_t)d * d;
-      static_assert(ABSMAX_BLOCKS == 64, "wmax_ref's partial layout");
-      CK(absmax4(P->projX_W, dd_, P->memKbProj2_W, dd_, P->memKbProj_W, dd_, P->memKbProj_W + dd_, dd_, saved + L.wmax,
-                 saved + L.wmax + 8, st, !use_chain(d, s->N)));
-    }
-    const bool fold = h2_mode() && use_chain(d, s->N);
-    auto mx = [&](int k) { return wmax_ref(saved, L.wmax, k, fold); };
-    if (units & U_READ) {
-      pk.add(P->projX_W, d, 1, d, d, saved + L.wx_p, -1, -1, wfmt_plain(), mx(0).src, nullptr, mx(0).n, mx(0).out);
-      if (use_chain(d, s->N)) {      // the chain kernel scales the A side by y: W1a and W1b are plain H2 weights there
-        pk.add(P->memKbProj_W, d, 1, d, d, saved + L.w1a_p, -1, -1, 3, mx(2).src, nullptr, mx(2).n, mx(2).out);
-        pk.add(P->memKbProj_W + (size_t)d * d, d, 1, d, d, saved + L.w1b_p, -1, -1, 3, mx(3).src, nullptr, mx(3).n, mx(3).out);
-      } else {
-        pk.add(P->memKbProj_W, d, 1, d, d, saved + L.w1a_p, -1, -1, wfmt_ymix());
-        pk.add(P->memKbProj_W + (size_t)d * d, d, 1, d, d, saved + L.w1b_p, -1, -1, wfmt_ymix());
-      }
-      pk.add(P->memKbProj2_W, d, 1, d, d, saved + L.w2_p, -1, -1, wfmt_plain(), mx(1).src, nullptr, mx(1).n, mx(1).out);
-      pk.add(P->projY_W, d, 1, d, d, saved + L.wy_p);
-    }
-    if (units & U_WRITE) {
-      pk.add(P->newMemory_W, d, 1, write_in_dim(o, d), d, saved + L.wm_p);
-      if (o->write_gate) pk.add(P->gate_W, d, 1, d, d, saved + L.wg_p);
-      if (o->write_self_att) pk.add(P->selfCtrl_W, d, 1, d, d, saved + L.ws_p);
-    }
-    // a run that keeps its activations will be differentiated: the backward pass's transposed packs ride this launch
-    if (keep && L.bwd_packs) CKI(add_bwd_packs(pk, o, s, P, saved + L.bwd_packs, make_bwd(o, s), saved, L, units, st));
-    if (!(units & U_CONTROL)) return pk.n ? pk.run(st) : hipSuccess;
-    pk.add(P->qInput_W, d, 1, d, d, saved + L.wq_p);
-    if (o->control_feed_prev) {
-      pk.add(P->contControl_W, d, 1, o->control_feed_inputs ? 2 * d : d, d, saved + L.wc_p);
-      if (o->control_cont_act != MACX_ACT_NON) pk.add(P->contControl2_W, d, 1, d, d, saved + L.wc2_p);
-    }
-    for (int i = 0; i < (o->control_input_unshared ? p : 1); ++i) {
-      if (pk.n == PACK_MAX) CK(pk.run(st));
-      pk.add(P->qInputU_W + (size_t)i * d * d, d, 1, d, d, saved + L.wqU_p + (size_t)i * d * d);
-    }
-    CK(pk.run(st));
+// the parameter block of a knowledge-base GEMM on H2 operands: sizes, timing knobs, the read-dropout scale
+GemmH2P CellRun::h2_gemm_params() const {
+  GemmH2P g;
+  memset(&g, 0, sizeof(g));
+  g.B = B; g.N = N; g.K = d; g.Nout = d;
+  g.dbg = kb_gemm_dbg() & (1 | 2 | 4 | 8 | 16 | 32 | 64 | 128);      // phase-timing knobs (results are wrong under a non-zero mask)
+  g.e_inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
+  return g;
+}
+
+// ---- weights -> MFMA operand layouts (memKbProj rows [0,d) multiply x*y, rows [d,2d) multiply x: ops.py:718).  One helper per
+// unit appends that unit's packs to the caller's Packer: the forward pass's into `saved`, or with W the backward pass's transposes
+// into saved + L.bwd_packs (BwdLayout's first region): a run that keeps its activations packs those in the same launch.
+// W: [K, Nout] row-major; T: pack W^T
+void add_pack(Packer& pk, bool T, const float* W, int K, int Nout, float* dst, int fmt = 0, WMaxRef m = WMaxRef{nullptr, 0, nullptr}) {
+  if (T) pk.add(W, 1, Nout, Nout, K, dst, -1, -1, fmt, m.src, nullptr, m.n, m.out);
+  else pk.add(W, Nout, 1, K, Nout, dst, -1, -1, fmt, m.src, nullptr, m.n, m.out);
+}
+
+// h2: per-matrix maxima -> weight exponents (plain weights) and the bound of the question-mixed tile (W1a, W1b)
+hipError_t CellRun::read_weight_maxima() const {
+  static_assert(ABSMAX_BLOCKS == 64, "wmax_ref's partial layout");
+  return absmax4(P->projX_W, dd, P->memKbProj2_W, dd, P->memKbProj_W, dd, P->memKbProj_W + dd, dd, saved + L.wmax,
+                 saved + L.wmax + 8, st, !chain);
+}
+
+void CellRun::add_read_packs(Packer& pk, const BwdLayout* W) const {
+  const bool T = W != nullptr;
+  float* wT = saved + L.bwd_packs;
+  const float* W1 = P->memKbProj_W;
+  float* w1a = T ? wT + W->w1aT_p : saved + L.w1a_p;
+  float* w1b = T ? wT + W->w1bT_p : saved + L.w1b_p;
+  add_pack(pk, T, P->projX_W, d, d, T ? wT + W->wxT_p : saved + L.wx_p, wfmt_plain(), mx(0));
+  if (chain) {      // the chain kernels apply y to the accumulators: W1a and W1b are plain H2 weights there
+    add_pack(pk, T, W1, d, d, w1a, 3, mx(2));
+    add_pack(pk, T, W1 + dd, d, d, w1b, 3, mx(3));
+  } else {
+    add_pack(pk, T, W1, d, d, w1a, wfmt_ymix());
+    add_pack(pk, T, W1 + dd, d, d, w1b, wfmt_ymix());
+  }
+  add_pack(pk, T, P->memKbProj2_W, d, d, T ? wT + W->w2T_p : saved + L.w2_p, wfmt_plain(), mx(1));
+  add_pack(pk, T, P->projY_W, d, d, T ? wT + W->wyT : saved + L.wy_p);
+}
+
+void CellRun::add_write_packs(Packer& pk, const BwdLayout* W) const {
+  const bool T = W != nullptr;
+  float* wT = saved + L.bwd_packs;
+  add_pack(pk, T, P->newMemory_W, write_in_dim(o, d), d, T ? wT + W->wmT : saved + L.wm_p);
+  if (o->write_gate) add_pack(pk, T, P->gate_W, d, d, T ? wT + W->wgT : saved + L.wg_p);
+  if (o->write_self_att) add_pack(pk, T, P->selfCtrl_W, d, d, T ? wT + W->wscT : saved + L.ws_p);
+}
+
+int CellRun::add_control_packs(Packer& pk, const BwdLayout* W) const {
+  const bool T = W != nullptr;
+  float* wT = saved + L.bwd_packs;
+  add_pack(pk, T, P->qInput_W, d, d, T ? wT + W->wqT : saved + L.wq_p);
+  if (o->control_feed_prev) {
+    add_pack(pk, T, P->contControl_W, o->control_feed_inputs ? 2 * d : d, d, T ? wT + W->wccT : saved + L.wc_p);
+    if (o->control_cont_act != MACX_ACT_NON) add_pack(pk, T, P->contControl2_W, d, d, T ? wT + W->wcc2T : saved + L.wc2_p);
+  }
+  float* wqU = T ? wT + W->wqUT : saved + L.wqU_p;
+  for (int i = 0; i < (o->control_input_unshared ? p : 1); ++i) {
+    if (pk.n == PACK_MAX) CK(pk.run(st));
+    add_pack(pk, T, P->qInputU_W + i * dd, d, d, wqU + i * dd);
   }
   return MACX_OK;
 }
@@ -820,17 +879,31 @@ int macx_cell_begin(const macx_opts* o, const macx_shapes* s, const macx_dropout
   if (!dp || !P || !in || !saved) return MACX_EINVAL;
   if (misaligned(saved) || misaligned(in->knowledgeBase) || misaligned(in->words) || misaligned(in->vecQuestions))
     return MACX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const SavedLayout L = make_saved(o, s, keep);
-  if (saved_floats < L.total) return MACX_ESMALL;
+  const CellRun r(o, s, dp, P, in, saved, keep, stream);
+  if (saved_floats < r.L.total) return MACX_ESMALL;
   (void)ws; (void)ws_floats;
-  const int B = s->B, d = s->d, p = s->p;
+  const SavedLayout& L = r.L;
+  const int B = r.B, d = r.d, p = r.p;
+  hipStream_t st = r.st;
 
-  CKI(pack_forward_weights(o, s, P, saved, L, keep, U_ALL, st));
+  {
+    Packer pk;
+    if (r.h2) CK(r.read_weight_maxima());
+    r.add_read_packs(pk);
+    r.add_write_packs(pk);
+    if (keep && L.bwd_packs) {        // a run that keeps its activations will be differentiated
+      const BwdLayout W = make_bwd(o, s);
+      r.add_read_packs(pk, &W);
+      r.add_write_packs(pk, &W);
+      CKI(r.add_control_packs(pk, &W));
+    }
+    CKI(r.add_control_packs(pk));
+    CK(pk.run(st));
+  }
 
   // initial state (mac_cell.py:546-553), both tensors in one launch
-  float* controls = saved + L.seg[MACX_SEG_CONTROLS];
-  float* memories = saved + L.seg[MACX_SEG_MEMORIES];
+  float* controls = r.controls();
+  float* memories = r.memories();
   // ... and step 0's dropped memory (mac_cell.py:214-217, ops.py:679) where macx_cell_step would otherwise launch drop2 for it
   // (md_fused there: the whole cell without a gate; later steps get theirs from the write unit's linear)
   {
@@ -873,143 +946,107 @@ namespace {
 struct ChainProbe { hipEvent_t ev[2 * 64]; int n; bool on; };
 inline ChainProbe* chain_probe() { static thread_local ChainProbe p = {}; return &p; }
 
-int cell_step_impl(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
-                   const macx_inputs* in, float* saved, size_t saved_floats, int keep, int step, int units, void* stream, int pre = 0) {
-  CKI(check_impl(o, s));
-  if (!dp || !P || !in || !saved) return MACX_EINVAL;
-  if (step < 0 || step >= s->p) return MACX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const SavedLayout L = make_saved(o, s, keep);
-  if (saved_floats < L.total) return MACX_ESMALL;
-  const int B = s->B, N = s->N, d = s->d;
-  const size_t Bd = (size_t)B * d;
-  const int i = step;
+// ---- forward: the units of step i
+// the control unit when it is recurrent (mac_cell.py:141-151, configs/args1.txt)
+int CellRun::control_step(int i) const {
+  const int S = s->S;
+  const float* prev = o->control_feed_prev_att ? controls() + (size_t)i * Bd
+                                               : (i == 0 ? controls() : saved + L.cc + (size_t)(i - 1) * Bd);
+  float* cc_i = saved + L.cc + (size_t)i * Bd;
+  const bool two = o->control_cont_act != MACX_ACT_NON;       // ops.linear stacks a second layer (ops.py:325-328)
+  float* lin1 = two ? saved + L.cc_h + (size_t)i * Bd : cc_i;
+  LinP l = lin_basic(prev, d, d, B, saved + L.wc_p, P->contControl_b, d, o->control_cont_act, lin1, d);
+  if (o->control_feed_inputs) { l.seg[1] = LinSeg{saved + L.cI + (size_t)i * Bd, d, d, 0}; l.Ktot = 2 * d; }
+  CK(small_linear_launch(l, 1, st));
+  if (two) {
+    LinP l2 = lin_basic(lin1, d, d, B, saved + L.wc2_p, P->contControl2_b, d, MACX_ACT_NON, cc_i, d);
+    CK(small_linear_launch(l2, 1, st));
+  }
+  CtrlP c;
+  c.B = B; c.S = S; c.d = d;
+  c.cc = cc_i; c.z_cc = 0;
+  c.words = in->words; c.lengths = in->questionLengths;
+  c.w = P->ctrlLogits_w; c.bias = P->ctrlLogits_b;
+  c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S; c.z_att = 0;
+  c.control = controls() + (size_t)(i + 1) * Bd; c.z_ctl = 0;
+  hipLaunchKernelGGL(control_attend_kernel, dim3(B, 1), dim3(256), 0, st, c);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
 
-  float* controls = saved + L.seg[MACX_SEG_CONTROLS];
-  float* memories = saved + L.seg[MACX_SEG_MEMORIES];
-  const float* c_i = controls + (size_t)(i + 1) * Bd;
-  const float* m_prev = memories + (size_t)i * Bd;
-  float* m_new = memories + (size_t)(i + 1) * Bd;
-  float* md = saved + L.md + (size_t)i * Bd;
-  const bool md_fused = units == U_ALL && !o->write_gate;   // the write unit's linear also writes the next step's dropped memory
-  float* y = saved + L.y + (size_t)i * Bd;
-  float* X = saved + L.X + (size_t)i * L.act_stride;
-  float* H1 = saved + L.H1 + (size_t)i * L.act_stride;
-  float* I2 = saved + L.I2 + (size_t)i * L.act_stride;
-  float* info = saved + L.seg[MACX_SEG_INFOS] + (size_t)i * Bd;
-  const bool wdrop = dp->keep_write < 1.0f;
-  float* info_raw = wdrop ? saved + L.info_raw + (size_t)i * Bd : info;
+// the read unit's three knowledge-base products, X = dropout(KB) Wx + bx, H1 = act(X (diag(y) W1a + W1b) + b1), I2 = H1 W2 + b2,
+// and the attention logits: KB -> X -> H1 -> I2 -> logits in one launch (macx_chain_h2.hip.h)
+int CellRun::read_products_chain(int i, int pre) const {
+  const ChainFwdP c = make_chain_fwd(o, s, dp, P, in, saved, L, keep, i, i, pre);
+  ChainProbe& cp = *chain_probe();
+  if (cp.on && cp.n < 64) {      // the kernel's own start / stop timestamps into the probe's event pair
+    CK(chain_fwd_launch(c, st, cp.ev[2 * cp.n], cp.ev[2 * cp.n + 1]));
+    ++cp.n;
+  } else {
+    CK(chain_fwd_launch(c, st));
+  }
+  return MACX_OK;
+}
 
-  // ---- control unit when it is recurrent (mac_cell.py:141-151, configs/args1.txt)
-  if ((units & U_CONTROL) && o->control_feed_prev) {
-    const float* prev = o->control_feed_prev_att ? controls + (size_t)i * Bd
-                                                 : (i == 0 ? controls : saved + L.cc + (size_t)(i - 1) * Bd);
-    float* cc_i = saved + L.cc + (size_t)i * Bd;
-    const bool two = o->control_cont_act != MACX_ACT_NON;       // ops.linear stacks a second layer (ops.py:325-328)
-    float* lin1 = two ? saved + L.cc_h + (size_t)i * Bd : cc_i;
-    LinP l = lin_basic(prev, d, d, B, saved + L.wc_p, P->contControl_b, d, o->control_cont_act, lin1, d);
-    if (o->control_feed_inputs) { l.seg[1] = LinSeg{saved + L.cI + (size_t)i * Bd, d, d, 0}; l.Ktot = 2 * d; }
-    CK(small_linear_launch(l, 1, st));
-    if (two) {
-      LinP l2 = lin_basic(lin1, d, d, B, saved + L.wc2_p, P->contControl2_b, d, MACX_ACT_NON, cc_i, d);
-      CK(small_linear_launch(l2, 1, st));
+// ... on H2 operands, one launch per product (macx_gemm_h2.hip.h): the knowledge base enters the format (through its dropout site)
+// once per step -- once per run without read dropout -- and X, H1, I2 never exist as fp32 tensors
+int CellRun::read_products_h2(int i) const {
+  const int R = B * N;
+  const H2View hX = h2_view(saved + L.X + (size_t)i * L.act_stride, R, d), hH1 = h2_view(saved + L.H1 + (size_t)i * L.act_stride, R, d),
+               hI2 = h2_view(saved + L.I2 + (size_t)i * L.act_stride, R, d);
+  const H2View hKB = h2_view(saved + L.KBd + (rdrop ? (size_t)i * L.act_stride : 0), R, d);
+  uint8_t* att_bytes = rdrop ? reinterpret_cast<uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
+  if (rdrop || i == 0) {
+    H2FromP f;
+    memset(&f, 0, sizeof(f));
+    f.src = in->knowledgeBase; f.B = B; f.N = N; f.C = d; f.out = hKB;
+    f.ldrop = dlog_of(s);
+    f.first = (uint32_t)((size_t)s->b0 * N * f.ldrop);
+    f.thr24 = 1u << 24; f.inv_keep = 1.0f; f.thr24_2 = 1u << 24;
+    if (rdrop) {
+      const DropSpec dk = make_drop(dp->keep_read, dp, SITE_READ_KB, i);
+      const DropSpec da = make_drop(dp->keep_read, dp, SITE_READ_ATT, i);
+      f.key = dk.key; f.thr24 = dk.thr24; f.inv_keep = dk.inv_keep;
+      f.bits = reinterpret_cast<uint32_t*>(saved + L.kb_bits + (size_t)i * L.bits_stride);
+      f.key2 = da.key; f.thr24_2 = da.thr24; f.bytes2 = att_bytes;
+      f.word = dp->mask_word;
     }
-    CtrlP c;
-    c.B = B; c.S = s->S; c.d = d;
-    c.cc = cc_i; c.z_cc = 0;
-    c.words = in->words; c.lengths = in->questionLengths;
-    c.w = P->ctrlLogits_w; c.bias = P->ctrlLogits_b;
-    c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * s->S; c.z_att = 0;
-    c.control = controls + (size_t)(i + 1) * Bd; c.z_ctl = 0;
-    hipLaunchKernelGGL(control_attend_kernel, dim3(B, 1), dim3(256), 0, st, c);
-    CK(hipGetLastError());
+    CK(h2_from_f32(f, st));
   }
-  // ---- read unit (mac_cell.py:209-277)
-  if (units & U_READ) {
-  // memory dropout (mac_cell.py:214-217) then the read-dropout of ops.mul's y input (ops.py:679)
-  const DropSpec dm = o->memory_variational_dropout ? make_drop(dp->keep_memory, dp, SITE_MEM_VAR, 0)
-                                                    : make_drop(dp->keep_memory, dp, SITE_MEM, i);
-  const DropSpec dry = make_drop(dp->keep_read, dp, SITE_READ_MEM, i);
-  // (md_fused: macx_cell_begin left step 0's dropped memory behind, the previous step's write unit every later one's)
-  if (!md_fused) {
-    hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, m_prev, B, d, (uint32_t)s->b0, dm, dry, md, dlog_of(s));
-    CK(hipGetLastError());
-  }
-  if (!((pre & 4) && h2_mode() && use_chain(d, s->N))) {     // (pre & 4: the chain launch's filler workgroups compute y, ChainPreP)
-    LinP l = lin_basic(md, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, y, d);
-    CK(small_linear_launch(l, 1, st));
-  }
-  // keep bits of the two [B,N,d] read-dropout sites of this step (ops.py:678 and ops.py:312 via :142)
-  const bool rdrop = dp->keep_read < 1.0f;
-  const size_t nwords = (size_t)B * N * d / 32;
-  uint32_t* kb_bits = reinterpret_cast<uint32_t*>(saved + L.kb_bits + (size_t)i * L.bits_stride);
+  GemmH2P g = h2_gemm_params();
+  // X = dropout(KB) Wx + bx  (ops.py:678,688)
+  g.A = hKB;
+  g.Wh = reinterpret_cast<const char*>(saved + L.wx_p); g.w_exp = reinterpret_cast<const int*>(saved + L.wx_p) + dd;
+  g.out = hX; g.bias = P->projX_b; g.act = MACX_ACT_NON;
+  if (rdrop || L.act_stride != 0 || i == 0) CK((kb_gemm_h2_launch<B_PLAIN, E_BIAS_ACT, false>(g, st)));
+  // H1 = act( X (diag(y) W1a + W1b) + b1 )   (ops.py:703,718; mac_cell.py:237)
+  g.A = hX; g.Wh = nullptr; g.w_exp = nullptr;
+  g.Wt = saved + L.w1a_p; g.Wt2 = saved + L.w1b_p; g.w_max = saved + L.wmax + 2; g.y = saved + L.y + (size_t)i * Bd; g.ldy = d;
+  g.out = hH1; g.bias = P->memKbProj_b; g.act = o->read_mem_act;
+  CK((kb_gemm_h2_launch<B_YMIX_ROW, E_BIAS_ACT, false>(g, st)));
+  // I2 = H1 W2 + b2 ; logits = dropout(act(I2 * c)) . w_k   (ops.py:326; mac_cell.py:248,262,266)
+  g.A = hH1; g.Wt = nullptr; g.Wt2 = nullptr; g.y = nullptr;
+  g.Wh = reinterpret_cast<const char*>(saved + L.w2_p); g.w_exp = reinterpret_cast<const int*>(saved + L.w2_p) + dd;
+  g.out = hI2; g.bias = P->memKbProj2_b; g.act = o->read_ctrl_act;
+  g.cvec = controls() + (size_t)(i + 1) * Bd; g.wvec = P->kbLogits_w; g.logit_part = saved + L.logit_part;
+  g.e_bytes = att_bytes;
+  CK((kb_gemm_h2_launch<B_PLAIN, E_I2_LOGIT, false>(g, st)));
+  return MACX_OK;
+}
+
+// ... on fp32 operands (the split and native kernel families)
+int CellRun::read_products_f32(int i) const {
   uint32_t* att_bits = reinterpret_cast<uint32_t*>(saved + L.att_bits + (size_t)i * L.bits_stride);
   float* KBd = saved + L.KBd + (size_t)i * L.act_stride;
-  if (h2_mode()) {
-    // the same three products on H2 operands (macx_gemm_h2.hip.h): the knowledge base enters the format (through its
-    // dropout site) once per step -- once per run without read dropout -- and X, H1, I2 never exist as fp32 tensors
-    const int R = B * N, CB = d / 128;
-    const H2View hX = h2_view(X, R, d), hH1 = h2_view(H1, R, d), hI2 = h2_view(I2, R, d);
-    const H2View hKB = h2_view(rdrop ? KBd : saved + L.KBd, R, d);
-    uint8_t* att_bytes = rdrop ? reinterpret_cast<uint8_t*>(att_bits) : nullptr;
-    if (use_chain(d, s->N)) {
-      // KB -> X -> H1 -> I2 -> logits in one launch (macx_chain_h2.hip.h)
-      const ChainFwdP c = make_chain_fwd(o, s, dp, P, in, saved, L, keep, i, i, pre);
-      ChainProbe& cp = *chain_probe();
-      if (cp.on && cp.n < 64) {      // the kernel's own start / stop timestamps into the probe's event pair
-        CK(chain_fwd_launch(c, st, cp.ev[2 * cp.n], cp.ev[2 * cp.n + 1]));
-        ++cp.n;
-      } else {
-        CK(chain_fwd_launch(c, st));
-      }
-    } else {
-    if (rdrop || i == 0) {
-      H2FromP f;
-      memset(&f, 0, sizeof(f));
-      f.src = in->knowledgeBase; f.B = B; f.N = N; f.C = d; f.out = hKB;
-      f.ldrop = dlog_of(s);
-      f.first = (uint32_t)((size_t)s->b0 * N * f.ldrop);
-      f.thr24 = 1u << 24; f.inv_keep = 1.0f; f.thr24_2 = 1u << 24;
-      if (rdrop) {
-        const DropSpec dk = make_drop(dp->keep_read, dp, SITE_READ_KB, i);
-        const DropSpec da = make_drop(dp->keep_read, dp, SITE_READ_ATT, i);
-        f.key = dk.key; f.thr24 = dk.thr24; f.inv_keep = dk.inv_keep; f.bits = kb_bits;
-        f.key2 = da.key; f.thr24_2 = da.thr24; f.bytes2 = att_bytes;
-        f.word = dp->mask_word;
-      }
-      CK(h2_from_f32(f, st));
-    }
-    GemmH2P g;
-    memset(&g, 0, sizeof(g));
-    g.B = B; g.N = N; g.K = d; g.Nout = d;
-    g.dbg = kb_gemm_dbg() & (1 | 2 | 4 | 8 | 16 | 32 | 64 | 128);      // phase-timing knobs (results are wrong under a non-zero mask)
-    g.e_inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-    // X = dropout(KB) Wx + bx  (ops.py:678,688)
-    g.A = hKB;
-    g.Wh = reinterpret_cast<const char*>(saved + L.wx_p); g.w_exp = reinterpret_cast<const int*>(saved + L.wx_p) + (size_t)d * d;
-    g.out = hX; g.bias = P->projX_b; g.act = MACX_ACT_NON;
-    if (rdrop || L.act_stride != 0 || i == 0) CK((kb_gemm_h2_launch<B_PLAIN, E_BIAS_ACT, false>(g, st)));
-    // H1 = act( X (diag(y) W1a + W1b) + b1 )   (ops.py:703,718; mac_cell.py:237)
-    g.A = hX; g.Wh = nullptr; g.w_exp = nullptr;
-    g.Wt = saved + L.w1a_p; g.Wt2 = saved + L.w1b_p; g.w_max = saved + L.wmax + 2; g.y = y; g.ldy = d;
-    g.out = hH1; g.bias = P->memKbProj_b; g.act = o->read_mem_act;
-    CK((kb_gemm_h2_launch<B_YMIX_ROW, E_BIAS_ACT, false>(g, st)));
-    // I2 = H1 W2 + b2 ; logits = dropout(act(I2 * c)) . w_k   (ops.py:326; mac_cell.py:248,262,266)
-    g.A = hH1; g.Wt = nullptr; g.Wt2 = nullptr; g.y = nullptr;
-    g.Wh = reinterpret_cast<const char*>(saved + L.w2_p); g.w_exp = reinterpret_cast<const int*>(saved + L.w2_p) + (size_t)d * d;
-    g.out = hI2; g.bias = P->memKbProj2_b; g.act = o->read_ctrl_act;
-    g.cvec = c_i; g.wvec = P->kbLogits_w; g.logit_part = saved + L.logit_part;
-    g.e_bytes = att_bytes;
-    CK((kb_gemm_h2_launch<B_PLAIN, E_I2_LOGIT, false>(g, st)));
-    }
-    (void)CB;
-  } else {
+  float* X = saved + L.X + (size_t)i * L.act_stride;
+  float* H1 = saved + L.H1 + (size_t)i * L.act_stride;
   if (rdrop) {
     const uint32_t first = (uint32_t)((size_t)s->b0 * N * d);
     const DropSpec dk = make_drop(dp->keep_read, dp, SITE_READ_KB, i);
     const DropSpec da = make_drop(dp->keep_read, dp, SITE_READ_ATT, i);     // same keep probability, own stream
     hipLaunchKernelGGL(kb_dropout_kernel, dim3(2048), dim3(256), 0, st, in->knowledgeBase, (size_t)B * N * d / 4, dk.key, dk.thr24,
-                       dk.inv_keep, first, KBd, kb_bits, da.key, att_bits, dp->mask_word);
+                       dk.inv_keep, first, KBd, reinterpret_cast<uint32_t*>(saved + L.kb_bits + (size_t)i * L.bits_stride), da.key,
+                       att_bits, dp->mask_word);
     CK(hipGetLastError());
   }
   GemmP g;
@@ -1025,38 +1062,63 @@ int cell_step_impl(const macx_opts* o, const macx_shapes* s, const macx_dropout*
   if (rdrop || L.act_stride != 0 || i == 0) CK((kb_gemm<A_PLAIN, B_PLAIN, E_BIAS_ACT, false>(g, st)));
   // H1 = act( concat([X*y, X]) W1 + b1 ) = act( X (diag(y) W1a + W1b) + b1 )   (ops.py:703,718; mac_cell.py:237)
   g.A = X;
-  g.Wp = saved + L.w1a_p; g.Wp2 = saved + L.w1b_p; g.y = y; g.ldy = d;
+  g.Wp = saved + L.w1a_p; g.Wp2 = saved + L.w1b_p; g.y = saved + L.y + (size_t)i * Bd; g.ldy = d;
   g.out = H1; g.bias = P->memKbProj_b; g.act = o->read_mem_act;
   CK((kb_gemm<A_PLAIN, B_YMIX_ROW, E_BIAS_ACT, false>(g, st)));
   // I2 = H1 W2 + b2 ; logits = dropout(act(I2 * c)) . w_k   (ops.py:326; mac_cell.py:248,262,266)
   g.A = H1; g.Wp = saved + L.w2_p; g.Wp2 = nullptr; g.y = nullptr;
-  g.out = I2; g.bias = P->memKbProj2_b; g.act = o->read_ctrl_act;
-  g.cvec = c_i; g.wvec = P->kbLogits_w;
+  g.out = saved + L.I2 + (size_t)i * L.act_stride; g.bias = P->memKbProj2_b; g.act = o->read_ctrl_act;
+  g.cvec = controls() + (size_t)(i + 1) * Bd; g.wvec = P->kbLogits_w;
   g.logit_part = saved + L.logit_part;
   g.e_bits = rdrop ? att_bits : nullptr;
   CK((kb_gemm<A_PLAIN, B_PLAIN, E_I2_LOGIT, false>(g, st)));
+  return MACX_OK;
+}
+
+// the read unit (mac_cell.py:209-277).  md_fused: the step's dropped memory is there already (macx_cell_begin left step 0's, the
+// previous step's write unit every later one's)
+int CellRun::read_step(int i, int pre, bool md_fused) const {
+  float* md = saved + L.md + (size_t)i * Bd;
+  if (!md_fused) {
+    // memory dropout (mac_cell.py:214-217) then the read-dropout of ops.mul's y input (ops.py:679)
+    const DropSpec dm = o->memory_variational_dropout ? make_drop(dp->keep_memory, dp, SITE_MEM_VAR, 0)
+                                                        : make_drop(dp->keep_memory, dp, SITE_MEM, i);
+    const DropSpec dry = make_drop(dp->keep_read, dp, SITE_READ_MEM, i);
+    hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)(memories() + (size_t)i * Bd), B, d,
+                       (uint32_t)s->b0, dm, dry, md, dlog_of(s));
+    CK(hipGetLastError());
   }
+  if (!((pre & PRE_YLIN) && chain)) {
+    LinP l = lin_basic(md, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, saved + L.y + (size_t)i * Bd, d);
+    CK(small_linear_launch(l, 1, st));
+  }
+  CKI(chain ? read_products_chain(i, pre) : h2 ? read_products_h2(i) : read_products_f32(i));
   // attention over the knowledge base + summary (mac_cell.py:266-275)
-  {
-    KbAttP a;
-    a.B = B; a.N = N; a.d = d; a.nparts = use_chain(d, s->N) ? 1 : d / (16 * kb_gemm_nw());
-    a.logit_part = saved + L.logit_part; a.bias = P->kbLogits_b;
-    a.kb = in->knowledgeBase;
-    a.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
-    a.info = info_raw;
-    hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, st, a);
-    CK(hipGetLastError());
-  }
-  if (pre & 8) return MACX_OK;      // the write unit: on the next chain launch's filler workgroups (ChainPreP::wlin)
-  }   // U_READ
-  if (!(units & U_WRITE)) return MACX_OK;
-  // write dropout (mac_cell.py:461-463); self.infos keeps the dropped value (mac_cell.py:474)
-  if (wdrop) {
+  KbAttP a;
+  a.B = B; a.N = N; a.d = d; a.nparts = chain ? 1 : d / (16 * kb_gemm_nw());
+  a.logit_part = saved + L.logit_part; a.bias = P->kbLogits_b;
+  a.kb = in->knowledgeBase;
+  a.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
+  a.info = info_raw(i);
+  hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, st, a);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// the write unit (mac_cell.py:305-375), writeInputs = BOTH: act(concat([memory, info (, selfSmry)]) W + b).  md_fused: its linear
+// also leaves the next step's dropped memory (mac_cell.py:214-217 and ops.py:679 ride the epilogue)
+int CellRun::write_step(int i, bool md_fused) const {
+  const float* c_i = controls() + (size_t)(i + 1) * Bd;
+  const float* m_prev = memories() + (size_t)i * Bd;
+  float* m_new = memories() + (size_t)(i + 1) * Bd;
+  float* info = saved + L.seg[MACX_SEG_INFOS] + (size_t)i * Bd;
+  // write dropout (mac_cell.py:461-463)
+  if (dp->keep_write < 1.0f) {
     const DropSpec dw = make_drop(dp->keep_write, dp, SITE_WRITE_INFO, i);
-    hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)info_raw, B, d, (uint32_t)s->b0, dw, no_drop(), info, dlog_of(s));
+    hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)info_raw(i), B, d, (uint32_t)s->b0, dw, no_drop(), info,
+                       dlog_of(s));
     CK(hipGetLastError());
   }
-  // ---- write unit (mac_cell.py:305-375), writeInputs = BOTH: act(concat([memory, info (, selfSmry)]) W + b)
   float* self_smry = nullptr;
   if (o->write_self_att) {
     // mac_cell.py:316-330.  selfControl = contControl (CONT) or the new control; histories hold the
@@ -1068,29 +1130,36 @@ int cell_step_impl(const macx_opts* o, const macx_shapes* s, const macx_dropout*
     self_smry = saved + L.self_smry + (size_t)i * Bd;
     SelfAttP q;
     q.B = B; q.d = d; q.nh = i + 1;
-    q.sc = sc; q.C = controls; q.M = memories; q.w = P->selfLogits_w; q.bias = P->selfLogits_b;
-    q.att = saved + L.seg[MACX_SEG_ATT_SELF] + (size_t)i * B * s->p; q.ld_att = s->p;
+    q.sc = sc; q.C = controls(); q.M = memories(); q.w = P->selfLogits_w; q.bias = P->selfLogits_b;
+    q.att = saved + L.seg[MACX_SEG_ATT_SELF] + (size_t)i * B * p; q.ld_att = p;
     q.smry = self_smry;
     hipLaunchKernelGGL(self_attend_kernel, dim3(B), dim3(256), 0, st, q);
     CK(hipGetLastError());
   }
-  {
-    float* wout = o->write_gate ? saved + L.mnew + (size_t)i * Bd : m_new;
-    // (md_fused: the new memory is the next step's read-unit input: its two dropouts, mac_cell.py:214-217 and ops.py:679, ride the epilogue)
-    LinP l = make_write_lin(o, s, dp, P, saved, L, i, info, wout, md_fused && i + 1 < s->p);
-    if (self_smry) { l.seg[2] = LinSeg{self_smry, d, d, 0}; l.Ktot = 3 * d; }
-    CK(small_linear_launch(l, 1, st));
-    if (o->write_gate) {
-      // z = sigmoid(control Wg + bg + gateBias); m = newMemory * z + memory * (1 - z)   (mac_cell.py:358-367)
-      float* z = saved + L.seg[MACX_SEG_ATT_GATE] + (size_t)i * Bd;
-      LinP gl = lin_basic(c_i, d, d, B, saved + L.wg_p, P->gate_b, d, MACX_ACT_SIGMOID, z, d);
-      gl.bias_const = o->write_gate_bias;
-      CK(small_linear_launch(gl, 1, st));
-      hipLaunchKernelGGL(gate_mix_kernel, dim3(64), dim3(256), 0, st, (const float*)wout, (const float*)z, m_prev, Bd, m_new);
-      CK(hipGetLastError());
-    }
+  float* wout = o->write_gate ? saved + L.mnew + (size_t)i * Bd : m_new;
+  LinP l = make_write_lin(o, s, dp, P, saved, L, i, info, wout, md_fused && i + 1 < p);
+  if (self_smry) { l.seg[2] = LinSeg{self_smry, d, d, 0}; l.Ktot = 3 * d; }
+  CK(small_linear_launch(l, 1, st));
+  if (o->write_gate) {
+    // z = sigmoid(control Wg + bg + gateBias); m = newMemory * z + memory * (1 - z)   (mac_cell.py:358-367)
+    float* z = saved + L.seg[MACX_SEG_ATT_GATE] + (size_t)i * Bd;
+    LinP gl = lin_basic(c_i, d, d, B, saved + L.wg_p, P->gate_b, d, MACX_ACT_SIGMOID, z, d);
+    gl.bias_const = o->write_gate_bias;
+    CK(small_linear_launch(gl, 1, st));
+    hipLaunchKernelGGL(gate_mix_kernel, dim3(64), dim3(256), 0, st, (const float*)wout, (const float*)z, m_prev, Bd, m_new);
+    CK(hipGetLastError());
   }
   return MACX_OK;
+}
+
+// step i of the cell; pre: what the chain launches' filler workgroups take over (PRE_*)
+int CellRun::cell_step(int i, int pre) const {
+  // without a gate the write unit's linear also writes the next step's dropped memory
+  const bool md_fused = !o->write_gate;
+  if (o->control_feed_prev) CKI(control_step(i));
+  CKI(read_step(i, pre, md_fused));
+  if (pre & PRE_WRITE_NEXT) return MACX_OK;
+  return write_step(i, md_fused);
 }
 }  // namespace
 
@@ -1099,7 +1168,12 @@ int macx_cell_step(const macx_opts* o, const macx_shapes* s, const macx_dropout*
                    int keep, int step, void* stream) {
   ModeScope ms(o);
   (void)ws; (void)ws_floats;
-  return cell_step_impl(o, s, dp, P, in, saved, saved_floats, keep, step, U_ALL, stream);
+  CKI(check_impl(o, s));
+  if (!dp || !P || !in || !saved) return MACX_EINVAL;
+  if (step < 0 || step >= s->p) return MACX_EINVAL;
+  const CellRun r(o, s, dp, P, in, saved, keep, stream);
+  if (saved_floats < r.L.total) return MACX_ESMALL;
+  return r.cell_step(step, 0);
 }
 
 int macx_cell_forward(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
@@ -1107,19 +1181,18 @@ int macx_cell_forward(const macx_opts* o, const macx_shapes* s, const macx_dropo
                       int keep, void* stream) {
   CKI(macx_cell_begin(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, keep, stream));
   ModeScope ms(o);
+  const CellRun r(o, s, dp, P, in, saved, keep, stream);
   // a training run's steps are sequenced here: stage 0 of the read unit's chain for step i + 1 (state-independent) rides the
   // launch of step i on its idle CUs (ChainPreP).  The step-wise entry point makes no assumption about what ran before it.
-  const bool fill = h2_mode() && use_chain(s->d, s->N) && s->p <= 32 && s->B <= 128 && pre_fill_count(s->d, (size_t)s->B * s->N, device_cu_count()) > 0;
+  const bool fill = r.chain && s->p <= 32 && s->B <= 128 && pre_fill_count(s->d, (size_t)s->B * s->N, device_cu_count()) > 0;
   const bool pre = fill && keep && dp && dp->keep_read < 1.0f;
   // the write unit's linear too, where it is one launch: the plain write unit of the published flag files
   const bool tail = fill && s->B <= 128 && !o->write_gate && !o->write_self_att && !o->control_feed_prev && dp && !(dp->keep_write < 1.0f) &&
                     tune_get(MACX_TUNE_PRE_FILL, 1) >= 1 && tune_get(MACX_TUNE_PRE_FILL, 1) != 2;
   for (int i = 0; i < s->p; ++i) {
-    // bit 0: stage 0 was done by the previous launch; 1: this launch does the next step's; 2: this launch's fillers compute y;
-    // 3: this step's write unit is left to the next launch; 4: this launch's fillers run the previous step's
-    const int flags = (pre && i > 0 ? 1 : 0) | (pre && i + 1 < s->p ? 2 : 0) | (fill ? 4 : 0) | (tail && i + 1 < s->p ? 8 : 0) |
-                      (tail && i > 0 ? 16 : 0);
-    CKI(cell_step_impl(o, s, dp, P, in, saved, saved_floats, keep, i, U_ALL, stream, flags));
+    const int flags = (pre && i > 0 ? PRE_STAGE0_DONE : 0) | (pre && i + 1 < s->p ? PRE_STAGE0_NEXT : 0) | (fill ? PRE_YLIN : 0) |
+                      (tail && i + 1 < s->p ? PRE_WRITE_NEXT : 0) | (tail && i > 0 ? PRE_WRITE_PREV : 0);
+    CKI(r.cell_step(i, flags));
   }
   return MACX_OK;
 }
@@ -1129,89 +1202,77 @@ int macx_cell_forward(const macx_opts* o, const macx_shapes* s, const macx_dropo
 // on the same buffers).  A data-parallel host launches the all-reduce of every gradient phase 1 completes on a side stream
 // while phase 2 -- the last ~10 % of the backward pass -- still runs (macx.dp.OverlappedBuckets).
 namespace {
-// gradients that cross a unit's boundary when one unit is differentiated on its own (macx_read_bwd / macx_write_bwd)
-struct UnitGrads {
-  const float* d_info_in = nullptr;     // read: dL/d(info), [B,d]
-  float* d_memory = nullptr;            // out: dL/d(memory input of the unit)
-  float* d_control = nullptr;           // out: dL/d(control input of the unit)
-  float* d_info_out = nullptr;          // write: dL/d(info) (before the write dropout)
+// a [B, ld] slab per step: step i's at base + i * step
+struct StepSlab {
+  const float* base; int ld; size_t step;
+  const float* at(int i) const { return base + (size_t)i * step; }
 };
 
-// the backward pass's weight packs into `wT` (offsets: BwdLayout's first region), appended to the caller's pack list
-int add_bwd_packs(Packer& pk, const macx_opts* o, const macx_shapes* s, const macx_params* P, float* wT, const BwdLayout& W,
-                  const float* saved, const SavedLayout& L, int units, hipStream_t st) {
-  const int d = s->d, p = s->p;
-  const size_t dd = (size_t)d * d;
-  const int win = write_in_dim(o, d);
-  const int nU = o->control_input_unshared ? p : 1;
+// step i's H2 operands of the read unit's backward products
+struct ReadH2 { H2View X, H1, I2, dI2, dI1, dX; };
 
-    const bool fold = h2_mode() && use_chain(d, s->N);        // (these packs ride the forward pass's pack launch: same rule as there)
-    auto mx = [&](int k) { return wmax_ref(saved, L.wmax, k, fold); };
-    if (units & U_READ) {
-      pk.add(P->projX_W, 1, d, d, d, wT + W.wxT_p, -1, -1, wfmt_plain(), mx(0).src, nullptr, mx(0).n, mx(0).out);            // Wx^T
-      if (use_chain(d, s->N)) {      // the chain kernel applies y to the accumulators: plain H2 weights
-        pk.add(P->memKbProj_W, 1, d, d, d, wT + W.w1aT_p, -1, -1, 3, mx(2).src, nullptr, mx(2).n, mx(2).out);       // W1a^T
-        pk.add(P->memKbProj_W + dd, 1, d, d, d, wT + W.w1bT_p, -1, -1, 3, mx(3).src, nullptr, mx(3).n, mx(3).out);  // W1b^T
-      } else {
-        pk.add(P->memKbProj_W, 1, d, d, d, wT + W.w1aT_p, -1, -1, wfmt_ymix());       // W1a^T
-        pk.add(P->memKbProj_W + dd, 1, d, d, d, wT + W.w1bT_p, -1, -1, wfmt_ymix());  // W1b^T
-      }
-      pk.add(P->memKbProj2_W, 1, d, d, d, wT + W.w2T_p, -1, -1, wfmt_plain(), mx(1).src, nullptr, mx(1).n, mx(1).out);       // W2^T
-      pk.add(P->projY_W, 1, d, d, d, wT + W.wyT);              // Wy^T
-    }
-    if (units & U_WRITE) {
-      pk.add(P->newMemory_W, 1, d, d, win, wT + W.wmT);        // Wm^T: [d] -> [win]
-      if (o->write_gate) pk.add(P->gate_W, 1, d, d, d, wT + W.wgT);
-      if (o->write_self_att) pk.add(P->selfCtrl_W, 1, d, d, d, wT + W.wscT);
-    }
-    if (units & U_CONTROL) pk.add(P->qInput_W, 1, d, d, d, wT + W.wqT);
-    if ((units & U_CONTROL) && o->control_feed_prev) {
-      pk.add(P->contControl_W, 1, d, d, o->control_feed_inputs ? 2 * d : d, wT + W.wccT);   // Wc^T: [d] -> [d or 2d]
-      if (o->control_cont_act != MACX_ACT_NON) pk.add(P->contControl2_W, 1, d, d, d, wT + W.wcc2T);
-    }
-    for (int i = 0; i < ((units & U_CONTROL) ? nU : 0); ++i) {
-      if (pk.n == PACK_MAX) CK(pk.run(st));
-      pk.add(P->qInputU_W + (size_t)i * dd, 1, d, d, d, wT + W.wqUT + (size_t)i * dd);
-    }
+// a backward call: the forward run's `saved` (only read here), the workspace, the gradients and the batches that collect the
+// call's small contractions
+struct CellBwd : CellRun {
+  float* ws;
+  BwdLayout W;
+  const float* wT;              // the backward pass's weight packs, left in `saved` by the forward pass's pack launch
+  float* DM;                    // [p + 1][B,d] dL/dm_i
+  float* DC;                    // [p + 1][B,d] dL/dc_i
+  float* dwlin_all;             // [p][B,d] dL/d(newMemory linear output); with writeMemAct = NON and no gate it IS dL/dm_{1..p}
+  const macx_param_grads* GP; const macx_input_grads* GI;
+  int win, nrb;
+  StepSlab dinfo;               // dL/d(info_i), the read unit's output (ahead of the write dropout)
+  // the recurrent control unit differentiates through dL/dc_i inside iteration i; otherwise every step's dc / db_k partials are
+  // reduced in one launch after the loop
+  bool dc_in_loop = false;
+  DkbFillPlan dkb_plan{0, 0, 0};
+  ChainDkbP dkb_q;
+  RowsumBatch rs;               // bias-gradient row sums of this call: one launch at the end of each phase
+  SmallWgradBatch wb;           // weight gradients of the [B,d] linears: one launch at the end of phase 1
+  CellBwd(const macx_opts* o_, const macx_shapes* s_, const macx_dropout* dp_, const macx_params* P_, const macx_inputs* in_,
+          const float* saved_, float* ws_, const macx_param_grads* GP_, const macx_input_grads* GI_, void* stream)
+      : CellRun(o_, s_, dp_, P_, in_, const_cast<float*>(saved_), 1, stream), ws(ws_), W(make_bwd(o_, s_)), wT(saved_ + L.bwd_packs),
+        DM(ws_ + W.DM), DC(ws_ + W.DC), dwlin_all((o_->write_mem_act == MACX_ACT_NON && !o_->write_gate) ? DM + Bd : ws_ + W.dwlin),
+        GP(GP_), GI(GI_), win(write_in_dim(o_, d)), nrb(nrb_of(N, B, d)), wb(ws_ + W.small_slab, W.small_slab_stride) {
+    dinfo = dp->keep_write < 1.0f ? StepSlab{ws + W.dinfo, d, Bd} : StepSlab{ws + W.dwin + d, win, (size_t)B * win};
+    memset(&dkb_q, 0, sizeof(dkb_q));
+  }
+  int check_bwd_buffers(size_t saved_floats, size_t ws_floats, int phase) const;
+  int init_state_grads(const float* d_memory, const float* d_control);
+  void plan_dkb_fill();
+  // the units of step i
+  int write_unit_bwd(int i);
+  int read_bwd_chain(int i, const ReadH2& v);
+  int read_bwd_h2(int i, const ReadH2& v);
+  int dkb_merged_h2();
+  int read_bwd_f32(int i);
+  int read_unit_bwd(int i);
+  int dy_linear_bwd(int i, bool with_write);
+  int control_step_bwd(int i);
+  // after the step loop
+  int read_dc_reduce_all();
+  int control_bwd_tail();
+  int gate_wgrads();
+  int control_inputs_bwd();
+  int initial_state_bwd();
+  int read_linear_wgrads();
+  int write_linear_wgrads();
+  int read_weight_contractions();
+};
+
+// the buffers of a backward call (checked before anything is launched)
+int CellBwd::check_bwd_buffers(size_t saved_floats, size_t ws_floats, int phase) const {
+  if (saved_floats < L.total || ws_floats < W.total) return MACX_ESMALL;
+  // a run is differentiated only if it kept its activations, and then it packed the backward pass's weights too
+  if (phase != 2 && !L.bwd_packs) return MACX_EINVAL;
   return MACX_OK;
 }
 
-int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
-                       const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
-                       const float* d_memory, const float* d_control, const macx_param_grads* GP,
-                       const macx_input_grads* GI, int phase, int units, const UnitGrads* ug, void* stream) {
-  if (phase < 0 || phase > 2) return MACX_EINVAL;
-  CKI(check_impl(o, s));
-  if (!dp || !P || !in || !saved || !ws || !GP || !GI) return MACX_EINVAL;
-  if ((units & U_READ) && !GI->knowledgeBase) return MACX_EINVAL;
-  if ((units & U_CONTROL) && (!GI->words || !GI->vecQuestions)) return MACX_EINVAL;
-  if (units != U_ALL && (!ug || s->p != 1)) return MACX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  RowsumBatch rs;                     // bias-gradient row sums of this call: one launch at the end of each phase
-  const SavedLayout L = make_saved(o, s, 1);
-  const BwdLayout W = make_bwd(o, s);
-  if (saved_floats < L.total || ws_floats < W.total) return MACX_ESMALL;
-  SmallWgradBatch wb(ws + W.small_slab, W.small_slab_stride);       // weight gradients of the [B,d] linears: one launch at the end of phase 1
-  const int B = s->B, N = s->N, d = s->d, p = s->p, S = s->S;
-  const size_t Bd = (size_t)B * d;
-  const size_t BNd = (size_t)B * N * d;
-  const size_t dd = (size_t)d * d;
-  const int win = write_in_dim(o, d);
-  const int nrb = nrb_of(N, B, d);
-  const bool rdrop = dp->keep_read < 1.0f;
-
-  if (phase != 2) {
-  // ---- weights in the layouts the backward kernels read: packed by the forward pass's pack launch into `saved`
-  //      (SavedLayout::bwd_packs; a run is differentiated only if it kept its activations, and then it packed these too)
-  if (!L.bwd_packs) return MACX_EINVAL;
-  const float* wT = saved + L.bwd_packs;
-
-  float* DM = ws + W.DM;
-  float* DC = ws + W.DC;
-  // dL/d(newMemory linear output) for all steps; with writeMemAct = NON it IS dL/dm_{1..p}
-  float* dwlin_all = (o->write_mem_act == MACX_ACT_NON && !o->write_gate) ? DM + Bd : ws + W.dwlin;
+// DM / DC: zeros, the incoming gradients in the last slabs
+int CellBwd::init_state_grads(const float* d_memory, const float* d_control) {
   if (DC == DM + (size_t)(p + 1) * Bd && !misaligned(d_memory) && !misaligned(d_control)) {
-    // (adjacent in the workspace: zeros and the incoming gradients in the last slabs in ONE launch)
+    // (adjacent in the workspace: one launch)
     hipLaunchKernelGGL(bwd_init_kernel, dim3(fill_grid(2 * (size_t)(p + 1) * Bd)), dim3(256), 0, st, DM, Bd, p, d_memory, d_control, 0);
     CK(hipGetLastError());
   } else {
@@ -1220,379 +1281,369 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     if (d_memory) CK(dev_copy(DM + (size_t)p * Bd, d_memory, Bd * sizeof(float), st));
     if (d_control) CK(dev_copy(DC + (size_t)p * Bd, d_control, Bd * sizeof(float), st));
   }
-  if ((units & U_CONTROL) && o->control_feed_prev) {
-    CK(dev_zero(GI->words, (size_t)B * S * d * sizeof(float), st));
-    CK(dev_zero(ws + W.dwc_part, Bd * sizeof(float), st));
-    CK(dev_zero(ws + W.dccx, (size_t)(p + 1) * Bd * sizeof(float), st));
-  }
+  return MACX_OK;
+}
 
-  const float* controls = saved + L.seg[MACX_SEG_CONTROLS];
-  const float* memories = saved + L.seg[MACX_SEG_MEMORIES];
-  const float* infos = saved + L.seg[MACX_SEG_INFOS];
-  const float* att_kb = saved + L.seg[MACX_SEG_ATT_KB];
-
-  // the recurrent control unit differentiates through dL/dc_i inside iteration i; otherwise every step's dc / db_k partials are
-  // reduced in one launch after the loop
-  const bool dc_in_loop = (units & U_CONTROL) && o->control_feed_prev;
-  // dKB of step i + 1 rides chain_bwd's launch of step i on the CUs that launch leaves idle (ChainDkbP, macx_chain_api.hip.h); what
-  // the fillers leave out and step 0 run in chain_dkb_rest_launch after the last step.  Off (njobs = 0): the merged dKB launch.
-  const DkbFillPlan dkb_plan = (units == U_ALL && h2_mode() && use_chain(d, s->N))
-                                   ? dkb_fill_plan(d, (size_t)B * N, N, p, device_cu_count()) : DkbFillPlan{0, 0, 0};
-  ChainDkbP dkb_q;
-  memset(&dkb_q, 0, sizeof(dkb_q));
-  if (dkb_plan.njobs) {
-    const bool wd = dp->keep_write < 1.0f;
-    dkb_q.njobs = dkb_plan.njobs; dkb_q.nfill = dkb_plan.nfill; dkb_q.nskip = dkb_plan.nskip; dkb_q.p = p;
-    dkb_q.dX = reinterpret_cast<const char*>(ws + W.dX); dkb_q.dx_step = W.act_floats * sizeof(float);
-    dkb_q.WxT = ChainW{reinterpret_cast<const char*>(wT + W.wxT_p), reinterpret_cast<const int*>(wT + W.wxT_p) + dd};
-    dkb_q.bits = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.kb_bits) : nullptr;
-    dkb_q.bits_step = L.bits_stride * sizeof(uint32_t);
-    dkb_q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-    dkb_q.att = att_kb; dkb_q.att_step = (size_t)B * N;
-    dkb_q.dinfo = wd ? ws + W.dinfo : ws + W.dwin + d; dkb_q.ld_dinfo = wd ? d : win; dkb_q.dinfo_step = wd ? Bd : (size_t)B * win;
-    dkb_q.out = GI->knowledgeBase;
-    dkb_q.dbg = (kb_gemm_dbg() >> 22) & 31;
+// dKB of step i + 1 rides chain_bwd's launch of step i on the CUs that launch leaves idle (ChainDkbP, macx_chain_api.hip.h); what
+// the fillers leave out and step 0 run in chain_dkb_rest_launch after the last step.  Off (njobs = 0): the merged dKB launch.
+void CellBwd::plan_dkb_fill() {
+  if (!chain) return;
+  dkb_plan = dkb_fill_plan(d, (size_t)B * N, N, p, device_cu_count());
+  if (!dkb_plan.njobs) return;
+  ChainDkbP& q = dkb_q;
+  q.njobs = dkb_plan.njobs; q.nfill = dkb_plan.nfill; q.nskip = dkb_plan.nskip; q.p = p;
+  q.dX = reinterpret_cast<const char*>(ws + W.dX); q.dx_step = W.act_floats * sizeof(float);
+  q.WxT = ChainW{reinterpret_cast<const char*>(wT + W.wxT_p), reinterpret_cast<const int*>(wT + W.wxT_p) + dd};
+  q.bits = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.kb_bits) : nullptr;
+  q.bits_step = L.bits_stride * sizeof(uint32_t);
+  q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
+  q.att = saved + L.seg[MACX_SEG_ATT_KB]; q.att_step = (size_t)B * N;
+  q.dinfo = dinfo.base; q.ld_dinfo = dinfo.ld; q.dinfo_step = dinfo.step;
+  q.out = GI->knowledgeBase;
+  q.dbg = (kb_gemm_dbg() >> 22) & 31;
 #ifdef MACX_FILL_PROF
-    dkb_q.prof = reinterpret_cast<uint32_t*>(const_cast<float*>(saved) + L.sync) + 48;
+  q.prof = reinterpret_cast<uint32_t*>(saved + L.sync) + 48;
 #endif
-  }
-  for (int i = p - 1; i >= 0; --i) {
-    const float* c_i = controls + (size_t)(i + 1) * Bd;
-    const float* X = saved + L.X + (size_t)i * L.act_stride;
-    const float* H1 = saved + L.H1 + (size_t)i * L.act_stride;
-    const float* I2 = saved + L.I2 + (size_t)i * L.act_stride;
-    const float* y = saved + L.y + (size_t)i * Bd;
-    const float* dm_i = DM + (size_t)(i + 1) * Bd;   // dL/d m_i, complete at this point
-    float* dm_prev = DM + (size_t)i * Bd;
-    float* dwlin = dwlin_all + (size_t)i * Bd;
-    float* dI2_i = ws + W.dI2 + (size_t)i * W.act_floats;
-    float* dX_i = ws + W.dX + (size_t)i * W.act_floats;
-    float* dwin = ws + W.dwin + (size_t)i * B * win;
+}
 
-    const float* dinfo = ug ? ug->d_info_in : nullptr;
-    int ld_dinfo = d;
-    if (units & U_WRITE) {
-    // ---- write unit backward
-    const float* dmnew = dm_i;              // gradient wrt the (post-activation) new memory
-    const float* mnew_out = memories + (size_t)(i + 1) * Bd;
-    if (o->write_gate) {
-      // m_i = mnew * z + m_{i-1} * (1 - z)
-      const float* z = saved + L.seg[MACX_SEG_ATT_GATE] + (size_t)i * Bd;
-      mnew_out = saved + L.mnew + (size_t)i * Bd;
-      float* dzpre = ws + W.dzpre + (size_t)i * Bd;
-      hipLaunchKernelGGL(gate_bwd_kernel, dim3(64), dim3(256), 0, st, dm_i, z, mnew_out, memories + (size_t)i * Bd, Bd,
-                         ws + W.tmpBd[2], ws + W.tmpBd[3], dzpre);
-      CK(hipGetLastError());
-      dmnew = ws + W.tmpBd[2];
-      // dL/dc_i += dzpre Wg^T
-      LinP gl = lin_basic(dzpre, d, d, B, wT + W.wgT, nullptr, d, MACX_ACT_NON, DC + (size_t)(i + 1) * Bd, d);
-      gl.addend = DC + (size_t)(i + 1) * Bd; gl.ld_add = d;
-      CK(small_linear_launch(gl, 1, st));
-    }
-    // dwlin = dmnew * act'(mnew) ; [dm_prev part | dinfo (| dselfSmry)] = dwlin Wm^T
-    if (o->write_mem_act != MACX_ACT_NON || o->write_gate) {
-      hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, dmnew, mnew_out, o->write_mem_act, Bd, dwlin);
-      CK(hipGetLastError());
-    }
-    {
-      LinP l = lin_basic(dwlin, d, d, B, wT + W.wmT, nullptr, win, MACX_ACT_NON, dwin, win);
-      CK(small_linear_launch(l, 1, st));
-    }
-    // d(info) through the write dropout (mac_cell.py:463); without write dropout it is a column view of dwin
-    dinfo = dwin + d;
-    ld_dinfo = win;
-    if (dp->keep_write < 1.0f) {
-      hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)dwin, win, d, B, d, (uint32_t)s->b0,
-                         make_drop(dp->keep_write, dp, SITE_WRITE_INFO, i), ws + W.dinfo + (size_t)i * Bd, dlog_of(s));
-      CK(hipGetLastError());
-      dinfo = ws + W.dinfo + (size_t)i * Bd;
-      ld_dinfo = d;
-    }
-
-    if (o->write_self_att) {
-      SelfAttBwdP q;
-      q.B = B; q.d = d; q.nh = i + 1;
-      q.dsmry = dwin + 2 * d; q.ld_ds = win;
-      q.sc = saved + L.sc + (size_t)i * Bd; q.C = controls; q.M = memories; q.w = P->selfLogits_w;
-      q.att = saved + L.seg[MACX_SEG_ATT_SELF] + (size_t)i * B * p; q.ld_att = p;
-      q.DMh = DM; q.DCh = DC;
-      q.dsc = ws + W.dsc + (size_t)i * Bd;
-      q.dw_part = ws + W.dws_part + (size_t)i * Bd;
-      q.db_part = ws + W.dbs_part + (size_t)i * B;
-      hipLaunchKernelGGL(self_attend_bwd_kernel, dim3(B), dim3(256), 0, st, q);
-      CK(hipGetLastError());
-    }
-    }   // U_WRITE
-    if (!(units & U_READ)) {
-      // the write unit alone: dL/d(memory) = dwin[:, :d] (+ dm (1 - z) under the gate), dL/d(info), dL/d(control) (the gate's)
-      const size_t pitch = (size_t)win * sizeof(float), wbytes = (size_t)d * sizeof(float);
-      CK(dev_copy2d(ug->d_memory, wbytes, dwin, pitch, wbytes, B, st));
-      if (o->write_gate) CK(axpy(ws + W.tmpBd[3], Bd, ug->d_memory, st));
-      CK(dev_copy2d(ug->d_info_out, wbytes, dinfo, (size_t)ld_dinfo * sizeof(float), wbytes, B, st));
-      CK(dev_copy(ug->d_control, DC + (size_t)(i + 1) * Bd, Bd * sizeof(float), st));
-      continue;
-    }
-
-    // ---- read unit backward
-    hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo, ld_dinfo, in->knowledgeBase, B, N, d,
-                       ws + W.da);
+// ---- backward: the units of step i
+// the write unit: dL/dm_i -> dwin = [dL/dm_{i-1} part | dL/d(info) (| dL/d(selfSmry))] and the gate's part of dL/dc_i; leaves
+// dL/d(info_i) at r.dinfo.at(i)
+int CellBwd::write_unit_bwd(int i) {
+  const float* dm_i = DM + (size_t)(i + 1) * Bd;   // dL/d m_i, complete at this point
+  float* dwlin = dwlin_all + (size_t)i * Bd;
+  float* dwin = ws + W.dwin + (size_t)i * B * win;
+  const float* dmnew = dm_i;              // gradient wrt the (post-activation) new memory
+  const float* mnew_out = memories() + (size_t)(i + 1) * Bd;
+  if (o->write_gate) {
+    // m_i = mnew * z + m_{i-1} * (1 - z)
+    const float* z = saved + L.seg[MACX_SEG_ATT_GATE] + (size_t)i * Bd;
+    mnew_out = saved + L.mnew + (size_t)i * Bd;
+    float* dzpre = ws + W.dzpre + (size_t)i * Bd;
+    hipLaunchKernelGGL(gate_bwd_kernel, dim3(64), dim3(256), 0, st, dm_i, z, mnew_out, memories() + (size_t)i * Bd, Bd,
+                       ws + W.tmpBd[2], ws + W.tmpBd[3], dzpre);
     CK(hipGetLastError());
-    if (h2_mode()) {
-      const int R = B * N, CB = d / 128;
-      const H2View hI2 = h2_view(I2, R, d), hH1 = h2_view(H1, R, d), hX = h2_view(X, R, d);
-      const H2View hdI2 = h2_view(dI2_i, R, d), hdI1 = h2_view(ws + W.dI1 + (size_t)i * W.dI1_stride, R, d), hdX = h2_view(dX_i, R, d);
-      const bool chain = use_chain(d, s->N);
-      if (!(chain && W.chain_sums)) {
-        ReadAttBwdH2P r;
-        r.dl = nullptr; r.no_out = chain ? 1 : 0;    // chain with tiny N: only dc / dw_k / db2 / db_k (dI2 comes from the chain kernel)
-        r.B = B; r.N = N; r.d = d;
-        r.att = att_kb + (size_t)i * B * N; r.da = ws + W.da; r.I2 = hI2; r.c = c_i; r.wk = P->kbLogits_w;
-        r.act = o->read_ctrl_act;
-        r.bytes = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
-        r.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-        r.dI2 = hdI2;
-        r.dc = DC + (size_t)(i + 1) * Bd;
-        r.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
-        r.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
-        r.dbk_part = ws + W.dbk_part + (size_t)i * B;
-        hipLaunchKernelGGL(read_att_bwd_h2_kernel, dim3(B, d / 128), dim3(RABH_THREADS), 0, st, r);
-        CK(hipGetLastError());
-      }
-      GemmH2P g;
-      memset(&g, 0, sizeof(g));
-      g.B = B; g.N = N; g.K = d; g.Nout = d;
-      g.dbg = kb_gemm_dbg() & (1 | 2 | 4 | 8 | 16 | 32 | 64 | 128);      // phase-timing knobs (results are wrong under a non-zero mask)
-      g.e_inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-      if (chain) {
-        // dl -> dI2 -> dI1 -> dX in one launch (macx_chain_h2.hip.h)
-        auto wref = [&](size_t off) { return ChainW{reinterpret_cast<const char*>(wT + off), reinterpret_cast<const int*>(wT + off) + dd}; };
-        ChainBwdP c;
-        memset(&c, 0, sizeof(c));
-        c.M = R; c.N = N; c.d = d;
-        c.dbg = (kb_gemm_dbg() >> 17) & 31;
-        c.att = att_kb + (size_t)i * B * N; c.da = ws + W.da;
-        c.I2 = hI2; c.c = c_i; c.wk = P->kbLogits_w; c.act2 = o->read_ctrl_act;
-        if (W.chain_sums) {
-          c.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
-          c.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
-          c.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; c.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
-        }
-        c.bytes2 = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
-        c.inv2 = rdrop ? 1.0f / dp->keep_read : 1.0f;
-        c.dI2 = hdI2;
-        c.W2T = wref(W.w2T_p); c.H1 = hH1; c.act1 = o->read_mem_act;
-        c.dI1 = hdI1; c.db1_part = ws + W.db1_part + (size_t)i * W.db_rows * d;
-        c.W1aT = wref(W.w1aT_p); c.W1bT = wref(W.w1bT_p); c.y = y;
-        c.dX = hdX; c.dbx_part = ws + W.dbx_part + (size_t)i * W.db_rows * d;
-        if (W.sb_deferred) { c.X = hX; c.dy_part = ws + W.dyc_part; }
-        if (dkb_plan.njobs && i + 1 < p) { c.dkb = dkb_q; c.dkb.step = i + 1; }
-        CK(chain_bwd_launch(c, st));
-        if (W.chain_sums && (dc_in_loop || (W.sb_deferred && !W.dy_in_linear))) {
-          // the per-tile partials of this step: dL/dc_i += read-unit part, db_k partials, dy_i (the next launch needs dy_i)
-          DcReduceP q;
-          memset(&q, 0, sizeof(q));
-          q.B = B; q.N = N; q.d = d;
-          q.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; q.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
-          q.dc = DC + (size_t)(i + 1) * Bd; q.dbk_part = ws + W.dbk_part + (size_t)i * B;
-          q.tile_shift = chain_tile_shift(d, (size_t)B * N);
-          if (W.sb_deferred && !W.dy_in_linear) { q.dy_part = ws + W.dyc_part; q.dy = ws + W.DY + (size_t)i * Bd; }
-          hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, 1), dim3(128), 0, st, q);
-          CK(hipGetLastError());
-        }
-      } else {
-      // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
-      g.A = hdI2;
-      g.Wh = reinterpret_cast<const char*>(wT + W.w2T_p); g.w_exp = reinterpret_cast<const int*>(wT + W.w2T_p) + dd;
-      g.out = hdI1; g.aux = hH1; g.act = o->read_mem_act;
-      g.colsum_part = ws + W.db1_part + (size_t)i * B * nrb * d;
-      CK((kb_gemm_h2_launch<B_PLAIN, E_MUL_DACT, true>(g, st)));
-      // dX = dI1 (diag(y) W1a + W1b)^T ; dbx partials
-      g.A = hdI1; g.Wh = nullptr; g.w_exp = nullptr;
-      g.Wt = wT + W.w1aT_p; g.Wt2 = wT + W.w1bT_p; g.w_max = saved + L.wmax + 2; g.y = y; g.ldy = d;
-      g.out = hdX;
-      g.colsum_part = ws + W.dbx_part + (size_t)i * B * nrb * d;
-      CK((kb_gemm_h2_launch<B_YMIX_COL, E_PLAIN, true>(g, st)));
-      }
-      // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials (deferred: one launch over all steps in phase 2, dy from the chain kernel)
-      if (!W.sb_deferred) {
-        SbH2P q;
-        memset(&q, 0, sizeof(q));
-        q.nsteps = 1;
-        q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
-        q.X = hX; q.dI1 = hdI1;
-        q.y = y; q.W1a = P->memKbProj_W;
-        q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
-        q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
-        q.dy_part = ws + W.dy_part;
-        q.dbg = kb_gemm_dbg();
-        CK(sb_h2_launch(q, st));
-      }
-      // dKB = sum_i (dX_i Wx^T) * kbmask_i + att_i (x) dinfo_i: ONE launch over all steps after step 0 -- or, where chain_bwd's
-      // launches carried the products of steps p - 1 .. 1 on their idle CUs, the closing launch of that route
-      if (i == 0 && dkb_plan.njobs) {
-        CK(chain_dkb_rest_launch(dkb_q, B * N, N, d, st));
-      } else if (i == 0) {
-        const int i0 = 0;
-        g.A = h2_view(ws + W.dX + (size_t)i0 * W.act_floats, B * N, d); g.Wt = nullptr; g.Wt2 = nullptr; g.y = nullptr;
-        g.Wh = reinterpret_cast<const char*>(wT + W.wxT_p); g.w_exp = reinterpret_cast<const int*>(wT + W.wxT_p) + dd;
-        g.nsteps = p; g.a_step_bytes = W.act_floats * sizeof(float);
-        g.a_row_exp = chain ? 1 : 0;          // chain_bwd_kernel gives a row of dX ONE exponent: the merged launch may fold once per step
-        g.out_f32 = GI->knowledgeBase; g.ldo = d;
-        const bool wd = dp->keep_write < 1.0f;
-        g.dr = wd ? ws + W.dinfo : ws + W.dwin + d; g.ld_dr = wd ? d : win; g.dr_step = wd ? Bd : (size_t)B * win;
-        if (!(units & U_WRITE)) { g.dr = dinfo; g.ld_dr = d; g.dr_step = Bd; }
-        else g.dr += (size_t)i0 * g.dr_step;
-        g.att = att_kb + (size_t)i0 * B * N; g.att_step = (size_t)B * N;
-        g.e_bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.kb_bits + (size_t)i0 * L.bits_stride) : nullptr;
-        g.bits_step_words = L.bits_stride;
-        g.accumulate = 0;
-        g.colsum_part = nullptr; g.aux = H2View{nullptr, 0, 0};
-        CK((kb_gemm_h2_launch<B_PLAIN, E_DKB, false>(g, st)));
-      }
-    } else {
-    {
-      ReadAttBwdP r;
-      r.B = B; r.N = N; r.d = d; r.b0 = s->b0;
-      r.att = att_kb + (size_t)i * B * N; r.da = ws + W.da; r.I2 = I2; r.c = c_i; r.wk = P->kbLogits_w;
-      r.act = o->read_ctrl_act;
-      r.bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
-      r.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-      r.dI2 = dI2_i;
-      r.dc = DC + (size_t)(i + 1) * Bd;   // dL/dc_i += read-unit part
-      r.dwk_part = ws + W.dwk_part + (size_t)i * Bd;
-      r.db2_part = ws + W.db2_part + (size_t)i * Bd;
-      r.dbk_part = ws + W.dbk_part + (size_t)i * B;
-      hipLaunchKernelGGL(read_att_bwd_kernel, dim3(B, d / 128), dim3(RAB_THREADS), 0, st, r);
-      CK(hipGetLastError());
-    }
-    GemmP g;
-    memset(&g, 0, sizeof(g));
-    g.B = B; g.N = N; g.K = d; g.Nout = d;
-    g.e_inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
-    const uint32_t* kb_bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.kb_bits + (size_t)i * L.bits_stride) : nullptr;
-    // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
-    g.A = dI2_i; g.lda = d; g.Wp = wT + W.w2T_p;
-    g.out = ws + W.dI1; g.ldo = d; g.aux = H1; g.act = o->read_mem_act;
-    g.colsum_part = ws + W.db1_part + (size_t)i * B * nrb * d;
-    CK((kb_gemm<A_PLAIN, B_PLAIN, E_MUL_DACT, true>(g, st)));
-    // dX = dI1 (diag(y) W1a + W1b)^T ; dbx partials
-    g.A = ws + W.dI1; g.Wp = wT + W.w1aT_p; g.Wp2 = wT + W.w1bT_p; g.y = y; g.ldy = d;
-    g.out = dX_i; g.aux = nullptr;
-    g.colsum_part = ws + W.dbx_part + (size_t)i * B * nrb * d;
-    CK((kb_gemm<A_PLAIN, B_YMIX_COL, E_PLAIN, true>(g, st)));
-    // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials
-    {
-      SbP q;
-      q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
-      q.X = X; q.dI1 = ws + W.dI1; q.y = y; q.W1a = P->memKbProj_W;
-      q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
-      q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
-      q.dy_part = ws + W.dy_part;
-      CK((gemm_split_mode() && !(kb_gemm_dbg() & 256)) ? sb6_wgrad_launch(q, st) : sb_wgrad_launch(q, st));   // dbg 256: f32 kernel
-    }
-    // dKB (+)= (dX Wx^T) * kbmask + att * dinfo
-    g.A = dX_i; g.Wp = wT + W.wxT_p; g.Wp2 = nullptr; g.y = nullptr;
-    g.out = GI->knowledgeBase; g.aux = dinfo; g.ld_aux = ld_dinfo; g.att = att_kb + (size_t)i * B * N;
-    g.e_bits = kb_bits;
-    g.accumulate = (i != p - 1);
-    g.colsum_part = nullptr;
-    CK((kb_gemm<A_PLAIN, B_PLAIN, E_DKB, false>(g, st)));
-    }
-    // dy -> d(md) -> dL/d m_{i-1} = dwin[:, :d] + (dy Wy^T) * memmask * readmask
-    float* DYi = ws + W.DY + (size_t)i * Bd;
-    if (!(h2_mode() && W.sb_deferred)) {
-      hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dy_part), (h2_mode() ? SBH_CW / 2 : 2) * d / 128, Bd, DYi);
-      CK(hipGetLastError());
-    }
-    {
-      // with self attention DM[i] already holds the parts later steps sent to this memory: accumulate
-      const bool acc_prev = (units & U_WRITE) && (o->write_self_att || o->write_gate);
-      LinP l = lin_basic(DYi, d, d, B, wT + W.wyT, nullptr, d, MACX_ACT_NON, acc_prev ? ws + W.tmpBd[0] : dm_prev, d);
-      l.use_drop = 1; l.drop_ld = dlog_of(s);
-      l.d1 = o->memory_variational_dropout ? make_drop(dp->keep_memory, dp, SITE_MEM_VAR, 0)
-                                           : make_drop(dp->keep_memory, dp, SITE_MEM, i);
-      l.d2 = make_drop(dp->keep_read, dp, SITE_READ_MEM, i);
-      l.drop_row0 = (uint32_t)s->b0;
-      if (units & U_WRITE) { l.addend = dwin; l.ld_add = win; }
-      const bool part_form = h2_mode() && W.dy_in_linear;
-      if (part_form) { l.part = ws + W.dyc_part; l.part_N = N; l.part_sum = DYi; l.part_shift = chain_tile_shift(d, (size_t)B * N); }
-      if (part_form) {
-        CK(small_linear_part_launch(l, st));
-      } else {
-        CK(small_linear_launch(l, 1, st));
-      }
-      if (acc_prev) {
-        CK(axpy(ws + W.tmpBd[0], Bd, dm_prev, st));
-        if (o->write_gate) CK(axpy(ws + W.tmpBd[3], Bd, dm_prev, st));   // dm * (1 - z)
-      }
-    }
-    // ---- recurrent control backward for this step (dL/dc_i is complete now)
-    if ((units & U_CONTROL) && o->control_feed_prev) {
-      const int cin = o->control_feed_inputs ? 2 * d : d;
-      const bool two = o->control_cont_act != MACX_ACT_NON;
-      if (o->write_self_att && !o->write_self_att_cont) {
-        LinP l = lin_basic(ws + W.dsc + (size_t)i * Bd, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, DC + (size_t)(i + 1) * Bd, d);
-        l.addend = DC + (size_t)(i + 1) * Bd; l.ld_add = d;
-        CK(small_linear_launch(l, 1, st));
-      }
-      CtrlBwdP c;
-      c.B = B; c.S = S; c.d = d; c.nz = 1;
-      c.dcontrol = DC + (size_t)(i + 1) * Bd; c.z_dc = 0;
-      c.cc = saved + L.cc + (size_t)i * Bd; c.z_cc = 0;
-      c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S; c.z_att = 0;
-      c.words = in->words; c.w = P->ctrlLogits_w;
-      c.dl = ws + W.ctrl_dl;
-      c.dcc = ws + W.dcc + (size_t)i * Bd; c.z_dcc = 0;
-      c.dwords = GI->words; c.acc_words = 1;
-      c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part + (size_t)i * B;
-      hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, 1), dim3(256), 0, st, c);
-      hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
-      CK(hipGetLastError());
-      float* dcc_i = ws + W.dcc + (size_t)i * Bd;
-      // parts of dL/dcc_i that did not come through the word attention
-      if (!o->control_feed_prev_att) CK(axpy(ws + W.dccx + (size_t)(i + 1) * Bd, Bd, dcc_i, st));
-      if (o->write_self_att && o->write_self_att_cont) {
-        LinP l = lin_basic(ws + W.dsc + (size_t)i * Bd, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, dcc_i, d);
-        l.addend = dcc_i; l.ld_add = d;
-        CK(small_linear_launch(l, 1, st));
-      }
-      // through contControl(_2): dlin1 = (dcc Wc2^T) * act'(h)  or  dcc
-      float* dlin1 = ws + W.dlin1 + (size_t)i * Bd;
-      if (two) {
-        LinP l2 = lin_basic(dcc_i, d, d, B, wT + W.wcc2T, nullptr, d, MACX_ACT_NON, dlin1, d);
-        l2.actgrad_src = saved + L.cc_h + (size_t)i * Bd; l2.actgrad_act = o->control_cont_act; l2.ld_ag = d;
-        CK(small_linear_launch(l2, 1, st));
-      } else {
-        CK(dev_copy(dlin1, dcc_i, Bd * sizeof(float), st));
-      }
-      // dx = dlin1 Wc^T = [d prev | d cI_i]
-      LinP lx = lin_basic(dlin1, d, d, B, wT + W.wccT, nullptr, cin, MACX_ACT_NON, ws + W.dxc, cin);
-      CK(small_linear_launch(lx, 1, st));
-      float* dprev_dst = o->control_feed_prev_att ? DC + (size_t)i * Bd : (i == 0 ? DC : ws + W.dccx + (size_t)i * Bd);
-      hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dxc), cin, 0, B, d, 0u, no_drop(),
-                         ws + W.tmpBd[0]);
-      CK(hipGetLastError());
-      CK(axpy(ws + W.tmpBd[0], Bd, dprev_dst, st));
-      if (o->control_feed_inputs) {
-        hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dxc), cin, d, B, d, 0u, no_drop(),
-                           ws + W.dcI + (size_t)i * Bd);
-        CK(hipGetLastError());
-      } else {
-        CK(dev_zero(ws + W.dcI + (size_t)i * Bd, Bd * sizeof(float), st));
-      }
-    }
+    dmnew = ws + W.tmpBd[2];
+    // dL/dc_i += dzpre Wg^T
+    LinP gl = lin_basic(dzpre, d, d, B, wT + W.wgT, nullptr, d, MACX_ACT_NON, DC + (size_t)(i + 1) * Bd, d);
+    gl.addend = DC + (size_t)(i + 1) * Bd; gl.ld_add = d;
+    CK(small_linear_launch(gl, 1, st));
   }
-  if ((units & U_READ) && h2_mode() && W.chain_sums && !(dc_in_loop || (W.sb_deferred && !W.dy_in_linear))) {
+  // dwlin = dmnew * act'(mnew) ; [dm_prev part | dinfo (| dselfSmry)] = dwlin Wm^T
+  if (o->write_mem_act != MACX_ACT_NON || o->write_gate) {
+    hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, dmnew, mnew_out, o->write_mem_act, Bd, dwlin);
+    CK(hipGetLastError());
+  }
+  LinP l = lin_basic(dwlin, d, d, B, wT + W.wmT, nullptr, win, MACX_ACT_NON, dwin, win);
+  CK(small_linear_launch(l, 1, st));
+  // d(info) through the write dropout (mac_cell.py:463); without write dropout r.dinfo is a column view of dwin
+  if (dp->keep_write < 1.0f) {
+    hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)dwin, win, d, B, d, (uint32_t)s->b0,
+                       make_drop(dp->keep_write, dp, SITE_WRITE_INFO, i), ws + W.dinfo + (size_t)i * Bd, dlog_of(s));
+    CK(hipGetLastError());
+  }
+  if (o->write_self_att) {
+    SelfAttBwdP q;
+    q.B = B; q.d = d; q.nh = i + 1;
+    q.dsmry = dwin + 2 * d; q.ld_ds = win;
+    q.sc = saved + L.sc + (size_t)i * Bd; q.C = controls(); q.M = memories(); q.w = P->selfLogits_w;
+    q.att = saved + L.seg[MACX_SEG_ATT_SELF] + (size_t)i * B * p; q.ld_att = p;
+    q.DMh = DM; q.DCh = DC;
+    q.dsc = ws + W.dsc + (size_t)i * Bd;
+    q.dw_part = ws + W.dws_part + (size_t)i * Bd;
+    q.db_part = ws + W.dbs_part + (size_t)i * B;
+    hipLaunchKernelGGL(self_attend_bwd_kernel, dim3(B), dim3(256), 0, st, q);
+    CK(hipGetLastError());
+  }
+  return MACX_OK;
+}
+
+// the read unit's products backward, dl -> dI2 -> dI1 -> dX, in one launch (macx_chain_h2.hip.h)
+int CellBwd::read_bwd_chain(int i, const ReadH2& v) {
+  auto wref = [&](size_t off) { return ChainW{reinterpret_cast<const char*>(wT + off), reinterpret_cast<const int*>(wT + off) + dd}; };
+  ChainBwdP c;
+  memset(&c, 0, sizeof(c));
+  c.M = B * N; c.N = N; c.d = d;
+  c.dbg = (kb_gemm_dbg() >> 17) & 31;
+  c.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N; c.da = ws + W.da;
+  c.I2 = v.I2; c.c = controls() + (size_t)(i + 1) * Bd; c.wk = P->kbLogits_w; c.act2 = o->read_ctrl_act;
+  if (W.chain_sums) {
+    c.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
+    c.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
+    c.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; c.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
+  }
+  c.bytes2 = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
+  c.inv2 = rdrop ? 1.0f / dp->keep_read : 1.0f;
+  c.dI2 = v.dI2;
+  c.W2T = wref(W.w2T_p); c.H1 = v.H1; c.act1 = o->read_mem_act;
+  c.dI1 = v.dI1; c.db1_part = ws + W.db1_part + (size_t)i * W.db_rows * d;
+  c.W1aT = wref(W.w1aT_p); c.W1bT = wref(W.w1bT_p); c.y = saved + L.y + (size_t)i * Bd;
+  c.dX = v.dX; c.dbx_part = ws + W.dbx_part + (size_t)i * W.db_rows * d;
+  if (W.sb_deferred) { c.X = v.X; c.dy_part = ws + W.dyc_part; }
+  if (dkb_plan.njobs && i + 1 < p) { c.dkb = dkb_q; c.dkb.step = i + 1; }
+  CK(chain_bwd_launch(c, st));
+  if (W.chain_sums && (dc_in_loop || (W.sb_deferred && !W.dy_in_linear))) {
+    // the per-tile partials of this step: dL/dc_i += read-unit part, db_k partials, dy_i (the next launch needs dy_i)
     DcReduceP q;
     memset(&q, 0, sizeof(q));
     q.B = B; q.N = N; q.d = d;
-    q.dc_part = ws + W.dc_part; q.dls_part = ws + W.dls_part; q.dc = DC + Bd; q.dbk_part = ws + W.dbk_part;
-    q.part_step = W.dwk_rows * 3 * d; q.dls_step = W.dwk_rows * 3; q.dc_step = Bd; q.dbk_step = B;
+    q.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; q.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
+    q.dc = DC + (size_t)(i + 1) * Bd; q.dbk_part = ws + W.dbk_part + (size_t)i * B;
     q.tile_shift = chain_tile_shift(d, (size_t)B * N);
-    hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, p), dim3(128), 0, st, q);
+    if (W.sb_deferred && !W.dy_in_linear) { q.dy_part = ws + W.dyc_part; q.dy = ws + W.DY + (size_t)i * Bd; }
+    hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, 1), dim3(128), 0, st, q);
     CK(hipGetLastError());
   }
-  if (units == U_ALL) {
+  return MACX_OK;
+}
+
+// ... on H2 operands, one launch per product
+int CellBwd::read_bwd_h2(int i, const ReadH2& v) {
+  const size_t parts = (size_t)i * B * nrb * d;
+  GemmH2P g = h2_gemm_params();
+  // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
+  g.A = v.dI2;
+  g.Wh = reinterpret_cast<const char*>(wT + W.w2T_p); g.w_exp = reinterpret_cast<const int*>(wT + W.w2T_p) + dd;
+  g.out = v.dI1; g.aux = v.H1; g.act = o->read_mem_act;
+  g.colsum_part = ws + W.db1_part + parts;
+  CK((kb_gemm_h2_launch<B_PLAIN, E_MUL_DACT, true>(g, st)));
+  // dX = dI1 (diag(y) W1a + W1b)^T ; dbx partials
+  g.A = v.dI1; g.Wh = nullptr; g.w_exp = nullptr;
+  g.Wt = wT + W.w1aT_p; g.Wt2 = wT + W.w1bT_p; g.w_max = saved + L.wmax + 2; g.y = saved + L.y + (size_t)i * Bd; g.ldy = d;
+  g.out = v.dX;
+  g.colsum_part = ws + W.dbx_part + parts;
+  CK((kb_gemm_h2_launch<B_YMIX_COL, E_PLAIN, true>(g, st)));
+  return MACX_OK;
+}
+
+// dKB = sum_i (dX_i Wx^T) * kbmask_i + att_i (x) dinfo_i: ONE launch over all steps
+int CellBwd::dkb_merged_h2() {
+  GemmH2P g = h2_gemm_params();
+  g.A = h2_view(ws + W.dX, B * N, d);
+  g.Wh = reinterpret_cast<const char*>(wT + W.wxT_p); g.w_exp = reinterpret_cast<const int*>(wT + W.wxT_p) + dd;
+  g.nsteps = p; g.a_step_bytes = W.act_floats * sizeof(float);
+  g.a_row_exp = chain ? 1 : 0;          // chain_bwd_kernel gives a row of dX ONE exponent: the merged launch may fold once per step
+  g.out_f32 = GI->knowledgeBase; g.ldo = d;
+  g.dr = dinfo.base; g.ld_dr = dinfo.ld; g.dr_step = dinfo.step;
+  g.att = saved + L.seg[MACX_SEG_ATT_KB]; g.att_step = (size_t)B * N;
+  g.e_bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.kb_bits) : nullptr;
+  g.bits_step_words = L.bits_stride;
+  CK((kb_gemm_h2_launch<B_PLAIN, E_DKB, false>(g, st)));
+  return MACX_OK;
+}
+
+// ... on fp32 operands: the attention, dI1, dX, S_b and this step's dKB term, one launch each
+int CellBwd::read_bwd_f32(int i) {
+  const float* att_i = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
+  const float* y = saved + L.y + (size_t)i * Bd;
+  float* dI2_i = ws + W.dI2 + (size_t)i * W.act_floats;
+  float* dX_i = ws + W.dX + (size_t)i * W.act_floats;
+  {
+    ReadAttBwdP q;
+    q.B = B; q.N = N; q.d = d; q.b0 = s->b0;
+    q.att = att_i; q.da = ws + W.da; q.I2 = saved + L.I2 + (size_t)i * L.act_stride; q.c = controls() + (size_t)(i + 1) * Bd;
+    q.wk = P->kbLogits_w;
+    q.act = o->read_ctrl_act;
+    q.bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
+    q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
+    q.dI2 = dI2_i;
+    q.dc = DC + (size_t)(i + 1) * Bd;   // dL/dc_i += read-unit part
+    q.dwk_part = ws + W.dwk_part + (size_t)i * Bd;
+    q.db2_part = ws + W.db2_part + (size_t)i * Bd;
+    q.dbk_part = ws + W.dbk_part + (size_t)i * B;
+    hipLaunchKernelGGL(read_att_bwd_kernel, dim3(B, d / 128), dim3(RAB_THREADS), 0, st, q);
+    CK(hipGetLastError());
+  }
+  GemmP g;
+  memset(&g, 0, sizeof(g));
+  g.B = B; g.N = N; g.K = d; g.Nout = d;
+  g.e_inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
+  // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
+  g.A = dI2_i; g.lda = d; g.Wp = wT + W.w2T_p;
+  g.out = ws + W.dI1; g.ldo = d; g.aux = saved + L.H1 + (size_t)i * L.act_stride; g.act = o->read_mem_act;
+  g.colsum_part = ws + W.db1_part + (size_t)i * B * nrb * d;
+  CK((kb_gemm<A_PLAIN, B_PLAIN, E_MUL_DACT, true>(g, st)));
+  // dX = dI1 (diag(y) W1a + W1b)^T ; dbx partials
+  g.A = ws + W.dI1; g.Wp = wT + W.w1aT_p; g.Wp2 = wT + W.w1bT_p; g.y = y; g.ldy = d;
+  g.out = dX_i; g.aux = nullptr;
+  g.colsum_part = ws + W.dbx_part + (size_t)i * B * nrb * d;
+  CK((kb_gemm<A_PLAIN, B_YMIX_COL, E_PLAIN, true>(g, st)));
+  // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials
+  {
+    SbP q;
+    q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
+    q.X = saved + L.X + (size_t)i * L.act_stride; q.dI1 = ws + W.dI1; q.y = y; q.W1a = P->memKbProj_W;
+    q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
+    q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
+    q.dy_part = ws + W.dy_part;
+    CK((gemm_split_mode() && !(kb_gemm_dbg() & 256)) ? sb6_wgrad_launch(q, st) : sb_wgrad_launch(q, st));   // dbg 256: f32 kernel
+  }
+  // dKB (+)= (dX Wx^T) * kbmask + att * dinfo
+  g.A = dX_i; g.Wp = wT + W.wxT_p; g.Wp2 = nullptr; g.y = nullptr;
+  g.out = GI->knowledgeBase; g.aux = dinfo.at(i); g.ld_aux = dinfo.ld; g.att = att_i;
+  g.e_bits = rdrop ? reinterpret_cast<const uint32_t*>(saved + L.kb_bits + (size_t)i * L.bits_stride) : nullptr;
+  g.accumulate = (i != p - 1);
+  g.colsum_part = nullptr;
+  CK((kb_gemm<A_PLAIN, B_PLAIN, E_DKB, false>(g, st)));
+  return MACX_OK;
+}
+
+// the read unit, from dL/d(info_i): dL/dc_i += its part, the dy partials, the products' gradients and dKB
+int CellBwd::read_unit_bwd(int i) {
+  const int R = B * N;
+  hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo.at(i), dinfo.ld, in->knowledgeBase, B, N, d,
+                     ws + W.da);
+  CK(hipGetLastError());
+  if (!h2) return read_bwd_f32(i);
+  const size_t a = (size_t)i * L.act_stride;
+  const ReadH2 v{h2_view(saved + L.X + a, R, d), h2_view(saved + L.H1 + a, R, d), h2_view(saved + L.I2 + a, R, d),
+                 h2_view(ws + W.dI2 + (size_t)i * W.act_floats, R, d), h2_view(ws + W.dI1 + (size_t)i * W.dI1_stride, R, d),
+                 h2_view(ws + W.dX + (size_t)i * W.act_floats, R, d)};
+  if (!(chain && W.chain_sums)) {
+    ReadAttBwdH2P q;
+    q.dl = nullptr; q.no_out = chain ? 1 : 0;    // chain with tiny N: only dc / dw_k / db2 / db_k (dI2 comes from the chain kernel)
+    q.B = B; q.N = N; q.d = d;
+    q.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N; q.da = ws + W.da; q.I2 = v.I2;
+    q.c = controls() + (size_t)(i + 1) * Bd; q.wk = P->kbLogits_w;
+    q.act = o->read_ctrl_act;
+    q.bytes = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
+    q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
+    q.dI2 = v.dI2;
+    q.dc = DC + (size_t)(i + 1) * Bd;
+    q.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
+    q.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
+    q.dbk_part = ws + W.dbk_part + (size_t)i * B;
+    hipLaunchKernelGGL(read_att_bwd_h2_kernel, dim3(B, d / 128), dim3(RABH_THREADS), 0, st, q);
+    CK(hipGetLastError());
+  }
+  CKI(chain ? read_bwd_chain(i, v) : read_bwd_h2(i, v));
+  // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials (deferred: one launch over all steps in phase 2, dy from the chain kernel)
+  if (!W.sb_deferred) {
+    SbH2P q;
+    memset(&q, 0, sizeof(q));
+    q.nsteps = 1;
+    q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
+    q.X = v.X; q.dI1 = v.dI1;
+    q.y = saved + L.y + (size_t)i * Bd; q.W1a = P->memKbProj_W;
+    q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
+    q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
+    q.dy_part = ws + W.dy_part;
+    q.dbg = kb_gemm_dbg();
+    CK(sb_h2_launch(q, st));
+  }
+  // dKB of every step after step 0: the merged launch, or where chain_bwd's launches carried steps p - 1 .. 1 on their idle CUs,
+  // the closing launch of that route
+  if (i == 0 && dkb_plan.njobs) CK(chain_dkb_rest_launch(dkb_q, B * N, N, d, st));
+  else if (i == 0) CKI(dkb_merged_h2());
+  return MACX_OK;
+}
+
+// dy -> d(md) -> dL/d m_{i-1} = dwin[:, :d] + (dy Wy^T) * memmask * readmask  (dwin: with_write, the write unit is in the call)
+int CellBwd::dy_linear_bwd(int i, bool with_write) {
+  float* DYi = ws + W.DY + (size_t)i * Bd;
+  float* dm_prev = DM + (size_t)i * Bd;
+  if (!(h2 && W.sb_deferred)) {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dy_part), (h2 ? SBH_CW / 2 : 2) * d / 128, Bd, DYi);
+    CK(hipGetLastError());
+  }
+  // with self attention DM[i] already holds the parts later steps sent to this memory: accumulate
+  const bool acc_prev = with_write && (o->write_self_att || o->write_gate);
+  LinP l = lin_basic(DYi, d, d, B, wT + W.wyT, nullptr, d, MACX_ACT_NON, acc_prev ? ws + W.tmpBd[0] : dm_prev, d);
+  l.use_drop = 1; l.drop_ld = dlog_of(s);
+  l.d1 = o->memory_variational_dropout ? make_drop(dp->keep_memory, dp, SITE_MEM_VAR, 0)
+                                       : make_drop(dp->keep_memory, dp, SITE_MEM, i);
+  l.d2 = make_drop(dp->keep_read, dp, SITE_READ_MEM, i);
+  l.drop_row0 = (uint32_t)s->b0;
+  if (with_write) { l.addend = ws + W.dwin + (size_t)i * B * win; l.ld_add = win; }
+  if (h2 && W.dy_in_linear) {
+    l.part = ws + W.dyc_part; l.part_N = N; l.part_sum = DYi; l.part_shift = chain_tile_shift(d, (size_t)B * N);
+    CK(small_linear_part_launch(l, st));
+  } else {
+    CK(small_linear_launch(l, 1, st));
+  }
+  if (acc_prev) {
+    CK(axpy(ws + W.tmpBd[0], Bd, dm_prev, st));
+    if (o->write_gate) CK(axpy(ws + W.tmpBd[3], Bd, dm_prev, st));   // dm * (1 - z)
+  }
+  return MACX_OK;
+}
+
+// the recurrent control unit of step i (dL/dc_i is complete now)
+int CellBwd::control_step_bwd(int i) {
+  const int S = s->S;
+  const int cin = o->control_feed_inputs ? 2 * d : d;
+  if (o->write_self_att && !o->write_self_att_cont) {
+    LinP l = lin_basic(ws + W.dsc + (size_t)i * Bd, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, DC + (size_t)(i + 1) * Bd, d);
+    l.addend = DC + (size_t)(i + 1) * Bd; l.ld_add = d;
+    CK(small_linear_launch(l, 1, st));
+  }
+  CtrlBwdP c;
+  c.B = B; c.S = S; c.d = d; c.nz = 1;
+  c.dcontrol = DC + (size_t)(i + 1) * Bd; c.z_dc = 0;
+  c.cc = saved + L.cc + (size_t)i * Bd; c.z_cc = 0;
+  c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S; c.z_att = 0;
+  c.words = in->words; c.w = P->ctrlLogits_w;
+  c.dl = ws + W.ctrl_dl;
+  c.dcc = ws + W.dcc + (size_t)i * Bd; c.z_dcc = 0;
+  c.dwords = GI->words; c.acc_words = 1;
+  c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part + (size_t)i * B;
+  hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, 1), dim3(256), 0, st, c);
+  hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
+  CK(hipGetLastError());
+  float* dcc_i = ws + W.dcc + (size_t)i * Bd;
+  // parts of dL/dcc_i that did not come through the word attention
+  if (!o->control_feed_prev_att) CK(axpy(ws + W.dccx + (size_t)(i + 1) * Bd, Bd, dcc_i, st));
+  if (o->write_self_att && o->write_self_att_cont) {
+    LinP l = lin_basic(ws + W.dsc + (size_t)i * Bd, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, dcc_i, d);
+    l.addend = dcc_i; l.ld_add = d;
+    CK(small_linear_launch(l, 1, st));
+  }
+  // through contControl(_2): dlin1 = (dcc Wc2^T) * act'(h)  or  dcc
+  float* dlin1 = ws + W.dlin1 + (size_t)i * Bd;
+  if (o->control_cont_act != MACX_ACT_NON) {
+    LinP l2 = lin_basic(dcc_i, d, d, B, wT + W.wcc2T, nullptr, d, MACX_ACT_NON, dlin1, d);
+    l2.actgrad_src = saved + L.cc_h + (size_t)i * Bd; l2.actgrad_act = o->control_cont_act; l2.ld_ag = d;
+    CK(small_linear_launch(l2, 1, st));
+  } else {
+    CK(dev_copy(dlin1, dcc_i, Bd * sizeof(float), st));
+  }
+  // dx = dlin1 Wc^T = [d prev | d cI_i]
+  LinP lx = lin_basic(dlin1, d, d, B, wT + W.wccT, nullptr, cin, MACX_ACT_NON, ws + W.dxc, cin);
+  CK(small_linear_launch(lx, 1, st));
+  float* dprev_dst = o->control_feed_prev_att ? DC + (size_t)i * Bd : (i == 0 ? DC : ws + W.dccx + (size_t)i * Bd);
+  hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dxc), cin, 0, B, d, 0u, no_drop(),
+                     ws + W.tmpBd[0]);
+  CK(hipGetLastError());
+  CK(axpy(ws + W.tmpBd[0], Bd, dprev_dst, st));
+  if (o->control_feed_inputs) {
+    hipLaunchKernelGGL(copy_cols_drop_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dxc), cin, d, B, d, 0u, no_drop(),
+                       ws + W.dcI + (size_t)i * Bd);
+    CK(hipGetLastError());
+  } else {
+    CK(dev_zero(ws + W.dcI + (size_t)i * Bd, Bd * sizeof(float), st));
+  }
+  return MACX_OK;
+}
+
+// ---- backward: after the step loop
+// the chain launches' per-tile partials of every step that did not reduce its own: dL/dc_i += read-unit part, db_k partials
+int CellBwd::read_dc_reduce_all() {
+  if (!(h2 && W.chain_sums) || dc_in_loop || (W.sb_deferred && !W.dy_in_linear)) return MACX_OK;
+  DcReduceP q;
+  memset(&q, 0, sizeof(q));
+  q.B = B; q.N = N; q.d = d;
+  q.dc_part = ws + W.dc_part; q.dls_part = ws + W.dls_part; q.dc = DC + Bd; q.dbk_part = ws + W.dbk_part;
+  q.part_step = W.dwk_rows * 3 * d; q.dls_step = W.dwk_rows * 3; q.dc_step = Bd; q.dbk_step = B;
+  q.tile_shift = chain_tile_shift(d, (size_t)B * N);
+  hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, p), dim3(128), 0, st, q);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// the control unit (not recurrent: every control depends on the question only, so all p steps at once; recurrent: the parameters
+// of its linears) and the self attention's control projection
+int CellBwd::control_bwd_tail() {
+  const int S = s->S;
   if (o->write_self_att && !o->write_self_att_cont && !o->control_feed_prev) {
     // selfControl = the NEW control: dL/dc_i += dsc_i Ws^T before the word attention is differentiated
     LinP l = lin_basic(ws + W.dsc, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, DC + Bd, d);
@@ -1604,13 +1655,11 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     CK(rs.add(ws + W.dwc_part, B, d, d, GP->ctrlLogits_w, st));
     CK(rs.add(ws + W.dbc_part, p * B, 1, 1, GP->ctrlLogits_b, st));
     // contControl weights: one contraction over all p*B rows per input segment
-    const bool two = o->control_cont_act != MACX_ACT_NON;
-    const float* prev_all = o->control_feed_prev_att ? controls : nullptr;   // rows of step i = c_{i-1} = controls[i]
-    if (o->control_feed_prev_att) {
-      CKI(wgrad_impl(prev_all, d, ws + W.dlin1, d, p * B, d, d, GP->contControl_W, ws + W.small_slab, st));
+    if (o->control_feed_prev_att) {   // rows of step i = c_{i-1} = controls[i]
+      CKI(wgrad_impl(controls(), d, ws + W.dlin1, d, p * B, d, d, GP->contControl_W, ws + W.small_slab, st));
     } else {
       // prev of step 0 is the initial control, prev of step i > 0 is cc_{i-1}
-      CKI(wgrad_impl(controls, d, ws + W.dlin1, d, B, d, d, GP->contControl_W, ws + W.small_slab, st));
+      CKI(wgrad_impl(controls(), d, ws + W.dlin1, d, B, d, d, GP->contControl_W, ws + W.small_slab, st));
       if (p > 1) {
         CKI(wgrad_impl(saved + L.cc, d, ws + W.dlin1 + Bd, d, (p - 1) * B, d, d, ws + W.tmp_dd, ws + W.small_slab, st));
         CK(axpy(ws + W.tmp_dd, dd, GP->contControl_W, st));
@@ -1619,14 +1668,11 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     if (o->control_feed_inputs)
       CKI(wgrad_impl(saved + L.cI, d, ws + W.dlin1, d, p * B, d, d, GP->contControl_W + dd, ws + W.small_slab, st));
     CK(rs.add(ws + W.dlin1, p * B, d, d, GP->contControl_b, st));
-    if (two) {
+    if (o->control_cont_act != MACX_ACT_NON) {
       CKI(wgrad_impl(saved + L.cc_h, d, ws + W.dcc, d, p * B, d, d, GP->contControl2_W, ws + W.small_slab, st));
       CK(rs.add(ws + W.dcc, p * B, d, d, GP->contControl2_b, st));
     }
-  }
-  // ---- control unit backward.  Not recurrent: every control depends on the question only, so all
-  // p steps are handled together.
-  if (!o->control_feed_prev) {
+  } else {
     CtrlBwdP c;
     c.B = B; c.S = S; c.d = d; c.nz = p;
     c.dcontrol = DC + Bd; c.z_dc = Bd;
@@ -1650,36 +1696,36 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     LinP l = lin_basic(ws + W.dsc, d, d, B, wT + W.wscT, nullptr, d, MACX_ACT_NON, dst, d);
     l.seg[0].zstride = Bd; l.zout = Bd; l.addend = dst; l.ld_add = d; l.zadd = Bd;
     if (o->write_self_att_cont && !o->control_feed_prev) CK(small_linear_launch(l, p, st));
-    const float* src = o->write_self_att_cont ? saved + L.cc : controls + Bd;
+    const float* src = o->write_self_att_cont ? saved + L.cc : controls() + Bd;
     CKI(wb.add(src, d, ws + W.dsc, d, p * B, d, d, GP->selfCtrl_W, st));
     CK(rs.add(ws + W.dsc, p * B, d, d, GP->selfCtrl_b, st));
     CK(rs.add(ws + W.dws_part, p * B, d, d, GP->selfLogits_w, st));
     CK(rs.add(ws + W.dbs_part, p * B, 1, 1, GP->selfLogits_b, st));
   }
-  }   // U_ALL
-  if (o->write_gate && (units & U_WRITE)) {
-    CKI(wb.add(controls + Bd, d, ws + W.dzpre, d, p * B, d, d, GP->gate_W, st));
-    CK(rs.add(ws + W.dzpre, p * B, d, d, GP->gate_b, st));
-  }
-  if (units == U_ALL) {
-  // ---- control inputs backward (mac_cell.py:442-448): dt = sum_i dcI_i WqU_i^T ; du = dt * act'(t)
+  return MACX_OK;
+}
+
+int CellBwd::gate_wgrads() {
+  if (!o->write_gate) return MACX_OK;
+  CKI(wb.add(controls() + Bd, d, ws + W.dzpre, d, p * B, d, d, GP->gate_W, st));
+  CK(rs.add(ws + W.dzpre, p * B, d, d, GP->gate_b, st));
+  return MACX_OK;
+}
+
+// the control inputs (mac_cell.py:442-448): dt = sum_i dcI_i WqU_i^T ; du = dt * act'(t) ; dvecQ = du Wq^T
+int CellBwd::control_inputs_bwd() {
   const float* ctrl_t = saved + L.ctrl_t;
-  float* dcI_sum = ws + W.tmpBd[1];
   if (o->control_input_unshared) {
-    // dt = sum_i dcI_i WqU_i^T: one linear over K = p d (the per-step inputs read as one [B, p d] operand, the per-step
-    // packed transposes are contiguous = one packed [p d, d] matrix)
-    // dt = sum_i dcI_i WqU_i^T: one batched launch of the p products (1536 workgroups at p = 12, one batch of operand loads each)
-    // and a fixed-order sum over the steps.  (Rounds 2-5 ran it as ONE linear over K = p d: 128 workgroups whose waves walked 96
-    // k-groups in twelve dependent load batches -- 27.6 us of latency for 0.4 GFLOP.)
-    {
-      LinP li = lin_basic(ws + W.dcI, d, d, B, wT + W.wqUT, nullptr, d, MACX_ACT_NON, ws + W.dt_part, d);
-      li.seg[0].zstride = Bd; li.zW = dd; li.zout = Bd;
-      CK(small_linear_launch(li, p, st));
-      // ... which also leaves du = dt * act'(t) (the mul_actgrad launch of the shared-weights path below)
-      hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dt_part), p, Bd, ws + W.dt, ctrl_t,
-                         (int)o->control_input_act, ws + W.du);
-      CK(hipGetLastError());
-    }
+    // dt: one batched launch of the p products (1536 workgroups at p = 12, one batch of operand loads each) and a fixed-order sum
+    // over the steps.  (Rounds 2-5 ran it as ONE linear over K = p d: 128 workgroups whose waves walked 96 k-groups in twelve
+    // dependent load batches -- 27.6 us of latency for 0.4 GFLOP.)
+    LinP li = lin_basic(ws + W.dcI, d, d, B, wT + W.wqUT, nullptr, d, MACX_ACT_NON, ws + W.dt_part, d);
+    li.seg[0].zstride = Bd; li.zW = dd; li.zout = Bd;
+    CK(small_linear_launch(li, p, st));
+    // ... which also leaves du = dt * act'(t)
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dt_part), p, Bd, ws + W.dt, ctrl_t,
+                       (int)o->control_input_act, ws + W.du);
+    CK(hipGetLastError());
     // the p weight gradients ctrl_t^T dcI_i share A: one batched launch (B rows -> a single split, no slabs)
     if (gemm_split_mode() && !(kb_gemm_dbg() & 128) && wgrad_splits(B, d, d) == 1) {
       TnP t;
@@ -1694,14 +1740,13 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     }
     CK(rs.add(ws + W.dcI, B, d, d, GP->qInputU_b, st, p, Bd, d));
   } else {
+    float* dcI_sum = ws + W.tmpBd[1];
     hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dcI), p, Bd, dcI_sum);
     CK(hipGetLastError());
     LinP ls = lin_basic(dcI_sum, d, d, B, wT + W.wqUT, nullptr, d, MACX_ACT_NON, ws + W.dt, d);
     CK(small_linear_launch(ls, 1, st));
     CKI(wgrad_impl(ctrl_t, d, dcI_sum, d, B, d, d, GP->qInputU_W, ws + W.small_slab, st));
     CK(rs.add(dcI_sum, B, d, d, GP->qInputU_b, st));
-  }
-  if (!o->control_input_unshared) {
     hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dt), ctrl_t, o->control_input_act, Bd,
                        ws + W.du);
     CK(hipGetLastError());
@@ -1709,49 +1754,46 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
   // dvecQ = du Wq^T (+ dL/d(initial state) where a state is initialised from the question vector, mac_cell.py:496-505: the first of
   // them rides this launch's epilogue instead of an axpy of its own)
   const float* q_add = o->init_ctrl == MACX_INIT_Q ? DC : (o->init_mem == MACX_INIT_Q ? DM : nullptr);
-  {
-    LinP l = lin_basic(ws + W.du, d, d, B, wT + W.wqT, nullptr, d, MACX_ACT_NON, GI->vecQuestions, d);
-    if (q_add) { l.addend = q_add; l.ld_add = d; }
-    CK(small_linear_launch(l, 1, st));
-  }
+  LinP l = lin_basic(ws + W.du, d, d, B, wT + W.wqT, nullptr, d, MACX_ACT_NON, GI->vecQuestions, d);
+  if (q_add) { l.addend = q_add; l.ld_add = d; }
+  CK(small_linear_launch(l, 1, st));
   CKI(wb.add(in->vecQuestions, d, ws + W.du, d, B, d, d, GP->qInput_W, st));
   CK(rs.add(ws + W.du, B, d, d, GP->qInput_b, st));
+  return MACX_OK;
+}
 
-  // ---- initial state (mac_cell.py:496-505)
+// the initial state (mac_cell.py:496-505)
+int CellBwd::initial_state_bwd() {
   if (o->init_mem == MACX_INIT_PRM) CK(rs.add(DM, B, d, d, GP->initMem, st));
-  else if (o->init_mem == MACX_INIT_Q && q_add != DM) CK(axpy(DM, Bd, GI->vecQuestions, st));
+  else if (o->init_mem == MACX_INIT_Q && o->init_ctrl == MACX_INIT_Q) CK(axpy(DM, Bd, GI->vecQuestions, st));   // (else: dvecQ's addend)
   if (o->init_ctrl == MACX_INIT_PRM) CK(rs.add(DC, B, d, d, GP->initCtrl, st));
+  return MACX_OK;
+}
 
-  }   // U_ALL
-  // ---- weight gradients of the [B,d] linears, one contraction over all p*B rows each
-  if (units & U_READ) {
-    CKI(wb.add(saved + L.md, d, ws + W.DY, d, p * B, d, d, GP->projY_W, st));
-    CK(rs.add(ws + W.DY, p * B, d, d, GP->projY_b, st));
-  }
-  if (units & U_WRITE) {
-    CKI(wb.add(memories, d, dwlin_all, d, p * B, d, d, GP->newMemory_W, st));
-    CKI(wb.add(infos, d, dwlin_all, d, p * B, d, d, GP->newMemory_W + dd, st));
-    if (o->write_self_att)
-      CKI(wb.add(saved + L.self_smry, d, dwlin_all, d, p * B, d, d, GP->newMemory_W + 2 * dd, st));
-    CK(rs.add(dwlin_all, p * B, d, d, GP->newMemory_b, st));
-  }
-  if (units == U_READ) {
-    // the read unit alone: dL/d(memory) = (dy Wy^T) through the two masks, dL/d(control) from the attention logits
-    CK(dev_copy(ug->d_memory, DM, Bd * sizeof(float), st));
-    CK(dev_copy(ug->d_control, DC + Bd, Bd * sizeof(float), st));
-  }
+// weight gradients of the [B,d] linears, one contraction over all p*B rows each: the read unit's projY ...
+int CellBwd::read_linear_wgrads() {
+  CKI(wb.add(saved + L.md, d, ws + W.DY, d, p * B, d, d, GP->projY_W, st));
+  CK(rs.add(ws + W.DY, p * B, d, d, GP->projY_b, st));
+  return MACX_OK;
+}
 
-  CKI(wb.run(st));
-  }   // phase != 2
-  CK(rs.run(st));
-  if (phase == 1 || !(units & U_READ)) return MACX_OK;
+// ... and the write unit's newMemory
+int CellBwd::write_linear_wgrads() {
+  const int rows = p * B;
+  CKI(wb.add(memories(), d, dwlin_all, d, rows, d, d, GP->newMemory_W, st));
+  CKI(wb.add(saved + L.seg[MACX_SEG_INFOS], d, dwlin_all, d, rows, d, d, GP->newMemory_W + dd, st));
+  if (o->write_self_att)
+    CKI(wb.add(saved + L.self_smry, d, dwlin_all, d, rows, d, d, GP->newMemory_W + 2 * dd, st));
+  CK(rs.add(dwlin_all, rows, d, d, GP->newMemory_b, st));
+  return MACX_OK;
+}
 
+// phase 2: the read unit's weights -- a fixed-order reduction of the per-step slabs.  dW2 = sum_i H1_i^T dI2_i and
+// dWx = sum_i dropout_i(KB)^T dX_i: ONE contraction each over all p*B*N rows (the per-step operands are kept; 288 GB of HBM makes
+// that the cheap choice)
+int CellBwd::read_weight_contractions() {
   int ns_w = (int)W.ns_big;          // reduction splits of the dW2 / dWx contractions (H2 family: decided below)
-  // ---- read-unit weights: fixed-order reduction of the per-step slabs
-  // dW2 = sum_i H1_i^T dI2_i and dWx = sum_i dropout_i(KB)^T dX_i: ONE contraction each over all
-  // p*B*N rows (the per-step operands are kept; 288 GB of HBM makes that the cheap choice)
-  if (h2_mode()) {
-    const int CB = d / 128;
+  if (h2) {
     int* ecom = reinterpret_cast<int*>(ws + W.ecom);       // [H1 | dI2 | KBd | dX][EMIN_NB][8]
     constexpr int ES = EMIN_NB * 8;
     {
@@ -1780,7 +1822,7 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     t.part = ws + W.slab_w2;
     const TnH2P t_w2 = t;
     t.A = reinterpret_cast<const char*>(saved + L.KBd);
-    t.a_mod = rdrop ? 0 : B * N;                              // no dropout: the same (converted) KB every step
+    t.a_mod = rdrop ? 0 : B * N;                            // no dropout: the same (converted) KB every step
     t.G = reinterpret_cast<const char*>(ws + W.dX);
     t.ecomA = ecom + 2 * ES; t.ecomG = ecom + 3 * ES;
     t.part = ws + W.slab_wx;
@@ -1793,17 +1835,15 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     t.A = saved + L.H1; t.lda = d; t.a_mod = t.M; t.G = ws + W.dI2; t.ldg = d;
     t.part = ws + W.slab_w2;
     CK(wgrad_any(t, st));
-    if (rdrop) { t.A = saved + L.KBd; t.a_mod = t.M; }          // the dropped KB of every step was kept
-    else { t.A = in->knowledgeBase; t.a_mod = B * N; }          // no dropout: the same KB each step
+    if (rdrop) { t.A = saved + L.KBd; t.a_mod = t.M; }        // the dropped KB of every step was kept
+    else { t.A = in->knowledgeBase; t.a_mod = B * N; }        // no dropout: the same KB each step
     t.G = ws + W.dX;
     t.part = ws + W.slab_wx;
     CK(wgrad_any(t, st));
   }
-
-  if (h2_mode() && W.sb_deferred) {
+  if (h2 && W.sb_deferred) {
     // dW1a = sum_i sum_b diag(y_ib) S_ib, dW1b = sum_i sum_b S_ib, S_ib = X_ib^T dI1_ib: every step in one launch, the two
     // accumulators of a workgroup run through all of them (macx_wgrad_h2.hip.h)
-    const int CB = d / 128;
     SbH2P q;
     memset(&q, 0, sizeof(q));
     q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
@@ -1816,15 +1856,13 @@ int cell_backward_impl(const macx_opts* o, const macx_shapes* s, const macx_drop
     q.qpg = W.sb_qpg;
     CK(W.sb_wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
   }
-  const int nslab1 = (int)((h2_mode() && W.sb_deferred ? 1 : p) * W.ngroup);
-  {
-    SlabList sl;
-    sl.d[0] = SlabDesc{ws + W.slab_w2, ns_w, dd / 4, GP->memKbProj2_W, 0};
-    sl.d[1] = SlabDesc{ws + W.slab_wx, ns_w, dd / 4, GP->projX_W, 0};
-    sl.d[2] = SlabDesc{ws + W.slab_w1a, nslab1, dd / 4, GP->memKbProj_W, 0};
-    sl.d[3] = SlabDesc{ws + W.slab_w1b, nslab1, dd / 4, GP->memKbProj_W + dd, 0};
-    CK(slab_reduce_list_launch(sl, 4, dd, st));
-  }
+  const int nslab1 = (int)((h2 && W.sb_deferred ? 1 : p) * W.ngroup);
+  SlabList sl;
+  sl.d[0] = SlabDesc{ws + W.slab_w2, ns_w, dd / 4, GP->memKbProj2_W, 0};
+  sl.d[1] = SlabDesc{ws + W.slab_wx, ns_w, dd / 4, GP->projX_W, 0};
+  sl.d[2] = SlabDesc{ws + W.slab_w1a, nslab1, dd / 4, GP->memKbProj_W, 0};
+  sl.d[3] = SlabDesc{ws + W.slab_w1b, nslab1, dd / 4, GP->memKbProj_W + dd, 0};
+  CK(slab_reduce_list_launch(sl, 4, dd, st));
   CK(rs.add(ws + W.db2_part, p * (int)W.dwk_rows, d, d, GP->memKbProj2_b, st));
   CK(rs.add(ws + W.db1_part, p * (int)W.db_rows, d, d, GP->memKbProj_b, st));
   CK(rs.add(ws + W.dbx_part, p * (int)W.db_rows, d, d, GP->projX_b, st));
@@ -1840,7 +1878,38 @@ int macx_cell_backward_phase(const macx_opts* o, const macx_shapes* s, const mac
                              const float* d_memory, const float* d_control, const macx_param_grads* GP,
                              const macx_input_grads* GI, int phase, void* stream) {
   ModeScope ms(o);
-  return cell_backward_impl(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, d_memory, d_control, GP, GI, phase, U_ALL, nullptr, stream);
+  if (phase < 0 || phase > 2) return MACX_EINVAL;
+  CKI(check_impl(o, s));
+  if (!dp || !P || !in || !saved || !ws || !GP || !GI) return MACX_EINVAL;
+  if (!GI->knowledgeBase || !GI->words || !GI->vecQuestions) return MACX_EINVAL;
+  CellBwd r(o, s, dp, P, in, saved, ws, GP, GI, stream);
+  CKI(r.check_bwd_buffers(saved_floats, ws_floats, phase));
+  if (phase != 2) {
+    CKI(r.init_state_grads(d_memory, d_control));
+    if (o->control_feed_prev) {
+      CK(dev_zero(GI->words, (size_t)r.B * s->S * r.d * sizeof(float), r.st));
+      CK(dev_zero(ws + r.W.dwc_part, r.Bd * sizeof(float), r.st));
+      CK(dev_zero(ws + r.W.dccx, (size_t)(r.p + 1) * r.Bd * sizeof(float), r.st));
+      r.dc_in_loop = true;
+    }
+    r.plan_dkb_fill();
+    for (int i = r.p - 1; i >= 0; --i) {
+      CKI(r.write_unit_bwd(i));
+      CKI(r.read_unit_bwd(i));
+      CKI(r.dy_linear_bwd(i, true));
+      if (o->control_feed_prev) CKI(r.control_step_bwd(i));
+    }
+    CKI(r.read_dc_reduce_all());
+    CKI(r.control_bwd_tail());
+    CKI(r.gate_wgrads());
+    CKI(r.control_inputs_bwd());
+    CKI(r.initial_state_bwd());
+    CKI(r.read_linear_wgrads());
+    CKI(r.write_linear_wgrads());
+    CKI(r.wb.run(r.st));
+  }
+  CK(r.rs.run(r.st));
+  return phase == 1 ? MACX_OK : r.read_weight_contractions();
 }
 
 int macx_cell_backward(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
@@ -1853,13 +1922,13 @@ int macx_cell_backward(const macx_opts* o, const macx_shapes* s, const macx_drop
 // =================================================================================================
 // unit-level entry points
 // =================================================================================================
-// ---- one read / write unit on caller-owned buffers: the cell's own step code restricted to a unit.
+// ---- one read / write unit on caller-owned buffers: the cell's own unit functions.
 // shapes->p == 1: the unit of step 0 (the dropout streams are keyed by (seed, site, step 0)).
 namespace {
-int unit_check(const macx_opts* o, const macx_shapes* s, int units) {
+int unit_check(const macx_opts* o, const macx_shapes* s, bool write) {
   CKI(check_impl(o, s));
   if (s->p != 1) return MACX_EINVAL;
-  if ((units & U_WRITE) && o->write_self_att) return MACX_EUNSUPPORTED;   // needs the histories of a running cell
+  if (write && o->write_self_att) return MACX_EUNSUPPORTED;   // needs the histories of a running cell
   return MACX_OK;
 }
 }  // namespace
@@ -1872,23 +1941,28 @@ int macx_read_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* 
                   const float* knowledgeBase, const float* memory, const float* control, float* saved, size_t saved_floats,
                   float* info, float* att, void* stream) {
   ModeScope ms(o);
-  CKI(unit_check(o, s, U_READ));
+  CKI(unit_check(o, s, false));
   if (!dp || !P || !knowledgeBase || !memory || !control || !saved || !info || !att) return MACX_EINVAL;
   if (misaligned(saved) || misaligned(knowledgeBase)) return MACX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const SavedLayout L = make_saved(o, s, 1);
-  if (saved_floats < L.total) return MACX_ESMALL;
-  const size_t Bd = (size_t)s->B * s->d;
-  CKI(pack_forward_weights(o, s, P, saved, L, 1, U_READ, st));
-  CK(dev_copy(saved + L.seg[MACX_SEG_MEMORIES], memory, Bd * sizeof(float), st));
-  CK(dev_copy(saved + L.seg[MACX_SEG_CONTROLS] + Bd, control, Bd * sizeof(float), st));
-  macx_inputs in;
-  memset(&in, 0, sizeof(in));
+  macx_inputs in{};
   in.knowledgeBase = knowledgeBase;
-  CKI(cell_step_impl(o, s, dp, P, &in, saved, saved_floats, 1, 0, U_READ, stream));
-  const float* info_raw = dp->keep_write < 1.0f ? saved + L.info_raw : saved + L.seg[MACX_SEG_INFOS];
-  CK(dev_copy(info, info_raw, Bd * sizeof(float), st));
-  CK(dev_copy(att, saved + L.seg[MACX_SEG_ATT_KB], (size_t)s->B * s->N * sizeof(float), st));
+  const CellRun r(o, s, dp, P, &in, saved, 1, stream);
+  if (saved_floats < r.L.total) return MACX_ESMALL;
+  {
+    Packer pk;
+    if (r.h2) CK(r.read_weight_maxima());
+    r.add_read_packs(pk);
+    if (r.L.bwd_packs) {
+      const BwdLayout W = make_bwd(o, s);
+      r.add_read_packs(pk, &W);
+    }
+    CK(pk.run(r.st));
+  }
+  CK(dev_copy(r.memories(), memory, r.Bd * sizeof(float), r.st));
+  CK(dev_copy(r.controls() + r.Bd, control, r.Bd * sizeof(float), r.st));
+  CKI(r.read_step(0, 0, false));
+  CK(dev_copy(info, r.info_raw(0), r.Bd * sizeof(float), r.st));
+  CK(dev_copy(att, saved + r.L.seg[MACX_SEG_ATT_KB], (size_t)r.B * r.N * sizeof(float), r.st));
   return MACX_OK;
 }
 
@@ -1897,39 +1971,52 @@ int macx_read_bwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* 
                   const float* d_info, const macx_param_grads* GP, float* d_knowledgeBase, float* d_memory, float* d_control,
                   void* stream) {
   ModeScope ms(o);
-  CKI(unit_check(o, s, U_READ));
+  CKI(unit_check(o, s, false));
   if (!knowledgeBase || !d_info || !d_knowledgeBase || !d_memory || !d_control) return MACX_EINVAL;
-  macx_inputs in;
-  memset(&in, 0, sizeof(in));
+  if (!dp || !P || !saved || !ws || !GP) return MACX_EINVAL;
+  macx_inputs in{};
   in.knowledgeBase = knowledgeBase;
-  macx_input_grads GI;
-  memset(&GI, 0, sizeof(GI));
+  macx_input_grads GI{};
   GI.knowledgeBase = d_knowledgeBase;
-  UnitGrads ug;
-  ug.d_info_in = d_info; ug.d_memory = d_memory; ug.d_control = d_control;
-  return cell_backward_impl(o, s, dp, P, &in, saved, saved_floats, ws, ws_floats, nullptr, nullptr, GP, &GI, 0, U_READ, &ug, stream);
+  CellBwd r(o, s, dp, P, &in, saved, ws, GP, &GI, stream);
+  CKI(r.check_bwd_buffers(saved_floats, ws_floats, 0));
+  CKI(r.init_state_grads(nullptr, nullptr));
+  r.dinfo = StepSlab{d_info, r.d, r.Bd};
+  CKI(r.read_unit_bwd(0));
+  CKI(r.dy_linear_bwd(0, false));
+  CKI(r.read_dc_reduce_all());
+  CKI(r.read_linear_wgrads());
+  // dL/d(memory) = (dy Wy^T) through the two masks, dL/d(control) from the attention logits
+  CK(dev_copy(d_memory, r.DM, r.Bd * sizeof(float), r.st));
+  CK(dev_copy(d_control, r.DC + r.Bd, r.Bd * sizeof(float), r.st));
+  CKI(r.wb.run(r.st));
+  CK(r.rs.run(r.st));
+  return r.read_weight_contractions();
 }
 
 int macx_write_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
                    const float* memory, const float* info, const float* control, float* saved, size_t saved_floats,
                    float* new_memory, void* stream) {
   ModeScope ms(o);
-  CKI(unit_check(o, s, U_WRITE));
+  CKI(unit_check(o, s, true));
   if (!dp || !P || !memory || !info || !control || !saved || !new_memory) return MACX_EINVAL;
   if (misaligned(saved)) return MACX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const SavedLayout L = make_saved(o, s, 1);
-  if (saved_floats < L.total) return MACX_ESMALL;
-  const size_t Bd = (size_t)s->B * s->d;
-  CKI(pack_forward_weights(o, s, P, saved, L, 1, U_WRITE, st));
-  float* info_raw = dp->keep_write < 1.0f ? saved + L.info_raw : saved + L.seg[MACX_SEG_INFOS];
-  CK(dev_copy(saved + L.seg[MACX_SEG_MEMORIES], memory, Bd * sizeof(float), st));
-  CK(dev_copy(info_raw, info, Bd * sizeof(float), st));
-  CK(dev_copy(saved + L.seg[MACX_SEG_CONTROLS] + Bd, control, Bd * sizeof(float), st));
-  macx_inputs in;
-  memset(&in, 0, sizeof(in));
-  CKI(cell_step_impl(o, s, dp, P, &in, saved, saved_floats, 1, 0, U_WRITE, stream));
-  CK(dev_copy(new_memory, saved + L.seg[MACX_SEG_MEMORIES] + Bd, Bd * sizeof(float), st));
+  const CellRun r(o, s, dp, P, nullptr, saved, 1, stream);
+  if (saved_floats < r.L.total) return MACX_ESMALL;
+  {
+    Packer pk;
+    r.add_write_packs(pk);
+    if (r.L.bwd_packs) {
+      const BwdLayout W = make_bwd(o, s);
+      r.add_write_packs(pk, &W);
+    }
+    CK(pk.run(r.st));
+  }
+  CK(dev_copy(r.memories(), memory, r.Bd * sizeof(float), r.st));
+  CK(dev_copy(r.info_raw(0), info, r.Bd * sizeof(float), r.st));
+  CK(dev_copy(r.controls() + r.Bd, control, r.Bd * sizeof(float), r.st));
+  CKI(r.write_step(0, false));
+  CK(dev_copy(new_memory, r.memories() + r.Bd, r.Bd * sizeof(float), r.st));
   return MACX_OK;
 }
 
@@ -1937,15 +2024,24 @@ int macx_write_bwd(const macx_opts* o, const macx_shapes* s, const macx_dropout*
                    const float* saved, size_t saved_floats, float* ws, size_t ws_floats, const float* d_new_memory,
                    const macx_param_grads* GP, float* d_memory, float* d_info, float* d_control, void* stream) {
   ModeScope ms(o);
-  CKI(unit_check(o, s, U_WRITE));
+  CKI(unit_check(o, s, true));
   if (!d_new_memory || !d_memory || !d_info || !d_control) return MACX_EINVAL;
-  macx_inputs in;
-  memset(&in, 0, sizeof(in));
-  macx_input_grads GI;
-  memset(&GI, 0, sizeof(GI));
-  UnitGrads ug;
-  ug.d_memory = d_memory; ug.d_info_out = d_info; ug.d_control = d_control;
-  return cell_backward_impl(o, s, dp, P, &in, saved, saved_floats, ws, ws_floats, d_new_memory, nullptr, GP, &GI, 0, U_WRITE, &ug, stream);
+  if (!dp || !P || !saved || !ws || !GP) return MACX_EINVAL;
+  CellBwd r(o, s, dp, P, nullptr, saved, ws, GP, nullptr, stream);
+  CKI(r.check_bwd_buffers(saved_floats, ws_floats, 0));
+  CKI(r.init_state_grads(d_new_memory, nullptr));
+  CKI(r.write_unit_bwd(0));
+  // dL/d(memory) = dwin[:, :d] (+ dm (1 - z) under the gate), dL/d(info), dL/d(control) (the gate's)
+  const size_t wbytes = (size_t)r.d * sizeof(float);
+  CK(dev_copy2d(d_memory, wbytes, ws + r.W.dwin, (size_t)r.win * sizeof(float), wbytes, r.B, r.st));
+  if (o->write_gate) CK(axpy(ws + r.W.tmpBd[3], r.Bd, d_memory, r.st));
+  CK(dev_copy2d(d_info, wbytes, r.dinfo.base, (size_t)r.dinfo.ld * sizeof(float), wbytes, r.B, r.st));
+  CK(dev_copy(d_control, r.DC + r.Bd, r.Bd * sizeof(float), r.st));
+  CKI(r.gate_wgrads());
+  CKI(r.write_linear_wgrads());
+  CKI(r.wb.run(r.st));
+  CK(r.rs.run(r.st));
+  return MACX_OK;
 }
 
 int macx_linear(const float* x1, int k1, const float* x2, int k2, int rows, const float* Wp, const float* b, float bias_const,
