@@ -256,6 +256,91 @@ constexpr int WH_APL = 8 * 2 * 512;         // one plane of a 128-column image
 template <int KW, int JW> constexpr int wh_stage_bytes() { return 2 * (KW + JW) * WH_APL + 256; }   // + the stage's factors
 template <int KW, int JW> constexpr int wh_ring() { return KW + JW == 4 ? 2 : (KW + JW == 3 ? 3 : 4); }
 
+// ---- the stage / fragment / product core shared by wgrad_h2_kernel, sb_h2_kernel and sb_h2w_kernel -------------------------
+// Everything is force-inlined with compile-time trip counts and takes its fragment and accumulator arrays by reference: they
+// stay in registers (wgrad_h2_kernel<2,2,*> holds 128 accumulator registers; see the CONT note on what a spill costs there).
+
+// The slot a lane copies in every data DMA instruction of a stage: (row half q / 32, row (q % 32) / 2, 8-column group q % 2 of
+// the instruction's column tile) -- the lane-linear order of the [half][row][16 columns] tile.
+struct WhSlot {
+  int m, kg;             // stage row 0..31, column group 0 / 1
+  // the lane's row of the stage that starts at row0: rows past the end re-read the last row (finite data, factor 0)
+  __device__ __forceinline__ int row(int row0, int nrows) const { return min(row0 + m, nrows - 1); }
+};
+__device__ __forceinline__ WhSlot wh_slot(int lane) { return WhSlot{(lane >> 5) * 16 + ((lane & 31) >> 1), lane & 1}; }
+
+// the two row halves of one column tile: this lane's 8-element fragment
+__device__ __forceinline__ u32x4 wh_frag(const char* tile, int lane) {
+  const u32x2 lo = tr_read(tile + lane * 8), hi = tr_read(tile + 512 + lane * 8);
+  return u32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+// the G fragments of both planes (hi, lo: `plane` bytes apart) of NC column tiles, brought to the common exponent.  `ft`: the
+// stage's 32 row factors; this lane's reduction rows are 4 g + {0..3} of each row half -> two packed factor pairs per half
+template <int NC>
+__device__ __forceinline__ void wh_load_g(const char* sg, int plane, const uint16_t* ft, int lane, u32x4 (&gf)[2][NC]) {
+  ft += (lane >> 4) * 4;
+  const u32x2 f0 = *reinterpret_cast<const u32x2*>(ft), f1 = *reinterpret_cast<const u32x2*>(ft + 16);
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      u32x4 w = wh_frag(sg + pl * plane + c * 1024, lane);
+      w[0] = pk_mul_f16(w[0], f0[0]); w[1] = pk_mul_f16(w[1], f0[1]);
+      w[2] = pk_mul_f16(w[2], f1[0]); w[3] = pk_mul_f16(w[3], f1[1]);
+      gf[pl][c] = w;
+    }
+}
+// the A fragments of NR row tiles of one plane
+template <int NR>
+__device__ __forceinline__ void wh_load_a(const char* sa, int lane, u32x4 (&af)[NR]) {
+#pragma unroll
+  for (int t = 0; t < NR; ++t) af[t] = wh_frag(sa + t * 1024, lane);
+}
+// one term: an A plane against a G plane
+template <int NR, int NC>
+__device__ __forceinline__ void wh_mfma(const u32x4 (&af)[NR], const u32x4 (&gf)[NC], f32x4 (&acc)[NR][NC]) {
+#pragma unroll
+  for (int t = 0; t < NR; ++t)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[t][c] = mfma_f16(af[t], gf[c], acc[t][c]);
+}
+// The ORDER OF TERMS of a stage, smallest first: A_lo x G_hi ; A_hi x {G_lo, G_hi}.  Plane 0 is hi, plane 1 is lo, so the A
+// planes run 1, 0 and against A plane ap the G planes 1 - ap .. 0.  wh_compute is the whole stage; the PIPE loop of
+// wgrad_h2_kernel runs the same pieces through the same two loops with its barriers and DMA requests in between.
+template <int NR, int NC>
+__device__ __forceinline__ void wh_compute(const char* sa, int a_plane, const char* sg, int g_plane, const uint16_t* ft, int lane,
+                                           f32x4 (&acc)[NR][NC]) {
+  u32x4 gf[2][NC];
+  wh_load_g<NC>(sg, g_plane, ft, lane, gf);
+#pragma unroll
+  for (int ap = 1; ap >= 0; --ap) {
+    u32x4 af[NR];
+    wh_load_a<NR>(sa + ap * a_plane, lane, af);
+#pragma unroll
+    for (int bp = 1 - ap; bp >= 0; --bp) wh_mfma<NR, NC>(af, gf[bp], acc);
+  }
+}
+// A slab leaves through LDS: NT row tiles (16 NT rows x 16 NC columns of a wave's share, from row tile t0) go row-major into the
+// wave's own corner `tw` of the idle ring and are read back as float4, so that a store instruction writes whole row segments
+// (64 NC bytes) instead of 64-byte pieces.  `out`: the share's first element, `ld` floats per row.
+template <int NC> constexpr int wh_slab_ldw() { return 16 * NC + 4; }      // floats per row of wh_store_slab's LDS image
+template <int NT, int NR, int NC>
+__device__ __forceinline__ void wh_store_slab(const f32x4 (&acc)[NR][NC], int t0, float scale, float* tw, float* out, int ld, int lane) {
+  constexpr int LDW = wh_slab_ldw<NC>();
+  constexpr int LPR = 4 * NC, RPI = 64 / LPR;               // lanes per row, rows per store instruction
+#pragma unroll
+  for (int u = 0; u < NT; ++u)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tw[(u * 16 + (lane >> 4) * 4 + e) * LDW + c * 16 + (lane & 15)] = acc[t0 + u][c][e] * scale;
+#pragma unroll
+  for (int i = 0; i < 16 * NT / RPI; ++i) {
+    const int r = i * RPI + lane / LPR, c4 = (lane % LPR) * 4;
+    *reinterpret_cast<f32x4*>(out + (size_t)(t0 * 16 + r) * ld + c4) = *reinterpret_cast<const f32x4*>(tw + r * LDW + c4);
+  }
+}
+
 // one thread per reduction row: the fp16 factor of every (A block, G block) pair
 __global__ __launch_bounds__(256) void wgrad_h2_factors_kernel(TnH2P p0, TnH2P p1) {
   const TnH2P& p = blockIdx.y ? p1 : p0;             // grid.y = 2: the tables of two contractions in one launch
@@ -354,100 +439,69 @@ __global__ __launch_bounds__(512) void wgrad_h2_kernel(TnH2P p0, TnH2P p1) {
     for (int c = 0; c < NC; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- staging: data instruction u of a stage (u = NI wave .. NI wave + NI - 1) fills one column tile: u < 16 KW -> plane
-  //      u / (8 KW), tile u % (8 KW) of A; else plane, tile of G likewise.  Lane q of it copies slot (row half q / 32,
-  //      row (q % 32) / 2, 8-column group 2 tile + q % 2), the lane-linear order of the [half][row][16 columns] tile.
+  //      u / (8 KW), tile u % (8 KW) of A; else plane, tile of G likewise; lane q of it copies its slot (wh_slot) of the tile.
   //      Wave 0 also fetches the stage's factors: lane l < 16 KW JW -> fp16 pair l % 16 of table (l / 16) = (A block, G block).
-  const int sl_m = (lane >> 5) * 16 + ((lane & 31) >> 1), sl_kg = lane & 1;
+  const WhSlot sl = wh_slot(lane);
   const int ft_t = lane < 16 * KW * JW ? (lane >> 4) : 0;
   const uint16_t* ft_src = p.ftab + ((size_t)(tk * KW + ft_t / JW) * gcb + tj * JW + ft_t % JW) * mpad + (lane < 16 * KW * JW ? (lane & 15) * 2 : 0);
-  auto issue = [&](int s_raw) __attribute__((always_inline)) {
+  // stage number -> its first reduction row, this lane's row (tensor ti, row rr of it) and its ring slot ...
+  struct Stage { int m0, mc, ti, rr; char* st; };
+  auto locate = [&](int s_raw) __attribute__((always_inline)) {
     const int ch = min(s_raw, nchunk - 1);
     const int m0 = m_begin + ch * 32;
-    const int mc = min(m0 + sl_m, p.M - 1);               // rows past the end re-read the last row (finite data, factor 0)
-    const int ti = mc / p.R, rr = mc - ti * p.R;
-    const int ar = p.a_mod ? (mc % p.a_mod) : rr;
-    const char* ab = p.A + (p.a_mod ? 0 : (size_t)ti * p.a_stride);
-    const char* gb = p.G + (size_t)ti * p.g_stride;
-    char* st = lds + (s_raw % RING) * STAGE;
+    const int mc = sl.row(m0, p.M);
+    const int ti = mc / p.R;
+    return Stage{m0, mc, ti, mc - ti * p.R, lds + (s_raw % RING) * STAGE};
+  };
+  // ... and data instruction u of it: u < 16 KW reads row ar of the A tensor at ab (dma_a), else row rr of the G tensor at gb (dma_g)
+  auto dma_a = [&](int u, const char* ab, int ar, char* st) __attribute__((always_inline)) {
+    const int pl = u / (8 * KW), ct = u - pl * 8 * KW;
+    dma16b(ab + pl * apb + ((size_t)(tk * 16 * KW + 2 * ct + sl.kg) * Rp + ar) * 16, st + pl * APL + ct * 1024);
+  };
+  auto dma_g = [&](int u, const char* gb, int rr, char* st) __attribute__((always_inline)) {
+    const int ug = u - 16 * KW;
+    const int pl = ug / (8 * JW), ct = ug - pl * 8 * JW;
+    dma16b(gb + pl * gpb + ((size_t)(tj * 16 * JW + 2 * ct + sl.kg) * Rp + rr) * 16, st + 2 * APL + pl * GPL + ct * 1024);
+  };
+  auto issue = [&](int s_raw) __attribute__((always_inline)) {
+    const Stage S = locate(s_raw);
+    const int ar = p.a_mod ? (S.mc % p.a_mod) : S.rr;
+    const char* ab = p.A + (p.a_mod ? 0 : (size_t)S.ti * p.a_stride);
+    const char* gb = p.G + (size_t)S.ti * p.g_stride;
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int u = wave * NI + j;
-      if (u < 16 * KW) {
-        const int pl = u / (8 * KW), ct = u - pl * 8 * KW;
-        dma16b(ab + pl * apb + ((size_t)(tk * 16 * KW + 2 * ct + sl_kg) * Rp + ar) * 16, st + pl * APL + ct * 1024);
-      } else {
-        const int ug = u - 16 * KW;
-        const int pl = ug / (8 * JW), ct = ug - pl * 8 * JW;
-        dma16b(gb + pl * gpb + ((size_t)(tj * 16 * JW + 2 * ct + sl_kg) * Rp + rr) * 16, st + 2 * APL + pl * GPL + ct * 1024);
-      }
+      if (u < 16 * KW) dma_a(u, ab, ar, S.st); else dma_g(u, gb, S.rr, S.st);
     }
-    if (wave == 0) dma4b(reinterpret_cast<const char*>(ft_src + m0), st + DATA);
+    if (wave == 0) dma4b(reinterpret_cast<const char*>(ft_src + S.m0), S.st + DATA);
   };
-  // PIPE: one half of a stage -- part 0 = the G planes + the factors (waves 4 - 7 and wave 0), part 1 = the A planes (waves 0 - 3)
+  // PIPE: one half of a stage -- part 0 = the G planes + the factors (waves 4 - 7 and wave 0), part 1 = the A planes (waves 0 - 3).
+  // It is not issue() under two flags: that form, with its test per instruction u in place of the one wave test around each half,
+  // ran wgrad_h2_kernel<2,2,1> 6 % slower (436 against 411 us alternated on one device) with the same requests in the same order.
   auto issue_part = [&](int s_raw, int part) __attribute__((always_inline)) {
     static_assert(!PIPE || (KW == 2 && JW == 2), "the split issue assumes waves 0-3 stage A and waves 4-7 stage G");
-    const int ch = min(s_raw, nchunk - 1);
-    const int m0 = m_begin + ch * 32;
-    const int mc = min(m0 + sl_m, p.M - 1);
-    const int ti = mc / p.R, rr = mc - ti * p.R;
-    char* st = lds + (s_raw % RING) * STAGE;
+    const Stage S = locate(s_raw);
     if (part == 1) {
       if (wave < 4) {
-        const int ar = p.a_mod ? (mc % p.a_mod) : rr;
-        const char* ab = p.A + (p.a_mod ? 0 : (size_t)ti * p.a_stride);
+        const int ar = p.a_mod ? (S.mc % p.a_mod) : S.rr;
+        const char* ab = p.A + (p.a_mod ? 0 : (size_t)S.ti * p.a_stride);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) {
-          const int u = wave * NI + j;
-          const int pl = u / (8 * KW), ct = u - pl * 8 * KW;
-          dma16b(ab + pl * apb + ((size_t)(tk * 16 * KW + 2 * ct + sl_kg) * Rp + ar) * 16, st + pl * APL + ct * 1024);
-        }
+        for (int j = 0; j < NI; ++j) dma_a(wave * NI + j, ab, ar, S.st);
       }
     } else {
       if (wave >= 4) {
-        const char* gb = p.G + (size_t)ti * p.g_stride;
+        const char* gb = p.G + (size_t)S.ti * p.g_stride;
 #pragma unroll
-        for (int j = 0; j < NI; ++j) {
-          const int ug = wave * NI + j - 16 * KW;
-          const int pl = ug / (8 * JW), ct = ug - pl * 8 * JW;
-          dma16b(gb + pl * gpb + ((size_t)(tj * 16 * JW + 2 * ct + sl_kg) * Rp + rr) * 16, st + 2 * APL + pl * GPL + ct * 1024);
-        }
+        for (int j = 0; j < NI; ++j) dma_g(wave * NI + j, gb, S.rr, S.st);
       }
-      if (wave == 0) dma4b(reinterpret_cast<const char*>(ft_src + m0), st + DATA);
+      if (wave == 0) dma4b(reinterpret_cast<const char*>(ft_src + S.m0), S.st + DATA);
     }
   };
-  auto frag = [&](const char* tile) __attribute__((always_inline)) {       // the two row halves of one column tile
-    const u32x2 lo = tr_read(tile + lane * 8), hi = tr_read(tile + 512 + lane * 8);
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
-  };
-  // smallest terms first: A_lo x G_hi ; A_hi x {G_lo, G_hi}
-  auto compute = [&](int buf) __attribute__((always_inline)) {
-    const char* sa = lds + buf * STAGE + (wr * NR) * 1024;
-    const char* sg = lds + buf * STAGE + 2 * APL + (wc * NC) * 1024;
-    // this lane's reduction rows: 4 g + {0..3} of each row half -> two packed factor pairs per half
-    const uint16_t* ft = reinterpret_cast<const uint16_t*>(lds + buf * STAGE + DATA) + (aq * JW + gq) * 32 + (lane >> 4) * 4;
-    const u32x2 f0 = *reinterpret_cast<const u32x2*>(ft), f1 = *reinterpret_cast<const u32x2*>(ft + 16);
-    u32x4 gf[2][NC];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        u32x4 w = frag(sg + pl * GPL + c * 1024);
-        w[0] = pk_mul_f16(w[0], f0[0]); w[1] = pk_mul_f16(w[1], f0[1]);
-        w[2] = pk_mul_f16(w[2], f1[0]); w[3] = pk_mul_f16(w[3], f1[1]);
-        gf[pl][c] = w;
-      }
-#pragma unroll
-    for (int ap = 1; ap >= 0; --ap) {
-      u32x4 af[NR];
-#pragma unroll
-      for (int t = 0; t < NR; ++t) af[t] = frag(sa + ap * APL + t * 1024);
-#pragma unroll
-      for (int bp = 1 - ap; bp >= 0; --bp)
-#pragma unroll
-        for (int t = 0; t < NR; ++t)
-#pragma unroll
-          for (int c = 0; c < NC; ++c) acc[t][c] = mfma_f16(af[t], gf[bp][c], acc[t][c]);
-    }
+  // this wave's fragments of ring slot `buf`: its NR row tiles of A, its NC column tiles of G, the factors of its (A block, G block)
+  auto tiles_a = [&](int buf) __attribute__((always_inline)) { return lds + buf * STAGE + (wr * NR) * 1024; };
+  auto tiles_g = [&](int buf) __attribute__((always_inline)) { return lds + buf * STAGE + 2 * APL + (wc * NC) * 1024; };
+  auto factors = [&](int buf) __attribute__((always_inline)) {
+    return reinterpret_cast<const uint16_t*>(lds + buf * STAGE + DATA) + (aq * JW + gq) * 32;
   };
 
   if constexpr (PIPE) {
@@ -459,43 +513,22 @@ __global__ __launch_bounds__(512) void wgrad_h2_kernel(TnH2P p0, TnH2P p1) {
       __syncthreads();
 #pragma unroll 1
       for (int s = 0; s < nchunk; ++s) {
+        // wh_compute's pieces in wh_compute's order, with a barrier and a DMA request behind the G reads and behind the last A reads
         const int buf = s & 1;
-        const char* sa = lds + buf * STAGE + (wr * NR) * 1024;
-        const char* sg = lds + buf * STAGE + 2 * APL + (wc * NC) * 1024;
-        const uint16_t* ft = reinterpret_cast<const uint16_t*>(lds + buf * STAGE + DATA) + (aq * JW + gq) * 32 + (lane >> 4) * 4;
-        const u32x2 f0 = *reinterpret_cast<const u32x2*>(ft), f1 = *reinterpret_cast<const u32x2*>(ft + 16);
+        const char* sa = tiles_a(buf);
         u32x4 gf[2][NC];
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            u32x4 w = frag(sg + pl * GPL + c * 1024);
-            w[0] = pk_mul_f16(w[0], f0[0]); w[1] = pk_mul_f16(w[1], f0[1]);
-            w[2] = pk_mul_f16(w[2], f1[0]); w[3] = pk_mul_f16(w[3], f1[1]);
-            gf[pl][c] = w;
-          }
+        wh_load_g<NC>(tiles_g(buf), GPL, factors(buf), lane, gf);
         __syncthreads();                                    // every wave holds its G fragments and factors: the G half is free
         if (!(p.dbg & 2048)) issue_part(s + 2, 0);
         u32x4 af[NR];
-#pragma unroll
-        for (int t = 0; t < NR; ++t) af[t] = frag(sa + APL + t * 1024);          // A lo
-        if (!(p.dbg & 1024)) {
-#pragma unroll
-          for (int t = 0; t < NR; ++t)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[t][c] = mfma_f16(af[t], gf[0][c], acc[t][c]);   // A_lo x G_hi
-        }
-#pragma unroll
-        for (int t = 0; t < NR; ++t) af[t] = frag(sa + t * 1024);                // A hi
+        wh_load_a<NR>(sa + APL, lane, af);                  // A lo
+        if (!(p.dbg & 1024)) wh_mfma<NR, NC>(af, gf[0], acc);                    // A_lo x G_hi
+        wh_load_a<NR>(sa, lane, af);                        // A hi
         __syncthreads();                                    // every wave holds its last A fragments: the A half is free
         if (!(p.dbg & 2048)) issue_part(s + 2, 1);
         if (!(p.dbg & 1024)) {
-#pragma unroll
-          for (int bp = 1; bp >= 0; --bp)
-#pragma unroll
-            for (int t = 0; t < NR; ++t)
-#pragma unroll
-              for (int c = 0; c < NC; ++c) acc[t][c] = mfma_f16(af[t], gf[bp][c], acc[t][c]);   // A_hi x G_lo, A_hi x G_hi
+          wh_mfma<NR, NC>(af, gf[1], acc);                  // A_hi x G_lo
+          wh_mfma<NR, NC>(af, gf[0], acc);                  // A_hi x G_hi
         }
         if (p.dbg & 2048) wait_vmcnt<0>(); else wait_vmcnt_n(my_n);              // stage s + 1 has landed (s + 2 may fly)
         __syncthreads();
@@ -512,7 +545,7 @@ __global__ __launch_bounds__(512) void wgrad_h2_kernel(TnH2P p0, TnH2P p1) {
 #pragma unroll 1
     for (int s = 0; s < nchunk; ++s) {
       if (!(p.dbg & 2048)) issue(s + RING - 1);           // ring slot (s - 1) % RING was last read in iteration s - 1
-      if (!(p.dbg & 1024)) compute(s % RING);
+      if (!(p.dbg & 1024)) wh_compute<NR, NC>(tiles_a(s % RING), APL, tiles_g(s % RING), GPL, factors(s % RING), lane, acc);
       wait_vmcnt_n(my_n);                                 // stage s + 1 has landed
       __syncthreads();
     }
@@ -521,76 +554,53 @@ __global__ __launch_bounds__(512) void wgrad_h2_kernel(TnH2P p0, TnH2P p1) {
 
   __syncthreads();                                        // every wave's DMA has landed: the ring is about to be reused
 
-  // ---- the slab leaves through LDS, 32 rows of the wave's share at a time (row-major in the wave's own corner of the idle
-  //      ring, read back as float4): a store instruction writes whole 128 / 256-byte row segments instead of 64-byte pieces
+  // ---- the slab leaves through LDS, 32 rows of the wave's share at a time
   const float sc = h2_unscale(h2_emin_final(p.ecomA, p.ecom_nb, tk * KW + aq), h2_emin_final(p.ecomG, p.ecom_nb, tj * JW + gq));
   float* out = p.part + (size_t)split * p.Kd * p.Jd + (size_t)(tk * KT + wr * 16 * NR) * p.Jd + tj * JT + wc * 32 * JW;
-  constexpr int CW = 32 * JW, LDW = CW + 4;
-  constexpr int LPR = CW / 4, RPI = 64 / LPR;             // lanes per row, rows per store instruction
-  float* tw = reinterpret_cast<float*>(lds) + wave * (32 * LDW);
+  float* tw = reinterpret_cast<float*>(lds) + wave * (32 * wh_slab_ldw<NC>());
 #pragma unroll
-  for (int tp = 0; tp < NR; tp += 2) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tw[(u * 16 + (lane >> 4) * 4 + e) * LDW + c * 16 + (lane & 15)] = acc[tp + u][c][e] * sc;
-#pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
-      const int r = i * RPI + lane / LPR, c4 = (lane % LPR) * 4;
-      f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)(tp * 16 + r) * p.Jd + c4);
-      f32x4 val = *reinterpret_cast<const f32x4*>(tw + r * LDW + c4);
-      *dst = val;
-    }
-  }
+  for (int tp = 0; tp < NR; tp += 2) wh_store_slab<2>(acc, tp, sc, tw, out, p.Jd, lane);
 }
 
 inline int wgrad_h2_jw(int Jd) { return (Jd % 256 == 0) ? 2 : 1; }
 inline int wgrad_h2_kw(int Kd) { return (Kd % 256 == 0) ? 2 : 1; }
 inline int wgrad_h2_tiles(int Kd, int Jd) { return (Kd / (wgrad_h2_kw(Kd) * T_TILE)) * (Jd / (wgrad_h2_jw(Jd) * T_TILE)); }
 
+// the factor tables of ny = 1 (a alone) or 2 (a and b) contractions
+inline hipError_t wgrad_h2_factors_launch(const TnH2P& a, const TnH2P& b, int ny, hipStream_t st) {
+  if (a.rows_per_split % 32 != 0 || !a.ftab || !b.ftab) return hipErrorInvalidValue;
+  const size_t mpad = wgrad_h2_mpad((size_t)a.M);
+  hipLaunchKernelGGL(wgrad_h2_factors_kernel, dim3((unsigned)((mpad + 255) / 256), ny), dim3(256), 0, st, a, b);
+  return hipGetLastError();
+}
+// ... and the contractions themselves (grid.y = ny), a's shape and split
 template <int KW, int JW, int PIPE = 0>
-inline hipError_t wgrad_h2_launch_t(const TnH2P& p, hipStream_t st) {
+inline hipError_t wgrad_h2_launch_t(const TnH2P& a, const TnH2P& b, int ny, hipStream_t st) {
   auto kern = wgrad_h2_kernel<KW, JW, PIPE>;
   constexpr size_t lds = (size_t)wh_ring<KW, JW>() * wh_stage_bytes<KW, JW>();
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);
   if (e != hipSuccess) return e;
-  const int grid = wgrad_h2_tiles(p.Kd, p.Jd) * p.nsplit;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p, p);
+  hipLaunchKernelGGL(kern, dim3(wgrad_h2_tiles(a.Kd, a.Jd) * a.nsplit, ny), dim3(512), lds, st, a, b);
   return hipGetLastError();
+}
+inline hipError_t wgrad_h2_launch(const TnH2P& p, hipStream_t st) {
+  hipError_t e = wgrad_h2_factors_launch(p, p, 1, st);
+  if (e != hipSuccess) return e;
+  const int kw = wgrad_h2_kw(p.Kd), jw = wgrad_h2_jw(p.Jd);
+  if (kw == 2 && jw == 2) return wgrad_pipe_mode() ? wgrad_h2_launch_t<2, 2, 1>(p, p, 1, st) : wgrad_h2_launch_t<2, 2, 0>(p, p, 1, st);
+  if (kw == 2) return wgrad_h2_launch_t<2, 1>(p, p, 1, st);
+  return jw == 2 ? wgrad_h2_launch_t<1, 2>(p, p, 1, st) : wgrad_h2_launch_t<1, 1>(p, p, 1, st);
 }
 // two contractions with the same M, Kd, Jd and split (own operands, tables and slabs) as one launch each of the factor and the
 // contraction kernel; wgrad_pipe_mode() < 2 or another tile shape: two launches each
-inline hipError_t wgrad_h2_launch(const TnH2P& p, hipStream_t st);
 inline hipError_t wgrad_h2_launch_pair(const TnH2P& a, const TnH2P& b, hipStream_t st) {
   const bool same = a.M == b.M && a.Kd == b.Kd && a.Jd == b.Jd && a.nsplit == b.nsplit && a.rows_per_split == b.rows_per_split && a.R == b.R;
   if (!(same && wgrad_pipe_mode() >= 2 && wgrad_h2_kw(a.Kd) == 2 && wgrad_h2_jw(a.Jd) == 2 && a.ftab != b.ftab && a.part != b.part)) {
     hipError_t e = wgrad_h2_launch(a, st);
     return e != hipSuccess ? e : wgrad_h2_launch(b, st);
   }
-  if (a.rows_per_split % 32 != 0 || !a.ftab || !b.ftab) return hipErrorInvalidValue;
-  const size_t mpad = wgrad_h2_mpad((size_t)a.M);
-  hipLaunchKernelGGL(wgrad_h2_factors_kernel, dim3((unsigned)((mpad + 255) / 256), 2), dim3(256), 0, st, a, b);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  auto kern = wgrad_h2_kernel<2, 2, 1>;
-  constexpr size_t lds = (size_t)wh_ring<2, 2>() * wh_stage_bytes<2, 2>();
-  e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(wgrad_h2_tiles(a.Kd, a.Jd) * a.nsplit, 2), dim3(512), lds, st, a, b);
-  return hipGetLastError();
-}
-inline hipError_t wgrad_h2_launch(const TnH2P& p, hipStream_t st) {
-  if (p.rows_per_split % 32 != 0 || !p.ftab) return hipErrorInvalidValue;
-  const size_t mpad = wgrad_h2_mpad((size_t)p.M);
-  hipLaunchKernelGGL(wgrad_h2_factors_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, st, p, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const int kw = wgrad_h2_kw(p.Kd), jw = wgrad_h2_jw(p.Jd);
-  if (kw == 2 && jw == 2) return wgrad_pipe_mode() ? wgrad_h2_launch_t<2, 2, 1>(p, st) : wgrad_h2_launch_t<2, 2, 0>(p, st);
-  if (kw == 2) return wgrad_h2_launch_t<2, 1>(p, st);
-  return jw == 2 ? wgrad_h2_launch_t<1, 2>(p, st) : wgrad_h2_launch_t<1, 1>(p, st);
+  hipError_t e = wgrad_h2_factors_launch(a, b, 2, st);
+  return e != hipSuccess ? e : wgrad_h2_launch_t<2, 2, 1>(a, b, 2, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -670,22 +680,20 @@ __global__ __launch_bounds__(512) void sb_h2_kernel(SbH2P p) {
   const int rows_q = nchunk * 32;                         // table rows per question (rows past N hold factor 0)
 
   // ---- staging: instruction u of a stage (u = 4 wave .. 4 wave + 3) fills column tile u & 7 of image u >> 3
-  //      (0: X hi, 1: X lo, 2: dI1 hi, 3: dI1 lo); lane q of it copies slot (row half q / 32, row (q % 32) / 2, 8-column group
-  //      2 (u & 7) + q % 2), the lane-linear order of the [half][row][16 columns] tile
-  const int sl_half = lane >> 5, sl_row = (lane & 31) >> 1, sl_kg = lane & 1;
-  const int sl_m = sl_half * 16 + sl_row;                 // stage row of this lane's slot
+  //      (0: X hi, 1: X lo, 2: dI1 hi, 3: dI1 lo); lane q of it copies its slot (wh_slot) of the tile
+  const WhSlot sl = wh_slot(lane);
   auto issue = [&](int s_raw) __attribute__((always_inline)) {
     const int s = min(s_raw, total - 1);
     const int qi = s / nchunk, ch = s - qi * nchunk;
-    const int n = min(ch * 32 + sl_m, p.N - 1);           // rows past the end re-read the last row (finite data, factor 0)
+    const int n = sl.row(ch * 32, p.N);
     const size_t row = (size_t)(b_begin + qi) * p.N + n;
     char* st = lds + (s_raw % SBH_RING) * SBH_STAGE;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int u = wave * 4 + j;
       const int im = u >> 3, ct = u & 7;
-      const char* src = (im < 2 ? vX.base + (im & 1) * xpb + ((size_t)(tk * 16 + 2 * ct + sl_kg) * Rp + row) * 16
-                                : vG.base + (im & 1) * gpb + ((size_t)(tj * 16 + 2 * ct + sl_kg) * Rp + row) * 16);
+      const char* src = (im < 2 ? vX.base + (im & 1) * xpb + ((size_t)(tk * 16 + 2 * ct + sl.kg) * Rp + row) * 16
+                                : vG.base + (im & 1) * gpb + ((size_t)(tj * 16 + 2 * ct + sl.kg) * Rp + row) * 16);
       dma16b(src, st + im * WH_APL + ct * 1024);
     }
   };
@@ -734,39 +742,10 @@ __global__ __launch_bounds__(512) void sb_h2_kernel(SbH2P p) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) accS[t][c] = accA[t][c] = accB[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto frag = [&](const char* tile) __attribute__((always_inline)) {
-    const u32x2 lo = tr_read(tile + lane * 8), hi = tr_read(tile + 512 + lane * 8);
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
-  };
-  // smallest terms first: X_lo x dI1_hi ; X_hi x {dI1_lo, dI1_hi}
+  // one stage: this wave's 4 row tiles of X against its 2 column tiles of dI1, factors of rows ch * 32 .. of question qi
   auto compute = [&](int buf, int qi, int ch) __attribute__((always_inline)) {
-    const char* sa = lds + buf * SBH_STAGE + (wr * 4) * 1024;
-    const char* sg = lds + buf * SBH_STAGE + 2 * WH_APL + (wc * 2) * 1024;
-    // this lane's reduction rows: 4 g + {0..3} of each row half -> two packed factor pairs per half
-    const uint16_t* ft = ftab + qi * rows_q + ch * 32 + (lane >> 4) * 4;
-    const u32x2 f0 = *reinterpret_cast<const u32x2*>(ft), f1 = *reinterpret_cast<const u32x2*>(ft + 16);
-    u32x4 gf[2][2];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        u32x4 w = frag(sg + pl * WH_APL + c * 1024);
-        w[0] = pk_mul_f16(w[0], f0[0]); w[1] = pk_mul_f16(w[1], f0[1]);
-        w[2] = pk_mul_f16(w[2], f1[0]); w[3] = pk_mul_f16(w[3], f1[1]);
-        gf[pl][c] = w;
-      }
-#pragma unroll
-    for (int ap = 1; ap >= 0; --ap) {
-      u32x4 af[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) af[t] = frag(sa + ap * WH_APL + t * 1024);
-#pragma unroll
-      for (int bp = 1 - ap; bp >= 0; --bp)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int c = 0; c < 2; ++c) accS[t][c] = mfma_f16(af[t], gf[bp][c], accS[t][c]);
-    }
+    const char* st = lds + buf * SBH_STAGE;
+    wh_compute<4, 2>(st + (wr * 4) * 1024, WH_APL, st + 2 * WH_APL + (wc * 2) * 1024, WH_APL, ftab + qi * rows_q + ch * 32, lane, accS);
   };
   // this wave's 64 x 32 share of W1a stays in registers for the whole kernel (32 per lane; the staging needs none) and y_b
   // comes from the LDS table: the per-question fold has no global load to wait for, so it does not drain the DMA queue
@@ -849,7 +828,9 @@ __global__ __launch_bounds__(512) void sb_h2_kernel(SbH2P p) {
   }   // step
 
   // ---- the two slabs leave through LDS: a wave's 64 x 32 share row-major in its own 9 KB of the (now idle) ring, read back
-  //      as float4 so that a store instruction writes 8 rows x 128 contiguous bytes instead of 64-byte pieces
+  //      as float4 so that a store instruction writes 8 rows x 128 contiguous bytes instead of 64-byte pieces.  This is
+  //      wh_store_slab<4>'s pattern written out: through the helper the DY instantiation takes 235 registers instead of 225.
+  //      (dy itself does not come this way: it is per question and leaves from consume(), 16-lane sums stored as they are made.)
   float* oa = p.dW1a_part + (size_t)group * p.d * p.d;
   float* ob = p.dW1b_part + (size_t)group * p.d * p.d;
   constexpr int LDW = 36;
@@ -944,25 +925,25 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
 
   // ---- staging: 48 column tiles of 16 per stage (X: 2 planes x 8, dI1: 2 planes x 16).  Wave w copies X tiles 2 w, 2 w + 1
   //      and dI1 tiles 4 w .. 4 w + 3 (tile = plane * tiles-per-plane + column tile); every one of its six instructions is a
-  //      wave-uniform base + the SAME per-lane offset (slot of row sl_m, column group sl_kg of the tile): one address register
-  const int sl_half = lane >> 5, sl_row = (lane & 31) >> 1, sl_kg = lane & 1;
-  const int sl_m = sl_half * 16 + sl_row;
+  //      wave-uniform base + the SAME per-lane offset (its slot of the tile, wh_slot): one address register.
+  //      issue(): ring slot s_raw % SBW_RING <- stage s (question s / nchunk, rows 32 (s % nchunk) ..) of the step whose X / dI1
+  //      lie at xb / gb
+  const WhSlot sl = wh_slot(lane);
   const uint32_t lds0 = lds_addr_of(lds);
-  auto issue = [&](int s_raw) __attribute__((always_inline)) {
-    const int s = min(s_raw, total - 1);
+  auto issue = [&](int s_raw, int s, const char* xb, const char* gb) __attribute__((always_inline)) {
     const int qi = s / nchunk, ch = s - qi * nchunk;
-    const int n = min(ch * 32 + sl_m, p.N - 1);
-    const uint32_t voff = (uint32_t)(((size_t)sl_kg * Rp + (size_t)(b_begin + qi) * p.N + n) * 16);
+    const int n = sl.row(ch * 32, p.N);
+    const uint32_t voff = (uint32_t)(((size_t)sl.kg * Rp + (size_t)(b_begin + qi) * p.N + n) * 16);
     const uint32_t st = lds0 + (uint32_t)((s_raw % SBW_RING) * SBW_STAGE);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int u = wave * 2 + j, pl = u >> 3, ct = u & 7;
-      dma16b_s(vX.base + pl * xpb + (size_t)(tk * 16 + 2 * ct) * Rp * 16, voff, st + pl * WH_APL + ct * 1024);
+      dma16b_s(xb + pl * xpb + (size_t)(tk * 16 + 2 * ct) * Rp * 16, voff, st + pl * WH_APL + ct * 1024);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int u = wave * 4 + j, pl = u >> 4, ct = u & 15;
-      dma16b_s(vG.base + pl * gpb + (size_t)(tj * 32 + 2 * ct) * Rp * 16, voff, st + 2 * WH_APL + pl * 2 * WH_APL + ct * 1024);
+      dma16b_s(gb + pl * gpb + (size_t)(tj * 32 + 2 * ct) * Rp * 16, voff, st + 2 * WH_APL + pl * 2 * WH_APL + ct * 1024);
     }
   };
   // per step: the questions' common exponents (integer minima through LDS), the combined row factors (one table per dI1
@@ -1015,37 +996,11 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) accT[t][c] = accA[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto frag = [&](const char* tile) __attribute__((always_inline)) {
-    const u32x2 lo = tr_read(tile + lane * 8), hi = tr_read(tile + 512 + lane * 8);
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
-  };
+  // one stage: this wave's 4 row tiles of X against its 4 column tiles of dI1, factors of its dI1 block in the table set in use
   auto compute = [&](int buf, int qi, int ch) __attribute__((always_inline)) {
-    const char* sa = lds + buf * SBW_STAGE + (wr * 4) * 1024;
-    const char* sg = lds + buf * SBW_STAGE + 2 * WH_APL + (wc * 4) * 1024;
-    const uint16_t* ft = ftab_c + gq * (SBW_MAXROWS / 2) + qi * rows_q + ch * 32 + (lane >> 4) * 4;
-    const u32x2 f0 = *reinterpret_cast<const u32x2*>(ft), f1 = *reinterpret_cast<const u32x2*>(ft + 16);
-    u32x4 gf[2][4];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        u32x4 w = frag(sg + pl * 2 * WH_APL + c * 1024);
-        w[0] = pk_mul_f16(w[0], f0[0]); w[1] = pk_mul_f16(w[1], f0[1]);
-        w[2] = pk_mul_f16(w[2], f1[0]); w[3] = pk_mul_f16(w[3], f1[1]);
-        gf[pl][c] = w;
-      }
-#pragma unroll
-    for (int ap = 1; ap >= 0; --ap) {                     // smallest terms first: X_lo x dI1_hi ; X_hi x {dI1_lo, dI1_hi}
-      u32x4 af[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) af[t] = frag(sa + ap * WH_APL + t * 1024);
-#pragma unroll
-      for (int bp = 1 - ap; bp >= 0; --bp)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) accT[t][c] = mfma_f16(af[t], gf[bp][c], accT[t][c]);
-    }
+    const char* st = lds + buf * SBW_STAGE;
+    wh_compute<4, 4>(st + (wr * 4) * 1024, WH_APL, st + 2 * WH_APL + (wc * 4) * 1024, 2 * WH_APL,
+                     ftab_c + gq * (SBW_MAXROWS / 2) + qi * rows_q + ch * 32, lane, accT);
   };
   // the fold of the question that just ended, run when the next one (its y in `ynext`, its unit exponent `e_next`) starts:
   //   dW1a += (y_k - y_next) * T_k * 2^-e_k ;  T_k (unit 2^-e_k) -> unit 2^-e_next
@@ -1083,25 +1038,10 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
 
   if constexpr (CONT) {
     const int G = p.nsteps * total;
-    auto issue_g = [&](int g_raw) __attribute__((always_inline)) {
+    auto issue_g = [&](int g_raw) __attribute__((always_inline)) {        // stage g of the stream: stage g % total of step g / total
       const int g = min(g_raw, G - 1);
-      const int ist = g / total, sg = g - ist * total;
-      const int qi = sg / nchunk, ch = sg - qi * nchunk;
-      const int n = min(ch * 32 + sl_m, p.N - 1);
-      const uint32_t voff = (uint32_t)(((size_t)sl_kg * Rp + (size_t)(b_begin + qi) * p.N + n) * 16);
-      const uint32_t st = lds0 + (uint32_t)((g_raw % SBW_RING) * SBW_STAGE);
-      const char* xb = p.X.base + (size_t)ist * p.x_step;
-      const char* gb = p.dI1.base + (size_t)ist * p.g_step;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int u = wave * 2 + j, pl = u >> 3, ct = u & 7;
-        dma16b_s(xb + pl * xpb + (size_t)(tk * 16 + 2 * ct) * Rp * 16, voff, st + pl * WH_APL + ct * 1024);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int u = wave * 4 + j, pl = u >> 4, ct = u & 15;
-        dma16b_s(gb + pl * gpb + (size_t)(tj * 32 + 2 * ct) * Rp * 16, voff, st + 2 * WH_APL + pl * 2 * WH_APL + ct * 1024);
-      }
+      const int ist = g / total;
+      issue(g_raw, g - ist * total, p.X.base + (size_t)ist * p.x_step, p.dI1.base + (size_t)ist * p.g_step);
     };
     issue_g(0);
     issue_g(1);
@@ -1192,7 +1132,8 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
   for (int step = 0; step < p.nsteps; ++step) {
     vX.base = p.X.base + (size_t)step * p.x_step; vG.base = p.dI1.base + (size_t)step * p.g_step;
     yS = p.y + (size_t)step * p.y_step;
-    if (total > 0) { issue(0); issue(1); }
+    auto issue_s = [&](int s_raw) __attribute__((always_inline)) { issue(s_raw, min(s_raw, total - 1), vX.base, vG.base); };
+    if (total > 0) { issue_s(0); issue_s(1); }
     tables();
     if (total > 0) {
       wait_vmcnt<6>();                                      // stage 0 has landed (stage 1 may be in flight)
@@ -1200,7 +1141,7 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
       int qi = 0, qch = 0;
 #pragma unroll 1
       for (int s = 0; s < total; ++s) {
-        if (!(p.dbg & 2048)) issue(s + 2);                  // ring slot (s + 2) % 3 was last read in iteration s - 1
+        if (!(p.dbg & 2048)) issue_s(s + 2);                // ring slot (s + 2) % 3 was last read in iteration s - 1
         if (qch == 0) {
           // a question starts: the fold of the one before it (none in front of the very first), or just its y and unit
           const float* yn = ytab + qi * T_TILE;
@@ -1226,27 +1167,11 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
   if (pending && !(p.dbg & 512)) fold(nullptr, ex_prev, eg_prev);     // y_{K+1} = 0; T stays in its unit
   const float scT = h2_unscale(ex_prev, eg_prev);
 
-  // ---- the two slabs leave through LDS (a wave's 64 x 64 share row-major in its own 17 KB of the idle ring)
-  float* oa = p.dW1a_part + (size_t)group * p.d * p.d;
-  float* ob = p.dW1b_part + (size_t)group * p.d * p.d;
-  constexpr int LDW = 68;
-  float* tw = reinterpret_cast<float*>(lds) + wave * (64 * LDW);
-#pragma unroll
-  for (int which = 0; which < 2; ++which) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          tw[(t * 16 + (lane >> 4) * 4 + e) * LDW + c * 16 + (lane & 15)] = which ? accT[t][c][e] * scT : accA[t][c][e];
-    float* o = (which ? ob : oa) + (size_t)(tk * T_TILE + wr * 64) * p.d + tj * 2 * T_TILE + wc * 64;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int r = i * 4 + (lane >> 4), c4 = (lane & 15) * 4;
-      *reinterpret_cast<f32x4*>(o + (size_t)r * p.d + c4) = *reinterpret_cast<const f32x4*>(tw + r * LDW + c4);
-    }
-  }
+  // ---- the two slabs leave through LDS, a wave's 64 x 64 share in one pass (17 KB of the idle ring per wave)
+  float* tw = reinterpret_cast<float*>(lds) + wave * (64 * wh_slab_ldw<4>());
+  const size_t o = (size_t)group * p.d * p.d + (size_t)(tk * T_TILE + wr * 64) * p.d + tj * 2 * T_TILE + wc * 64;
+  wh_store_slab<4>(accA, 0, 1.f, tw, p.dW1a_part + o, p.d, lane);      // scale 1: dW1a is already in its unit (x * 1.f is x)
+  wh_store_slab<4>(accT, 0, scT, tw, p.dW1b_part + o, p.d, lane);
 }
 
 inline bool sb_h2_wide_ok(int B, int N, int d) { return d % 256 == 0 && B >= 1 && N >= 1 && ((N + 31) / 32) * 32 <= SBW_MAXROWS / 2; }
