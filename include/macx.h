@@ -11,7 +11,8 @@
  *     question lengths int32.  All pointers are DEVICE pointers unless marked host.
  *   - ownership: the caller owns every buffer (parameters, inputs, `saved`, `ws`, gradients).
  *     The library never allocates, frees or retains device memory.
- *   - asynchronous: work is enqueued on `stream`; nothing synchronises the device.
+ *   - asynchronous: work is enqueued on `stream`; nothing synchronises the device (the timing hooks, macx_run_status and
+ *     macx_handoff_selftest say so where they do).
  *   - errors: 0 on success, a negative MACX_E* code for a rejected call, or the positive
  *     hipError_t of a failed launch.  No exceptions, no abort().
  *   - determinism: no floating-point atomics anywhere; weight gradients use fixed-order
@@ -34,7 +35,8 @@ enum {
   MACX_EINVAL = -1,      /* malformed shapes / null pointer / misaligned pointer            */
   MACX_EUNSUPPORTED = -2,/* legal reference option combination without a HIP path yet       */
   MACX_EREJECTED = -3,   /* option value that raises in the reference   */
-  MACX_ESMALL = -4       /* `saved` or `ws` smaller than macx_saved_floats / macx_ws_floats */
+  MACX_ESMALL = -4,      /* `saved` or `ws` smaller than macx_saved_floats / macx_ws_floats */
+  MACX_EWAIT = -5        /* macx_run_status: a workgroup gave up waiting for another one of its own launch; the run is poisoned */
 };
 
 /* activation codes (ops.py:181-187; "RELU" resolves through config.relu, ops.py:161-179) */
@@ -206,7 +208,8 @@ enum {
   MACX_SEG_ATT_KB = 4,     /* [p,B,N]    attentions["kb"]                     (mac_cell.py:268)     */
   MACX_SEG_ATT_SELF = 5,   /* [p,B,p]    attentions["self"], row i uses i+1   (mac_cell.py:329)     */
   MACX_SEG_ATT_GATE = 6,   /* [p,B,d|1]  attentions["gate"]                   (mac_cell.py:365)     */
-  MACX_SEG_COUNT = 7
+  MACX_SEG_STATUS = 7,     /* 16 uint32 words (not floats): the run's hand-off status, see macx_run_status           */
+  MACX_SEG_COUNT = 8
 };
 
 /* ---- sizing -------------------------------------------------------------------------------- */
@@ -219,6 +222,32 @@ int macx_saved_segment(const macx_opts*, const macx_shapes*, int keep_activation
                        size_t* offset, size_t* count);
 /* validates an option/shape combination exactly as macx_cell_begin would */
 int macx_check(const macx_opts*, const macx_shapes*);
+
+/* ---- did the run's in-launch hand-offs complete? ------------------------------------------------ */
+/* In the default d = 512 path (macx_cell_forward, MACX_TUNE_PRE_FILL) workgroups of ONE launch hand results to each other through
+ * counters; the waits are bounded.  A workgroup whose wait runs out does not use the unfinished data: it computes on quiet NaNs, so
+ * the run's final memory and every gradient derived from it are NaN, and it reports into 16 status words of `saved`
+ * (MACX_SEG_STATUS, directly in front of the run's counters):
+ *   word 0  bits: 1 = a tile gave up waiting for its step's projected memory y, 2 = a filler workgroup gave up waiting for the
+ *           previous step's write unit;   word 1  1 + the step of the first give-up (0: none);   the rest: spare.
+ * The words are STICKY: macx_cell_begin does not touch them (a captured step replayed on one `saved` keeps the evidence), nothing
+ * but the reset call clears them.  Contract: reset once after allocating `saved` and again after handling an error.
+ * The arguments before `saved` are those of the sizing calls (they locate the words); `saved` smaller than macx_saved_floats is
+ * MACX_ESMALL, a null `saved` MACX_EINVAL.
+ *   macx_run_status        copies the words to the host on `stream` and SYNCHRONISES that stream (the one cell entry point that
+ *                          does): MACX_OK when word 0 is 0, else MACX_EWAIT.  *host_status = word 0, *host_first_step = the step or
+ *                          -1; either pointer may be NULL.  On a stream that is being captured: the hipError_t of the refusal.
+ *   macx_run_status_reset  zeroes the words: one launch, asynchronous, capturable.
+ *   macx_handoff_selftest  runs the kernels' wait routine on words of its own (allocated and freed inside the call -- the one
+ *                          exception to "never allocates"), twice, and synchronises: a counter that already holds the wanted value,
+ *                          then one that holds less, waited for with a budget of 0 polls.  host_out[8] = per call {arrived,
+ *                          status bits, step word (1 + step), every thread of the workgroup was told to poison}: {1,0,0,0} and
+ *                          {0,2,7,1}.  The give-up branch of a real run cannot be tested without making a run fail. */
+int macx_run_status(const macx_opts*, const macx_shapes*, int keep_activations, const float* saved, size_t saved_floats,
+                    void* stream, uint32_t* host_status, int32_t* host_first_step);
+int macx_run_status_reset(const macx_opts*, const macx_shapes*, int keep_activations, float* saved, size_t saved_floats,
+                          void* stream);
+int macx_handoff_selftest(void* stream, uint32_t* host_out /* host, [8] */);
 
 /* ---- the cell ------------------------------------------------------------------------------ */
 /* Replaces MACCell.zero_state (mac_cell.py:539-592): initial control/memory, histories, memory

@@ -10,11 +10,15 @@ from . import build as _build
 
 ABI_VERSION = 5
 
-MACX_OK, MACX_EINVAL, MACX_EUNSUPPORTED, MACX_EREJECTED, MACX_ESMALL = 0, -1, -2, -3, -4
+MACX_OK, MACX_EINVAL, MACX_EUNSUPPORTED, MACX_EREJECTED, MACX_ESMALL, MACX_EWAIT = 0, -1, -2, -3, -4, -5
+# macx_run_status word 0 (include/macx.h): which in-launch hand-off wait gave up
+HANDOFF_BITS = {1: "a chain tile gave up waiting for its step's y", 2: "a filler workgroup gave up waiting for the previous step's write unit"}
+STATUS_WORDS = 16
 ACT = {"NON": 0, "TANH": 1, "SIGMOID": 2, "ELU": 3, "RELU": 4}
 INIT = {"PRM": 0, "ZERO": 1, "Q": 2}
 WRITE_INPUTS = {"MEM": 0, "INFO": 1, "SUM": 2, "BOTH": 3}
-SEG = {"controls": 0, "memories": 1, "infos": 2, "att_question": 3, "att_kb": 4, "att_self": 5, "att_gate": 6}
+SEG = {"controls": 0, "memories": 1, "infos": 2, "att_question": 3, "att_kb": 4, "att_self": 5, "att_gate": 6,
+       "status": 7}
 
 
 class MacxOpts(C.Structure):
@@ -137,7 +141,7 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_control_attend_bwd_ws_floats", "macx_read_fwd", "macx_read_bwd",
            "macx_write_fwd", "macx_write_bwd", "macx_read_chain_time", "macx_cell_forward_chain_time", "macx_saved_activation", "macx_ctrl_inputs_ws_floats",
            "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd", "macx_conv2d_ws_floats", "macx_conv2d_fwd", "macx_conv2d_bwd_data",
-           "macx_conv2d_wgrad")
+           "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest")
 
 _lib = None
 
@@ -147,6 +151,18 @@ class MacxError(RuntimeError):
         self.code = code
         msg = lib().macx_strerror(code).decode() if _lib is not None else str(code)
         super().__init__("%s failed: %s (code %d)" % (where, msg, code))
+
+
+class HandoffTimeout(RuntimeError):
+    """A run's in-launch hand-off wait gave up (macx_run_status returned MACX_EWAIT): the run's final memory and gradients are
+    NaN.  `bits`: the status word (HANDOFF_BITS), `first_step`: the step of the first give-up.  The status is sticky: clear it
+    with the cell's / captured step's reset_status() once the error is handled."""
+
+    def __init__(self, bits, first_step, where="MAC cell run"):
+        self.bits, self.first_step = int(bits), int(first_step)
+        what = [t for b, t in sorted(HANDOFF_BITS.items()) if self.bits & b] or ["unknown bits"]
+        super().__init__("%s: in-launch hand-off timeout (status 0x%x: %s; first at step %d); the run's results are NaN"
+                         % (where, self.bits, "; ".join(what), self.first_step))
 
 
 def lib():
@@ -230,6 +246,9 @@ def lib():
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("macx_check",):
             f.restype = C.c_int
+    L.macx_run_status.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_uint32), P(C.c_int32)]
+    L.macx_run_status_reset.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.macx_handoff_selftest.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.macx_conv2d_ws_floats.argtypes = [P(MacxConvShapes)]
     L.macx_conv2d_fwd.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.macx_conv2d_bwd_data.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -85,6 +85,35 @@ class _Run:
                                       questionLengths=cell.questionLengths.data_ptr(),
                                       knowledgeBase=cell.knowledgeBase.data_ptr())
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # the hand-off status words of `saved` are sticky (macx_run_status): zero them once, here.  Not inside a graph capture -- the
+        # status must survive replays -- so a run allocated under capture is reset by its capturer afterwards (graph.py)
+        self.status_reset_pending = torch.cuda.is_current_stream_capturing()
+        if not self.status_reset_pending:
+            self.reset_status()
+
+    def _status_args(self):
+        return (C.byref(self.opts), C.byref(self.shapes), self.keep, _ptr(self.saved), C.c_size_t(self.saved_floats))
+
+    def reset_status(self):
+        """zero the run's hand-off status words: asynchronous, on torch's current stream (the run's own when it is allocated)"""
+        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        _lib.check(self.L.macx_run_status_reset(*self._status_args(), stream), "macx_run_status_reset")
+        self.status_reset_pending = False
+
+    def status(self):
+        """(bits, first_step) of macx_run_status: (0, -1) when every in-launch hand-off of the runs on this buffer completed.
+        Synchronises torch's current stream."""
+        bits, first = C.c_uint32(0), C.c_int32(-1)
+        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        rc = self.L.macx_run_status(*self._status_args(), stream, C.byref(bits), C.byref(first))
+        if rc not in (_lib.MACX_OK, _lib.MACX_EWAIT):
+            raise _lib.MacxError(rc, "macx_run_status")
+        return int(bits.value), int(first.value)
+
+    def check(self, where="MAC cell run"):
+        bits, first = self.status()
+        if bits:
+            raise _lib.HandoffTimeout(bits, first, where)
 
     def _common(self):
         return (C.byref(self.opts), C.byref(self.shapes), C.byref(self.drop), C.byref(self.pstruct), C.byref(self.inputs),
@@ -214,6 +243,10 @@ class MACCell:
     mask_word  None, or a 1-element int32 tensor on the device: every dropout site XORs it into its key WHEN THE KERNELS RUN
              (macx.h, macx_dropout.mask_word).  The seed is baked into a captured HIP graph, this word is not: write a new
              value between replays and one capture draws fresh masks per step (graph.CapturedTrainStep).  None == word 0.
+    Did the run go wrong?  At d = 512 workgroups of one launch hand results to each other with bounded waits; a wait that runs out
+    poisons the run (its final memory and gradients are NaN) and is reported by
+    status()  -> (bits, first_step): (0, -1) for a clean run (include/macx.h, macx_run_status);  check()  raises macx.HandoffTimeout.
+    Both SYNCHRONISE the current stream -- call them where the loop synchronises anyway (after reading the loss), not per launch.
     gemm     kernel family of the knowledge-base GEMMs of THIS cell: "h2" | "split" | "native" (None: the process default)
     tune     {key: value} for macx_opts.tune, the per-call A/B hooks (_lib.TUNE; measurement only, never needed for results)
     """
@@ -367,6 +400,24 @@ class MACCell:
                                                   *self.params.tensors())
         return self.none, MACCellTuple(control, memory)
 
+    # ---- macx_run_status of the latest run
+    def status(self):
+        """(bits, first_step) of the latest run's hand-off status words; (0, -1): clean.  Synchronises the current stream."""
+        if self._run is None:
+            raise RuntimeError("no run yet: call zero_state() or run() first")
+        return self._run.status()
+
+    def check(self):
+        """raises macx.HandoffTimeout if an in-launch hand-off of the latest run gave up.  Synchronises the current stream."""
+        if self._run is None:
+            raise RuntimeError("no run yet: call zero_state() or run() first")
+        self._run.check()
+
+    def reset_status(self):
+        """clears the sticky status of the latest run's buffer (after a HandoffTimeout has been handled)"""
+        if self._run is not None:
+            self._run.reset_status()
+
     # ---- the whole loop of model.py:453-458 in one ABI call
     def run(self):
         self._run = _Run(self, keep_activations=self._needs_grad())
@@ -492,6 +543,15 @@ class PaddedMACCell:
 
     def run(self):
         return self._cut(self.inner.run())
+
+    def status(self):
+        return self.inner.status()
+
+    def check(self):
+        return self.inner.check()
+
+    def reset_status(self):
+        return self.inner.reset_status()
 
     controls = property(lambda self: self.inner.controls[..., :self.d])
     memories = property(lambda self: self.inner.memories[..., :self.d])

@@ -153,6 +153,8 @@ struct SavedLayout {
   size_t act_floats;                // floats of one such tensor (B*N*d, or the H2 size in h2 mode)
   size_t wmax;                      // h2: max |W| of projX, memKbProj2, W1a, W1b (4 floats)
   size_t bwd_packs;                 // keep: the backward pass's weight packs (bwd_packs_floats), written by the forward pack launch; else 0
+  size_t status;                    // STATUS_WORDS uint32 (macx_chain_api.hip.h; = seg[MACX_SEG_STATUS]): what the in-launch hand-offs report.
+                                    // NOT zeroed by macx_cell_begin: macx_run_status reads it, only macx_run_status_reset clears it
   size_t sync;                      // SYNC_WORDS uint32: [i] the y counter of step i's chain launch (ChainPreP::yflag, p <= 32), [63] the fail
                                     // word, [64 + 16 i ..] step i's per-block counters (gflag); zeroed by macx_cell_begin's init_states launch
   size_t total;
@@ -165,9 +167,9 @@ SavedLayout make_saved(const macx_opts* o, const macx_shapes* s, int keep) {
   size_t off = 0;
   auto take = [&](size_t n) { size_t r = off; off += al4(n); return r; };
   const size_t gate_w = o->write_gate ? (o->write_gate_shared ? 1 : d) : 0;
-  const size_t counts[MACX_SEG_COUNT] = {(p + 1) * B * d, (p + 1) * B * d, p * B * d, p * B * S, p * B * N,
-                                         o->write_self_att ? p * B * p : 0, p * B * gate_w};
-  for (int i = 0; i < MACX_SEG_COUNT; ++i) {
+  const size_t counts[MACX_SEG_STATUS] = {(p + 1) * B * d, (p + 1) * B * d, p * B * d, p * B * S, p * B * N,
+                                          o->write_self_att ? p * B * p : 0, p * B * gate_w};
+  for (int i = 0; i < MACX_SEG_STATUS; ++i) {
     L.seg_count[i] = counts[i];
     L.seg[i] = take(counts[i]);
   }
@@ -217,6 +219,10 @@ SavedLayout make_saved(const macx_opts* o, const macx_shapes* s, int keep) {
   L.att_bits = take(pk * bits_floats);
   L.wmax = take(8 + 4 * 64);          // the four maxima (+ 4 spare), then absmax4's per-workgroup partials
   L.bwd_packs = keep ? take(bwd_packs_floats(o, s)) : 0;
+  // the status words, then the counters: the last two segments, adjacent (the profiling stamps address one from the other)
+  static_assert(STATUS_WORDS % 4 == 0 && SYNC_WORDS == SYNC_GFLAG0 + 32 * 16, "al4 adds nothing between status and sync");
+  L.status = L.seg[MACX_SEG_STATUS] = take(STATUS_WORDS);
+  L.seg_count[MACX_SEG_STATUS] = STATUS_WORDS;
   L.sync = take(SYNC_WORDS);
   L.total = off;
   return L;
@@ -486,12 +492,13 @@ ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dr
     c.pre.ylin = lin_basic(saved + L.md + (size_t)i * Bd, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, saved + L.y + (size_t)i * Bd, d);
     c.pre.step = i;
     c.pre.yflag = reinterpret_cast<uint32_t*>(saved + L.sync) + i;
-    c.pre.fail = reinterpret_cast<uint32_t*>(saved + L.sync) + 63;
+    c.pre.fail = reinterpret_cast<uint32_t*>(saved + L.sync) + SYNC_FAIL;
+    c.pre.status = reinterpret_cast<uint32_t*>(saved + L.status);
     if ((pre & PRE_WRITE_PREV) && i > 0) {
       // ... after the previous step's write unit (cell_step did not launch it)
       c.pre.wlin = make_write_lin(o, s, dp, P, saved, L, i - 1, saved + L.seg[MACX_SEG_INFOS] + (size_t)(i - 1) * Bd,
                                   saved + L.seg[MACX_SEG_MEMORIES] + (size_t)i * Bd, true);
-      c.pre.gflag = reinterpret_cast<uint32_t*>(saved + L.sync) + 64 + 16 * i;
+      c.pre.gflag = reinterpret_cast<uint32_t*>(saved + L.sync) + SYNC_GFLAG0 + 16 * i;
     }
   }
   if (rdrop && (pre & PRE_STAGE0_NEXT) && c.pre.nfill) {
@@ -510,7 +517,8 @@ hipError_t pack(const float* src, int ld_k, int ld_j, int K, int Nout, float* ds
   hipLaunchKernelGGL(pack_weight_kernel, dim3(256), dim3(256), 0, st, src, ld_k, ld_j, K, Nout, dst);
   return hipGetLastError();
 }
-// ---- device-side fills and copies as KERNELS.  No hipMemsetAsync / hipMemcpyAsync anywhere in this library: under HIP-graph
+// ---- device-side fills and copies as KERNELS.  No hipMemsetAsync / hipMemcpyAsync on any capturable path of this library (the one
+// copy call is macx_run_status's read-back to the host, which refuses a capturing stream): under HIP-graph
 // replay (ROCm 7.2) a memset node was seen to run out of order with the kernel nodes around it -- in round 3 behind the packed
 // weights' maxima, in round 4 behind dL/dc of a captured training step (the control unit's gradients differed from the eager
 // step's in three of four fresh processes, every replay alike; tools/graph_train_probe_verify.py) -- while kernel nodes keep
@@ -733,6 +741,7 @@ const char* macx_strerror(int code) {
     case MACX_EUNSUPPORTED: return "option combination has no HIP path yet";
     case MACX_EREJECTED: return "option value that raises in the reference";
     case MACX_ESMALL: return "saved/ws buffer too small";
+    case MACX_EWAIT: return "an in-launch hand-off wait gave up: the run's results are poisoned (NaN)";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown macx error";
   }
 }
@@ -760,6 +769,89 @@ int macx_saved_segment(const macx_opts* o, const macx_shapes* s, int keep, int s
   *offset = L.seg[segment];
   *count = L.seg_count[segment];
   return MACX_OK;
+}
+
+// ---- the run's hand-off status (SavedLayout::status) ----------------------------------------------
+namespace {
+__global__ void run_status_reset_kernel(uint32_t* st) {
+  if (threadIdx.x < STATUS_WORDS) st[threadIdx.x] = 0u;
+}
+// wait_counter's two exits on words of its own: w[0] a counter that holds the wanted value, w[1] one that holds less and is waited
+// for with budget 0; w[2] the fail word, w[4 + 2 c], w[5 + 2 c] the status pair of call c.  out[4 c ..]: arrived, status bits, step
+// word, whether EVERY thread of the workgroup learnt of a give-up (the LDS flag + barrier protocol of the chain kernel)
+__global__ __launch_bounds__(256) void handoff_selftest_kernel(uint32_t* w, uint32_t* out) {
+  __shared__ uint32_t sGave;
+  if (threadIdx.x == 0) __hip_atomic_store(w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int c = 0; c < 2; ++c) {
+    bool ok = true;
+    if (threadIdx.x == 0) {
+      ok = wait_counter<1>(w + c, 1u, c == 0 ? HANDOFF_BUDGET : 0u, w + 2, w + 4 + 2 * c, 6, c == 0 ? HANDOFF_Y : HANDOFF_WRITE);
+      sGave = ok ? 0u : 1u;
+    }
+    __syncthreads();
+    const int told = __syncthreads_count(sGave != 0u);
+    if (threadIdx.x == 0) {
+      out[4 * c + 0] = ok ? 1u : 0u;
+      out[4 * c + 1] = __hip_atomic_load(w + 4 + 2 * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[4 * c + 2] = __hip_atomic_load(w + 5 + 2 * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[4 * c + 3] = told == (int)blockDim.x ? 1u : 0u;
+    }
+    __syncthreads();
+  }
+}
+int status_layout(const macx_opts* o, const macx_shapes* s, int keep, const float* saved, size_t saved_floats, size_t* off) {
+  ModeScope ms(o);
+  CKI(check_impl(o, s));
+  if (!saved || misaligned(saved)) return MACX_EINVAL;
+  const SavedLayout L = make_saved(o, s, keep);
+  if (saved_floats < L.total) return MACX_ESMALL;
+  *off = L.status;
+  return MACX_OK;
+}
+}  // namespace
+
+int macx_run_status(const macx_opts* o, const macx_shapes* s, int keep, const float* saved, size_t saved_floats, void* stream,
+                    uint32_t* host_status, int32_t* host_first_step) {
+  size_t off = 0;
+  CKI(status_layout(o, s, keep, saved, saved_floats, &off));
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  CK(hipStreamIsCapturing(st, &cap));
+  if (cap != hipStreamCaptureStatusNone) return (int)hipErrorStreamCaptureUnsupported;    // a synchronising call cannot be a graph node
+  uint32_t w[2] = {0u, 0u};
+  CK(hipMemcpyAsync(w, saved + off, sizeof(w), hipMemcpyDeviceToHost, st));     // (never captured: the library's only copy call)
+  CK(hipStreamSynchronize(st));
+  if (host_status) *host_status = w[0];
+  if (host_first_step) *host_first_step = (int32_t)w[1] - 1;
+  return w[0] ? MACX_EWAIT : MACX_OK;
+}
+
+int macx_run_status_reset(const macx_opts* o, const macx_shapes* s, int keep, float* saved, size_t saved_floats, void* stream) {
+  size_t off = 0;
+  CKI(status_layout(o, s, keep, saved, saved_floats, &off));
+  hipLaunchKernelGGL(run_status_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<uint32_t*>(saved + off));
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int macx_handoff_selftest(void* stream, uint32_t* host_out) {
+  if (!host_out) return MACX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  CK(hipStreamIsCapturing(st, &cap));
+  if (cap != hipStreamCaptureStatusNone) return (int)hipErrorStreamCaptureUnsupported;
+  uint32_t* dev = nullptr;          // 16 words for the waits + 8 for the report: this self-test's own, freed before it returns
+  CK(hipMalloc(&dev, 24 * sizeof(uint32_t)));
+  hipError_t e = dev_zero(dev, 24 * sizeof(uint32_t), st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(handoff_selftest_kernel, dim3(1), dim3(256), 0, st, dev, dev + 16);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out, dev + 16, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const hipError_t ef = hipFree(dev);
+  if (e != hipSuccess) return (int)e;
+  return ef == hipSuccess ? MACX_OK : (int)ef;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1302,7 +1394,7 @@ void CellBwd::plan_dkb_fill() {
   q.out = GI->knowledgeBase;
   q.dbg = (kb_gemm_dbg() >> 22) & 31;
 #ifdef MACX_FILL_PROF
-  q.prof = reinterpret_cast<uint32_t*>(saved + L.sync) + 48;
+  q.prof = reinterpret_cast<uint32_t*>(saved + L.sync) + SYNC_PROF_DKB;
 #endif
 }
 

@@ -18,9 +18,9 @@ struct ChainW {          // a weight matrix in pack format 3 (macx_h2.hip.h: pac
 // The same workgroups first compute THIS step's y = md Wy + by (the [B,d] linear that would otherwise be a launch of its own in front
 // of the chain launch): tiles of small_linear_kernel's arithmetic (macx_lin_tile.hip.h), outputs written through the L2 (agent-scope
 // stores), then one increment of `yflag` per filler workgroup.  The chain tiles need y only after their second product (~45 us
-// into the launch); they wait for yflag == nfill (bounded: `fail` is set if a tile gives up) and read y with agent-scope loads --
-// the per-XCD L2s are not coherent inside a launch.  Fillers carry the LOWEST workgroup ids: they are dispatched before any tile,
-// so a tile never waits for a workgroup that is not running.
+// into the launch); they wait for yflag == nfill (wait_counter below: bounded; a tile that gives up reports it and poisons its y) and
+// read y with agent-scope loads -- the per-XCD L2s are not coherent inside a launch.  Fillers carry the LOWEST workgroup ids: they
+// are dispatched before any tile, so a tile never waits for a workgroup that is not running.
 struct ChainPreP {
   int nfill;                // filler workgroups; 0: none
   uint32_t key1, key2;      // the next step's site keys (thresholds and scales are the step's own: one keep probability per run)
@@ -29,7 +29,8 @@ struct ChainPreP {
   H2View KBd;               // base null: no stage 0 to do (the last step)
   LinP ylin;                // n_out = 0: y was computed by a launch
   uint32_t* yflag;          // device word, zero when the launch starts
-  uint32_t* fail;           // device word, sticky
+  uint32_t* fail;           // device word of THIS run (SavedLayout::sync word 63, zeroed by macx_cell_begin): 1 after a give-up
+  uint32_t* status;         // [STATUS_WORDS] device words that outlive the run (SavedLayout::status; macx_run_status): see wait_counter
   // ... and, in front of y, the PREVIOUS step's write unit (wlin.n_out = 0: a launch did it): the [B,d] linears between two chain
   // launches then run beside the tiles' first two stages instead of between the launches.  Filler-to-filler order per block of 16
   // questions: its write tiles -> its y tiles (which read the dropped new memory the write tiles leave); a filler finishes ALL its
@@ -38,8 +39,71 @@ struct ChainPreP {
   // 30 us over the 25.7 MB the launch reads in 6.8, the tiles wait 39 us for y; profiles/r06_fillers.txt.)
   LinP wlin;                // [m_prev, info] Wm + bm -> m_new, and the dropped copy this step's y reads
   uint32_t* gflag;          // [8] device words, zero when the launch starts: write tiles finished per block of 16 questions
-  int step;                 // (-DMACX_FILL_PROF: step 5's filler 0 / tile 0 leave 100 MHz timestamps in sync[32..47], tools/fill_prof.py)
+  int step;                 // (-DMACX_FILL_PROF: step 5's filler 0 / tile 0 leave 100 MHz timestamps in sync[32..43], tools/fill_prof.py)
 };
+
+// ---- the in-launch hand-offs' wait -----------------------------------------------------------------------------------------
+// SavedLayout::status: words a run's hand-offs report into and that nothing but macx_run_status_reset clears
+constexpr int STATUS_WORDS = 16;          // [0] HANDOFF_* bits, [1] 1 + the step of the FIRST give-up (0: none), [2..7] spare,
+                                          // [8..15] -DMACX_FILL_PROF: chain_bwd's stamps of tile 0 (the other stamps: sync[32..62])
+constexpr int STATUS_PROF_BWD = 8;
+// SavedLayout::sync (SYNC_WORDS, macx_small.hip.h; directly behind the status words): [i] the y counter of step i (p <= 32), [63] the
+// run's fail word, [64 + 16 i .. + 7] step i's write-tile counters.  The -DMACX_FILL_PROF stamps live in words no counter uses:
+constexpr int SYNC_YFLAGS = 32, SYNC_FAIL = 63, SYNC_GFLAG0 = 64;
+constexpr int SYNC_PROF_FWD = 32, PROF_FWD_STAMPS = 12;      // chain_fwd: filler 0 (0..3) and tile 0 (8..11) of step 5, fail[-31 + k]
+constexpr int SYNC_PROF_DKB = 48, PROF_DKB_STAMPS = 15;      // chain_bwd's dKB filler 0 (ChainDkbP::prof = sync + 48)
+constexpr int PROF_BWD_STAMPS = 8;                           // chain_bwd's tile 0: status words, prof[PROF_BWD_OFF + k]
+constexpr int PROF_BWD_OFF = STATUS_PROF_BWD - STATUS_WORDS - SYNC_PROF_DKB;
+static_assert(SYNC_PROF_FWD >= SYNC_YFLAGS && SYNC_PROF_FWD + PROF_FWD_STAMPS <= SYNC_PROF_DKB &&
+              SYNC_PROF_DKB + PROF_DKB_STAMPS <= SYNC_FAIL && SYNC_FAIL < SYNC_GFLAG0,
+              "profiling stamps between the y counters and the fail word");
+static_assert(SYNC_FAIL - 31 == SYNC_PROF_FWD, "MACX_STAMP addresses its words from the fail word");
+static_assert(STATUS_PROF_BWD >= 2 && STATUS_PROF_BWD + PROF_BWD_STAMPS <= STATUS_WORDS && STATUS_WORDS % 4 == 0,
+              "chain_bwd's stamps in the status segment's spare words");
+enum : uint32_t {
+  HANDOFF_Y = 1,            // a tile of chain_fwd gave up waiting for its launch's y (ChainPreP::yflag)
+  HANDOFF_WRITE = 2,        // a filler of chain_fwd gave up waiting for the previous step's write tiles (ChainPreP::gflag)
+};
+// Memory order of the hand-offs.  The payload (y, the new memory and its dropped copy) leaves through agent-scope (write-through)
+// stores that every storing wave drains (s_waitcnt vmcnt(0)) in front of the barrier the counter's increment follows, and every
+// load of it is an agent-scope load: data and counter meet in the device-coherent level whatever the order of the counter's own
+// accesses.  1: the increment is also an agent-scope RELEASE and a successful poll is followed by an agent-scope ACQUIRE load of
+// the counter (what the language's memory model asks for: an L2 write-back / invalidate per hand-off on this hardware); 0, the
+// shipped form: both relaxed.  Measured on one MI355X (profiles/run_status_bench_ab.txt): 1 costs 0.065 ms
+// of a 3.81 ms step, 0 costs nothing.
+#ifndef MACX_HANDOFF_ACQ_REL
+#define MACX_HANDOFF_ACQ_REL 0
+#endif
+constexpr bool HANDOFF_ACQ_REL = MACX_HANDOFF_ACQ_REL != 0;
+constexpr uint32_t HANDOFF_BUDGET = 1u << 22;      // polls before a wait gives up (x s_sleep: seconds; a launch lasts ~0.1 ms)
+
+// the producer's side: one increment of a hand-off counter (the caller has drained its stores and passed the workgroup's barrier)
+__device__ __forceinline__ void signal_counter(uint32_t* counter) {
+  __hip_atomic_fetch_add(counter, 1u, HANDOFF_ACQ_REL ? __ATOMIC_RELEASE : __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ONE thread of the waiting workgroup polls `counter` until it holds at least `want`: at most `budget` polls that find less, SLEEP
+// (the immediate of s_sleep: 64 clocks each) between two polls; budget 0 returns after one look.  Returns whether the value
+// arrived.  On give-up: the run's word `fail` becomes 1, `bit` is ORed into status[0] and status[1] takes step + 1 unless an
+// earlier give-up already left its own there -- and the CALLER must not use what it waited for: it hands the result to the other
+// threads of its workgroup (an LDS flag in front of the barrier that follows the wait) and they substitute NaN for it.
+template <int SLEEP>
+__device__ __forceinline__ bool wait_counter(const uint32_t* counter, uint32_t want, uint32_t budget, uint32_t* fail, uint32_t* status,
+                                             int step, uint32_t bit) {
+  uint32_t spins = 0;
+  while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+    if (spins++ >= budget) {
+      __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_or(status, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t none = 0u;
+      __hip_atomic_compare_exchange_strong(status + 1, &none, (uint32_t)step + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(SLEEP);
+  }
+  if (HANDOFF_ACQ_REL) (void)__hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
+}
+__device__ __forceinline__ float handoff_poison() { return __uint_as_float(0x7fc00000u); }      // a quiet NaN
 
 struct ChainFwdP {
   int M, N, d;              // rows (B*N), rows per question, width
@@ -161,6 +225,10 @@ hipError_t chain_dkb_rest_launch(const ChainDkbP& q, int M, int N, int d, hipStr
 // jobs per filler workgroup of a chain_bwd launch (0: the merged dKB launch instead) and what follows from it
 // MACX_TUNE_PRE_FILL: 1 (default) stage 0 of step i + 1 on the idle CUs of chain_fwd's launch of step i; 0 every launch its own
 inline int pre_fill_mode() { return tune_get(MACX_TUNE_PRE_FILL, 1); }
+// (The fillers are the workgroups 0 .. nfill - 1 of the launch, the tiles wait for them: this relies on the dispatcher starting
+// workgroups in ascending id order, so that every filler is resident before the first tile that could wait for it -- what every
+// launch on this hardware has shown, but no documented guarantee.  Were it ever violated with every CU held by waiting tiles, the
+// waits would run out of their budget: wait_counter reports that and poisons the run instead of hanging or returning garbage.)
 inline int pre_fill_count(int d, size_t M, int ncu) {
   if (!pre_fill_mode() || d != 512 || ncu <= 0) return 0;
   const int ntile = (int)chain_tiles(d, M);

@@ -574,18 +574,21 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
       auto signal = [&](uint32_t* c0, uint32_t* c1) __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (x.tid == 0 && c0) __hip_atomic_fetch_add(c0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (x.tid == 64 && c1) __hip_atomic_fetch_add(c1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (x.tid == 0 && c0) signal_counter(c0);
+        if (x.tid == 64 && c1) signal_counter(c1);
       };
-      auto wait_ge = [&](uint32_t* c, uint32_t v) __attribute__((always_inline)) {
+      // the write tiles of one or two blocks of 16 questions are there (wait_counter; thread 0 polls, an LDS word no filler
+      // stage uses in front of the barrier tells every thread): returns whether the wait gave up
+      static_assert(C::G::P_BYTES >= sizeof(float) * 16 * 16 * 20, "the fillers' linear tiles stay inside P: sPart is free");
+      uint32_t* sGave = reinterpret_cast<uint32_t*>(x.sPart);
+      auto wait_tiles = [&](uint32_t* ca, uint32_t* cb, uint32_t v) __attribute__((always_inline)) {
         if (x.tid == 0) {
-          uint32_t spins = 0;
-          while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1u << 22)) { __hip_atomic_store(p.pre.fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-          }
+          bool ok = wait_counter<4>(ca, v, HANDOFF_BUDGET, p.pre.fail, p.pre.status, p.pre.step, HANDOFF_WRITE);
+          if (ok && cb != ca) ok = wait_counter<4>(cb, v, HANDOFF_BUDGET, p.pre.fail, p.pre.status, p.pre.step, HANDOFF_WRITE);
+          *sGave = ok ? 0u : 1u;
         }
         __syncthreads();
+        return __builtin_amdgcn_readfirstlane(*sGave) != 0u;
       };
       const bool tail = p.pre.wlin.n_out != 0;
       if (tail) {
@@ -608,13 +611,11 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
 #pragma unroll 1
         for (int u0 = 2 * f; u0 < nunits; u0 += 2 * nf) {
           const int ua = u0, ub = min(u0 + 1, nunits - 1), bya = ua / ntx, byb = ub / ntx;
-          if (tail) {
-            wait_ge(p.pre.gflag + bya, wtiles);
-            if (byb != bya) wait_ge(p.pre.gflag + byb, wtiles);
-          }
+          // (a wait that gave up: NaN instead of the unfinished new memory, so y, the step's memory and all behind them are NaN)
+          const bool gave = tail && wait_tiles(p.pre.gflag + bya, p.pre.gflag + byb, wtiles);
           const int u = half ? ub : ua;
-          small_linear_tile<1, false, true, true, 2>(yl, u % ntx, u / ntx, 0, red + 8 * half, tl, u0 + half < nunits);
-          __syncthreads();
+          small_linear_tile<1, false, true, true, 2>(yl, u % ntx, u / ntx, 0, red + 8 * half, tl, u0 + half < nunits, gave);
+          __syncthreads();                       // (also: every thread has read sGave before thread 0 writes it again)
         }
         signal(p.pre.yflag, nullptr);
       }
@@ -698,16 +699,18 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
   constexpr bool YCOH = D == 512;                 // y may come from this launch's fillers (ChainPreP): agent-scope loads
   if constexpr (YCOH) {
     MACX_STAMP((int)blockIdx.x == p.pre.nfill, 9);
-    if (p.pre.ylin.n_out && x.tid == 0) {
-      uint32_t spins = 0;
-      while (__hip_atomic_load(p.pre.yflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (uint32_t)p.pre.nfill) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > (1u << 22)) { __hip_atomic_store(p.pre.fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-    }
+    // (sPart is idle until stage 3: its first word tells every thread, behind the barrier, whether the wait gave up)
+    if (p.pre.ylin.n_out && x.tid == 0)
+      *reinterpret_cast<uint32_t*>(x.sPart) =
+          wait_counter<8>(p.pre.yflag, (uint32_t)p.pre.nfill, HANDOFF_BUDGET, p.pre.fail, p.pre.status, p.pre.step, HANDOFF_Y) ? 0u : 1u;
   }
   if constexpr (YCOH) MACX_STAMP((int)blockIdx.x == p.pre.nfill, 10);
   __syncthreads();                         // every wave is done reading X (and y is complete)
+  // a wait that gave up: a quiet NaN instead of the unfinished y -- and, whatever the activations do to it, instead of the logits
+  bool ygave = false;
+  if constexpr (YCOH) {
+    if (p.pre.ylin.n_out) ygave = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(x.sPart)) != 0u;
+  }
   {
     float v[IT][8];
     float m = 0.f;
@@ -737,6 +740,12 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
         v[j][q] = xv[q] * (q < 4 ? y0[q & 3] : y1[q & 3]);      // ops.py:703: the product the reference rounds to fp32
         m = fmaxf(m, fabsf(v[j][q]));
       }
+    }
+    if (ygave) {
+#pragma unroll
+      for (int j = 0; j < IT; ++j)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[j][q] = handoff_poison();
     }
     x.convert_finish(v, m, x.sE2, H2View{nullptr, M, D});
   }
@@ -810,7 +819,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
     float s = x.sPart[w0 * R + x.tid];
 #pragma unroll
     for (int w = 1; w < C::NWC; ++w) s += x.sPart[(w0 + w) * R + x.tid];          // fixed order
-    p.logits[x.grow0 + x.tid] = s;
+    p.logits[x.grow0 + x.tid] = ygave ? handoff_poison() : s;
   }
 }
 
@@ -1047,7 +1056,7 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
     }
   }
 #ifdef MACX_FILL_PROF
-#define MACX_BSTAMP(k) do { if (p.dkb.prof && p.dkb.step == 5 && blockIdx.x == 0 && x.tid == 0) p.dkb.prof[336 + (k)] = (uint32_t)__builtin_readcyclecounter(); } while (0)
+#define MACX_BSTAMP(k) do { if (p.dkb.prof && p.dkb.step == 5 && blockIdx.x == 0 && x.tid == 0) p.dkb.prof[PROF_BWD_OFF + (k)] = (uint32_t)__builtin_readcyclecounter(); } while (0)
 #else
 #define MACX_BSTAMP(k) do { } while (0)
 #endif

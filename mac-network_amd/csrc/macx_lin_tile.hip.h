@@ -38,11 +38,13 @@ constexpr int LIN_PART_TILES = 6;     // tiles a question may touch in the PART 
 // with their own tile, tid and `red`, and meet in the same barrier).  live = false: a half without a tile goes through the motions
 // and stores nothing.  COH: the outputs leave as agent-scope stores (written through the XCD's L2: another workgroup of the SAME
 // launch reads them with agent-scope loads, macx_chain_h2.hip.h).
-// COHIN: the input rows are read with agent-scope loads too (another workgroup of the same launch wrote them).
+// COHIN: the input rows are read with agent-scope loads too (another workgroup of the same launch wrote them); `poison` (uniform
+// over the workgroup): the wait for them gave up -- a quiet NaN stands in for every input value.
 // CTL: 16-column tiles side by side (1 for the launches; 2 -- `red` then holds [2 x 4] slabs -- where fewer, wider tiles save a
 // round on a handful of workgroups): every output keeps its products and its summation order.
 template <int RTL, bool PART = false, bool COH = false, bool COHIN = false, int CTL = 1>
-__device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by, int z, float (*red)[16 * RTL][20], int tid, bool live = true) {
+__device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by, int z, float (*red)[16 * RTL][20], int tid, bool live = true,
+                                                  bool poison = false) {
   constexpr int L_ROWS = 16 * RTL;
   constexpr int NWV = 4;               // waves that share the tile's reduction dimension
   static_assert(CTL == 1 || (CTL == 2 && !PART), "one or two column tiles");
@@ -141,6 +143,7 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
           const uint64_t hi = __hip_atomic_load(q8 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           af[u][t] = f32x4{__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)), __uint_as_float((uint32_t)hi),
                            __uint_as_float((uint32_t)(hi >> 32))};
+          if (poison) { const float nan = __uint_as_float(0x7fc00000u); af[u][t] = f32x4{nan, nan, nan, nan}; }
         } else {
           af[u][t] = *reinterpret_cast<const f32x4*>(xs + (size_t)rowc[t] * ld);
         }

@@ -219,6 +219,7 @@ __global__ void drop2_kernel(const float* __restrict__ x, int rows, int d, uint3
 // ... and, with md != null, step 0's dropped memory md = m_0 * f1 * f2 (mac_cell.py:214-217 then ops.py:679: what drop2_kernel would
 // write in a launch of its own in front of the first projY linear); dl: the logical width of a zero-padded cell, 0 = d
 constexpr int SYNC_WORDS = 64 + 32 * 16;      // SavedLayout::sync: [i] y counter of step i, [63] fail word, [64 + 16 i ..] step i's block counters
+                                              // (macx_chain_api.hip.h names the words; the status words in front of it are NOT zeroed here)
 __global__ void init_states_kernel(int mode_c, const float* __restrict__ prm_c, float* out_c, int mode_m, const float* __restrict__ prm_m,
                                    float* out_m, const float* __restrict__ vecQ, int rows, int d, float* md = nullptr, uint32_t row0 = 0,
                                    DropSpec d1 = DropSpec{}, DropSpec d2 = DropSpec{}, int dl = 0, uint32_t* sync = nullptr) {

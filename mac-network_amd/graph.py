@@ -28,6 +28,11 @@ used to start from a memset write per-workgroup partials that a later kernel com
 (What torch adds around the library inside a capture is not under its control: the two `.clone()`s of the final state are
 device-to-device copy nodes.  They deliver `memory`, which the self-check compares on every verification replay, and they have
 never been seen out of order -- but they are the reason the check stays on by default.)
+
+Did a replay go wrong?  The captured run's `saved` buffer carries the sticky hand-off status of include/macx.h (macx_run_status):
+every class here has `.check()` (raises macx.HandoffTimeout; SYNCHRONISES), `.reset_status()` and a constructor argument
+`check_every=k`: with k > 0 every k-th replay() / step() ends in a check(); the default 0 adds nothing to a replay.  The reset is
+never part of a graph -- the status survives replays until the caller clears it.
 """
 import warnings
 
@@ -50,13 +55,53 @@ def mix32(x):
     return h
 
 
-class CapturedForward:
-    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True):
+class _RunStatus:
+    """check() / reset_status() / check_every of the captured classes: `_status_run()` is the cell._Run whose `saved` the replays
+    write (None before the first run)."""
+    check_every = 0
+    _replays = 0
+
+    def _status_run(self):
+        cell = getattr(self, "cell", None)
+        cell = getattr(cell, "inner", cell)          # (a zero-padded cell wraps the real one)
+        return getattr(cell, "_run", None)
+
+    def _after_capture(self):
+        """a run allocated under capture could not zero its status words (the reset must not become a graph node): do it now"""
+        run = self._status_run()
+        if run is not None and getattr(run, "status_reset_pending", False):
+            run.reset_status()
+
+    def status(self):
+        run = self._status_run()
+        return run.status() if run is not None else (0, -1)
+
+    def check(self):
+        """raises macx.HandoffTimeout if an in-launch hand-off of any replay since the last reset gave up.  Synchronises."""
+        run = self._status_run()
+        if run is not None:
+            run.check(type(self).__name__)
+
+    def reset_status(self):
+        run = self._status_run()
+        if run is not None:
+            run.reset_status()
+
+    def _count_replay(self):
+        if self.check_every > 0:
+            self._replays += 1
+            if self._replays % self.check_every == 0:
+                self.check()
+
+
+class CapturedForward(_RunStatus):
+    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True, check_every=0):
         dev = torch.device(device) if device is not None else params.tensors()[0].device
         if dev.type != "cuda":
             raise RuntimeError("CapturedForward needs the HIP device: the MAC cell has no CPU path")
         d = int(get(config, "memDim"))
         self.config, self.params = config, params
+        self.check_every = int(check_every)
         self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
         self.vecQuestions = torch.zeros(B, d, device=dev)
         self.words = torch.zeros(B, S, d, device=dev)
@@ -74,6 +119,7 @@ class CapturedForward:
             self.cell = self._cell()
             state = self.cell.run()
             self.memory, self.control = state.memory, state.control
+        self._after_capture()
         self.attentions = self.cell.attentions
         self.captured = True
         if verify and not self._replays_match_eager():
@@ -94,6 +140,7 @@ class CapturedForward:
             self.graph.replay()
             ok = ok and bool(torch.equal(self.memory, want))
         torch.cuda.synchronize(dev)
+        self.check()
         return ok
 
     def _cell(self):
@@ -118,6 +165,7 @@ class CapturedForward:
                 state = self.cell.run()
             self.memory, self.control = state.memory, state.control
             self.attentions = self.cell.attentions
+        self._count_replay()
         return self.memory
 
     def __call__(self, vecQuestions, words, lengths, knowledgeBase):
@@ -125,7 +173,7 @@ class CapturedForward:
         return self.replay()
 
 
-class CapturedTrainStep:
+class CapturedTrainStep(_RunStatus):
     """Forward + backward of the cell (train-mode dropout, every gradient) replayed from ONE captured HIP graph.
 
         step = macx.CapturedTrainStep(cfg, params, B=64, S=50, N=196, seed=1234)
@@ -152,12 +200,13 @@ class CapturedTrainStep:
     `verify=True` replays three times against the eager step on random inputs and falls back to eager launches when a replay
     differs in any gradient (`captured` False, a warning says so)."""
 
-    def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True):
+    def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True, check_every=0):
         dev = torch.device(device) if device is not None else params.tensors()[0].device
         if dev.type != "cuda":
             raise RuntimeError("CapturedTrainStep needs the HIP device: the MAC cell has no CPU path")
         d = int(get(config, "memDim"))
         self.config, self.params, self.seed, self.b0 = config, params, int(seed), int(b0)
+        self.check_every = int(check_every)
         self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
         self.vecQuestions = torch.zeros(B, d, device=dev, requires_grad=True)
         self.words = torch.zeros(B, S, d, device=dev, requires_grad=True)
@@ -176,6 +225,8 @@ class CapturedTrainStep:
         self._clear_grads()
         with torch.cuda.graph(self.graph):
             self.memory = self._eager()
+        self._after_capture()
+        self._captured_cell = self.cell          # the run whose buffers the graph replays on
         self.captured = True
         if verify and not self._replays_match_eager():
             self.captured = False
@@ -197,6 +248,7 @@ class CapturedTrainStep:
                        writeDropout=float(get(self.config, "writeDropout")), batchSize=self.vecQuestions.shape[0], train=True,
                        config=self.config, params=self.params, netLength=self.netLength, seed=self.seed, b0=self.b0,
                        mask_word=self.mask_word)
+        self.cell = cell                          # (status(): the latest run's buffers)
         state = cell.run()
         torch.autograd.backward([state.memory], [self.d_memory])
         return state.memory.detach()
@@ -215,6 +267,8 @@ class CapturedTrainStep:
                 t.copy_(torch.randn(t.shape, generator=g).to(dev))
         captured_grads = [t.grad for t in self._leaves()]        # the tensors the graph writes
         mem = self._eager().clone()
+        self.check()                              # the eager run's own buffers
+        self.cell = self._captured_cell
         want = [t.grad.clone() for t in self._leaves()]
         for t, gcap in zip(self._leaves(), captured_grads):
             t.grad = gcap
@@ -229,6 +283,7 @@ class CapturedTrainStep:
                     self.verify_report.append((r, i + 1))
         torch.cuda.synchronize(dev)
         self.set_mask_word(0)
+        self.check()
         ok = not self.verify_report
         return ok
 
@@ -248,10 +303,11 @@ class CapturedTrainStep:
             self.graph.replay()
         else:
             self.memory = self._eager()
+        self._count_replay()
         return self.memory
 
 
-class CapturedDPTrainStep(TwoPhaseStep):
+class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
     """One DATA-PARALLEL training step of the cell as TWO graph replays with the gradient exchange between and behind them.
 
     The eager data-parallel step is ~125 host-issued launches per rank; at 8 questions per GPU that is more host work than GPU work
@@ -276,7 +332,8 @@ class CapturedDPTrainStep(TwoPhaseStep):
         step.step(iteration=it)              # params' .grad = the all-reduced full-batch gradient; step.memory: [shard, d]
     """
 
-    def __init__(self, config, params, bucket, B, S, N, global_batch, seed=0, b0=0, device=None, netLength=None, warmup=2, capture=True):
+    def __init__(self, config, params, bucket, B, S, N, global_batch, seed=0, b0=0, device=None, netLength=None, warmup=2, capture=True,
+                 check_every=0):
         dev = torch.device(device) if device is not None else params.tensors()[0].device
         if dev.type != "cuda":
             raise RuntimeError("CapturedDPTrainStep needs the HIP device: the MAC cell has no CPU path")
@@ -286,6 +343,7 @@ class CapturedDPTrainStep(TwoPhaseStep):
         d = int(get(config, "memDim"))
         super().__init__(params, bucket, B, global_batch)
         self.config = config
+        self.check_every = int(check_every)
         self.seed, self.b0 = int(seed), int(b0)
         self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
         self.vecQuestions = torch.zeros(B, d, device=dev)
@@ -312,6 +370,7 @@ class CapturedDPTrainStep(TwoPhaseStep):
                 self._phase_a()
             with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool()):
                 self._phase_b()
+            self._after_capture()
             self.captured = True
         params.release_grad_buffer()
 
@@ -336,6 +395,9 @@ class CapturedDPTrainStep(TwoPhaseStep):
         self.d_vecQuestions, self.d_words, self.d_knowledgeBase = gi
         self._grads = grads
         self._run, self._args, self._keep = run, args, (keep, cell)
+
+    def _status_run(self):
+        return getattr(self, "_run", None)
 
     def _phase_b(self):
         with torch.no_grad():
@@ -373,4 +435,5 @@ class CapturedDPTrainStep(TwoPhaseStep):
         if iteration is not None:
             self.set_mask_word(mix32(int(iteration)))
         self.exchange_step()
+        self._count_replay()
         return self.memory

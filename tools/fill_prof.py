@@ -29,7 +29,9 @@ for i in range(4):
     torch.cuda.synchronize()
 import gc
 saved = cell._run.saved if cell._run is not None else max((o for o in gc.get_objects() if isinstance(o, RunCls)), key=lambda o: o.saved.numel()).saved
+STATUS_WORDS = 16        # macx_chain_api.hip.h: the status segment in front of the 576 sync words; chain_bwd's stamps in its words 8..15
 w = saved.view(torch.int32)[-576:].cpu().numpy().astype("uint32")
+st = saved.view(torch.int32)[-576 - STATUS_WORDS:-576].cpu().numpy().astype("uint32")
 t = w[32:48].astype("int64")
 print("pre_fill", v, "raw", t.tolist())
 f0, t0 = t[0], t[8]
@@ -41,7 +43,7 @@ for k in sorted(names):
 d = w[48:63].astype("int64")
 print("chain_bwd filler 0 of step 5 (dKB jobs): start | per job: tile in LDS, K loop done, staged, row pass issued -- ticks since start")
 print([int((v - d[0]) & 0xFFFFFFFF) if v else 0 for v in d])
-b = w[48 + 336:48 + 336 + 8].astype("int64")
+b = st[8:16].astype("int64")
 print("chain_bwd tile 0 of step 5: start, B0 done, B1 product, B1 epilogue, B2 product 1, dy + y scaling, B2 product 2, dX emitted -- ticks since start")
 print([int((v - b[0]) & 0xFFFFFFFF) if v else 0 for v in b])
 
