@@ -317,6 +317,17 @@ int macx_output_backward(const macx_out_shapes*, int act, float keep, uint32_t s
                          const float* memory, const float* vecQuestions, const float* saved, size_t saved_floats,
                          float* ws, size_t ws_floats, const float* d_logits, const macx_out_grads*,
                          float* d_memory, float* d_vecQuestions, void* stream);
+/* The same two calls under a run's mask word.  mask_word: one 32-bit word in DEVICE memory (NULL == 0), XORed into the site key of
+ * both layer-input dropouts (sites 7, 8) when the kernels RUN, exactly as macx_dropout.mask_word inside the cell: a captured
+ * graph bakes `seed` but draws the masks of (seed, *mask_word) on every replay.  The backward call must see the word the
+ * forward call saw.  NULL, or a word holding 0, gives the bits of the calls above (which forward here with NULL). */
+int macx_output_forward_w(const macx_out_shapes*, int act, float keep, uint32_t seed, const macx_out_params*,
+                          const float* memory, const float* vecQuestions, float* logits,
+                          float* saved, size_t saved_floats, const uint32_t* mask_word, void* stream);
+int macx_output_backward_w(const macx_out_shapes*, int act, float keep, uint32_t seed, const macx_out_params*,
+                           const float* memory, const float* vecQuestions, const float* saved, size_t saved_floats,
+                           float* ws, size_t ws_floats, const float* d_logits, const macx_out_grads*,
+                           float* d_memory, float* d_vecQuestions, const uint32_t* mask_word, void* stream);
 
 /* ---- stem CNN (producer of the knowledge base) -------------------------------- */
 /* MACnet.stem (model.py:165-204) -> ops.CNNLayer / ops.cnn (ops.py:380-438) for the default
@@ -335,6 +346,14 @@ int macx_stem_forward(const macx_stem_shapes*, int act, float keep, uint32_t see
 int macx_stem_backward(const macx_stem_shapes*, int act, float keep, uint32_t seed, const macx_stem_params*,
                        const float* kb, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
                        const float* d_kb, const macx_stem_grads*, void* stream);
+/* Under a run's mask word (device memory, NULL == 0; see macx_output_forward_w): XORed into the keys of both layer-input dropouts
+ * (sites 9, 10) when the forward kernels run.  The backward pass hashes nothing -- layer 0's dropped input and layer 1's keep
+ * bits are in `saved` -- so macx_stem_backward_w takes the word for symmetry and ignores it. */
+int macx_stem_forward_w(const macx_stem_shapes*, int act, float keep, uint32_t seed, const macx_stem_params*,
+                        const float* images, float* kb, float* saved, size_t saved_floats, const uint32_t* mask_word, void* stream);
+int macx_stem_backward_w(const macx_stem_shapes*, int act, float keep, uint32_t seed, const macx_stem_params*,
+                         const float* kb, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
+                         const float* d_kb, const macx_stem_grads*, const uint32_t* mask_word, void* stream);
 
 /* ---- general convolution (the generic stem: any --stemNumLayers / --stemKernelSize(s) / --stemStrideSizes) ---------- */
 /* ops.cnn's tf.nn.conv2d(inp, kernel, strides = [1, s, s, 1], padding = "SAME") (ops.py:380-411) for any kernel size k >= 1
@@ -376,6 +395,17 @@ int macx_encoder_backward(const macx_enc_shapes*, float keep_input, float keep_q
                           const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats,
                           float* ws, size_t ws_floats, const float* d_words, const float* d_vecQuestions,
                           const macx_enc_grads*, void* stream);
+/* Under a run's mask word (device memory, NULL == 0; see macx_output_forward_w): XORed into the keys of the input dropout
+ * (site 11) and the question dropout (site 12) when the kernels run.  Both sites are re-hashed by the backward pass (the
+ * embedding gradient and d vecQuestions), which must therefore see the word the forward pass saw. */
+int macx_encoder_forward_w(const macx_enc_shapes*, float keep_input, float keep_question, uint32_t seed, const macx_enc_params*,
+                           const int32_t* questions /*[B,S]*/, const int32_t* lengths /*[B]*/, float* words /*[B,S,2h]*/,
+                           float* vecQuestions /*[B,2h]*/, float* saved, size_t saved_floats, const uint32_t* mask_word,
+                           void* stream);
+int macx_encoder_backward_w(const macx_enc_shapes*, float keep_input, float keep_question, uint32_t seed, const macx_enc_params*,
+                            const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats,
+                            float* ws, size_t ws_floats, const float* d_words, const float* d_vecQuestions,
+                            const macx_enc_grads*, const uint32_t* mask_word, void* stream);
 
 /* ---- optimizer step ---------------------------------------------------------- */
 /* addTrainingOp (model.py:639-669) over ONE flat fp32 buffer of n elements:
@@ -386,6 +416,23 @@ int macx_encoder_backward(const macx_enc_shapes*, float keep_input, float keep_q
 int macx_adam_ema_step(size_t n, float* params, const float* grads, float* m, float* v, float* ema,
                        float lr, float beta1, float beta2, float eps, int step, float clip_norm, float ema_decay,
                        float* ws, float* norm_out, void* stream);
+/* The same step with the bias-corrected rate in DEVICE memory: lr_t_dev[0] = (float)(lr * sqrt(1 - b2^t) / (1 - b1^t)), computed
+ * by the caller in double as the call above computes it, read by the update kernel when it RUNS.  A captured graph therefore
+ * follows the step count and a changed learning rate: write the 4 bytes between replays, outside the graph.  With the same
+ * rate the result is bit-identical to macx_adam_ema_step. */
+int macx_adam_ema_step_p(size_t n, float* params, const float* grads, float* m, float* v, float* ema,
+                         const float* lr_t_dev, float beta1, float beta2, float eps, float clip_norm, float ema_decay,
+                         float* ws, float* norm_out, void* stream);
+
+/* ---- flat gather -------------------------------------------------------------------------------- */
+/* ONE launch copies `entries` tensors into their slices of a flat buffer: flat[dst_offset .. dst_offset + count) = src[0 .. count)
+ * per table entry; src == NULL zero-fills the slice (a parameter that received no gradient).  The table lives in device memory
+ * (8-byte aligned) and is read when the kernel runs.  Slices must not overlap each other or a source; floats of `flat` outside
+ * every slice (the pad between 16-byte aligned segments) are not written.  Entries whose source and destination are both 16-byte
+ * aligned move as dwordx4, the others and every tail float by float.  The workgroup-to-chunk mapping is a function of the table
+ * alone (chunks of 1024 floats, dealt round-robin); no atomics.  The caller guarantees that every slice lies inside `flat`. */
+typedef struct macx_gather_entry { const float* src; uint64_t dst_offset; uint64_t count; } macx_gather_entry;
+int macx_gather_flat(const macx_gather_entry* table_dev, int entries, float* flat, void* stream);
 
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)

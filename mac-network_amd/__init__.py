@@ -12,7 +12,8 @@ from .output import GenericOutputClassifier, OutputClassifier   # noqa: F401
 from .stem import GenericStem, Stem                 # noqa: F401
 from .encoder import GenericQuestionEncoder, QuestionEncoder   # noqa: F401
 from .model import MACNet, MACNetCore               # noqa: F401
-from .graph import CapturedForward, CapturedTrainStep, CapturedDPTrainStep  # noqa: F401
+from .graph import (CapturedDPTrainStep, CapturedForward, CapturedTowerForward, CapturedTowerTrainStep,   # noqa: F401
+                    CapturedTrainStep)
 
 __all__ = ["MACCell", "MACCellTuple", "MACCellParams", "OutputClassifier", "GenericOutputClassifier", "UnsupportedOptions", "freeze",
            "HandoffTimeout"]

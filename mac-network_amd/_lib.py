@@ -117,6 +117,11 @@ class MacxEncGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ENC_FIELDS]
 
 
+class MacxGatherEntry(C.Structure):
+    """macx_gather_entry: one row of macx_gather_flat's device table (24 bytes = three int64 of a torch tensor)"""
+    _fields_ = [("src", C.c_void_p), ("dst_offset", C.c_uint64), ("count", C.c_uint64)]
+
+
 class MacxInputs(C.Structure):
     _fields_ = [("vecQuestions", C.c_void_p), ("words", C.c_void_p), ("questionLengths", C.c_void_p),
                 ("knowledgeBase", C.c_void_p)]
@@ -141,7 +146,9 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_control_attend_bwd_ws_floats", "macx_read_fwd", "macx_read_bwd",
            "macx_write_fwd", "macx_write_bwd", "macx_read_chain_time", "macx_cell_forward_chain_time", "macx_saved_activation", "macx_ctrl_inputs_ws_floats",
            "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd", "macx_conv2d_ws_floats", "macx_conv2d_fwd", "macx_conv2d_bwd_data",
-           "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest")
+           "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest",
+           "macx_encoder_forward_w", "macx_encoder_backward_w", "macx_stem_forward_w", "macx_stem_backward_w",
+           "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat")
 
 _lib = None
 
@@ -294,6 +301,14 @@ def lib():
                                   C.c_void_p]
     L.macx_op_dropout_w.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
+    # the entry points under a run's mask word: the plain signature + the device word in front of the stream
+    for n in ("macx_encoder_forward", "macx_encoder_backward", "macx_stem_forward", "macx_stem_backward", "macx_output_forward",
+              "macx_output_backward"):
+        a = getattr(L, n).argtypes
+        getattr(L, n + "_w").argtypes = list(a[:-1]) + [C.c_void_p, a[-1]]
+    L.macx_adam_ema_step_p.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.macx_gather_flat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     for n in EXPORTS:
         if n.endswith("_floats"):
             getattr(L, n).restype = C.c_size_t

@@ -100,6 +100,12 @@ inline DropSpec make_drop(float keep, const macx_dropout* dp, uint32_t site, uin
   s.word = dp->mask_word;
   return s;
 }
+// a site outside the cell under a run's mask word (the _w entry points of the encoder, the stem and the output unit)
+inline DropSpec make_drop(float keep, uint32_t seed, uint32_t site, uint32_t step, const uint32_t* word) {
+  DropSpec s = make_drop(keep, seed, site, step);
+  s.word = word;
+  return s;
+}
 inline DropSpec no_drop() {
   DropSpec s;
   s.word = nullptr;
@@ -2424,6 +2430,12 @@ size_t macx_output_ws_floats(const macx_out_shapes* s) { return out_check(s) ? 0
 
 int macx_output_forward(const macx_out_shapes* s, int act, float keep, uint32_t seed, const macx_out_params* P, const float* memory,
                         const float* vecQ, float* logits, float* saved, size_t saved_floats, void* stream) {
+  return macx_output_forward_w(s, act, keep, seed, P, memory, vecQ, logits, saved, saved_floats, nullptr, stream);
+}
+
+int macx_output_forward_w(const macx_out_shapes* s, int act, float keep, uint32_t seed, const macx_out_params* P, const float* memory,
+                          const float* vecQ, float* logits, float* saved, size_t saved_floats, const uint32_t* mask_word,
+                          void* stream) {
   CKI(out_check(s));
   if (!P || !memory || !vecQ || !logits || !saved) return MACX_EINVAL;
   const OutLayout L = make_out(s);
@@ -2439,7 +2451,7 @@ int macx_output_forward(const macx_out_shapes* s, int act, float keep, uint32_t 
   LinP q = lin_basic(vecQ, d, d, B, saved + L.woq_p, P->outQuestion_b, d, MACX_ACT_NON, saved + L.eq, d);
   CK(small_linear_launch(q, 1, st));
   // classifier (model.py:547-576 -> ops.FCLayer ops.py:349-359): dropout on every layer input, act between layers
-  const DropSpec d0 = make_drop(keep, seed, SITE_OUT_FC0, 0), d1 = make_drop(keep, seed, SITE_OUT_FC1, 0);
+  const DropSpec d0 = make_drop(keep, seed, SITE_OUT_FC0, 0, mask_word), d1 = make_drop(keep, seed, SITE_OUT_FC1, 0, mask_word);
   // the concat is built in place: columns [0,d) memory, [d,2d) eq, with the layer-input mask indexed over [B, 2d]
   CK(dev_copy2d(saved + L.x0, (size_t)in * sizeof(float), memory, (size_t)d * sizeof(float), (size_t)d * sizeof(float), B, st));
   CK(dev_copy2d(saved + L.x0 + d, (size_t)in * sizeof(float), saved + L.eq, (size_t)d * sizeof(float), (size_t)d * sizeof(float), B, st));
@@ -2464,6 +2476,14 @@ int macx_output_forward(const macx_out_shapes* s, int act, float keep, uint32_t 
 int macx_output_backward(const macx_out_shapes* s, int act, float keep, uint32_t seed, const macx_out_params* P, const float* memory,
                          const float* vecQ, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
                          const float* d_logits, const macx_out_grads* G, float* d_memory, float* d_vecQ, void* stream) {
+  return macx_output_backward_w(s, act, keep, seed, P, memory, vecQ, saved, saved_floats, ws, ws_floats, d_logits, G, d_memory, d_vecQ,
+                                nullptr, stream);
+}
+
+int macx_output_backward_w(const macx_out_shapes* s, int act, float keep, uint32_t seed, const macx_out_params* P, const float* memory,
+                           const float* vecQ, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
+                           const float* d_logits, const macx_out_grads* G, float* d_memory, float* d_vecQ, const uint32_t* mask_word,
+                           void* stream) {
   CKI(out_check(s));
   if (!P || !memory || !vecQ || !saved || !ws || !d_logits || !G || !d_memory || !d_vecQ) return MACX_EINVAL;
   const OutLayout L = make_out(s);
@@ -2476,7 +2496,7 @@ int macx_output_backward(const macx_out_shapes* s, int act, float keep, uint32_t
   pk.add(P->fc0_W, 1, H, H, in, ws + W.w0T);          // W0^T: [H] -> [2d]
   pk.add(P->fc1_W, 1, A, Ap, H, ws + W.w1T, A, H);    // W1^T: [Ap] -> [H], rows past A are zero
   CK(pk.run(st));
-  const DropSpec d0 = make_drop(keep, seed, SITE_OUT_FC0, 0), d1 = make_drop(keep, seed, SITE_OUT_FC1, 0);
+  const DropSpec d0 = make_drop(keep, seed, SITE_OUT_FC0, 0, mask_word), d1 = make_drop(keep, seed, SITE_OUT_FC1, 0, mask_word);
   hipLaunchKernelGGL(pad_cols_kernel, dim3(16), dim3(256), 0, st, d_logits, A, B, Ap, ws + W.dlog_pad);
   // fc_1
   hipLaunchKernelGGL(outer_sum_kernel, dim3(64), dim3(256), 0, st, saved + L.x1, H, d_logits, A, B, H, A, G->fc1_W);
@@ -2578,9 +2598,9 @@ int stem_check(const macx_stem_shapes* s) {
   return MACX_OK;
 }
 hipError_t launch_pad_drop(const float* src, const PadP& q, float keep, uint32_t seed, uint32_t site, uint32_t first, float* dst,
-                           uint32_t* bits, hipStream_t st) {
+                           uint32_t* bits, const uint32_t* word, hipStream_t st) {
   const DropSpec ds = make_drop(keep, seed, site, 0);
-  hipLaunchKernelGGL(pad_drop_kernel, dim3(2048), dim3(256), 0, st, src, q, ds.key, ds.thr24, ds.inv_keep, first, dst, bits);
+  hipLaunchKernelGGL(pad_drop_kernel, dim3(2048), dim3(256), 0, st, src, q, ds.key, ds.thr24, ds.inv_keep, first, dst, bits, word);
   return hipGetLastError();
 }
 void conv_gemm_params(GemmP& g, const macx_stem_shapes* s, const StemGeo& geo, const float* Apad, int cin, int nout, int sign) {
@@ -2613,6 +2633,11 @@ size_t macx_stem_ws_floats(const macx_stem_shapes* s) { return stem_check(s) ? 0
 
 int macx_stem_forward(const macx_stem_shapes* s, int act, float keep, uint32_t seed, const macx_stem_params* P, const float* images,
                       float* kb, float* saved, size_t saved_floats, void* stream) {
+  return macx_stem_forward_w(s, act, keep, seed, P, images, kb, saved, saved_floats, nullptr, stream);
+}
+
+int macx_stem_forward_w(const macx_stem_shapes* s, int act, float keep, uint32_t seed, const macx_stem_params* P, const float* images,
+                        float* kb, float* saved, size_t saved_floats, const uint32_t* mask_word, void* stream) {
   CKI(stem_check(s));
   if (!P || !images || !kb || !saved || misaligned(images) || misaligned(kb) || misaligned(saved)) return MACX_EINVAL;
   const StemLayout L = make_stem(s);
@@ -2639,7 +2664,8 @@ int macx_stem_forward(const macx_stem_shapes* s, int act, float keep, uint32_t s
   PadP q0{s->B, geo.N, s->W, geo.wp, geo.np, Ci};
   PadP q1{s->B, geo.N, s->W, geo.wp, geo.np, Cm};
   // cnn_0: dropout -> conv3x3 SAME -> + b -> act   (ops.py:400-411)
-  CK(launch_pad_drop(images, q0, keep, seed, SITE_STEM0, (uint32_t)((size_t)s->b0 * geo.N * Ci), saved + L.in0p, nullptr, st));
+  CK(launch_pad_drop(images, q0, keep, seed, SITE_STEM0, (uint32_t)((size_t)s->b0 * geo.N * Ci), saved + L.in0p, nullptr,
+                     mask_word, st));
   GemmP g;
   conv_gemm_params(g, s, geo, saved + L.in0p, Ci, Cm, +1);
   g.Wp = saved + L.k0_p; g.out = saved + L.X1; g.bias = P->bias0; g.act = act;
@@ -2651,7 +2677,7 @@ int macx_stem_forward(const macx_stem_shapes* s, int act, float keep, uint32_t s
   CK((kb_gemm<A_PLAIN, B_PLAIN, E_BIAS_ACT, false>(g, st)));
   // cnn_1
   CK(launch_pad_drop(saved + L.X1, q1, keep, seed, SITE_STEM1, (uint32_t)((size_t)s->b0 * geo.N * Cm), saved + L.in1p,
-                     reinterpret_cast<uint32_t*>(saved + L.bits1), st));
+                     reinterpret_cast<uint32_t*>(saved + L.bits1), mask_word, st));
   conv_gemm_params(g, s, geo, saved + L.in1p, Cm, Co, +1);
   g.Wp = saved + L.k1_p; g.out = kb; g.bias = P->bias1; g.act = act;
   if (h3) {
@@ -2666,6 +2692,15 @@ int macx_stem_forward(const macx_stem_shapes* s, int act, float keep, uint32_t s
 int macx_stem_backward(const macx_stem_shapes* s, int act, float keep, uint32_t seed, const macx_stem_params* P, const float* kb,
                        const float* saved, size_t saved_floats, float* ws, size_t ws_floats, const float* d_kb,
                        const macx_stem_grads* G, void* stream) {
+  return macx_stem_backward_w(s, act, keep, seed, P, kb, saved, saved_floats, ws, ws_floats, d_kb, G, nullptr, stream);
+}
+
+// (the backward pass hashes nothing: layer 0's dropped input and layer 1's keep bits are in `saved`, written by the forward pass
+// under its word -- mask_word is taken so that the pair of calls has one shape, and ignored)
+int macx_stem_backward_w(const macx_stem_shapes* s, int act, float keep, uint32_t seed, const macx_stem_params* P, const float* kb,
+                         const float* saved, size_t saved_floats, float* ws, size_t ws_floats, const float* d_kb,
+                         const macx_stem_grads* G, const uint32_t* mask_word, void* stream) {
+  (void)mask_word;
   CKI(stem_check(s));
   if (!P || !kb || !saved || !ws || !d_kb || !G) return MACX_EINVAL;
   const StemLayout L = make_stem(s);
@@ -2851,6 +2886,12 @@ size_t macx_encoder_ws_floats(const macx_enc_shapes* s) { return enc_check(s) ? 
 int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
                          const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved,
                          size_t saved_floats, void* stream) {
+  return macx_encoder_forward_w(s, keep_input, keep_question, seed, P, questions, lengths, words, vecQ, saved, saved_floats, nullptr, stream);
+}
+
+int macx_encoder_forward_w(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
+                           const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved,
+                           size_t saved_floats, const uint32_t* mask_word, void* stream) {
   CKI(enc_check(s));
   if (!P || !questions || !lengths || !words || !vecQ || !saved) return MACX_EINVAL;
   const EncLayout L = make_enc(s);
@@ -2866,7 +2907,7 @@ int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_
   }
   CK(pk.run(st));
   hipLaunchKernelGGL(embed_gather_kernel, dim3(512), dim3(256), 0, st, questions, P->emb, B * S, E, Ep, (uint32_t)s->b0 * (uint32_t)S,
-                     make_drop(keep_input, seed, SITE_ENC_INPUT, 0), saved + L.Xp);
+                     make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), saved + L.Xp);
   CK(hipGetLastError());
   // input projections of every position, Zx = X Wx + b: the cell bias is added here once per position, so the per-step
   // recurrent linear needs none and both directions go in one launch (the two bias vectors are separate tensors)
@@ -2891,7 +2932,7 @@ int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_
     CK(dev_copy2d(vecQ + dir * h, (size_t)2 * h * sizeof(float), saved + L.hs + ((size_t)dir * (S + 1) + S) * Bh,
                         (size_t)h * sizeof(float), (size_t)h * sizeof(float), B, st));
   hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)vecQ, B, 2 * h, (uint32_t)s->b0,
-                     make_drop(keep_question, seed, SITE_QUESTION, 0), no_drop(), vecQ);
+                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), vecQ);
   CK(hipGetLastError());
   return MACX_OK;
 }
@@ -2899,6 +2940,14 @@ int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_
 int macx_encoder_backward(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
                           const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats, float* ws,
                           size_t ws_floats, const float* d_words, const float* d_vecQ, const macx_enc_grads* Gr, void* stream) {
+  return macx_encoder_backward_w(s, keep_input, keep_question, seed, P, questions, lengths, saved, saved_floats, ws, ws_floats, d_words,
+                                 d_vecQ, Gr, nullptr, stream);
+}
+
+int macx_encoder_backward_w(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
+                            const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats, float* ws,
+                            size_t ws_floats, const float* d_words, const float* d_vecQ, const macx_enc_grads* Gr,
+                            const uint32_t* mask_word, void* stream) {
   CKI(enc_check(s));
   if (!P || !questions || !lengths || !saved || !ws || !d_words || !d_vecQ || !Gr) return MACX_EINVAL;
   const EncLayout L = make_enc(s);
@@ -2918,7 +2967,7 @@ int macx_encoder_backward(const macx_enc_shapes* s, float keep_input, float keep
   CK(dev_zero(ws + W.dc, 2 * Bh * sizeof(float), st));
   // d(final states) = d_vecQ through the question dropout, split per direction
   hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, d_vecQ, B, 2 * h, (uint32_t)s->b0,
-                     make_drop(keep_question, seed, SITE_QUESTION, 0), no_drop(), ws + W.dq);
+                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), ws + W.dq);
   for (int dir = 0; dir < 2; ++dir)
     CK(dev_copy2d(ws + W.dh + (size_t)dir * Bh, (size_t)h * sizeof(float), ws + W.dq + dir * h, (size_t)2 * h * sizeof(float),
                         (size_t)h * sizeof(float), B, st));
@@ -2957,7 +3006,7 @@ int macx_encoder_backward(const macx_enc_shapes* s, float keep_input, float keep
     CK(small_linear_launch(l, 1, st));
   }
   hipLaunchKernelGGL(embed_grad_kernel, dim3(s->V, (E + 1023) / 1024), dim3(256), 0, st, questions, (const float*)(ws + W.dXp), B * S, E, Ep,
-                     (uint32_t)s->b0 * (uint32_t)S, make_drop(keep_input, seed, SITE_ENC_INPUT, 0), Gr->emb);
+                     (uint32_t)s->b0 * (uint32_t)S, make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), Gr->emb);
   CK(hipGetLastError());
   return MACX_OK;
 }
@@ -2965,22 +3014,49 @@ int macx_encoder_backward(const macx_enc_shapes* s, float keep_input, float keep
 // =================================================================================================
 // optimizer step (model.py:615-669): SURVEY 8f row 3
 // =================================================================================================
-int macx_adam_ema_step(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr, float beta1,
-                       float beta2, float eps, int step, float clip_norm, float ema_decay, float* ws, float* norm_out,
-                       void* stream) {
-  if (!params || !grads || !m || !v || !ws || n == 0 || step < 1) return MACX_EINVAL;
-  if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
+namespace {
+// lr_t_dev null: the by-value rate `lr_t`; else the kernel reads the rate from device memory when it runs
+int adam_ema_launch(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr_t, const float* lr_t_dev,
+                    float beta1, float beta2, float eps, float clip_norm, float ema_decay, float* ws, float* norm_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   int blocks = (int)((n + 255) / 256);
   if (blocks > OPT_BLOCKS) blocks = OPT_BLOCKS;
   hipLaunchKernelGGL(opt_sumsq_kernel, dim3(blocks), dim3(256), 0, st, grads, n, ws);
   OptP q;
   q.n = n; q.p = params; q.g = grads; q.m = m; q.v = v; q.ema = ema;
-  // tf.train.AdamOptimizer: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
-  q.lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step)));
+  q.lr_t = lr_t; q.lr_t_dev = lr_t_dev;
   q.beta1 = beta1; q.beta2 = beta2; q.eps = eps; q.clip = clip_norm; q.ema_decay = ema_decay;
   q.part = ws; q.nparts = blocks; q.norm_out = norm_out;
   hipLaunchKernelGGL(opt_apply_kernel, dim3(blocks), dim3(256), 0, st, q);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+}  // namespace
+
+int macx_adam_ema_step(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr, float beta1,
+                       float beta2, float eps, int step, float clip_norm, float ema_decay, float* ws, float* norm_out,
+                       void* stream) {
+  if (!params || !grads || !m || !v || !ws || n == 0 || step < 1) return MACX_EINVAL;
+  if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
+  // tf.train.AdamOptimizer: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step)));
+  return adam_ema_launch(n, params, grads, m, v, ema, lr_t, nullptr, beta1, beta2, eps, clip_norm, ema_decay, ws, norm_out, stream);
+}
+
+int macx_adam_ema_step_p(size_t n, float* params, const float* grads, float* m, float* v, float* ema, const float* lr_t_dev,
+                         float beta1, float beta2, float eps, float clip_norm, float ema_decay, float* ws, float* norm_out,
+                         void* stream) {
+  if (!params || !grads || !m || !v || !ws || !lr_t_dev || n == 0) return MACX_EINVAL;
+  if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
+  return adam_ema_launch(n, params, grads, m, v, ema, 0.f, lr_t_dev, beta1, beta2, eps, clip_norm, ema_decay, ws, norm_out, stream);
+}
+
+int macx_gather_flat(const macx_gather_entry* table_dev, int entries, float* flat, void* stream) {
+  static_assert(sizeof(macx_gather_entry) == sizeof(GatherEntry) && sizeof(GatherEntry) == 24, "gather table entry layout");
+  if (!table_dev || !flat || entries < 0 || ((uintptr_t)table_dev & 7) || ((uintptr_t)flat & 3)) return MACX_EINVAL;
+  if (entries == 0) return MACX_OK;
+  hipLaunchKernelGGL(gather_flat_kernel, dim3(GATHER_BLOCKS), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const GatherEntry*>(table_dev), entries, flat);
   CK(hipGetLastError());
   return MACX_OK;
 }

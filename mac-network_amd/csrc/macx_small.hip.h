@@ -936,7 +936,8 @@ __global__ void crop_cols_kernel(const float* __restrict__ src, int ld_src, int 
 struct PadP { int B, N, w, wp, np, C; };
 // dst_pad[b][pp(n)] = dropout(src[b][n]);  optional keep bits indexed like src ([B*N][C/32])
 __global__ __launch_bounds__(256) void pad_drop_kernel(const float* __restrict__ src, PadP q, uint32_t key, uint32_t thr24, float inv_keep,
-                                                      uint32_t first, float* dst, uint32_t* bits) {
+                                                      uint32_t first, float* dst, uint32_t* bits, const uint32_t* word = nullptr) {
+  key = run_key(key, word);
   const int c4n = q.C >> 2;
   const size_t total = (size_t)q.B * q.np * c4n;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -1003,6 +1004,7 @@ __global__ __launch_bounds__(256) void pad_mul_actgrad_kernel(const float* __res
 // x[b][s][0:E] = dropout(embeddings[idx]) with embeddings = concat([zeros(1,E), emb]) (model.py:217); columns E..Ep-1 = 0
 __global__ void embed_gather_kernel(const int32_t* __restrict__ idx, const float* __restrict__ emb, int rows, int E, int Ep, uint32_t row0,
                                     DropSpec ds, float* x) {
+  ds = drop_resolve(ds);
   const size_t total = (size_t)rows * Ep;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / Ep;
@@ -1231,6 +1233,7 @@ inline size_t lstm_step_bwd_lds(int h) { return ((size_t)16 * (4 * h + 4) + 256 
 // ascending row order: the scan is rows / 256 short passes instead of `rows` sequential compares per thread.
 __global__ __launch_bounds__(256) void embed_grad_kernel(const int32_t* __restrict__ idx, const float* __restrict__ dx, int rows, int E, int Ep,
                                                         uint32_t row0, DropSpec ds, float* demb) {
+  ds = drop_resolve(ds);
   __shared__ int list[256];
   __shared__ int wcount[4];
   const int v = blockIdx.x + 1;
@@ -1293,6 +1296,7 @@ struct OptP {
   size_t n;
   float* p; const float* g; float* m; float* v; float* ema;
   float lr_t, beta1, beta2, eps, clip, ema_decay;   // lr_t already holds sqrt(1-b2^t)/(1-b1^t); clip <= 0: off; ema_decay < 0: off
+  const float* lr_t_dev;                             // non-null: lr_t is read from device memory when the kernel RUNS (macx_adam_ema_step_p)
   const float* part; int nparts;
   float* norm_out;                                   // [1] global gradient norm (before clipping)
 };
@@ -1307,13 +1311,48 @@ __global__ __launch_bounds__(256) void opt_apply_kernel(OptP q) {
   __syncthreads();
   // tf.clip_by_global_norm: g * clip / max(norm, clip)
   const float scale = q.clip > 0.f ? q.clip / fmaxf(s_norm, q.clip) : 1.0f;
+  const float lr_t = q.lr_t_dev ? *q.lr_t_dev : q.lr_t;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (size_t)gridDim.x * 256) {
     const float g = q.g[i] * scale;
     const float m = q.beta1 * q.m[i] + (1.0f - q.beta1) * g;
     const float v = q.beta2 * q.v[i] + (1.0f - q.beta2) * g * g;
-    const float p = q.p[i] - q.lr_t * m / (sqrtf(v) + q.eps);
+    const float p = q.p[i] - lr_t * m / (sqrtf(v) + q.eps);
     q.m[i] = m; q.v[i] = v; q.p[i] = p;
     if (q.ema_decay >= 0.f) q.ema[i] = q.ema[i] - (1.0f - q.ema_decay) * (q.ema[i] - p);   // tf.train.ExponentialMovingAverage
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// flat gather (macx_gather_flat): `entries` tensors copied into their slices of one flat buffer in ONE launch.  The table lives
+// in device memory (its pointers are read when the kernel RUNS, so a captured graph follows a table written after the capture).
+// Work is cut into chunks of 1024 floats, numbered through the table in order; workgroup b takes the chunks b, b + grid, ... --
+// a mapping fixed by the table alone, no atomics.  A chunk starts a multiple of 4096 bytes into its entry, so one alignment
+// test per entry decides between dwordx4 and scalar accesses; the last, partial quad of an entry goes scalar; the pad floats
+// between two slices are never written.  src == null: the slice is zero-filled.
+// ---------------------------------------------------------------------------------------------
+struct GatherEntry { const float* src; unsigned long long dst_offset; unsigned long long count; };
+constexpr int GATHER_CHUNK = 1024;
+constexpr int GATHER_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void gather_flat_kernel(const GatherEntry* __restrict__ table, int entries, float* __restrict__ flat) {
+  const unsigned long long G = gridDim.x, b = blockIdx.x;
+  unsigned long long base = 0;                           // chunks of the entries in front of this one
+  for (int e = 0; e < entries; ++e) {
+    const GatherEntry t = table[e];
+    const unsigned long long nchunks = (t.count + GATHER_CHUNK - 1) / GATHER_CHUNK;
+    float* dst = flat + t.dst_offset;
+    const bool vec = (((uintptr_t)dst | (uintptr_t)t.src) & 15) == 0;
+    for (unsigned long long c = (b + G - base % G) % G; c < nchunks; c += G) {
+      const unsigned long long i = c * GATHER_CHUNK + (unsigned long long)threadIdx.x * 4;
+      if (vec && i + 4 <= t.count) {
+        const f32x4 v = t.src ? *reinterpret_cast<const f32x4*>(t.src + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(dst + i) = v;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (i + k < t.count) dst[i + k] = t.src ? t.src[i + k] : 0.f;
+      }
+    }
+    base += nchunks;
   }
 }
 

@@ -8,6 +8,8 @@ gradient buffer (cell only: 2.1 M + p * 0.26 M parameters = 21 MB at p = 12).  E
 the MEAN loss over its shard (model.py:596); shard gradients are combined weighted by shard size so
 that the result equals the full-batch gradient.
 """
+import ctypes as C
+
 import torch
 import torch.distributed as dist
 
@@ -209,10 +211,24 @@ class TowerBuckets:
 
         bucket = TowerBuckets(net); opt = FlatAdamEMA(bucket.tensors(), ...)
         bucket.begin_step(shard, global_batch); loss.backward(); bucket.allreduce_(shard, global_batch); opt.step(bucket.flat)
+
+    fused_gather=True gathers with ONE launch of macx_gather_flat per gather instead of one copy_ per tensor (17 outside the cell):
+    a table of (gradient pointer, offset, count) in device memory, uploaded when the gradients' addresses change -- in a steady
+    training loop the allocator hands the same blocks back, so once.  It is also what makes the gather capturable: a per-tensor
+    copy_ becomes a memcpy node, which HIP graph replay does not keep in stream order with kernel nodes (graph.py).  Under a
+    capture the gradients live in the graph's pool and nothing can be uploaded, so the capture only points the kernel at a
+    SPARE table and flush_tables() fills it once the capture has ended.  The spares are allocated here, in ordinary memory,
+    zeroed (an unflushed table gathers nothing): a buffer allocated under the capture would sit in a block of the graph's
+    pool that an earlier temporary of the same graph has given back, and that temporary's kernels write it again on every
+    replay -- behind the upload, in front of the gather.  Two spares per captured step (reserve_tables() adds more).
     """
 
-    def __init__(self, net, group=None):
+    def __init__(self, net, group=None, fused_gather=False):
         self.net, self.group = net, group
+        self.fused_gather = bool(fused_gather)
+        self._tables = {}                    # (lo, hi) -> [host rows, device table]: the eager gathers
+        self._captured_tables = []           # [host rows, device table, uploaded]: one per gather issued under a capture
+        self._spare_tables = []              # device tables for gathers issued under a capture (see the class docstring)
         cell = net.cell
         if not hasattr(cell, "early_floats"):
             raise TypeError("TowerBuckets needs the fused cell's parameters (MACCellParams); a generic-path cell is exchanged with "
@@ -243,6 +259,8 @@ class TowerBuckets:
         self.side = torch.cuda.Stream(device=dev) if self.flat.is_cuda else None
         self.overlapped_steps = 0
         self.allreduce_ms = None
+        if self.fused_gather:
+            self.reserve_tables(4)
 
     def tensors(self):
         """the parameters in the flat buffer's order (what optim.FlatAdamEMA must be built over to take `flat` as it is)"""
@@ -255,7 +273,55 @@ class TowerBuckets:
         self.weight = float(shard_size) / float(global_size)
         self._early_started, self._early_work = False, None
 
+    def _gather_fused(self, lo, hi):
+        from . import _lib
+        base = self.flat.data_ptr()
+        rows = []
+        for t, o, n in zip(self._tensors[lo:hi], self.offsets[lo:hi], self.sizes[lo:hi]):
+            g = t.grad
+            if g is None:
+                rows.append((0, o, n))                               # no gradient: the slice is zero-filled
+                continue
+            if g.dtype != torch.float32 or g.device != self.flat.device or g.numel() != n:
+                raise TypeError("fused gather: a gradient that is not a float32 tensor of its parameter's size on the buffer's device")
+            if not g.is_contiguous():
+                g = g.contiguous()
+            if g.data_ptr() != base + 4 * o:
+                rows.append((g.data_ptr(), o, n))
+        if not rows:
+            return
+        flatrows = [x for r in rows for x in r]
+        if torch.cuda.is_current_stream_capturing():
+            if not self._spare_tables:
+                raise RuntimeError("fused gather under a capture: no spare table left (call bucket.reserve_tables(k) before capturing)")
+            table = self._spare_tables.pop()
+            self._captured_tables.append([flatrows, table, False])
+        else:
+            slot = self._tables.get((lo, hi))
+            if slot is None or slot[0] != flatrows:
+                table = torch.tensor(flatrows, dtype=torch.int64).to(self.flat.device)
+                self._tables[(lo, hi)] = [flatrows, table]
+            table = self._tables[(lo, hi)][1]
+        st = C.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
+        _lib.check(_lib.lib().macx_gather_flat(C.c_void_p(table.data_ptr()), len(rows), C.c_void_p(base), st), "macx_gather_flat")
+
+    def reserve_tables(self, k):
+        """k more spare device tables for gathers issued under a capture; call it outside any capture"""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("reserve_tables() inside a capture: the tables must not live in the graph's pool")
+        for _ in range(int(k)):
+            self._spare_tables.append(torch.zeros(3 * len(self._tensors), dtype=torch.int64, device=self.flat.device))
+
+    def flush_tables(self):
+        """upload the tables of the gathers issued under a capture (call once the capture has ended, before the first replay)"""
+        for slot in self._captured_tables:
+            if not slot[2]:
+                slot[1][:len(slot[0])].copy_(torch.tensor(slot[0], dtype=torch.int64))
+                slot[2] = True
+
     def _gather(self, lo, hi):
+        if self.fused_gather:
+            return self._gather_fused(lo, hi)
         for t, o, n in zip(self._tensors[lo:hi], self.offsets[lo:hi], self.sizes[lo:hi]):
             dst = self.flat[o:o + n]
             if t.grad is None:

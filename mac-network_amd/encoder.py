@@ -24,7 +24,8 @@ REF_NAMES = {"emb": "qEmbeddings/emb",
 
 class _EncoderFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, keep_in, keep_q, seed, b0, questions, lengths, *params):
+    def forward(ctx, mod, keep_in, keep_q, seed, b0, word, questions, lengths, *params):
+        # word: None (macx_encoder_forward / _backward) or the run's mask word, a 1-element int32 device tensor (the _w entry points)
         L = _lib.lib()
         B, S = questions.shape
         sh = _lib.MacxEncShapes(B=B, S=S, V=mod.vocab, E=mod.E, h=mod.h, b0=b0)
@@ -37,15 +38,22 @@ class _EncoderFunction(torch.autograd.Function):
         vecQ = torch.empty(B, 2 * mod.h, dtype=torch.float32, device=dev)
         ps = _lib.MacxEncParams(*[p.data_ptr() for p in params])
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(L.macx_encoder_forward(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(),
-                                          lengths.data_ptr(), words.data_ptr(), vecQ.data_ptr(), saved.data_ptr(), n_saved, st),
-                   "macx_encoder_forward")
-        ctx.stuff = (mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params)
+        args = (C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(), words.data_ptr(),
+                vecQ.data_ptr(), saved.data_ptr(), n_saved)
+        if word is None:
+            _lib.check(L.macx_encoder_forward(*args, st), "macx_encoder_forward")
+        else:
+            _lib.check(L.macx_encoder_forward_w(*args, word.data_ptr(), st), "macx_encoder_forward_w")
+        ctx.stuff = (mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params, word)
+        if torch.cuda.is_current_stream_capturing():
+            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
+            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
+            mod._capture_keep = saved
         return words, vecQ
 
     @staticmethod
     def backward(ctx, d_words, d_vecQ):
-        mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params = ctx.stuff
+        mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params, word = ctx.stuff
         L = _lib.lib()
         dev = saved.device
         n_ws = L.macx_encoder_ws_floats(C.byref(sh))
@@ -56,12 +64,15 @@ class _EncoderFunction(torch.autograd.Function):
         d_words = saved.new_zeros((sh.B, sh.S, 2 * sh.h)) if d_words is None else d_words.contiguous()
         d_vecQ = saved.new_zeros((sh.B, 2 * sh.h)) if d_vecQ is None else d_vecQ.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(L.macx_encoder_backward(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(),
-                                           lengths.data_ptr(), saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_words.data_ptr(),
-                                           d_vecQ.data_ptr(), C.byref(gs), st), "macx_encoder_backward")
+        args = (C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(), saved.data_ptr(),
+                n_saved, ws.data_ptr(), n_ws, d_words.data_ptr(), d_vecQ.data_ptr(), C.byref(gs))
+        if word is None:
+            _lib.check(L.macx_encoder_backward(*args, st), "macx_encoder_backward")
+        else:                                   # the word the forward pass hashed with
+            _lib.check(L.macx_encoder_backward_w(*args, word.data_ptr(), st), "macx_encoder_backward_w")
         if not mod.emb.requires_grad:
             grads[0] = None
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 8 + tuple(grads)
 
 
 def _check_fused(config):
@@ -130,8 +141,10 @@ class QuestionEncoder(torch.nn.Module):
         B, S = questions.shape
         return _Embed.apply(questions, self.emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
 
-    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True):
-        """questions [B,S] int32 (0 = pad), lengths [B] int32 -> (questionCntxWords [B,S,2h], vecQuestions [B,2h])."""
+    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
+        """questions [B,S] int32 (0 = pad), lengths [B] int32 -> (questionCntxWords [B,S,2h], vecQuestions [B,2h]).
+        mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's): XORed into the keys of the input
+        and the question dropout when the kernels run, so that one captured graph draws fresh masks per replay."""
         if not questions.is_cuda:
             raise RuntimeError("the question encoder has no CPU path")
         questions = questions.to(torch.int32).contiguous()
@@ -146,7 +159,9 @@ class QuestionEncoder(torch.nn.Module):
                 raise ValueError("question length outside [0, %d]" % questions.shape[1])
         keep_in = self.keep_in if train else 1.0
         keep_q = self.keep_q if train else 1.0
-        return _EncoderFunction.apply(self, keep_in, keep_q, fresh_seed(seed, train), int(b0), questions, lengths, *self.tensors())
+        from .cell import _mask_word
+        return _EncoderFunction.apply(self, keep_in, keep_q, fresh_seed(seed, train), int(b0), _mask_word(mask_word, questions),
+                                      questions, lengths, *self.tensors())
 
 
 class GenericQuestionEncoder(torch.nn.Module):
@@ -262,8 +277,11 @@ class GenericQuestionEncoder(torch.nn.Module):
             emb = self.params.get("emb", (self.vocab, self.E), "normal")
         return _Embed.apply(questions, emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
 
-    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True):
+    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
         """questions [B,S] int (0 = pad), lengths [B] -> (questionCntxWords [B,S,w], vecQuestions [B,w]), w = ctrlDim when projected."""
+        if mask_word is not None:
+            raise UnsupportedOptions("encoder: a run's mask word is taken by the fused encoder only (macx_encoder_forward_w); the "
+                                     "generic encoder has no such path")
         from . import generic as G
         from .generic import B_CHANNEL, B_ROW, B_SAME, OP_ADD, OP_MUL, _Act, _Binary, _Dropout, _Embed, _Linear
         G._require_device(questions, "questions")                       # no CPU path

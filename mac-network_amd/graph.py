@@ -40,7 +40,7 @@ import torch
 
 from .cell import MACCell
 from .dp import TwoPhaseStep
-from .options import get
+from .options import UnsupportedOptions, get
 
 
 def mix32(x):
@@ -437,3 +437,315 @@ class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
         self.exchange_step()
         self._count_replay()
         return self.memory
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the whole tower (model.MACNet: question ids, lengths, image features in; logits out) from one graph
+# ---------------------------------------------------------------------------------------------------------------------------
+def _require_fused_tower(net, who):
+    """the tower's captured classes take a model.MACNet whose four modules are the fused ones (UnsupportedOptions otherwise), on
+    the HIP device (RuntimeError otherwise); returns the device"""
+    from .encoder import QuestionEncoder
+    from .output import OutputClassifier
+    from .params import MACCellParams
+    from .stem import Stem
+    want = (("enc", QuestionEncoder), ("stem", Stem), ("cell", MACCellParams), ("out", OutputClassifier))
+    for name, cls in want:
+        mod = getattr(net, name, None)
+        if mod is None:
+            raise TypeError("%s takes a macx.MACNet (question encoder, stem, cell, output unit); this net has no .%s" % (who, name))
+        if not isinstance(mod, cls):
+            raise UnsupportedOptions("%s: net.%s is a %s; only a tower of the fused modules (%s) is captured -- the generic "
+                                     "one-kernel-per-op modules are out of its scope" % (who, name, type(mod).__name__,
+                                                                                        ", ".join(c.__name__ for _, c in want)))
+    dev = net.tensors()[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("%s needs the HIP device: the tower has no CPU path" % who)
+    return dev
+
+
+def _random_tower_inputs(gen, B, S, vocab, shape_images, answers, dev):
+    """(images, questions, lengths, answer ids) for the self-checks: relu(N(0,1)) features, ids in [1, vocab] up to each question's
+    length (question 0 at full length, one of length 1 when B > 1), zero pad ids behind it"""
+    images = torch.relu(torch.randn(shape_images, generator=gen))
+    lengths = torch.randint(1, S + 1, (B,), generator=gen, dtype=torch.int32)
+    lengths[0] = S
+    if B > 1:
+        lengths[1] = 1
+    q = torch.randint(1, vocab + 1, (B, S), generator=gen, dtype=torch.int32)
+    q = q * (torch.arange(S).unsqueeze(0) < lengths.unsqueeze(1)).to(torch.int32)
+    ans = torch.randint(0, answers, (B,), generator=gen, dtype=torch.int32)
+    return images.to(dev), q.to(dev), lengths.to(dev), ans.to(dev)
+
+
+class _TowerInputs:
+    """the static input tensors of a captured tower and load() into them"""
+
+    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev):
+        self.B, self.S, self.H, self.W, self.imageInDim = int(B), int(S), int(H), int(W), int(imageInDim)
+        if (net.stem.H, net.stem.W, net.stem.inDim) != (self.H, self.W, self.imageInDim):
+            raise ValueError("the net's stem was built for %d x %d x %d image features, not %d x %d x %d"
+                             % (net.stem.H, net.stem.W, net.stem.inDim, self.H, self.W, self.imageInDim))
+        self.images = torch.zeros(self.B, self.H * self.W, self.imageInDim, device=dev)          # NHWC, what the stem's kernels read
+        self.questions = torch.zeros(self.B, self.S, dtype=torch.int32, device=dev)
+        self.lengths = torch.full((self.B,), self.S, dtype=torch.int32, device=dev)
+
+    def _load_inputs(self, images, questions, lengths, check_ids):
+        if check_ids:                          # the encoder's own validation (host synchronisation), outside the graph
+            vocab = self.net.enc.vocab
+            if int(questions.max()) > vocab or int(questions.min()) < 0:
+                raise IndexError("question word id outside [0, %d]" % vocab)
+            if int(lengths.max()) > self.S or int(lengths.min()) < 0:
+                raise ValueError("question length outside [0, %d]" % self.S)
+        with torch.no_grad():
+            if images.dim() == 4 and images.shape[1] == self.imageInDim and tuple(images.shape[2:]) == (self.H, self.W):
+                from .stem import k_nchw_to_nhwc          # the feed-dict layout [B, C, H, W]: transposed on the device
+                images = k_nchw_to_nhwc(images.to(self.images.device).contiguous(), self.imageInDim, self.H * self.W)
+            self.images.copy_(images.reshape(self.images.shape))
+            self.questions.copy_(questions)
+            self.lengths.copy_(lengths)
+
+
+class CapturedTowerForward(_RunStatus, _TowerInputs):
+    """Evaluation forward of a whole macx.MACNet -- embedding + biLSTM encoder (about 100 dependent LSTM step launches), stem, cell,
+    output unit + classifier, argmax -- replayed from ONE captured HIP graph on static input tensors.
+
+        fwd = macx.CapturedTowerForward(net, B=64, S=50)
+        logits = fwd(images, questions, lengths)          # [B, answers], valid until the next call; fwd.pred: int32 argmax
+        att_kb = fwd.attentions["kb"]                     # the captured cell's p x [B, N] views, refreshed by every replay
+
+    Evaluation only (train=False: no dropout, nothing kept for a backward pass).  Parameters are read at replay time: an optimizer
+    step or a checkpoint load between calls is seen; changing a parameter's storage needs a new capture.  `load()` validates ids
+    and lengths on the host as QuestionEncoder.forward does (check_ids=False skips the synchronisation); the graph itself runs
+    the net with check_ids=False.  verify / captured / check() / check_every: as CapturedForward.
+    Copies on the captured path: none -- every module writes into outputs it allocates from the graph's pool, the cell's final
+    state and attentions are views of its `saved` buffer."""
+
+    def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0):
+        dev = _require_fused_tower(net, "CapturedTowerForward")
+        self.net = net
+        self.check_every = int(check_every)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev)
+        self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                self._eager()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        with torch.cuda.graph(self.graph):
+            self.logits, self.pred = self._eager()
+        self._after_capture()
+        self._captured_cell = self.cell
+        self.attentions = self.cell.attentions
+        self.captured = True
+        if verify and not self._replays_match_eager():
+            self.captured = False
+            warnings.warn("CapturedTowerForward: replays of the captured tower do not reproduce the eager forward in this process; "
+                          "falling back to eager launches", RuntimeWarning)
+
+    def _eager(self):
+        from .output import _AnswerLoss
+        with torch.no_grad():
+            logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False)
+            self.cell = self.net.last_cell                  # (status(): the latest run's buffers)
+            _, pred = _AnswerLoss.apply(logits, self._no_answers)      # addPredOp's argmax (first maximum), one kernel
+        return logits, pred
+
+    def _replays_match_eager(self, replays=3):
+        g = torch.Generator().manual_seed(20240521)
+        dev = self.images.device
+        images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, dev)
+        self._load_inputs(images, q, lengths, False)
+        want, want_pred = [t.clone() for t in self._eager()]
+        self.check()                                        # the eager run's own buffers
+        self.cell = self._captured_cell
+        self.verify_report = []                             # (replay, "logits" | "pred") of everything that differed
+        for r in range(replays):
+            self.graph.replay()
+            if not torch.equal(self.logits, want):
+                self.verify_report.append((r, "logits"))
+            if not torch.equal(self.pred, want_pred):
+                self.verify_report.append((r, "pred"))
+        torch.cuda.synchronize(dev)
+        self.check()
+        return not self.verify_report
+
+    def load(self, images, questions, lengths, check_ids=True):
+        self._load_inputs(images, questions, lengths, check_ids)
+
+    def replay(self):
+        if self.captured:
+            self.graph.replay()
+        else:                                               # (module docstring: slower where the host is slow, never wrong)
+            self.logits, self.pred = self._eager()
+            self.attentions = self.cell.attentions
+        self._count_replay()
+        return self.logits
+
+    def __call__(self, images, questions, lengths, check_ids=True):
+        self.load(images, questions, lengths, check_ids)
+        return self.replay()
+
+
+class CapturedTowerTrainStep(_RunStatus, _TowerInputs):
+    """One whole training step of a macx.MACNet replayed from ONE captured HIP graph: forward (train-mode dropout), mean CE loss,
+    backward, the gather of every gradient into the tower's flat buffer, global-norm clip + Adam + EMA.
+
+        bucket = macx.dp.TowerBuckets(net, fused_gather=True)
+        opt = macx.optim.FlatAdamEMA(bucket.tensors(), lr=1e-4)
+        step = macx.CapturedTowerTrainStep(net, opt, bucket, B=64, S=50, H=14, W=14, imageInDim=1024, seed=1234)
+        for it in range(steps):
+            step.load(images, questions, lengths, answers)
+            step.replay(iteration=it)                     # step.loss, step.logits, step.pred, step.norm
+
+    Three things a capture would otherwise freeze travel through device memory and are written by replay(), outside the graph:
+    the dropout masks -- every site of the tower (encoder, stem, cell, classifier) XORs `step.mask_word` into its key when the
+    kernel runs, replay(iteration=i) sets it to mix32(i), replay() keeps it; the optimizer's bias-corrected rate -- opt.advance()
+    counts the step and writes lr * sqrt(1 - b2^t) / (1 - b1^t) from the CURRENT opt.lr (so --lrReduce is followed); and the
+    inputs (`load`, which also runs the encoder's id / length validation on the host; check_ids=False skips that sync).
+
+    The graph holds exactly what the eager step issues: net(..., train=True, check_ids=False, mask_word=...), loss_and_pred,
+    bucket.begin_step / allreduce_(B, B) for this one process (macx_gather_flat: one launch per gather, its table uploaded after
+    the capture) and opt.step(flat_grad=bucket.flat, device_lr=True).  Data parallelism over several processes is not captured
+    here (CapturedDPTrainStep is the cell-level route).  `opt` must be built over bucket.tensors(), `bucket` with
+    fused_gather=True.
+
+    verify=True replays three times against the eager step on random inputs -- loss, logits, pred, norm, the flat gradient, every
+    parameter, m, v, ema -- each time from the same restored state, and falls back to eager launches when anything differs
+    (`captured` False, a RuntimeWarning; `verify_report` lists what differed).  Parameters, m, v, ema and t are restored
+    afterwards: a constructed step has not trained.
+
+    Copies on the captured path: none issued by the library or by this class.  What autograd adds is torch's own business: it
+    adopts each returned gradient as the parameter's .grad without a copy as long as nobody else holds it (the module functions
+    return fresh tensors), and sums the two gradients of vecQuestions with a kernel."""
+
+    def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0):
+        dev = _require_fused_tower(net, "CapturedTowerTrainStep")
+        if not getattr(bucket, "fused_gather", False):
+            raise ValueError("CapturedTowerTrainStep needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
+                             "nodes, which graph replay does not keep in stream order")
+        if bucket.net is not net:
+            raise ValueError("the bucket was built over another net")
+        own = bucket.tensors()
+        if len(opt.params) != len(own) or any(a is not b for a, b in zip(opt.params, own)) or opt.flat.numel() != bucket.flat.numel():
+            raise ValueError("the optimizer must be built over bucket.tensors() (FlatAdamEMA(bucket.tensors(), ...)): it steps on "
+                             "bucket.flat as it is")
+        self.net, self.opt, self.bucket, self.seed = net, opt, bucket, int(seed)
+        self.check_every = int(check_every)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev)
+        self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.mask_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.norm = opt.norm
+        state = self._state()
+        self.graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                opt.advance()
+                self._eager()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self._clear_grads()
+        with torch.cuda.graph(self.graph):
+            self.loss, self.logits, self.pred = self._eager()
+        bucket.flush_tables()
+        self._after_capture()
+        self._captured_cell = self.cell
+        self._captured_grads = [t.grad for t in own]       # views of bucket.flat: what a replay leaves in .grad
+        self.captured = True
+        self.verify_report = []
+        if verify and not self._replays_match_eager(state):
+            self.captured = False
+            warnings.warn("CapturedTowerTrainStep: replays of the captured step do not reproduce the eager step in this process; "
+                          "falling back to eager launches", RuntimeWarning)
+        self._restore(state)                                # warm-up (and verification) trained on zeros: undo
+
+    # ---- the optimizer's state, saved and restored around warm-up and verification
+    def _buffers(self):
+        o = self.opt
+        return [b for b in (o.flat, o.m, o.v, o.ema) if b is not None]
+
+    def _state(self):
+        return [b.clone() for b in self._buffers()], self.opt.t, self.opt.lr_t.clone()
+
+    def _restore(self, state):
+        bufs, t, lr_t = state
+        with torch.no_grad():
+            for b, s in zip(self._buffers(), bufs):
+                b.copy_(s)
+            self.opt.lr_t.copy_(lr_t)
+        self.opt.t = t
+
+    def _clear_grads(self):
+        for t in self.bucket.tensors():
+            t.grad = None
+
+    def _eager(self):
+        """the step's launches on the current stream (opt.advance() is the caller's: it is not part of the graph)"""
+        self._clear_grads()
+        net, B = self.net, self.B
+        logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word)
+        self.cell = net.last_cell
+        loss, pred = net.loss_and_pred(logits, self.answers)
+        self.bucket.begin_step(B, B)
+        loss.backward()
+        self.bucket.allreduce_(B, B)                        # one process: the gather; nothing is exchanged
+        self.opt.step(flat_grad=self.bucket.flat, device_lr=True)
+        return loss.detach(), logits.detach(), pred
+
+    def set_mask_word(self, word):
+        """the raw 32-bit word the next replays XOR into every dropout key (0: the masks of the plain seed)"""
+        word &= 0xFFFFFFFF
+        self.mask_word.fill_(word - (1 << 32) if word >= (1 << 31) else word)
+
+    def _replays_match_eager(self, state, replays=3):
+        g = torch.Generator().manual_seed(20240522)
+        dev = self.images.device
+        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers, dev)
+        self._load_inputs(images, q, lengths, False)
+        self.answers.copy_(ans)
+        self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
+        self._restore(state)
+        self.opt.advance()
+        out = self._eager()
+        names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
+        got = lambda o: list(o) + [self.opt.norm, self.bucket.flat] + self._buffers()
+        want = [t.clone() for t in got(out)]
+        self.check()                                        # the eager run's own buffers
+        self.cell = self._captured_cell
+        for t, gcap in zip(self.bucket.tensors(), self._captured_grads):
+            t.grad = gcap
+        self.verify_report = []                             # (replay, name) of everything that differed
+        for r in range(replays):
+            self._restore(state)
+            self.opt.advance()
+            self.graph.replay()
+            for n, a, b in zip(names, got((self.loss, self.logits, self.pred)), want):
+                if not torch.equal(a, b):
+                    self.verify_report.append((r, n))
+        torch.cuda.synchronize(dev)
+        self.set_mask_word(0)
+        self.check()
+        return not self.verify_report
+
+    def load(self, images, questions, lengths, answers, check_ids=True):
+        self._load_inputs(images, questions, lengths, check_ids)
+        with torch.no_grad():
+            self.answers.copy_(answers)
+
+    def replay(self, iteration=None):
+        """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration).  Counts the optimizer's
+        step and refreshes its rate from opt.lr (opt.advance()), then replays."""
+        if iteration is not None:
+            self.set_mask_word(mix32(int(iteration)))
+        self.opt.advance()
+        if self.captured:
+            self.graph.replay()
+        else:
+            self.loss, self.logits, self.pred = self._eager()
+        self._count_replay()
+        return self.loss

@@ -44,8 +44,14 @@ class MACNetCore(torch.nn.Module):
         return self.stem.tensors() + self.cell.tensors() + self.out.tensors()
 
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
-                questionWords=None):
+                questionWords=None, mask_word=None):
+        """mask_word: None, or one 1-element int32 device tensor (MACCell's mask_word) handed to the stem, the cell and the output
+        unit: every dropout site of the tower XORs it into its key when the kernels run (graph.CapturedTowerTrainStep).  Fused
+        modules only."""
         cfg = self.config
+        if mask_word is not None and not isinstance(self.cell, MACCellParams):
+            raise UnsupportedOptions("a run's mask word over the whole tower needs the fused cell (MACCellParams); this option set "
+                                     "runs the cell on the generic path")
         if questionWords is None:
             if not get(cfg, "controlContextual"):
                 # mac_cell.py:570 would select the raw word embeddings; silently attending over the encoder outputs instead
@@ -54,14 +60,15 @@ class MACNetCore(torch.nn.Module):
                                          "(mac_cell.py:570): pass them as questionWords=[B,S,ctrlDim]")
             questionWords = questionCntxWords
         seed = fresh_seed(seed, train)
-        kb = self.stem(images, train=train, seed=seed, b0=b0)                       # model.py:791
+        word = {} if mask_word is None else {"mask_word": mask_word}               # (None: the modules' calls of before)
+        kb = self.stem(images, train=train, seed=seed, b0=b0, **word)               # model.py:791
         cell = MACCell(vecQuestions=vecQuestions, questionWords=questionWords, questionCntxWords=questionCntxWords,
                        questionLengths=questionLengths, knowledgeBase=kb, memoryDropout=get(cfg, "memoryDropout"),
                        readDropout=get(cfg, "readDropout"), writeDropout=get(cfg, "writeDropout"), batchSize=images.shape[0],
-                       train=train, config=cfg, params=self.cell, netLength=self.netLength, seed=seed, b0=b0)
+                       train=train, config=cfg, params=self.cell, netLength=self.netLength, seed=seed, b0=b0, **word)
         state = cell.run()                                                           # model.py:801 (MACnetwork)
         self.last_cell = cell
-        return self.out(state.memory, vecQuestions, train=train, seed=seed, b0=b0)   # model.py:805-809
+        return self.out(state.memory, vecQuestions, train=train, seed=seed, b0=b0, **word)   # model.py:805-809
 
     @staticmethod
     def loss_and_pred(logits, answers):
@@ -78,9 +85,10 @@ class MACNet(MACNetCore):
     def tensors(self):
         return self.enc.tensors() + super().tensors()
 
-    def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True):
+    def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
         seed = fresh_seed(seed, train)
-        words, vecQ = self.enc(questions, questionLengths, train=train, seed=seed, b0=b0, check_ids=check_ids)   # model.py:783-788
+        word = {} if mask_word is None else {"mask_word": mask_word}
+        words, vecQ = self.enc(questions, questionLengths, train=train, seed=seed, b0=b0, check_ids=check_ids, **word)   # model.py:783-788
         raw = None
         if not get(self.config, "controlContextual"):
             # mac_cell.py:570: the control unit attends over the embedded words themselves (embeddingsOp's output, no dropout)
@@ -88,4 +96,4 @@ class MACNet(MACNetCore):
             if raw.shape[-1] != get(self.config, "ctrlDim"):
                 raise ValueError("Dimensions must be equal: without --controlContextual the question words are wrdEmbDim = %d wide, "
                                  "the control state ctrlDim = %d (mac_cell.py:154)" % (raw.shape[-1], get(self.config, "ctrlDim")))
-        return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw)
+        return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw, **word)

@@ -5,6 +5,7 @@ The parameters are re-pointed at slices of one flat tensor; gradients are gather
 macx.dp.GradBucket.allreduce_, already live in) one flat tensor; Adam moments and the EMA shadow are flat
 buffers too.  SURVEY.md 8f row 3."""
 import ctypes as C
+import math
 
 import torch
 
@@ -45,9 +46,29 @@ class FlatAdamEMA:
         self.clip_norm = clip_norm if clip_norm else 0.0
         self.ema_decay = ema_decay if self.ema is not None else -1.0
         self.t = 0
+        # the bias-corrected rate of step t in DEVICE memory (macx_adam_ema_step_p reads it when the kernel runs): written by advance()
+        self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
 
-    def step(self, flat_grad=None):
-        """flat_grad: an already flat gradient in THIS layout -- the parameters in order, each segment padded to a multiple of
+    @staticmethod
+    def bias_corrected_lr(lr, beta1, beta2, t):
+        """(float) (lr * sqrt(1 - beta2^t) / (1 - beta1^t)) as macx_adam_ema_step computes it: lr, beta1, beta2 arrive there as C
+        floats, the expression is evaluated in double and rounded to float once."""
+        f = lambda x: C.c_float(x).value
+        return f(f(lr) * math.sqrt(1.0 - math.pow(f(beta2), t)) / (1.0 - math.pow(f(beta1), t)))
+
+    def advance(self):
+        """The host half of a step(device_lr=True): t += 1, and the rate of step t from the CURRENT self.lr into the device scalar.
+        Call it outside a captured graph, before each replay: the captured update kernel then follows the step count and any
+        change of self.lr (--lrReduce)."""
+        self.t += 1
+        self.lr_t.fill_(self.bias_corrected_lr(self.lr, self.beta1, self.beta2, self.t))
+        return self.t
+
+    def step(self, flat_grad=None, device_lr=False):
+        """device_lr: False -- the step of before: t += 1 here, lr and t travel by value (macx_adam_ema_step).  True -- this call only
+        ENQUEUES the update (macx_adam_ema_step_p): the kernel reads the rate advance() wrote, t is not touched; the pair
+        advance(); step(device_lr=True) gives the bits of step().  What a captured graph holds (graph.CapturedTowerTrainStep).
+        flat_grad: an already flat gradient in THIS layout -- the parameters in order, each segment padded to a multiple of
         4 floats: dp.GradBucket.flat / TowerBuckets.flat after the all-reduce, or MACCellParams.grad_buffer() for a cell-only
         optimizer built with grad_owner= (without a registered consumer the backward pass does not write into that buffer: a
         stale or zero gradient would be stepped on -- refused below; a dp bucket over the parameters is such a consumer).  A buffer of any other size is rejected.  Without
@@ -70,10 +91,17 @@ class FlatAdamEMA:
         elif flat_grad.numel() != self.flat.numel() or flat_grad.dtype != torch.float32:
             raise ValueError("flat_grad holds %d floats, this optimizer's layout %d (segments padded to 4 floats, parameters in "
                              "the order given at construction)" % (flat_grad.numel(), self.flat.numel()))
-        self.t += 1
         L = _lib.lib()
         dev = self.flat.device
         p_ = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        if device_lr:
+            _lib.check(L.macx_adam_ema_step_p(self.flat.numel(), p_(self.flat), p_(flat_grad), p_(self.m), p_(self.v), p_(self.ema),
+                                              p_(self.lr_t), self.beta1, self.beta2, self.eps, self.clip_norm, self.ema_decay, p_(self.ws),
+                                              p_(self.norm), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "macx_adam_ema_step_p")
+            if self.grad_owner is not None:
+                self.grad_owner.release_grad_buffer()
+            return self.norm
+        self.t += 1
         _lib.check(L.macx_adam_ema_step(self.flat.numel(), p_(self.flat), p_(flat_grad), p_(self.m), p_(self.v), p_(self.ema), self.lr,
                                         self.beta1, self.beta2, self.eps, self.t, self.clip_norm, self.ema_decay, p_(self.ws),
                                         p_(self.norm), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "macx_adam_ema_step")

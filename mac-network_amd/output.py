@@ -27,7 +27,7 @@ REF_NAMES = {
 
 class _OutFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, keep, seed, b0, memory, vecQ, *params):
+    def forward(ctx, mod, keep, seed, b0, word, memory, vecQ, *params):
         L = _lib.lib()
         B, d = memory.shape
         sh = _lib.MacxOutShapes(B=B, d=d, hidden=mod.hidden, answers=mod.answers, b0=b0)
@@ -39,14 +39,22 @@ class _OutFunction(torch.autograd.Function):
         logits = torch.empty(B, mod.answers, dtype=torch.float32, device=memory.device)
         memory, vecQ = memory.contiguous(), vecQ.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(memory.device).cuda_stream)
-        _lib.check(L.macx_output_forward(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
-                                         logits.data_ptr(), saved.data_ptr(), n_saved, st), "macx_output_forward")
-        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, memory, vecQ, params)
+        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(), logits.data_ptr(),
+                saved.data_ptr(), n_saved)
+        if word is None:
+            _lib.check(L.macx_output_forward(*args, st), "macx_output_forward")
+        else:                                   # the run's mask word (1-element int32 device tensor)
+            _lib.check(L.macx_output_forward_w(*args, word.data_ptr(), st), "macx_output_forward_w")
+        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, memory, vecQ, params, word)
+        if torch.cuda.is_current_stream_capturing():
+            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
+            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
+            mod._capture_keep = saved
         return logits
 
     @staticmethod
     def backward(ctx, d_logits):
-        mod, keep, seed, sh, saved, n_saved, memory, vecQ, params = ctx.stuff
+        mod, keep, seed, sh, saved, n_saved, memory, vecQ, params, word = ctx.stuff
         L = _lib.lib()
         n_ws = L.macx_output_ws_floats(C.byref(sh))
         ws = torch.empty(n_ws, dtype=torch.float32, device=memory.device)
@@ -56,10 +64,13 @@ class _OutFunction(torch.autograd.Function):
         dmem, dvq = torch.empty_like(memory), torch.empty_like(vecQ)
         d_logits = d_logits.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(memory.device).cuda_stream)
-        _lib.check(L.macx_output_backward(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
-                                          saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_logits.data_ptr(), C.byref(gs),
-                                          dmem.data_ptr(), dvq.data_ptr(), st), "macx_output_backward")
-        return (None, None, None, None, dmem, dvq) + tuple(grads)
+        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(), saved.data_ptr(), n_saved,
+                ws.data_ptr(), n_ws, d_logits.data_ptr(), C.byref(gs), dmem.data_ptr(), dvq.data_ptr())
+        if word is None:
+            _lib.check(L.macx_output_backward(*args, st), "macx_output_backward")
+        else:                                   # the word the forward pass hashed with
+            _lib.check(L.macx_output_backward_w(*args, word.data_ptr(), st), "macx_output_backward_w")
+        return (None, None, None, None, None, dmem, dvq) + tuple(grads)
 
 
 class OutputClassifier(torch.nn.Module):
@@ -101,11 +112,15 @@ class OutputClassifier(torch.nn.Module):
     def to_reference_dict(self):
         return {REF_NAMES[f]: getattr(self, f).detach().clone() for f in _lib.OUT_FIELDS}
 
-    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0):
+    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0, mask_word=None):
+        """mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's), XORed into the keys of both
+        layer-input dropouts when the kernels run."""
         if not memory.is_cuda:
             raise RuntimeError("the output unit has no CPU path")
         keep = self.keep if train else 1.0          # model.py:118-125
-        return _OutFunction.apply(self, keep, fresh_seed(seed, train), int(b0), memory, vecQuestions, *self.tensors())
+        from .cell import _mask_word
+        return _OutFunction.apply(self, keep, fresh_seed(seed, train), int(b0), _mask_word(mask_word, memory), memory, vecQuestions,
+                                  *self.tensors())
 
 
 def _check_fused(config):
@@ -196,7 +211,10 @@ class GenericOutputClassifier(torch.nn.Module):
         self.params.device = t[0].device if t else self.params.device
         return out
 
-    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0):
+    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0, mask_word=None):
+        if mask_word is not None:
+            raise UnsupportedOptions("output unit: a run's mask word is taken by the fused output unit only (macx_output_forward_w); "
+                                     "the generic classifier has no such path")
         from . import generic as G
         from .generic import B_SAME, OP_MUL, _Binary, _Dropout, _Linear
         G._require_device(memory, "memory")                              # no CPU path

@@ -25,7 +25,7 @@ REF_NAMES = {"kernel0": "stem/cnnLayercnn_0/kernels/kernel", "bias0": "stem/cnnL
 
 class _StemFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, keep, seed, b0, images, *params):
+    def forward(ctx, mod, keep, seed, b0, word, images, *params):
         L = _lib.lib()
         B = images.shape[0]
         sh = _lib.MacxStemShapes(B=B, H=mod.H, W=mod.W, Cin=mod.inDim, Cmid=mod.midDim, Cout=mod.outDim, b0=b0)
@@ -37,14 +37,21 @@ class _StemFunction(torch.autograd.Function):
         kb = torch.empty(B, mod.H * mod.W, mod.outDim, dtype=torch.float32, device=images.device)
         ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
         st = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-        _lib.check(L.macx_stem_forward(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), images.data_ptr(), kb.data_ptr(),
-                                       saved.data_ptr(), n_saved, st), "macx_stem_forward")
-        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, kb, params)
+        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), images.data_ptr(), kb.data_ptr(), saved.data_ptr(), n_saved)
+        if word is None:
+            _lib.check(L.macx_stem_forward(*args, st), "macx_stem_forward")
+        else:                                   # the run's mask word (1-element int32 device tensor)
+            _lib.check(L.macx_stem_forward_w(*args, word.data_ptr(), st), "macx_stem_forward_w")
+        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, kb, params, word)
+        if torch.cuda.is_current_stream_capturing():
+            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
+            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
+            mod._capture_keep = saved
         return kb
 
     @staticmethod
     def backward(ctx, d_kb):
-        mod, keep, seed, sh, saved, n_saved, kb, params = ctx.stuff
+        mod, keep, seed, sh, saved, n_saved, kb, params, word = ctx.stuff
         L = _lib.lib()
         n_ws = L.macx_stem_ws_floats(C.byref(sh))
         ws = torch.empty(n_ws, dtype=torch.float32, device=kb.device)
@@ -53,9 +60,13 @@ class _StemFunction(torch.autograd.Function):
         ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
         d_kb = d_kb.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(kb.device).cuda_stream)
-        _lib.check(L.macx_stem_backward(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), kb.data_ptr(), saved.data_ptr(),
-                                        n_saved, ws.data_ptr(), n_ws, d_kb.data_ptr(), C.byref(gs), st), "macx_stem_backward")
-        return (None, None, None, None, None) + tuple(grads)     # image features are inputs, not trained (extract_features.py)
+        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), kb.data_ptr(), saved.data_ptr(), n_saved, ws.data_ptr(), n_ws,
+                d_kb.data_ptr(), C.byref(gs))
+        if word is None:
+            _lib.check(L.macx_stem_backward(*args, st), "macx_stem_backward")
+        else:
+            _lib.check(L.macx_stem_backward_w(*args, word.data_ptr(), st), "macx_stem_backward_w")
+        return (None, None, None, None, None, None) + tuple(grads)     # image features are inputs, not trained (extract_features.py)
 
 
 def _check_fused(config):
@@ -104,9 +115,11 @@ class Stem(torch.nn.Module):
     def to_reference_dict(self):
         return {REF_NAMES[f]: getattr(self, f).detach().clone() for f in _lib.STEM_FIELDS}
 
-    def forward(self, images, train=False, seed=None, b0=0):
+    def forward(self, images, train=False, seed=None, b0=0, mask_word=None):
         """images: [B, H*W, inDim] / [B, H, W, inDim] (NHWC, what the graph sees after model.py:68) or the feed-dict layout
-        [B, inDim, H, W] (h5 features, extract_features.py), which is transposed on the device first."""
+        [B, inDim, H, W] (h5 features, extract_features.py), which is transposed on the device first.
+        mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's), XORed into both dropout keys when
+        the kernels run."""
         if not images.is_cuda:
             raise RuntimeError("the stem has no CPU path")
         if images.dim() == 4 and images.shape[1] == self.inDim and tuple(images.shape[2:]) == (self.H, self.W):
@@ -118,7 +131,8 @@ class Stem(torch.nn.Module):
         elif images.dim() == 4:
             images = images.reshape(images.shape[0], self.H * self.W, self.inDim)
         keep = self.keep if train else 1.0
-        return _StemFunction.apply(self, keep, fresh_seed(seed, train), int(b0), images, *self.tensors())
+        from .cell import _mask_word
+        return _StemFunction.apply(self, keep, fresh_seed(seed, train), int(b0), _mask_word(mask_word, images), images, *self.tensors())
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -325,9 +339,12 @@ class GenericStem(torch.nn.Module):
                 p.copy_(v.to(p.dtype))
         return self
 
-    def forward(self, images, train=False, seed=None, b0=0):
+    def forward(self, images, train=False, seed=None, b0=0, mask_word=None):
         """images: [B, H*W, inDim] / [B, H, W, inDim] (NHWC) or the feed-dict layout [B, inDim, H, W].
         Returns the knowledge base [B, Ho*Wo, memDim]."""
+        if mask_word is not None:
+            raise UnsupportedOptions("stem: a run's mask word is taken by the fused stem only (macx_stem_forward_w); the generic "
+                                     "stem has no such path")
         generic._require_device(images, "images")
         H, W, B = self.H, self.W, images.shape[0]
         if images.dim() == 4 and images.shape[1] == self.inDim and tuple(images.shape[2:]) == (H, W):
