@@ -434,6 +434,24 @@ int macx_adam_ema_step_p(size_t n, float* params, const float* grads, float* m, 
 typedef struct macx_gather_entry { const float* src; uint64_t dst_offset; uint64_t count; } macx_gather_entry;
 int macx_gather_flat(const macx_gather_entry* table_dev, int entries, float* flat, void* stream);
 
+/* ---- questions that share images ---------------------------------------------------------------- */
+/* A batch of B questions about G images (an evaluation set has many questions per image): the stem runs on the G images and each
+ * question's knowledge-base block [N, d] is a copy of its image's block.
+ *   macx_kb_gather      kb[b] = kb_images[image_index[b]]
+ *   macx_kb_gather_bwd  dkb_images[g] = sum over {b : image_index[b] == g} of dkb[b]
+ * image_index: [B] int32 in DEVICE memory, read when the kernel runs (a captured graph follows an index rewritten between replays).
+ * Forward: an index outside [0, G) is never dereferenced; that question's block is filled with quiet NaN (the call still returns
+ * MACX_OK: the index is device data), every other block is exact.  Nothing outside kb[0 .. B*N*d) is written.
+ * Backward: no atomics.  Each output element is summed by one thread over b = 0 .. B-1 in ascending order with plain fp32 adds
+ * starting from +0, so identical calls give identical bits; an image that no question names gets zeros; every element of
+ * dkb_images is written (no clearing beforehand); an index outside [0, G) contributes nowhere.
+ * MACX_EINVAL (nothing is launched): G, B, N or d < 1, N*d % 4 != 0, a NULL pointer, a float pointer off a 16-byte boundary.
+ * Like every call here: no allocation, no memcpy / memset, stream-ordered only. */
+int macx_kb_gather(const float* kb_images /*[G,N,d]*/, const int32_t* image_index /*[B], device*/, int G, int B, int N, int d,
+                   float* kb /*[B,N,d]*/, void* stream);
+int macx_kb_gather_bwd(const float* dkb /*[B,N,d]*/, const int32_t* image_index /*[B], device*/, int G, int B, int N, int d,
+                       float* dkb_images /*[G,N,d]*/, void* stream);
+
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)
  * on fp32 MFMA; `W_packed` from macx_pack_weight(W, k1 + k2, n_out, 0); k1, k2, n_out % 16 == 0. */

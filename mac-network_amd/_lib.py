@@ -148,7 +148,8 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd", "macx_conv2d_ws_floats", "macx_conv2d_fwd", "macx_conv2d_bwd_data",
            "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest",
            "macx_encoder_forward_w", "macx_encoder_backward_w", "macx_stem_forward_w", "macx_stem_backward_w",
-           "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat")
+           "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat",
+           "macx_kb_gather", "macx_kb_gather_bwd")
 
 _lib = None
 
@@ -309,6 +310,9 @@ def lib():
     L.macx_adam_ema_step_p.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                        C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.macx_gather_flat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    # (block source, index [B] int32, G, B, N, d, destination, stream): forward images -> questions, backward questions -> images
+    L.macx_kb_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.macx_kb_gather_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for n in EXPORTS:
         if n.endswith("_floats"):
             getattr(L, n).restype = C.c_size_t

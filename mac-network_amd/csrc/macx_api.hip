@@ -20,6 +20,7 @@
 #include "macx_small.hip.h"
 #include "macx_ops.hip.h"
 #include "macx_conv.hip.h"
+#include "macx_kb_gather.hip.h"
 
 using namespace macx;
 
@@ -3057,6 +3058,26 @@ int macx_gather_flat(const macx_gather_entry* table_dev, int entries, float* fla
   if (entries == 0) return MACX_OK;
   hipLaunchKernelGGL(gather_flat_kernel, dim3(GATHER_BLOCKS), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const GatherEntry*>(table_dev), entries, flat);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int macx_kb_gather(const float* kb_images, const int32_t* image_index, int G, int B, int N, int d, float* kb, void* stream) {
+  if (!kb_images || !image_index || !kb || G < 1 || B < 1 || N < 1 || d < 1 || ((size_t)N * d) % 4) return MACX_EINVAL;
+  if (misaligned(kb_images) || misaligned(kb) || ((uintptr_t)image_index & 3)) return MACX_EINVAL;
+  const size_t quads = (size_t)N * d / 4;
+  hipLaunchKernelGGL(kb_gather_kernel, kbg_grid(quads, KBG_CHUNK, B), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const f32x4*>(kb_images), image_index, G, B, quads, reinterpret_cast<f32x4*>(kb));
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int macx_kb_gather_bwd(const float* dkb, const int32_t* image_index, int G, int B, int N, int d, float* dkb_images, void* stream) {
+  if (!dkb || !image_index || !dkb_images || G < 1 || B < 1 || N < 1 || d < 1 || ((size_t)N * d) % 4) return MACX_EINVAL;
+  if (misaligned(dkb) || misaligned(dkb_images) || ((uintptr_t)image_index & 3)) return MACX_EINVAL;
+  const size_t quads = (size_t)N * d / 4;
+  hipLaunchKernelGGL(kb_gather_bwd_kernel, kbg_grid(quads, 256, G), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const f32x4*>(dkb), image_index, G, B, quads, reinterpret_cast<f32x4*>(dkb_images));
   CK(hipGetLastError());
   return MACX_OK;
 }

@@ -481,16 +481,35 @@ def _random_tower_inputs(gen, B, S, vocab, shape_images, answers, dev):
 class _TowerInputs:
     """the static input tensors of a captured tower and load() into them"""
 
-    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev):
+    G, image_index = None, None            # questions that share images (CapturedTowerForward(images=G)): see _alloc_inputs
+
+    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev, images=None):
+        """images: None (one image per question), or G: the static image tensor holds G images and a static [B] int32
+        `image_index`, read by the captured gather kernel at replay time, says which one each question looks at"""
         self.B, self.S, self.H, self.W, self.imageInDim = int(B), int(S), int(H), int(W), int(imageInDim)
+        if images is not None:
+            if int(images) < 1:
+                raise ValueError("images = %r: the number of distinct images of a batch is at least 1" % (images,))
+            self.G = int(images)
+            self.image_index = torch.zeros(self.B, dtype=torch.int32, device=dev)
         if (net.stem.H, net.stem.W, net.stem.inDim) != (self.H, self.W, self.imageInDim):
             raise ValueError("the net's stem was built for %d x %d x %d image features, not %d x %d x %d"
                              % (net.stem.H, net.stem.W, net.stem.inDim, self.H, self.W, self.imageInDim))
-        self.images = torch.zeros(self.B, self.H * self.W, self.imageInDim, device=dev)          # NHWC, what the stem's kernels read
+        self.images = torch.zeros(self.B if self.G is None else self.G, self.H * self.W, self.imageInDim, device=dev)   # NHWC, what the stem's kernels read
         self.questions = torch.zeros(self.B, self.S, dtype=torch.int32, device=dev)
         self.lengths = torch.full((self.B,), self.S, dtype=torch.int32, device=dev)
 
-    def _load_inputs(self, images, questions, lengths, check_ids):
+    def _load_inputs(self, images, questions, lengths, check_ids, image_index=None):
+        if self.G is None and image_index is not None:
+            raise ValueError("this graph was captured with one image per question (images=None): it takes no image_index")
+        if self.G is not None:
+            if image_index is None:
+                raise ValueError("this graph was captured for %d shared images (images=%d): load() needs the [%d] image_index"
+                                 % (self.G, self.G, self.B))
+            if tuple(image_index.shape) != (self.B,) or image_index.dtype.is_floating_point or image_index.dtype == torch.bool:
+                raise ValueError("image_index must be a [%d] integer tensor" % self.B)
+            if check_ids and (int(image_index.max()) >= self.G or int(image_index.min()) < 0):
+                raise IndexError("image_index outside [0, %d)" % self.G)
         if check_ids:                          # the encoder's own validation (host synchronisation), outside the graph
             vocab = self.net.enc.vocab
             if int(questions.max()) > vocab or int(questions.min()) < 0:
@@ -504,6 +523,8 @@ class _TowerInputs:
             self.images.copy_(images.reshape(self.images.shape))
             self.questions.copy_(questions)
             self.lengths.copy_(lengths)
+            if self.G is not None:
+                self.image_index.copy_(image_index)
 
 
 class CapturedTowerForward(_RunStatus, _TowerInputs):
@@ -514,6 +535,13 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         logits = fwd(images, questions, lengths)          # [B, answers], valid until the next call; fwd.pred: int32 argmax
         att_kb = fwd.attentions["kb"]                     # the captured cell's p x [B, N] views, refreshed by every replay
 
+    Questions that share images (an evaluation set asks many questions per image): `images=G` captures the stem on G images and
+    the gather of its output into the [B, N, d] knowledge base (macx_kb_gather), which reads the static `fwd.image_index` when it
+    runs -- any grouping of the B questions over the G images replays from the one graph:
+
+        fwd = macx.CapturedTowerForward(net, B=64, S=50, images=7)
+        logits = fwd(images7, questions, lengths, image_index=index)      # question b looks at images7[index[b]]
+
     Evaluation only (train=False: no dropout, nothing kept for a backward pass).  Parameters are read at replay time: an optimizer
     step or a checkpoint load between calls is seen; changing a parameter's storage needs a new capture.  `load()` validates ids
     and lengths on the host as QuestionEncoder.forward does (check_ids=False skips the synchronisation); the graph itself runs
@@ -521,11 +549,11 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
     Copies on the captured path: none -- every module writes into outputs it allocates from the graph's pool, the cell's final
     state and attentions are views of its `saved` buffer."""
 
-    def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0):
+    def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None):
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
-        self._alloc_inputs(net, B, S, H, W, imageInDim, dev)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images)
         self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(device=dev)
@@ -549,7 +577,8 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
     def _eager(self):
         from .output import _AnswerLoss
         with torch.no_grad():
-            logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False)
+            group = {} if self.G is None else {"image_index": self.image_index}
+            logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **group)
             self.cell = self.net.last_cell                  # (status(): the latest run's buffers)
             _, pred = _AnswerLoss.apply(logits, self._no_answers)      # addPredOp's argmax (first maximum), one kernel
         return logits, pred
@@ -558,7 +587,11 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         g = torch.Generator().manual_seed(20240521)
         dev = self.images.device
         images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, dev)
-        self._load_inputs(images, q, lengths, False)
+        index = None
+        if self.G is not None:                              # repeats, and (G > 1) one image that no question names
+            index = torch.randint(0, max(self.G - 1, 1), (self.B,), generator=g, dtype=torch.int32)
+            index[-1] = index[0]
+        self._load_inputs(images, q, lengths, False, index)
         want, want_pred = [t.clone() for t in self._eager()]
         self.check()                                        # the eager run's own buffers
         self.cell = self._captured_cell
@@ -573,8 +606,10 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         self.check()
         return not self.verify_report
 
-    def load(self, images, questions, lengths, check_ids=True):
-        self._load_inputs(images, questions, lengths, check_ids)
+    def load(self, images, questions, lengths, check_ids=True, image_index=None):
+        """image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
+        validated with the ids (check_ids)"""
+        self._load_inputs(images, questions, lengths, check_ids, image_index)
 
     def replay(self):
         if self.captured:
@@ -585,8 +620,8 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         self._count_replay()
         return self.logits
 
-    def __call__(self, images, questions, lengths, check_ids=True):
-        self.load(images, questions, lengths, check_ids)
+    def __call__(self, images, questions, lengths, check_ids=True, image_index=None):
+        self.load(images, questions, lengths, check_ids, image_index)
         return self.replay()
 
 

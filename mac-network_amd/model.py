@@ -15,7 +15,7 @@ from .encoder import QuestionEncoder
 from .options import UnsupportedOptions, freeze, fresh_seed, get
 from .output import OutputClassifier, answer_loss_and_pred
 from .params import MACCellParams
-from .stem import Stem
+from .stem import Stem, check_image_index, kb_gather
 
 
 class MACNetCore(torch.nn.Module):
@@ -44,11 +44,17 @@ class MACNetCore(torch.nn.Module):
         return self.stem.tensors() + self.cell.tensors() + self.out.tensors()
 
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
-                questionWords=None, mask_word=None):
+                questionWords=None, mask_word=None, image_index=None, check_index=False):
         """mask_word: None, or one 1-element int32 device tensor (MACCell's mask_word) handed to the stem, the cell and the output
         unit: every dropout site of the tower XORs it into its key when the kernels run (graph.CapturedTowerTrainStep).  Fused
-        modules only."""
+        modules only.
+        image_index: None (one image per question), or a [B] integer tensor for a batch whose questions share images: `images`
+        then holds the G distinct images, question b looks at images[image_index[b]], the stem runs once per image and its output
+        is gathered into the cell's [B, N, d] knowledge base (macx_kb_gather; gradients flow back through macx_kb_gather_bwd).
+        With train=True the stem must not drop (stemDropout = 1.0): the reference draws that mask per question.  An index outside
+        [0, G) gives that question a NaN knowledge base; check_index=True tests the range on the host first (synchronises)."""
         cfg = self.config
+        image_index = check_image_index(image_index, vecQuestions.shape[0], train, self.stem, images, host_check=check_index)
         if mask_word is not None and not isinstance(self.cell, MACCellParams):
             raise UnsupportedOptions("a run's mask word over the whole tower needs the fused cell (MACCellParams); this option set "
                                      "runs the cell on the generic path")
@@ -62,9 +68,12 @@ class MACNetCore(torch.nn.Module):
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}               # (None: the modules' calls of before)
         kb = self.stem(images, train=train, seed=seed, b0=b0, **word)               # model.py:791
+        if image_index is not None:
+            kb = kb_gather(kb, image_index.to(kb.device))
+        batch = images.shape[0] if image_index is None else vecQuestions.shape[0]
         cell = MACCell(vecQuestions=vecQuestions, questionWords=questionWords, questionCntxWords=questionCntxWords,
                        questionLengths=questionLengths, knowledgeBase=kb, memoryDropout=get(cfg, "memoryDropout"),
-                       readDropout=get(cfg, "readDropout"), writeDropout=get(cfg, "writeDropout"), batchSize=images.shape[0],
+                       readDropout=get(cfg, "readDropout"), writeDropout=get(cfg, "writeDropout"), batchSize=batch,
                        train=train, config=cfg, params=self.cell, netLength=self.netLength, seed=seed, b0=b0, **word)
         state = cell.run()                                                           # model.py:801 (MACnetwork)
         self.last_cell = cell
@@ -85,7 +94,10 @@ class MACNet(MACNetCore):
     def tensors(self):
         return self.enc.tensors() + super().tensors()
 
-    def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
+    def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None,
+                image_index=None, check_index=False):
+        """image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B])."""
+        check_image_index(image_index, questions.shape[0], train, self.stem, images, host_check=check_index)
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}
         words, vecQ = self.enc(questions, questionLengths, train=train, seed=seed, b0=b0, check_ids=check_ids, **word)   # model.py:783-788
@@ -96,4 +108,5 @@ class MACNet(MACNetCore):
             if raw.shape[-1] != get(self.config, "ctrlDim"):
                 raise ValueError("Dimensions must be equal: without --controlContextual the question words are wrdEmbDim = %d wide, "
                                  "the control state ctrlDim = %d (mac_cell.py:154)" % (raw.shape[-1], get(self.config, "ctrlDim")))
-        return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw, **word)
+        return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw,
+                               image_index=image_index, **word)

@@ -374,3 +374,62 @@ class GenericStem(torch.nn.Module):
                 w = torch.nn.functional.pad(w, (0, 0, 0, pad))
             x = generic._Act.apply(_Conv.apply(x, w, getattr(self, "bias%d" % i), s), self.act, None)
         return x.reshape(B, self.N, self.outDim)
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# questions that share images: the stem runs once per image, every question gets a copy of its image's block
+# -------------------------------------------------------------------------------------------------------------------
+def check_image_index(image_index, B, train, stem, images=None, host_check=False):
+    """The validation of model.MACNet(Core).forward's image_index (a [B] integer tensor: question b looks at images[image_index[b]]),
+    done before anything asks for the device.  Returns None for None.  host_check: also 0 <= index < G on the host (synchronises)."""
+    if image_index is None:
+        return None
+    if not torch.is_tensor(image_index) or image_index.dim() != 1 or image_index.shape[0] != B:
+        raise ValueError("image_index must be a [%d] tensor, one image number per question; got %s"
+                         % (B, tuple(image_index.shape) if torch.is_tensor(image_index) else type(image_index).__name__))
+    if image_index.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError("image_index must have an integer dtype, not %s" % image_index.dtype)
+    keep = 1.0 if getattr(stem, "linear", False) else float(stem.keep)       # (--stemLinear has no dropout)
+    if train and keep < 1.0:
+        # model.py:165-204 feeds every question its own copy of the image and draws the stem's dropout mask per question
+        raise ValueError("image_index with train=True needs stemDropout = 1.0 (this stem keeps %g): the reference draws the stem's "
+                         "dropout mask per question, which one stem pass per image cannot reproduce" % keep)
+    if host_check and images is not None and B > 0:
+        G = images.shape[0]
+        lo, hi = int(image_index.min()), int(image_index.max())
+        if lo < 0 or hi >= G:
+            raise IndexError("image_index outside [0, %d)" % G)
+    return image_index
+
+
+class _KBGather(torch.autograd.Function):
+    """kb[b] = kb_images[index[b]] (macx_kb_gather); backward: the fixed-order sum of macx_kb_gather_bwd.  index: [B] int32 on the
+    device, read when the kernels run."""
+
+    @staticmethod
+    def forward(ctx, kb_images, index):
+        kb_images = generic._dev(kb_images, "the stem's output")
+        generic._require_device(index, "image_index")
+        if index.dtype != torch.int32 or not index.is_contiguous():
+            index = index.to(torch.int32).contiguous()
+        G, N, d = kb_images.shape
+        B = index.shape[0]
+        kb = torch.empty(B, N, d, dtype=torch.float32, device=kb_images.device)
+        _lib.check(_lib.lib().macx_kb_gather(generic._p(kb_images), generic._p(index), G, B, N, d, generic._p(kb), generic._st(kb)),
+                   "macx_kb_gather")
+        ctx.index, ctx.G = index, G
+        return kb
+
+    @staticmethod
+    def backward(ctx, dkb):
+        dkb = dkb.contiguous()
+        B, N, d = dkb.shape
+        out = torch.empty(ctx.G, N, d, dtype=torch.float32, device=dkb.device)
+        _lib.check(_lib.lib().macx_kb_gather_bwd(generic._p(dkb), generic._p(ctx.index), ctx.G, B, N, d, generic._p(out), generic._st(out)),
+                   "macx_kb_gather_bwd")
+        return out, None
+
+
+def kb_gather(kb_images, image_index):
+    """[G, N, d] stem output -> the [B, N, d] knowledge base of B questions (differentiable in kb_images)"""
+    return _KBGather.apply(kb_images, image_index)
