@@ -3,7 +3,7 @@
 Forward only at p = 4 (BASELINE.json configs[1]) is about 70 kernel launches of 5 - 80 us each: issued one ctypes call at a
 time the host, not the GPU, sets the pace (3.2 ms per batch of 64 against 0.7 ms of kernel time).  The loop of
 model.py:453-458 has no data-dependent control flow, every buffer is caller-owned and every launch goes to the stream the
-caller passes, so the whole run is capturable: `CapturedForward` captures `MACCell(...).run()` once on static input / output
+caller passes, so the whole run is capturable: `CapturedForward` captures a `MACCell`'s `run()` once on static input / output
 tensors and replays it per batch.
 
     fwd = macx.CapturedForward(cfg, params, B=64, S=50, N=196)
@@ -33,14 +33,23 @@ Did a replay go wrong?  The captured run's `saved` buffer carries the sticky han
 every class here has `.check()` (raises macx.HandoffTimeout; SYNCHRONISES), `.reset_status()` and a constructor argument
 `check_every=k`: with k > 0 every k-th replay() / step() ends in a check(); the default 0 adds nothing to a replay.  The reset is
 never part of a graph -- the status survives replays until the caller clears it.
+
+Five classes, one protocol, written once in `_Captured`: warm up on a side stream and capture (`_capture`), compare replays with
+the eager run and fall back (`_self_check`, `_eager_on_captured`, `_compare_replays`), report the status.  A class adds its static
+inputs (`_CellInputs`, `_TowerInputs`; the training classes' mask word: `_MaskWord`), `_eager()` -- its launches on the current
+stream -- and `_issue()`, which publishes what they return: the body of the capture and the eager fallback of `replay()`.
 """
 import warnings
 
 import torch
 
-from .cell import MACCell
+from .cell import MACCell, _Run
 from .dp import TwoPhaseStep
 from .options import UnsupportedOptions, get
+from .params import MACCellParams
+# (encoder, output and stem are imported where the tower's classes use them, not here.  No cycle: `from macx.graph import mix32`,
+# the package under its alias, executes this module a second time, and an import at this level would make second copies of those
+# modules too and bind them to the package's attributes.)
 
 
 def mix32(x):
@@ -55,11 +64,80 @@ def mix32(x):
     return h
 
 
-class _RunStatus:
-    """check() / reset_status() / check_every of the captured classes: `_status_run()` is the cell._Run whose `saved` the replays
-    write (None before the first run)."""
+def _require_hip(dev, who, what):
+    if dev.type != "cuda":
+        raise RuntimeError("%s needs the HIP device: %s has no CPU path" % (who, what))
+    return dev
+
+
+class _Captured:
+    """The protocol of the captured classes (module docstring): capture, self-check with the eager fallback behind it, and
+    check() / reset_status() / check_every.  `_status_run()` is the cell._Run whose `saved` the replays write (None before the
+    first run); `_WHAT` names the captured and the eager side in the fallback's warning."""
     check_every = 0
     _replays = 0
+    captured = False
+    mask_word = None                                 # (the training classes have one: _MaskWord)
+    verify_report = ()                               # (replay, label) of everything the self-check saw differ
+    _WHAT = ("step", "step")
+
+    def _capture(self, dev, warmup, warm, graphs, before=None):
+        """warm() `warmup` times on a side stream -- code objects, LDS attributes and the allocator settle outside the capture --
+        then before() and one capture per (graph, body) of `graphs`, every later graph in the first one's pool"""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                warm()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        if before is not None:
+            before()
+        pool = None
+        for graph, body in graphs:
+            with torch.cuda.graph(graph, pool=pool):
+                body()
+            pool = pool or graph.pool()
+        self._after_capture()
+
+    def _self_check(self, verify, *args):
+        """use the capture unless `verify` and its replays do not reproduce the eager run (_replays_match_eager(*args))"""
+        self._captured_cell = self.cell              # the run whose buffers the graph replays on
+        self.captured = True
+        if verify and not self._replays_match_eager(*args):
+            self.captured = False
+            warnings.warn("%s: replays of the captured %s do not reproduce the eager %s in this process; "
+                          "falling back to eager launches" % ((type(self).__name__,) + self._WHAT), RuntimeWarning)
+
+    def _eager_on_captured(self, leaves, reference):
+        """reference(): an eager run on the static tensors, returning clones of what it wrote.  Afterwards the `.grad` tensors the
+        graph writes (`leaves`: who has one) and `self.cell` are the captured ones again, so the next replay writes where it is
+        looked at; a step that fell back to eager launches has nothing to put back.  Checks the eager run's status: synchronises."""
+        captured_grads = [t.grad for t in leaves]
+        want = reference()
+        self.check()                                 # the eager run's own buffers
+        if self.captured:
+            self.cell = self._captured_cell
+            for t, g in zip(leaves, captured_grads):
+                t.grad = g
+        return want
+
+    def _compare_replays(self, replays, written, want, before=None):
+        """`replays` replays (before() in front of each): written() is the (label, tensor) list of what the graph wrote, `want` the
+        eager run's clones of the same; (replay, label) of everything that differed goes to `verify_report`"""
+        self.verify_report = []
+        for r in range(replays):
+            if before is not None:
+                before()
+            self.graph.replay()
+            for (label, t), w in zip(written(), want):
+                if not torch.equal(t, w):
+                    self.verify_report.append((r, label))
+        torch.cuda.synchronize(want[0].device)
+        if self.mask_word is not None:
+            self.set_mask_word(0)
+        self.check()
+        return not self.verify_report
 
     def _status_run(self):
         cell = getattr(self, "cell", None)
@@ -94,77 +172,100 @@ class _RunStatus:
                 self.check()
 
 
-class CapturedForward(_RunStatus):
-    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True, check_every=0):
-        dev = torch.device(device) if device is not None else params.tensors()[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("CapturedForward needs the HIP device: the MAC cell has no CPU path")
+class _MaskWord:
+    """the device word of a captured training step, which every dropout site XORs into its key when the kernel runs"""
+
+    def _alloc_mask_word(self, dev):
+        self.mask_word = torch.zeros(1, dtype=torch.int32, device=dev)        # macx_dropout.mask_word of every run of this step
+
+    def set_mask_word(self, word):
+        """the raw 32-bit word the next replays XOR into every dropout key (0: the masks of the plain seed)"""
+        word &= 0xFFFFFFFF
+        self.mask_word.fill_(word - (1 << 32) if word >= (1 << 31) else word)
+
+    def _set_iteration(self, iteration):
+        """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration)"""
+        if iteration is not None:
+            self.set_mask_word(mix32(int(iteration)))
+
+
+class _CellInputs:
+    """the static input tensors of a captured cell, load() into them and the cell built on them"""
+
+    d_memory = None                                  # [B, d] gradient of the final memory: the training classes
+
+    def _alloc_inputs(self, config, params, B, S, N, device, netLength, train=False, requires_grad=False):
+        dev = _require_hip(torch.device(device) if device is not None else params.tensors()[0].device, type(self).__name__, "the MAC cell")
         d = int(get(config, "memDim"))
         self.config, self.params = config, params
-        self.check_every = int(check_every)
         self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
-        self.vecQuestions = torch.zeros(B, d, device=dev)
-        self.words = torch.zeros(B, S, d, device=dev)
+        self.vecQuestions = torch.zeros(B, d, device=dev, requires_grad=requires_grad)
+        self.words = torch.zeros(B, S, d, device=dev, requires_grad=requires_grad)
         self.lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
-        self.knowledgeBase = torch.zeros(B, N, d, device=dev)
+        self.knowledgeBase = torch.zeros(B, N, d, device=dev, requires_grad=requires_grad)
+        if train:
+            self.d_memory = torch.zeros(B, d, device=dev)
+        return dev
+
+    def _randomise(self, seed):
+        """N(0, 1) inputs for the self-check"""
+        g = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for t in (self.vecQuestions, self.words, self.knowledgeBase) + (() if self.d_memory is None else (self.d_memory,)):
+                t.copy_(torch.randn(t.shape, generator=g).to(t.device))
+
+    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory=None):
+        """Copy a batch into the captured run's input tensors (or write into .knowledgeBase etc. directly and skip this);
+        d_memory: the training classes' [B, d] gradient of the final memory, and theirs only"""
+        if (d_memory is None) != (self.d_memory is None):
+            raise TypeError("%s.load() takes %s d_memory" % (type(self).__name__, "no" if self.d_memory is None else "a"))
+        with torch.no_grad():
+            self.vecQuestions.copy_(vecQuestions)
+            self.words.copy_(words)
+            self.lengths.copy_(lengths)
+            self.knowledgeBase.copy_(knowledgeBase)
+            if d_memory is not None:
+                self.d_memory.copy_(d_memory)
+
+    def _make_cell(self, train):
+        """evaluation: no dropout, no seed, no word; training: the config's keep values, seed, b0 and the mask word"""
+        keep = [float(get(self.config, k)) if train else 1.0 for k in ("memoryDropout", "readDropout", "writeDropout")]
+        drawn = dict(seed=self.seed, b0=self.b0, mask_word=self.mask_word) if train else {}
+        return MACCell(vecQuestions=self.vecQuestions, questionWords=self.words, questionCntxWords=self.words,
+                       questionLengths=self.lengths, knowledgeBase=self.knowledgeBase, memoryDropout=keep[0], readDropout=keep[1],
+                       writeDropout=keep[2], batchSize=self.vecQuestions.shape[0], train=train, config=self.config,
+                       params=self.params, netLength=self.netLength, **drawn)
+
+
+class CapturedForward(_Captured, _CellInputs):
+    _WHAT = ("run", "run")
+
+    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True, check_every=0):
+        self.check_every = int(check_every)
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength)
         self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):          # code objects, LDS attributes and the allocator settle outside the capture
-                self._cell().run()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.cell = self._cell()
-            state = self.cell.run()
-            self.memory, self.control = state.memory, state.control
-        self._after_capture()
-        self.attentions = self.cell.attentions
-        self.captured = True
-        if verify and not self._replays_match_eager():
-            self.captured = False
-            warnings.warn("CapturedForward: replays of the captured run do not reproduce the eager run in this process; "
-                          "falling back to eager launches", RuntimeWarning)
+        self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
+        self._self_check(verify)
+
+    @torch.no_grad()
+    def _eager(self):
+        self.cell = self._make_cell(train=False)      # (status(): the latest run's buffers)
+        return self.cell.run()
+
+    def _issue(self):
+        state = self._eager()
+        self.memory, self.control, self.attentions = state.memory, state.control, self.cell.attentions
 
     def _replays_match_eager(self, replays=3):
-        g = torch.Generator().manual_seed(20240519)
-        dev = self.knowledgeBase.device
-        self.vecQuestions.copy_(torch.randn(self.vecQuestions.shape, generator=g).to(dev))
-        self.words.copy_(torch.randn(self.words.shape, generator=g).to(dev))
-        self.knowledgeBase.copy_(torch.randn(self.knowledgeBase.shape, generator=g).to(dev))
-        with torch.no_grad():
-            want = self._cell().run().memory.clone()
-        ok = True
-        for _ in range(replays):
-            self.graph.replay()
-            ok = ok and bool(torch.equal(self.memory, want))
-        torch.cuda.synchronize(dev)
-        self.check()
-        return ok
-
-    def _cell(self):
-        return MACCell(vecQuestions=self.vecQuestions, questionWords=self.words, questionCntxWords=self.words,
-                       questionLengths=self.lengths, knowledgeBase=self.knowledgeBase, memoryDropout=1.0, readDropout=1.0,
-                       writeDropout=1.0, batchSize=self.vecQuestions.shape[0], train=False, config=self.config,
-                       params=self.params, netLength=self.netLength)
-
-    def load(self, vecQuestions, words, lengths, knowledgeBase):
-        """Copy a batch into the captured run's input tensors (or write into fwd.knowledgeBase etc. directly and skip this)."""
-        self.vecQuestions.copy_(vecQuestions)
-        self.words.copy_(words)
-        self.lengths.copy_(lengths)
-        self.knowledgeBase.copy_(knowledgeBase)
+        self._randomise(20240519)
+        want = self._eager_on_captured([], lambda: [self._eager().memory.clone()])
+        return self._compare_replays(replays, lambda: [("memory", self.memory)], want)
 
     def replay(self):
         if self.captured:
             self.graph.replay()
         else:                                    # (see the module docstring)
-            with torch.no_grad():
-                self.cell = self._cell()
-                state = self.cell.run()
-            self.memory, self.control = state.memory, state.control
-            self.attentions = self.cell.attentions
+            self._issue()
         self._count_replay()
         return self.memory
 
@@ -173,7 +274,7 @@ class CapturedForward(_RunStatus):
         return self.replay()
 
 
-class CapturedTrainStep(_RunStatus):
+class CapturedTrainStep(_Captured, _CellInputs, _MaskWord):
     """Forward + backward of the cell (train-mode dropout, every gradient) replayed from ONE captured HIP graph.
 
         step = macx.CapturedTrainStep(cfg, params, B=64, S=50, N=196, seed=1234)
@@ -201,37 +302,13 @@ class CapturedTrainStep(_RunStatus):
     differs in any gradient (`captured` False, a warning says so)."""
 
     def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True, check_every=0):
-        dev = torch.device(device) if device is not None else params.tensors()[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("CapturedTrainStep needs the HIP device: the MAC cell has no CPU path")
-        d = int(get(config, "memDim"))
-        self.config, self.params, self.seed, self.b0 = config, params, int(seed), int(b0)
+        self.seed, self.b0 = int(seed), int(b0)
         self.check_every = int(check_every)
-        self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
-        self.vecQuestions = torch.zeros(B, d, device=dev, requires_grad=True)
-        self.words = torch.zeros(B, S, d, device=dev, requires_grad=True)
-        self.lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
-        self.knowledgeBase = torch.zeros(B, N, d, device=dev, requires_grad=True)
-        self.d_memory = torch.zeros(B, d, device=dev)
-        self.mask_word = torch.zeros(1, dtype=torch.int32, device=dev)        # macx_dropout.mask_word of every run of this step
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, requires_grad=True)
+        self._alloc_mask_word(dev)
         self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._eager()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self._clear_grads()
-        with torch.cuda.graph(self.graph):
-            self.memory = self._eager()
-        self._after_capture()
-        self._captured_cell = self.cell          # the run whose buffers the graph replays on
-        self.captured = True
-        if verify and not self._replays_match_eager():
-            self.captured = False
-            warnings.warn("CapturedTrainStep: replays of the captured step do not reproduce the eager step in this process; "
-                          "falling back to eager launches", RuntimeWarning)
+        self._capture(dev, warmup, self._eager, [(self.graph, self._issue)], before=self._clear_grads)
+        self._self_check(verify)
 
     def _leaves(self):
         return [self.vecQuestions, self.words, self.knowledgeBase] + list(self.params.tensors())
@@ -242,72 +319,39 @@ class CapturedTrainStep(_RunStatus):
 
     def _eager(self):
         self._clear_grads()
-        cell = MACCell(vecQuestions=self.vecQuestions, questionWords=self.words, questionCntxWords=self.words,
-                       questionLengths=self.lengths, knowledgeBase=self.knowledgeBase,
-                       memoryDropout=float(get(self.config, "memoryDropout")), readDropout=float(get(self.config, "readDropout")),
-                       writeDropout=float(get(self.config, "writeDropout")), batchSize=self.vecQuestions.shape[0], train=True,
-                       config=self.config, params=self.params, netLength=self.netLength, seed=self.seed, b0=self.b0,
-                       mask_word=self.mask_word)
-        self.cell = cell                          # (status(): the latest run's buffers)
-        state = cell.run()
+        self.cell = self._make_cell(train=True)   # (status(): the latest run's buffers)
+        state = self.cell.run()
         torch.autograd.backward([state.memory], [self.d_memory])
         return state.memory.detach()
 
-    def set_mask_word(self, word):
-        """the raw 32-bit word the next replays XOR into every dropout key (0: the masks of the plain seed)"""
-        word &= 0xFFFFFFFF
-        self.mask_word.fill_(word - (1 << 32) if word >= (1 << 31) else word)
+    def _issue(self):
+        self.memory = self._eager()
+
+    def eager_reference(self):
+        """The eager step on the static tensors under the current mask word: (memory, [gradient of each of _leaves()]), all clones.
+        The captured `.grad` tensors and `cell` are put back, so the next replay() writes where the graph writes.  Synchronises."""
+        leaves = self._leaves()
+        return self._eager_on_captured(leaves, lambda: (self._eager().clone(), [t.grad.clone() for t in leaves]))
 
     def _replays_match_eager(self, replays=3):
-        g = torch.Generator().manual_seed(20240520)
-        dev = self.knowledgeBase.device
         self.set_mask_word(0x5bd1e995)          # a non-trivial word: the check covers the device-read path as well
-        with torch.no_grad():
-            for t in (self.vecQuestions, self.words, self.knowledgeBase, self.d_memory):
-                t.copy_(torch.randn(t.shape, generator=g).to(dev))
-        captured_grads = [t.grad for t in self._leaves()]        # the tensors the graph writes
-        mem = self._eager().clone()
-        self.check()                              # the eager run's own buffers
-        self.cell = self._captured_cell
-        want = [t.grad.clone() for t in self._leaves()]
-        for t, gcap in zip(self._leaves(), captured_grads):
-            t.grad = gcap
-        ok = True
-        self.verify_report = []              # (replay, index into [memory] + leaves) of every tensor that differed
-        for r in range(replays):
-            self.graph.replay()
-            if not torch.equal(self.memory, mem):
-                self.verify_report.append((r, 0))
-            for i, (t, w) in enumerate(zip(self._leaves(), want)):
-                if not torch.equal(t.grad, w):
-                    self.verify_report.append((r, i + 1))
-        torch.cuda.synchronize(dev)
-        self.set_mask_word(0)
-        self.check()
-        ok = not self.verify_report
-        return ok
-
-    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory):
-        with torch.no_grad():
-            self.vecQuestions.copy_(vecQuestions)
-            self.words.copy_(words)
-            self.lengths.copy_(lengths)
-            self.knowledgeBase.copy_(knowledgeBase)
-            self.d_memory.copy_(d_memory)
+        self._randomise(20240520)
+        memory, grads = self.eager_reference()
+        written = lambda: enumerate([self.memory] + [t.grad for t in self._leaves()])     # labels: the index into [memory] + leaves
+        return self._compare_replays(replays, written, [memory] + grads)
 
     def replay(self, iteration=None):
         """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration)"""
-        if iteration is not None:
-            self.set_mask_word(mix32(int(iteration)))
+        self._set_iteration(iteration)
         if self.captured:
             self.graph.replay()
         else:
-            self.memory = self._eager()
+            self._issue()
         self._count_replay()
         return self.memory
 
 
-class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
+class CapturedDPTrainStep(_Captured, _CellInputs, _MaskWord, TwoPhaseStep):
     """One DATA-PARALLEL training step of the cell as TWO graph replays with the gradient exchange between and behind them.
 
     The eager data-parallel step is ~125 host-issued launches per rank; at 8 questions per GPU that is more host work than GPU work
@@ -334,56 +378,30 @@ class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
 
     def __init__(self, config, params, bucket, B, S, N, global_batch, seed=0, b0=0, device=None, netLength=None, warmup=2, capture=True,
                  check_every=0):
-        dev = torch.device(device) if device is not None else params.tensors()[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("CapturedDPTrainStep needs the HIP device: the MAC cell has no CPU path")
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True)
         if bucket.flat.data_ptr() != params.grad_buffer().data_ptr():
             raise ValueError("the bucket must be built over params' own flat gradient buffer (OverlappedBuckets(params) / "
                              "GradBucket(params.tensors(), params=params))")
-        d = int(get(config, "memDim"))
         super().__init__(params, bucket, B, global_batch)
-        self.config = config
         self.check_every = int(check_every)
         self.seed, self.b0 = int(seed), int(b0)
-        self.netLength = int(netLength if netLength is not None else get(config, "netLength"))
-        self.vecQuestions = torch.zeros(B, d, device=dev)
-        self.words = torch.zeros(B, S, d, device=dev)
-        self.lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
-        self.knowledgeBase = torch.zeros(B, N, d, device=dev)
-        self.d_memory = torch.zeros(B, d, device=dev)
-        self.mask_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._alloc_mask_word(dev)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        self.captured = False
         for t in params.tensors():
             t.grad = None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                      # (warm-up outside capture: code objects, LDS attributes, allocator)
-            for _ in range(max(1, warmup)):
-                self._phase_a()
-                self._phase_b()
-                params.release_grad_buffer()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        if capture:
-            with torch.cuda.graph(self.graph_a):
-                self._phase_a()
-            with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool()):
-                self._phase_b()
-            self._after_capture()
-            self.captured = True
+        self._capture(dev, warmup, self._warm, [(self.graph_a, self._phase_a), (self.graph_b, self._phase_b)] if capture else [])
+        self.captured = bool(capture)
         params.release_grad_buffer()
+
+    def _warm(self):
+        self._phase_a()
+        self._phase_b()
+        self.params.release_grad_buffer()
 
     def _phase_a(self):
         """forward + backward phase 1 on the current stream; leaves self._run / self._args for phase 2"""
-        from .cell import _Run
         with torch.no_grad():
-            cell = MACCell(vecQuestions=self.vecQuestions, questionWords=self.words, questionCntxWords=self.words,
-                           questionLengths=self.lengths, knowledgeBase=self.knowledgeBase,
-                           memoryDropout=float(get(self.config, "memoryDropout")), readDropout=float(get(self.config, "readDropout")),
-                           writeDropout=float(get(self.config, "writeDropout")), batchSize=self.shard, train=True,
-                           config=self.config, params=self.params, netLength=self.netLength, seed=self.seed, b0=self.b0,
-                           mask_word=self.mask_word)
+            cell = self._make_cell(train=True)
             run = _Run(cell, True)
             run.forward()
             args, grads, gi, flat, keep = run.backward_begin(None, self.d_memory)
@@ -403,18 +421,6 @@ class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
         with torch.no_grad():
             self._run.backward_phase(self._args, 2)
 
-    def set_mask_word(self, word):
-        word &= 0xFFFFFFFF
-        self.mask_word.fill_(word - (1 << 32) if word >= (1 << 31) else word)
-
-    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory):
-        with torch.no_grad():
-            self.vecQuestions.copy_(vecQuestions)
-            self.words.copy_(words)
-            self.lengths.copy_(lengths)
-            self.knowledgeBase.copy_(knowledgeBase)
-            self.d_memory.copy_(d_memory)
-
     def run_part_a(self):
         if self.captured:
             self.graph_a.replay()
@@ -432,8 +438,7 @@ class CapturedDPTrainStep(_RunStatus, TwoPhaseStep):
 
     def step(self, iteration=None):
         """one data-parallel step; afterwards every parameter's .grad is its view of the all-reduced flat buffer"""
-        if iteration is not None:
-            self.set_mask_word(mix32(int(iteration)))
+        self._set_iteration(iteration)
         self.exchange_step()
         self._count_replay()
         return self.memory
@@ -447,7 +452,6 @@ def _require_fused_tower(net, who):
     the HIP device (RuntimeError otherwise); returns the device"""
     from .encoder import QuestionEncoder
     from .output import OutputClassifier
-    from .params import MACCellParams
     from .stem import Stem
     want = (("enc", QuestionEncoder), ("stem", Stem), ("cell", MACCellParams), ("out", OutputClassifier))
     for name, cls in want:
@@ -458,10 +462,7 @@ def _require_fused_tower(net, who):
             raise UnsupportedOptions("%s: net.%s is a %s; only a tower of the fused modules (%s) is captured -- the generic "
                                      "one-kernel-per-op modules are out of its scope" % (who, name, type(mod).__name__,
                                                                                         ", ".join(c.__name__ for _, c in want)))
-    dev = net.tensors()[0].device
-    if dev.type != "cuda":
-        raise RuntimeError("%s needs the HIP device: the tower has no CPU path" % who)
-    return dev
+    return _require_hip(net.tensors()[0].device, who, "the tower")
 
 
 def _random_tower_inputs(gen, B, S, vocab, shape_images, answers, dev):
@@ -527,7 +528,7 @@ class _TowerInputs:
                 self.image_index.copy_(image_index)
 
 
-class CapturedTowerForward(_RunStatus, _TowerInputs):
+class CapturedTowerForward(_Captured, _TowerInputs):
     """Evaluation forward of a whole macx.MACNet -- embedding + biLSTM encoder (about 100 dependent LSTM step launches), stem, cell,
     output unit + classifier, argmax -- replayed from ONE captured HIP graph on static input tensors.
 
@@ -548,6 +549,7 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
     the net with check_ids=False.  verify / captured / check() / check_every: as CapturedForward.
     Copies on the captured path: none -- every module writes into outputs it allocates from the graph's pool, the cell's final
     state and attentions are views of its `saved` buffer."""
+    _WHAT = ("tower", "forward")
 
     def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None):
         dev = _require_fused_tower(net, "CapturedTowerForward")
@@ -556,55 +558,32 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images)
         self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._eager()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        with torch.cuda.graph(self.graph):
-            self.logits, self.pred = self._eager()
-        self._after_capture()
-        self._captured_cell = self.cell
-        self.attentions = self.cell.attentions
-        self.captured = True
-        if verify and not self._replays_match_eager():
-            self.captured = False
-            warnings.warn("CapturedTowerForward: replays of the captured tower do not reproduce the eager forward in this process; "
-                          "falling back to eager launches", RuntimeWarning)
+        self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
+        self._self_check(verify)
 
+    @torch.no_grad()
     def _eager(self):
         from .output import _AnswerLoss
-        with torch.no_grad():
-            group = {} if self.G is None else {"image_index": self.image_index}
-            logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **group)
-            self.cell = self.net.last_cell                  # (status(): the latest run's buffers)
-            _, pred = _AnswerLoss.apply(logits, self._no_answers)      # addPredOp's argmax (first maximum), one kernel
+        group = {} if self.G is None else {"image_index": self.image_index}
+        logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **group)
+        self.cell = self.net.last_cell                      # (status(): the latest run's buffers)
+        _, pred = _AnswerLoss.apply(logits, self._no_answers)          # addPredOp's argmax (first maximum), one kernel
         return logits, pred
+
+    def _issue(self):
+        self.logits, self.pred = self._eager()
+        self.attentions = self.cell.attentions
 
     def _replays_match_eager(self, replays=3):
         g = torch.Generator().manual_seed(20240521)
-        dev = self.images.device
-        images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, dev)
+        images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, self.images.device)
         index = None
         if self.G is not None:                              # repeats, and (G > 1) one image that no question names
             index = torch.randint(0, max(self.G - 1, 1), (self.B,), generator=g, dtype=torch.int32)
             index[-1] = index[0]
         self._load_inputs(images, q, lengths, False, index)
-        want, want_pred = [t.clone() for t in self._eager()]
-        self.check()                                        # the eager run's own buffers
-        self.cell = self._captured_cell
-        self.verify_report = []                             # (replay, "logits" | "pred") of everything that differed
-        for r in range(replays):
-            self.graph.replay()
-            if not torch.equal(self.logits, want):
-                self.verify_report.append((r, "logits"))
-            if not torch.equal(self.pred, want_pred):
-                self.verify_report.append((r, "pred"))
-        torch.cuda.synchronize(dev)
-        self.check()
-        return not self.verify_report
+        want = self._eager_on_captured([], lambda: [t.clone() for t in self._eager()])
+        return self._compare_replays(replays, lambda: [("logits", self.logits), ("pred", self.pred)], want)
 
     def load(self, images, questions, lengths, check_ids=True, image_index=None):
         """image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
@@ -615,8 +594,7 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         if self.captured:
             self.graph.replay()
         else:                                               # (module docstring: slower where the host is slow, never wrong)
-            self.logits, self.pred = self._eager()
-            self.attentions = self.cell.attentions
+            self._issue()
         self._count_replay()
         return self.logits
 
@@ -625,7 +603,7 @@ class CapturedTowerForward(_RunStatus, _TowerInputs):
         return self.replay()
 
 
-class CapturedTowerTrainStep(_RunStatus, _TowerInputs):
+class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     """One whole training step of a macx.MACNet replayed from ONE captured HIP graph: forward (train-mode dropout), mean CE loss,
     backward, the gather of every gradient into the tower's flat buffer, global-norm clip + Adam + EMA.
 
@@ -672,32 +650,21 @@ class CapturedTowerTrainStep(_RunStatus, _TowerInputs):
         self.check_every = int(check_every)
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev)
         self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.mask_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._alloc_mask_word(dev)
         self.norm = opt.norm
         state = self._state()
         self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                opt.advance()
-                self._eager()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self._clear_grads()
-        with torch.cuda.graph(self.graph):
-            self.loss, self.logits, self.pred = self._eager()
-        bucket.flush_tables()
-        self._after_capture()
-        self._captured_cell = self.cell
-        self._captured_grads = [t.grad for t in own]       # views of bucket.flat: what a replay leaves in .grad
-        self.captured = True
-        self.verify_report = []
-        if verify and not self._replays_match_eager(state):
-            self.captured = False
-            warnings.warn("CapturedTowerTrainStep: replays of the captured step do not reproduce the eager step in this process; "
-                          "falling back to eager launches", RuntimeWarning)
+
+        def warm():
+            opt.advance()
+            self._eager()
+        self._capture(dev, warmup, warm, [(self.graph, self._issue)], before=self._clear_grads)
+        self._self_check(verify, state)
         self._restore(state)                                # warm-up (and verification) trained on zeros: undo
+
+    def _after_capture(self):
+        self.bucket.flush_tables()                          # the gathers' tables, which a capture can only point at (dp.TowerBuckets)
+        super()._after_capture()
 
     # ---- the optimizer's state, saved and restored around warm-up and verification
     def _buffers(self):
@@ -732,40 +699,34 @@ class CapturedTowerTrainStep(_RunStatus, _TowerInputs):
         self.opt.step(flat_grad=self.bucket.flat, device_lr=True)
         return loss.detach(), logits.detach(), pred
 
-    def set_mask_word(self, word):
-        """the raw 32-bit word the next replays XOR into every dropout key (0: the masks of the plain seed)"""
-        word &= 0xFFFFFFFF
-        self.mask_word.fill_(word - (1 << 32) if word >= (1 << 31) else word)
+    def _issue(self):
+        self.loss, self.logits, self.pred = self._eager()
+
+    def _stepped(self):
+        """what a step writes besides its outputs"""
+        return [self.opt.norm, self.bucket.flat] + self._buffers()
+
+    def _eager_reference(self):
+        """the eager step from the optimizer's state as it is: clones of loss, logits, pred and _stepped(); the captured `.grad`
+        tensors and `cell` are put back (CapturedTrainStep.eager_reference)"""
+        return self._eager_on_captured(self.bucket.tensors(), lambda: [t.clone() for t in list(self._eager()) + self._stepped()])
 
     def _replays_match_eager(self, state, replays=3):
         g = torch.Generator().manual_seed(20240522)
-        dev = self.images.device
-        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers, dev)
+        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers,
+                                                       self.images.device)
         self._load_inputs(images, q, lengths, False)
         self.answers.copy_(ans)
         self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
-        self._restore(state)
-        self.opt.advance()
-        out = self._eager()
-        names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
-        got = lambda o: list(o) + [self.opt.norm, self.bucket.flat] + self._buffers()
-        want = [t.clone() for t in got(out)]
-        self.check()                                        # the eager run's own buffers
-        self.cell = self._captured_cell
-        for t, gcap in zip(self.bucket.tensors(), self._captured_grads):
-            t.grad = gcap
-        self.verify_report = []                             # (replay, name) of everything that differed
-        for r in range(replays):
+
+        def from_state():                                   # the eager step and every replay start from the same state
             self._restore(state)
             self.opt.advance()
-            self.graph.replay()
-            for n, a, b in zip(names, got((self.loss, self.logits, self.pred)), want):
-                if not torch.equal(a, b):
-                    self.verify_report.append((r, n))
-        torch.cuda.synchronize(dev)
-        self.set_mask_word(0)
-        self.check()
-        return not self.verify_report
+        from_state()
+        want = self._eager_reference()
+        names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
+        written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped())
+        return self._compare_replays(replays, written, want, before=from_state)
 
     def load(self, images, questions, lengths, answers, check_ids=True):
         self._load_inputs(images, questions, lengths, check_ids)
@@ -775,12 +736,11 @@ class CapturedTowerTrainStep(_RunStatus, _TowerInputs):
     def replay(self, iteration=None):
         """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration).  Counts the optimizer's
         step and refreshes its rate from opt.lr (opt.advance()), then replays."""
-        if iteration is not None:
-            self.set_mask_word(mix32(int(iteration)))
+        self._set_iteration(iteration)
         self.opt.advance()
         if self.captured:
             self.graph.replay()
         else:
-            self.loss, self.logits, self.pred = self._eager()
+            self._issue()
         self._count_replay()
         return self.loss

@@ -64,12 +64,7 @@ def test_captured_train_step_equals_eager(macx, dev):
         for _ in range(2):
             mem = step.replay().clone()
             got = [t.grad.clone() for t in step._leaves()]
-            # the eager step on the same static tensors (replays write into the captured .grad tensors: keep and restore them)
-            keep = [t.grad for t in step._leaves()]
-            ref_mem = step._eager().clone()
-            ref = [t.grad.clone() for t in step._leaves()]
-            for t, g in zip(step._leaves(), keep):
-                t.grad = g
+            ref_mem, ref = step.eager_reference()        # the eager step on the same static tensors
             torch.cuda.synchronize()
             assert torch.equal(mem, ref_mem)
             for a, b in zip(got, ref):
@@ -91,11 +86,7 @@ def test_captured_train_step_draws_fresh_masks_per_replay(macx, dev):
     for it in (1, 2, 1):
         mem = step.replay(iteration=it).clone()
         got = [t.grad.clone() for t in step._leaves()]
-        keep = [t.grad for t in step._leaves()]
-        ref_mem = step._eager().clone()                      # eager, same device word
-        ref = [t.grad.clone() for t in step._leaves()]
-        for t, g in zip(step._leaves(), keep):
-            t.grad = g
+        ref_mem, ref = step.eager_reference()                # eager, same device word
         torch.cuda.synchronize()
         assert torch.equal(mem, ref_mem) and all(torch.equal(a, b) for a, b in zip(got, ref))
         seen.append((mem, got))
@@ -113,6 +104,32 @@ def test_captured_train_step_draws_fresh_masks_per_replay(macx, dev):
     torch.autograd.backward([st.memory], [step.d_memory])
     torch.cuda.synchronize()
     assert torch.equal(mem0, st.memory) and torch.equal(kb0, kb2.grad)
+
+
+def test_train_step_eager_fallback_behind_the_same_interface(macx, dev):
+    """what a failed self-check selects: load() / replay(iteration=) issue the eager step, whose memory and every gradient are
+    those of a cell built by hand on copies of the inputs, under the same seed and mask word"""
+    B, S, N, d, p = 4, 6, 33, 128, 2
+    cfg = macx.configs.flag_file_config("args", netLength=p, memDim=d, ctrlDim=d, attDim=d)
+    params = macx.MACCellParams(cfg, p, generator=torch.Generator().manual_seed(0)).to(dev)
+    step = macx.CapturedTrainStep(cfg, params, B, S, N, seed=77, verify=False)
+    step.captured = False                      # what a failed self-check sets
+    vq, words, lengths, kb = [t.to(dev) for t in macx.configs.synthetic_inputs(B, S, N, d, seed=3)]
+    gm = torch.randn(B, d, generator=torch.Generator().manual_seed(3)).to(dev)
+    step.load(vq, words, lengths, kb, gm)
+    mem = step.replay(iteration=3).clone()
+    got = [t.grad.clone() for t in step._leaves()]
+    vq2, w2, kb2 = [t.detach().clone().requires_grad_(True) for t in (vq, words, kb)]
+    cell = macx.MACCell(vq2, w2, w2, lengths, kb2, cfg.memoryDropout, cfg.readDropout, cfg.writeDropout, B, True, config=cfg,
+                        params=params, seed=77, mask_word=step.mask_word)
+    for t in params.tensors():
+        t.grad = None
+    st = cell.run()
+    torch.autograd.backward([st.memory], [gm])
+    torch.cuda.synchronize()
+    assert torch.equal(mem, st.memory)
+    for a, b in zip(got, [vq2.grad, w2.grad, kb2.grad] + [t.grad for t in params.tensors()]):
+        assert torch.equal(a, b)
 
 
 def test_captured_train_step_metric_shape(macx, dev):
