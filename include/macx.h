@@ -191,6 +191,12 @@ typedef struct macx_inputs {
   const float* words;            /* [B,S,d]  questionCntxWords or questionWords (mac_cell.py:570) */
   const int32_t* questionLengths;/* [B]                                                          */
   const float* knowledgeBase;    /* [B,N,d]  stem output (model.py:202)                          */
+  const int32_t* kbLengths;      /* [B] device, or NULL */
+  /* kbLengths (appended; a zero-initialised struct keeps the old behaviour): question b's knowledge base is its first
+   * kbLengths[b] cells (clamped to [1, N]); the rest is padding.  The read unit's softmax and summary run over the live cells
+   * only, att_kb[b][n >= kbLengths[b]] is exactly 0, and the forward pass does not depend on what the padded rows hold.  The
+   * backward pass multiplies them by that 0, so padded rows must be FINITE (zeros recommended) when gradients are taken; the
+   * gradient of a padded row is exactly 0.  The padded rows are still computed: the mask changes results, not time. */
 } macx_inputs;
 
 typedef struct macx_input_grads {
@@ -581,9 +587,15 @@ int macx_answer_loss(const float* logits, const int32_t* answers, int B, int A, 
  *   macx_kb_attend_fwd   att[B,N] = softmax_n(logits[B,N] + bias[0]);  info[B,d] = sum_n att KB        (ops.py:140-150)
  *   macx_kb_attend_bwd   da = dinfo . KB;  dlogits = att (da - sum_n att da);  dkb (= | +=) att (x) dinfo (dkb may be NULL);
  *                        ws >= macx_kb_attend_bwd_ws_floats(B, N, d) floats
+ *   macx_kb_attend_fwd_l the same over the first kb_lengths[b] cells of question b (int32 [B] on the device, clamped to [1, N]; NULL =
+ *                        macx_kb_attend_fwd, bit for bit): att[b][n >= kb_lengths[b]] = 0 exactly; logits and kb rows of those cells
+ *                        are never used (they may hold NaN).  macx_kb_attend_bwd needs no lengths: it multiplies by that 0, so for
+ *                        it the padded kb rows must be finite
  * N <= 1024, d % 128 == 0. */
 int macx_kb_attend_fwd(int B, int N, int d, const float* logits, const float* bias, const float* kb, float* att, float* info,
                        void* stream);
+int macx_kb_attend_fwd_l(int B, int N, int d, const float* logits, const float* bias, const float* kb, const int32_t* kb_lengths,
+                         float* att, float* info, void* stream);
 size_t macx_kb_attend_bwd_ws_floats(int B, int N, int d);
 int macx_kb_attend_bwd(int B, int N, int d, const float* att, const float* kb, const float* dinfo, float* dlogits, float* dkb,
                        int accumulate, float* ws, size_t ws_floats, void* stream);

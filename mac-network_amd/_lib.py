@@ -124,7 +124,7 @@ class MacxGatherEntry(C.Structure):
 
 class MacxInputs(C.Structure):
     _fields_ = [("vecQuestions", C.c_void_p), ("words", C.c_void_p), ("questionLengths", C.c_void_p),
-                ("knowledgeBase", C.c_void_p)]
+                ("knowledgeBase", C.c_void_p), ("kbLengths", C.c_void_p)]     # kbLengths: int32 [B] on the device, or NULL
 
 
 class MacxInputGrads(C.Structure):
@@ -141,7 +141,7 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_encoder_saved_floats", "macx_encoder_ws_floats", "macx_encoder_forward", "macx_encoder_backward",
            "macx_images_to_nhwc", "macx_gemm_mode", "macx_h2_floats", "macx_h2_from_f32", "macx_h2_to_f32", "macx_h2_gemm",
            "macx_h2_pack_weight", "macx_h2_gemm_planes", "macx_op_act", "macx_op_act_bwd", "macx_op_binary", "macx_op_reduce",
-           "macx_op_softmax", "macx_op_softmax_bwd", "macx_op_dropout", "macx_op_dropout_w", "macx_kb_attend_fwd", "macx_kb_attend_bwd",
+           "macx_op_softmax", "macx_op_softmax_bwd", "macx_op_dropout", "macx_op_dropout_w", "macx_kb_attend_fwd", "macx_kb_attend_fwd_l", "macx_kb_attend_bwd",
            "macx_kb_attend_bwd_ws_floats", "macx_answer_loss", "macx_workspace_bytes", "macx_embed_lookup", "macx_embed_lookup_bwd", "macx_control_attend_bwd",
            "macx_control_attend_bwd_ws_floats", "macx_read_fwd", "macx_read_bwd",
            "macx_write_fwd", "macx_write_bwd", "macx_read_chain_time", "macx_cell_forward_chain_time", "macx_saved_activation", "macx_ctrl_inputs_ws_floats",
@@ -290,6 +290,7 @@ def lib():
     L.macx_write_fwd.argtypes = [P_] * 4 + [V_] * 3 + [V_, C.c_size_t, V_, V_]
     L.macx_write_bwd.argtypes = [P_] * 4 + [V_, C.c_size_t, V_, C.c_size_t, V_, P_, V_, V_, V_, V_]
     L.macx_kb_attend_fwd.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+    L.macx_kb_attend_fwd_l.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
     L.macx_kb_attend_bwd_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     L.macx_kb_attend_bwd.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.macx_op_act.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]

@@ -41,6 +41,19 @@ def _f32c(t, name):
     return t.contiguous()
 
 
+def _kb_lengths(t, batch):
+    """kb_lengths: None, or an integer tensor [batch] on the device -> contiguous int32 (what questionLengths goes through)"""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("kb_lengths must be an integer tensor")
+    if not t.is_cuda:
+        raise RuntimeError("kb_lengths must live on the HIP device: the MAC cell has no CPU path")
+    if t.shape != (batch,):
+        raise ValueError("kb_lengths must be [batchSize]")
+    return t.to(torch.int32).contiguous()
+
+
 def _mask_word(t, like):
     """macx_dropout.mask_word: one 32-bit word in device memory (an int32 / uint32 tensor with one element), or None."""
     if t is None:
@@ -83,7 +96,9 @@ class _Run:
             setattr(self.pstruct, f, t.data_ptr() if t is not None else None)
         self.inputs = _lib.MacxInputs(vecQuestions=cell.vecQuestions.data_ptr(), words=cell.words.data_ptr(),
                                       questionLengths=cell.questionLengths.data_ptr(),
-                                      knowledgeBase=cell.knowledgeBase.data_ptr())
+                                      knowledgeBase=cell.knowledgeBase.data_ptr(),
+                                      kbLengths=cell.kb_lengths.data_ptr() if cell.kb_lengths is not None else None)
+        self.kb_lengths = cell.kb_lengths          # held here: the backward pass of this run may outlive the cell
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         # the hand-off status words of `saved` are sticky (macx_run_status): zero them once, here.  Not inside a graph capture -- the
         # status must survive replays -- so a run allocated under capture is reset by its capturer afterwards (graph.py)
@@ -247,6 +262,11 @@ class MACCell:
     poisons the run (its final memory and gradients are NaN) and is reported by
     status()  -> (bits, first_step): (0, -1) for a clean run (include/macx.h, macx_run_status);  check()  raises macx.HandoffTimeout.
     Both SYNCHRONISE the current stream -- call them where the loop synchronises anyway (after reading the loss), not per launch.
+    kb_lengths  None, or an integer tensor [batchSize] on the device: question b's knowledge base is its first kb_lengths[b] cells
+             (1 <= kb_lengths[b] <= N; values outside are clamped by the kernel), the rest of its N rows is padding.  The read
+             unit attends over the live cells only: attentions["kb"][i][b, kb_lengths[b]:] are exact zeros and the forward pass
+             does not depend on what the padded rows hold.  The backward pass multiplies them by that zero: keep them FINITE
+             (zeros) when gradients are taken; their own gradient is exactly 0.  The padded rows are still computed.
     gemm     kernel family of the knowledge-base GEMMs of THIS cell: "h2" | "split" | "native" (None: the process default)
     tune     {key: value} for macx_opts.tune, the per-call A/B hooks (_lib.TUNE; measurement only, never needed for results)
     """
@@ -280,9 +300,10 @@ class MACCell:
 
     def __init__(self, vecQuestions, questionWords, questionCntxWords, questionLengths, knowledgeBase,
                  memoryDropout, readDropout, writeDropout, batchSize, train, reuse=None, *, config=None, params=None,
-                 netLength=None, seed=None, b0=0, gemm=None, d_logical=0, mask_word=None, tune=None):
+                 netLength=None, seed=None, b0=0, gemm=None, d_logical=0, mask_word=None, tune=None, kb_lengths=None):
         from types import SimpleNamespace
         self.mask_word = _mask_word(mask_word, knowledgeBase)
+        self.kb_lengths = _kb_lengths(kb_lengths, knowledgeBase.shape[0])
         self.d_logical = int(d_logical)        # > 0: this is the zero-padded image of a d_logical-wide cell (PaddedMACCell)
         self.config = config if config is not None else SimpleNamespace()
         self.opts = freeze(self.config, gemm, tune)     # raises for rejected / unsupported option sets
@@ -493,7 +514,7 @@ class PaddedMACCell:
 
     def __init__(self, vecQuestions, questionWords, questionCntxWords, questionLengths, knowledgeBase,
                  memoryDropout, readDropout, writeDropout, batchSize, train, reuse=None, *, config=None, params=None,
-                 netLength=None, seed=None, b0=0, gemm=None, mask_word=None, tune=None):
+                 netLength=None, seed=None, b0=0, gemm=None, mask_word=None, tune=None, kb_lengths=None):
         import copy
         from .options import UnsupportedOptions
         # the dropout index at the logical width (macx_shapes.d_logical) is implemented by the H2 kernel family: the padded cell runs
@@ -516,7 +537,8 @@ class PaddedMACCell:
         cntx_p = words_p if questionCntxWords is questionWords else pad(questionCntxWords)
         self.inner = MACCell(pad(vecQuestions), words_p, cntx_p, questionLengths, pad(knowledgeBase), memoryDropout, readDropout,
                              writeDropout, batchSize, train, reuse, config=wide, params=_PaddedParams(self.params, d, dp),
-                             netLength=self.netLength, seed=seed, b0=b0, gemm=gemm, d_logical=d, mask_word=mask_word, tune=tune)
+                             netLength=self.netLength, seed=seed, b0=b0, gemm=gemm, d_logical=d, mask_word=mask_word, tune=tune,
+                             kb_lengths=kb_lengths)
         self.batchSize, self.train, self.seed, self.b0 = self.inner.batchSize, self.inner.train, self.inner.seed, self.inner.b0
 
     none = property(lambda self: self.inner.none)

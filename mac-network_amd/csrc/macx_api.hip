@@ -1196,7 +1196,7 @@ int CellRun::read_step(int i, int pre, bool md_fused) const {
   KbAttP a;
   a.B = B; a.N = N; a.d = d; a.nparts = chain ? 1 : d / (16 * kb_gemm_nw());
   a.logit_part = saved + L.logit_part; a.bias = P->kbLogits_b;
-  a.kb = in->knowledgeBase;
+  a.kb = in->knowledgeBase; a.kb_len = in->kbLengths;
   a.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
   a.info = info_raw(i);
   hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, st, a);
@@ -2281,10 +2281,16 @@ int macx_answer_loss(const float* logits, const int32_t* answers, int B, int A, 
 // forward: att = softmax_n(logits + bias), info = sum_n att KB       (ops.inter2att :140-146 + ops.att2Smry :149-150)
 int macx_kb_attend_fwd(int B, int N, int d, const float* logits, const float* bias, const float* kb, float* att, float* info,
                        void* stream) {
+  return macx_kb_attend_fwd_l(B, N, d, logits, bias, kb, nullptr, att, info, stream);
+}
+// ... over the first kb_lengths[b] cells of question b (clamped to [1, N]; NULL: all N): att[b][n >= length] = 0 exactly, and neither the
+// logits nor the knowledge-base rows of those cells are used
+int macx_kb_attend_fwd_l(int B, int N, int d, const float* logits, const float* bias, const float* kb, const int32_t* kb_lengths,
+                         float* att, float* info, void* stream) {
   if (!logits || !bias || !kb || !att || !info || B < 1 || N < 1 || N > K_MAXN || d < 128 || d % 128) return MACX_EINVAL;
   KbAttP a;
   a.B = B; a.N = N; a.d = d; a.nparts = 1;
-  a.logit_part = logits; a.bias = bias; a.kb = kb; a.att = att; a.info = info;
+  a.logit_part = logits; a.bias = bias; a.kb = kb; a.att = att; a.info = info; a.kb_len = kb_lengths;
   hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, (hipStream_t)stream, a);
   CK(hipGetLastError());
   return MACX_OK;

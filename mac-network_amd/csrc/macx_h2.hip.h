@@ -51,11 +51,15 @@ __host__ __device__ inline size_t h2_floats(size_t R, size_t C) {
 inline H2View h2_view(float* buf, int R, int C) { return H2View{reinterpret_cast<char*>(buf), R, C}; }
 inline H2View h2_view(const float* buf, int R, int C) { return H2View{reinterpret_cast<char*>(const_cast<float*>(buf)), R, C}; }
 
-// exponent that lifts a block whose largest magnitude is `maxabs` into [2^14, 2^15)
+// exponent that lifts a block whose largest magnitude is `maxabs` into [2^14, 2^15).  An all-zero block takes the LARGEST exponent:
+// a contraction over rows brings every row to the minimum over the rows (h2_emin_list_kernel, the per-question minima of
+// sb_h2_kernel / sb_h2w_kernel) through an fp16 factor 2^(minimum - row's), so a zero row with exponent 0 among gradient rows
+// with exponents of +25 .. +35 would scale those to nothing.  With H2_E_MAX it is neutral in the minimum, its own factor is at
+// most 1 and multiplies zeros, and 2^-H2_E_MAX is a normal fp32: h2_unscale and the conversion back give exact zeros.
 __device__ __forceinline__ int h2_exponent(float maxabs) {
   const int be = (int)((__float_as_uint(maxabs) >> 23) & 0xFFu);
   int e = 141 - be;
-  e = maxabs == 0.0f ? 0 : e;
+  e = maxabs == 0.0f ? H2_E_MAX : e;
   return min(max(e, H2_E_MIN), H2_E_MAX);
 }
 __device__ __forceinline__ float h2_pow2(int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }   // 2^e, -126 <= e <= 127
@@ -339,8 +343,8 @@ __global__ __launch_bounds__(256) void h2_emin_list_kernel(EminList L) {
     L.part[((size_t)f * gridDim.x + blockIdx.x) * 8 + threadIdx.x] = x;
   }
 }
-// the family's common exponent of column block k from its nb partials (an all-zero family keeps exponent-0 rows: 127 never
-// reaches a kernel)
+// the family's common exponent of column block k from its nb partials (all-zero rows carry H2_E_MAX and so never lower it; an
+// all-zero family has H2_E_MAX throughout, every factor 1 on zeros; 127 -- a family without rows -- never reaches a kernel)
 __device__ __forceinline__ int h2_emin_final(const int* part, int nb, int k) {
   int m = 127;
   for (int b = 0; b < nb; ++b) m = min(m, part[(size_t)b * 8 + k]);

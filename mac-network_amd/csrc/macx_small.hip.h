@@ -586,6 +586,7 @@ struct KbAttP {
   const float* kb;           // [B][N][d]
   float* att;                // [B][N]
   float* info;               // [B][d]
+  const int32_t* kb_len;     // [B] live cells of each question (clamped to [1, N]); null = every question has N
 };
 constexpr int K_MAXN = 1024;
 
@@ -602,11 +603,14 @@ __global__ __launch_bounds__(KA_THREADS) void kb_attend_kernel(KbAttP p) {
   constexpr int KA_PRE = 8;
   const int rg = tid >> 5, c4 = tid & 31;
   const float* kb = p.kb + (size_t)b * p.N * p.d + slab * 128 + c4 * 4;
+  // cells n >= L are padding: out of the softmax, attention exactly 0, out of the summary -- whatever their logits and rows hold
+  // (the prefetch below still reads them: they are the caller's memory, and a value that is never used may be anything)
+  const int L = p.kb_len ? min(max(p.kb_len[b], 1), p.N) : p.N;
   f32x4 pv[KA_PRE];
 #pragma unroll
   for (int i = 0; i < KA_PRE; ++i) pv[i] = *reinterpret_cast<const f32x4*>(kb + (size_t)min(rg + i * NRG, p.N - 1) * p.d);
   float m = -INFINITY;
-  for (int n = tid; n < p.N; n += KA_THREADS) {
+  for (int n = tid; n < L; n += KA_THREADS) {
     float l = p.bias[0];
     for (int q = 0; q < p.nparts; ++q) l += p.logit_part[(size_t)q * p.B * p.N + (size_t)b * p.N + n];
     s_att[n] = l;
@@ -619,7 +623,7 @@ __global__ __launch_bounds__(KA_THREADS) void kb_attend_kernel(KbAttP p) {
 #pragma unroll
   for (int w = 1; w < NWV; ++w) m = fmaxf(m, s_red[w]);
   float sum = 0.f;
-  for (int n = tid; n < p.N; n += KA_THREADS) {
+  for (int n = tid; n < L; n += KA_THREADS) {
     const float e = expf(s_att[n] - m);
     s_att[n] = e;
     sum += e;
@@ -632,7 +636,7 @@ __global__ __launch_bounds__(KA_THREADS) void kb_attend_kernel(KbAttP p) {
   for (int w = 0; w < NWV; ++w) tot += s_red[NWV + w];      // fixed order
   const float inv = 1.0f / tot;
   for (int n = tid; n < p.N; n += KA_THREADS) {
-    const float a = s_att[n] * inv;
+    const float a = n < L ? s_att[n] * inv : 0.0f;
     s_att[n] = a;
     if (slab == 0) p.att[(size_t)b * p.N + n] = a;
   }
@@ -642,9 +646,9 @@ __global__ __launch_bounds__(KA_THREADS) void kb_attend_kernel(KbAttP p) {
 #pragma unroll
   for (int i = 0; i < KA_PRE; ++i) {
     const int n = rg + i * NRG;
-    if (n < p.N) acc += pv[i] * s_att[n];
+    if (n < L) acc += pv[i] * s_att[n];
   }
-  for (int n = rg + KA_PRE * NRG; n < p.N; n += NRG) {
+  for (int n = rg + KA_PRE * NRG; n < L; n += NRG) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(kb + (size_t)n * p.d);
     const float a = s_att[n];
     acc += v * a;

@@ -514,10 +514,12 @@ class GenericMACCell:
 
     def __init__(self, vecQuestions, questionWords, questionCntxWords, questionLengths, knowledgeBase,
                  memoryDropout, readDropout, writeDropout, batchSize, train, reuse=None, *, config=None, params=None,
-                 netLength=None, seed=None, b0=0, mask_word=None, tune=None):
-        from .cell import _mask_word
+                 netLength=None, seed=None, b0=0, mask_word=None, tune=None, kb_lengths=None):
+        from .cell import _mask_word, _kb_lengths
         del tune            # (the A/B hooks of macx_opts.tune select among FUSED kernels; this path has one kernel per op)
         self.mask_word = _mask_word(mask_word, knowledgeBase)
+        # live cells per question: the read unit's softmax of the plan then runs behind the length mask (plan.compile_cell)
+        self.kb_lengths = _kb_lengths(kb_lengths, knowledgeBase.shape[0])
         self.config = config if config is not None else SimpleNamespace()
         reject_like_reference(self.config)
         bad = [k for k in ("memDim", "ctrlDim", "attDim") if self.g(k) % 4]
@@ -560,7 +562,7 @@ class GenericMACCell:
         the reference's creation order -- unless a checkpoint already put them into `params`)"""
         if self._plan is None:
             from . import plan as _plan
-            self._plan = _plan.compile_cell(self.config, self.netLength)
+            self._plan = _plan.compile_cell(self.config, self.netLength, kb_lengths=self.kb_lengths is not None)
             for name, spec in self._plan.variables.items():
                 self.params.ensure(name, spec.shape, spec.init)
         return self._plan
@@ -597,7 +599,7 @@ class GenericMACCell:
             raise UnsupportedOptions("the plan names the cell's variables under MACnetwork/MACCell (model.py:453-458 passes no scope)")
         seg = self.plan().steps[int(self.iteration)]
         have = {"vecQuestions": self.vecQuestions, "knowledgeBase": self.knowledgeBase, "lengths": self.questionLengths,
-                "control": state.control, "memory": state.memory, **self._carry}
+                "kb_lengths": self.kb_lengths, "control": state.control, "memory": state.memory, **self._carry}
         if "controls" in seg.feeds:
             have["controls"], have["memories"] = self.controls, self.memories
         out = self._segment(seg, {k: have[k] for k in seg.feeds})

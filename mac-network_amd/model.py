@@ -44,8 +44,13 @@ class MACNetCore(torch.nn.Module):
         return self.stem.tensors() + self.cell.tensors() + self.out.tensors()
 
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
-                questionWords=None, mask_word=None, image_index=None, check_index=False):
-        """mask_word: None, or one 1-element int32 device tensor (MACCell's mask_word) handed to the stem, the cell and the output
+                questionWords=None, mask_word=None, image_index=None, check_index=False, kb_lengths=None,
+                check_kb_lengths=False):
+        """kb_lengths: None, or a [B] integer device tensor, ALWAYS per question: question b's knowledge base is the first
+        kb_lengths[b] of the stem's N output cells (MACCell's kb_lengths: object features padded to a common N, grids of mixed
+        sizes).  With image_index the caller passes lengths_per_image[image_index].  check_kb_lengths=True tests
+        1 <= kb_lengths <= N on the host first (synchronises) and raises ValueError; unchecked values are clamped by the kernel.
+        mask_word: None, or one 1-element int32 device tensor (MACCell's mask_word) handed to the stem, the cell and the output
         unit: every dropout site of the tower XORs it into its key when the kernels run (graph.CapturedTowerTrainStep).  Fused
         modules only.
         image_index: None (one image per question), or a [B] integer tensor for a batch whose questions share images: `images`
@@ -71,10 +76,16 @@ class MACNetCore(torch.nn.Module):
         if image_index is not None:
             kb = kb_gather(kb, image_index.to(kb.device))
         batch = images.shape[0] if image_index is None else vecQuestions.shape[0]
+        lens = {} if kb_lengths is None else {"kb_lengths": kb_lengths}             # (None: the cell's call of before)
+        if kb_lengths is not None:
+            if check_kb_lengths and torch.is_tensor(kb_lengths) and kb_lengths.numel():
+                lo, hi = int(kb_lengths.min()), int(kb_lengths.max())
+                if lo < 1 or hi > kb.shape[1]:
+                    raise ValueError("kb_lengths must lie in [1, %d] (the knowledge base's cells); got %d .. %d" % (kb.shape[1], lo, hi))
         cell = MACCell(vecQuestions=vecQuestions, questionWords=questionWords, questionCntxWords=questionCntxWords,
                        questionLengths=questionLengths, knowledgeBase=kb, memoryDropout=get(cfg, "memoryDropout"),
                        readDropout=get(cfg, "readDropout"), writeDropout=get(cfg, "writeDropout"), batchSize=batch,
-                       train=train, config=cfg, params=self.cell, netLength=self.netLength, seed=seed, b0=b0, **word)
+                       train=train, config=cfg, params=self.cell, netLength=self.netLength, seed=seed, b0=b0, **word, **lens)
         state = cell.run()                                                           # model.py:801 (MACnetwork)
         self.last_cell = cell
         return self.out(state.memory, vecQuestions, train=train, seed=seed, b0=b0, **word)   # model.py:805-809
@@ -95,8 +106,9 @@ class MACNet(MACNetCore):
         return self.enc.tensors() + super().tensors()
 
     def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None,
-                image_index=None, check_index=False):
-        """image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B])."""
+                image_index=None, check_index=False, kb_lengths=None):
+        """image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B]).
+        kb_lengths: MACNetCore.forward's (live knowledge-base cells per question); check_ids=True also tests its range on the host."""
         check_image_index(image_index, questions.shape[0], train, self.stem, images, host_check=check_index)
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}
@@ -109,4 +121,4 @@ class MACNet(MACNetCore):
                 raise ValueError("Dimensions must be equal: without --controlContextual the question words are wrdEmbDim = %d wide, "
                                  "the control state ctrlDim = %d (mac_cell.py:154)" % (raw.shape[-1], get(self.config, "ctrlDim")))
         return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw,
-                               image_index=image_index, **word)
+                               image_index=image_index, kb_lengths=kb_lengths, check_kb_lengths=check_ids, **word)

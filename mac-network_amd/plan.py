@@ -120,6 +120,7 @@ class _Emitter:
 
     def __init__(self, config, plan):
         self.cfg, self.plan, self.names, self.seg, self.w = config, plan, ScopeNames(), None, {}
+        self.kb_lengths = False        # compile_cell(kb_lengths=True): the read unit's attention takes a "kb_lengths" feed
 
     def opt(self, key):
         return get(self.cfg, key)
@@ -247,10 +248,12 @@ class _Emitter:
         return out
 
 
-def compile_cell(config, netLength):
-    """option set -> CellPlan.  Raises what the reference raises for option values it cannot build."""
+def compile_cell(config, netLength, kb_lengths=False):
+    """option set -> CellPlan.  Raises what the reference raises for option values it cannot build.  kb_lengths: the read unit's
+    softmax runs behind a length mask fed as "kb_lengths" (one length per question); without it the plan is what it always was."""
     plan = CellPlan()
     e = _Emitter(config, plan)
+    e.kb_lengths = bool(kb_lengths)
     o = e.opt
     dc, dm, da = int(o("ctrlDim")), int(o("memDim")), int(o("attDim"))
 
@@ -374,7 +377,8 @@ def _read_unit(e, i, kb, memory, control):
             source = first.get("projected_x")
             if source is None:
                 raise ValueError("None values not supported.")                        # attention * None
-        att_kb, info = e.attend(found, width, source, drop=("read_att", "read", i))
+        att_kb, info = e.attend(found, width, source, drop=("read_att", "read", i),
+                                lengths=seg.feed("kb_lengths") if e.kb_lengths else None)
     seg.results["att_kb"] = att_kb
     return info
 
