@@ -196,7 +196,8 @@ typedef struct macx_inputs {
    * kbLengths[b] cells (clamped to [1, N]); the rest is padding.  The read unit's softmax and summary run over the live cells
    * only, att_kb[b][n >= kbLengths[b]] is exactly 0, and the forward pass does not depend on what the padded rows hold.  The
    * backward pass multiplies them by that 0, so padded rows must be FINITE (zeros recommended) when gradients are taken; the
-   * gradient of a padded row is exactly 0.  The padded rows are still computed: the mask changes results, not time. */
+   * gradient of a padded row is exactly 0.  The padded rows are still computed: the mask changes results, not time.
+   * With shared images, macx_kb_gather_l makes both on the device: this array from the sizes per image, and the zero padding. */
 } macx_inputs;
 
 typedef struct macx_input_grads {
@@ -457,6 +458,24 @@ int macx_kb_gather(const float* kb_images /*[G,N,d]*/, const int32_t* image_inde
                    float* kb /*[B,N,d]*/, void* stream);
 int macx_kb_gather_bwd(const float* dkb /*[B,N,d]*/, const int32_t* image_index /*[B], device*/, int G, int B, int N, int d,
                        float* dkb_images /*[G,N,d]*/, void* stream);
+/* The same two with a knowledge-base SIZE per image (object features padded to a common N, grids of mixed sizes): with shared images
+ * the size belongs to the image, and the size of question b's knowledge base is that of the image it names.
+ * image_lengths: [G] int32 in DEVICE memory, read when the kernel runs like the index; L_g = clamp(image_lengths[g], 1, N), the
+ * clamp of macx_kb_attend_fwd_l.  NULL: exactly the plain call above (same kernel, same bits; kb_lengths_out is not written).
+ * Forward: rows n < L_g of question b are the copy of its image's rows; rows n >= L_g are written as +0.0f WITHOUT reading the
+ * source (what the stem computed in padded rows never reaches the cell, whose backward pass wants finite padding);
+ * kb_lengths_out[b] = L_g -- the per-question lengths the cell takes (macx_inputs.kbLengths), made on the device so that a captured
+ * graph follows an index and lengths rewritten between replays.  An index outside [0, G) gives the all-NaN block of the plain call
+ * and kb_lengths_out[b] = N, so the poison reaches the result.
+ * Backward: rows n < L_g of image g are the ascending-b fp32 sum of the plain call; rows n >= L_g are written as zeros without
+ * reading dkb; an image that no question names is all zeros; no atomics.
+ * MACX_EINVAL as above, and for d % 4 != 0 (a row is d/4 16-byte quads) or an int32 pointer off a 4-byte boundary. */
+int macx_kb_gather_l(const float* kb_images /*[G,N,d]*/, const int32_t* image_index /*[B], device*/,
+                     const int32_t* image_lengths /*[G], device, or NULL*/, int G, int B, int N, int d, float* kb /*[B,N,d]*/,
+                     int32_t* kb_lengths_out /*[B], device*/, void* stream);
+int macx_kb_gather_bwd_l(const float* dkb /*[B,N,d]*/, const int32_t* image_index /*[B], device*/,
+                         const int32_t* image_lengths /*[G], device, or NULL*/, int G, int B, int N, int d,
+                         float* dkb_images /*[G,N,d]*/, void* stream);
 
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)
@@ -609,6 +628,10 @@ int macx_kb_attend_bwd(int B, int N, int d, const float* att, const float* kb, c
  *   macx_param_grads are read / written (read: projX, projY, memKbProj, memKbProj2, kbLogits; write: newMemory, gate).
  *   read:  info[B,d], att[B,N] = read(knowledgeBase[B,N,d], memory[B,d], control[B,d]); memory / read dropout per macx_dropout
  *          bwd: d_info -> d_knowledgeBase[B,N,d], d_memory, d_control and the unit's parameter gradients
+ *          macx_read_fwd_l: the same with macx_inputs.kbLengths (kb_lengths: [B] int32 on the device, clamped to [1, N]; NULL =
+ *          macx_read_fwd, which forwards here).  No backward twin: every backward consumer multiplies by att, which is exactly 0
+ *          in the padded cells, so macx_read_bwd on this call's `saved` gives exact zeros in the padded rows of d_knowledgeBase
+ *          (the padded rows of knowledgeBase must be finite for that).
  *   write: new_memory[B,d] = write(memory, info, control); the write dropout (mac_cell.py:461-463) is applied to `info`
  *          bwd: d_new_memory -> d_memory, d_info, d_control (the gate's; zeros without --writeGate) + parameter gradients
  *          opts->write_self_att needs the histories of a running cell: MACX_EUNSUPPORTED here (use macx_cell_step). */
@@ -616,6 +639,9 @@ size_t macx_workspace_bytes(const macx_opts*, const macx_shapes*, int for_backwa
 int macx_read_fwd(const macx_opts*, const macx_shapes*, const macx_dropout*, const macx_params*, const float* knowledgeBase,
                   const float* memory, const float* control, float* saved, size_t saved_floats, float* info, float* att,
                   void* stream);
+int macx_read_fwd_l(const macx_opts*, const macx_shapes*, const macx_dropout*, const macx_params*, const float* knowledgeBase,
+                    const int32_t* kb_lengths, const float* memory, const float* control, float* saved, size_t saved_floats,
+                    float* info, float* att, void* stream);
 int macx_read_bwd(const macx_opts*, const macx_shapes*, const macx_dropout*, const macx_params*, const float* knowledgeBase,
                   const float* saved, size_t saved_floats, float* ws, size_t ws_floats, const float* d_info,
                   const macx_param_grads*, float* d_knowledgeBase, float* d_memory, float* d_control, void* stream);

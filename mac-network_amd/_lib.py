@@ -149,7 +149,7 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest",
            "macx_encoder_forward_w", "macx_encoder_backward_w", "macx_stem_forward_w", "macx_stem_backward_w",
            "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat",
-           "macx_kb_gather", "macx_kb_gather_bwd")
+           "macx_kb_gather", "macx_kb_gather_bwd", "macx_kb_gather_l", "macx_kb_gather_bwd_l", "macx_read_fwd_l")
 
 _lib = None
 
@@ -286,6 +286,7 @@ def lib():
     L.macx_workspace_bytes.restype = C.c_size_t
     L.macx_workspace_bytes.argtypes = [P_, P_, C.c_int]
     L.macx_read_fwd.argtypes = [P_] * 4 + [V_] * 3 + [V_, C.c_size_t, V_, V_, V_]
+    L.macx_read_fwd_l.argtypes = [P_] * 4 + [V_] * 4 + [V_, C.c_size_t, V_, V_, V_]          # (+ kb_lengths behind knowledgeBase)
     L.macx_read_bwd.argtypes = [P_] * 4 + [V_, V_, C.c_size_t, V_, C.c_size_t, V_, P_, V_, V_, V_, V_]
     L.macx_write_fwd.argtypes = [P_] * 4 + [V_] * 3 + [V_, C.c_size_t, V_, V_]
     L.macx_write_bwd.argtypes = [P_] * 4 + [V_, C.c_size_t, V_, C.c_size_t, V_, P_, V_, V_, V_, V_]
@@ -314,6 +315,9 @@ def lib():
     # (block source, index [B] int32, G, B, N, d, destination, stream): forward images -> questions, backward questions -> images
     L.macx_kb_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.macx_kb_gather_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    # (..., index, lengths [G] int32 or NULL, G, B, N, d, destination, [kb_lengths_out [B] int32,] stream)
+    L.macx_kb_gather_l.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3
+    L.macx_kb_gather_bwd_l.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2
     for n in EXPORTS:
         if n.endswith("_floats"):
             getattr(L, n).restype = C.c_size_t

@@ -2039,12 +2039,20 @@ size_t macx_workspace_bytes(const macx_opts* o, const macx_shapes* s, int for_ba
 int macx_read_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
                   const float* knowledgeBase, const float* memory, const float* control, float* saved, size_t saved_floats,
                   float* info, float* att, void* stream) {
+  return macx_read_fwd_l(o, s, dp, P, knowledgeBase, nullptr, memory, control, saved, saved_floats, info, att, stream);
+}
+
+// kb_lengths: macx_inputs.kbLengths of this one unit (NULL: every question attends over all N cells)
+int macx_read_fwd_l(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
+                    const float* knowledgeBase, const int32_t* kb_lengths, const float* memory, const float* control, float* saved,
+                    size_t saved_floats, float* info, float* att, void* stream) {
   ModeScope ms(o);
   CKI(unit_check(o, s, false));
   if (!dp || !P || !knowledgeBase || !memory || !control || !saved || !info || !att) return MACX_EINVAL;
   if (misaligned(saved) || misaligned(knowledgeBase)) return MACX_EINVAL;
   macx_inputs in{};
   in.knowledgeBase = knowledgeBase;
+  in.kbLengths = kb_lengths;
   const CellRun r(o, s, dp, P, &in, saved, 1, stream);
   if (saved_floats < r.L.total) return MACX_ESMALL;
   {
@@ -3084,6 +3092,33 @@ int macx_kb_gather_bwd(const float* dkb, const int32_t* image_index, int G, int 
   const size_t quads = (size_t)N * d / 4;
   hipLaunchKernelGGL(kb_gather_bwd_kernel, kbg_grid(quads, 256, G), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const f32x4*>(dkb), image_index, G, B, quads, reinterpret_cast<f32x4*>(dkb_images));
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int macx_kb_gather_l(const float* kb_images, const int32_t* image_index, const int32_t* image_lengths, int G, int B, int N, int d,
+                     float* kb, int32_t* kb_lengths_out, void* stream) {
+  if (!image_lengths) return macx_kb_gather(kb_images, image_index, G, B, N, d, kb, stream);
+  if (!kb_images || !image_index || !kb || !kb_lengths_out || G < 1 || B < 1 || N < 1 || d < 1 || d % 4) return MACX_EINVAL;
+  if (misaligned(kb_images) || misaligned(kb)) return MACX_EINVAL;
+  if (((uintptr_t)image_index | (uintptr_t)image_lengths | (uintptr_t)kb_lengths_out) & 3) return MACX_EINVAL;
+  const size_t quads = (size_t)N * d / 4;
+  hipLaunchKernelGGL(kb_gather_l_kernel, kbg_grid(quads, KBG_CHUNK, B), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const f32x4*>(kb_images), image_index, image_lengths, G, B, N, (size_t)d / 4,
+                     reinterpret_cast<f32x4*>(kb), kb_lengths_out);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int macx_kb_gather_bwd_l(const float* dkb, const int32_t* image_index, const int32_t* image_lengths, int G, int B, int N, int d,
+                         float* dkb_images, void* stream) {
+  if (!image_lengths) return macx_kb_gather_bwd(dkb, image_index, G, B, N, d, dkb_images, stream);
+  if (!dkb || !image_index || !dkb_images || G < 1 || B < 1 || N < 1 || d < 1 || d % 4) return MACX_EINVAL;
+  if (misaligned(dkb) || misaligned(dkb_images) || (((uintptr_t)image_index | (uintptr_t)image_lengths) & 3)) return MACX_EINVAL;
+  const size_t quads = (size_t)N * d / 4;
+  hipLaunchKernelGGL(kb_gather_bwd_l_kernel, kbg_grid(quads, 256, G), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const f32x4*>(dkb), image_index, image_lengths, G, B, N, (size_t)d / 4,
+                     reinterpret_cast<f32x4*>(dkb_images));
   CK(hipGetLastError());
   return MACX_OK;
 }

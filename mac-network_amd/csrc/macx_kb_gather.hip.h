@@ -56,6 +56,62 @@ __global__ __launch_bounds__(256) void kb_gather_bwd_kernel(const f32x4* __restr
   }
 }
 
+// ---- the same two with a knowledge-base SIZE per image (macx_kb_gather_l / macx_kb_gather_bwd_l) ----------------------------------
+// image_lengths[g] (int32, device, read when the kernel runs) says how many of image g's N rows are live: L_g = clamp(., 1, N), the
+// clamp of kb_attend_kernel.  A row is `row_quads` = d/4 quads, so the live part of a block is its first L_g * row_quads quads: a
+// contiguous prefix, and the chunking of the plain kernels carries over with one more bound.
+//
+//   forward    rows n <  L_g of question b: the copy of its image's rows;  rows n >= L_g: +0.0f, the source is NOT read there (the
+//              stem's output in padded rows is whatever it computed; the cell's backward pass wants finite padding);
+//              len_out[b] = L_g.  An index outside [0, G): the all-NaN block of the plain kernel and len_out[b] = N, so that the
+//              poison reaches the attention instead of hiding behind a length.
+//   backward   rows n <  L_g of image g: the ascending-b fp32 sum of the plain kernel;  rows n >= L_g: zeros, dkb is NOT read there.
+__global__ __launch_bounds__(256) void kb_gather_l_kernel(const f32x4* __restrict__ src, const int32_t* __restrict__ index,
+                                                          const int32_t* __restrict__ lengths, int G, int B, int N, size_t row_quads,
+                                                          f32x4* __restrict__ dst, int32_t* __restrict__ len_out) {
+  const float qnan = __int_as_float(0x7FC00000);
+  const size_t quads = (size_t)N * row_quads;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int g = index[b];
+    const bool ok = g >= 0 && g < G;
+    const int L = ok ? min(max(lengths[g], 1), N) : N;
+    const size_t live = ok ? (size_t)L * row_quads : 0;          // quads read from the source
+    const f32x4 fill = ok ? f32x4{0.f, 0.f, 0.f, 0.f} : f32x4{qnan, qnan, qnan, qnan};
+    if (blockIdx.x == 0 && threadIdx.x == 0) len_out[b] = L;
+    const f32x4* s = src + (size_t)(ok ? g : 0) * quads;
+    f32x4* o = dst + (size_t)b * quads;
+    for (size_t c = (size_t)blockIdx.x * KBG_CHUNK; c < quads; c += (size_t)gridDim.x * KBG_CHUNK) {
+      f32x4 v[KBG_LOADS];
+#pragma unroll
+      for (int k = 0; k < KBG_LOADS; ++k) {
+        const size_t i = c + (size_t)k * 256 + threadIdx.x;
+        v[k] = i < live ? s[i] : fill;
+      }
+#pragma unroll
+      for (int k = 0; k < KBG_LOADS; ++k) {
+        const size_t i = c + (size_t)k * 256 + threadIdx.x;
+        if (i < quads) o[i] = v[k];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void kb_gather_bwd_l_kernel(const f32x4* __restrict__ dkb, const int32_t* __restrict__ index,
+                                                              const int32_t* __restrict__ lengths, int G, int B, int N,
+                                                              size_t row_quads, f32x4* __restrict__ out) {
+  const size_t quads = (size_t)N * row_quads;
+  for (int g = blockIdx.y; g < G; g += gridDim.y) {
+    const size_t live = (size_t)min(max(lengths[g], 1), N) * row_quads;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < quads; i += (size_t)gridDim.x * 256) {
+      f32x4 acc{0.f, 0.f, 0.f, 0.f};
+      if (i < live)
+        for (int b = 0; b < B; ++b)
+          if (index[b] == g) acc += dkb[(size_t)b * quads + i];
+      out[(size_t)g * quads + i] = acc;
+    }
+  }
+}
+
 inline dim3 kbg_grid(size_t quads, int per_block, int outer) {
   const size_t chunks = (quads + per_block - 1) / per_block;
   const int oy = outer < 65535 ? outer : 65535;

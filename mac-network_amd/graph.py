@@ -13,6 +13,14 @@ tensors and replays it per batch.
 Evaluation only (no dropout, nothing kept for a backward pass); parameters are read at replay time, so an optimizer step or
 a checkpoint load between calls is seen.  Changing a parameter's storage (`.to()`, `.data = `) needs a new capture.
 
+Knowledge bases of per-question size (MACCell's kb_lengths): every class here takes `kb_lengths=True`.  The lengths are device data
+the attention kernel reads when it runs, so ONE graph serves every set of them: a static int32 [B] tensor `.kb_lengths` (all N) is
+allocated with the other inputs, `load(..., kb_lengths=)` copies into it (required exactly when the class was built with it), or
+write it directly.  The self-checks then draw lengths too (one N, one 1, the rest random).
+
+    fwd = macx.CapturedForward(cfg, params, B=64, S=50, N=100, kb_lengths=True)
+    memory = fwd(vecQuestions, questionCntxWords, questionLengths, knowledgeBase, kb_lengths=boxes)     # [B] integers in [1, N]
+
 A capture checks itself before it is used (`verify=True`): three replays on random inputs must reproduce the eager run bit
 for bit; a process whose replays do not falls back to eager launches (`captured` is False, a warning says so): slower where
 the host is slow, never wrong.  The check exists because of a bug it would have caught.  Until the end of round 3 the
@@ -189,12 +197,40 @@ class _MaskWord:
             self.set_mask_word(mix32(int(iteration)))
 
 
+def _draw_lengths(gen, n, N):
+    """n knowledge-base sizes for the self-checks: one N, one 1 (n > 1), the rest random in [1, N]"""
+    L = torch.randint(1, N + 1, (n,), generator=gen, dtype=torch.int32)
+    L[0] = N
+    if n > 1:
+        L[-1] = 1
+    return L
+
+
+def _check_lengths(t, n, N, check, name):
+    """load()'s validation of a [n] tensor of knowledge-base sizes; check: also 1 <= size <= N on the host (synchronises)"""
+    if not torch.is_tensor(t) or tuple(t.shape) != (n,) or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError("%s must be a [%d] integer tensor" % (name, n))
+    if check and n and (int(t.min()) < 1 or int(t.max()) > N):
+        raise ValueError("%s must lie in [1, %d] (the knowledge base's cells); got %d .. %d" % (name, N, int(t.min()), int(t.max())))
+
+
+def _lengths_argument(who, name, given, built):
+    """load() takes `name` exactly when the class was built with it (as d_memory)"""
+    if given != built:
+        raise TypeError("%s.load() %s %s: the graph was captured %s %s=True"
+                        % (who, "needs" if built else "takes no", name, "with" if built else "without", name))
+
+
 class _CellInputs:
     """the static input tensors of a captured cell, load() into them and the cell built on them"""
 
     d_memory = None                                  # [B, d] gradient of the final memory: the training classes
+    kb_lengths = None                                # [B] int32 live knowledge-base cells per question: kb_lengths=True
 
-    def _alloc_inputs(self, config, params, B, S, N, device, netLength, train=False, requires_grad=False):
+    def _alloc_inputs(self, config, params, B, S, N, device, netLength, train=False, requires_grad=False, kb_lengths=False):
+        """kb_lengths: also a static [B] int32 `kb_lengths` (all N), which the cell's attention kernel reads when it runs -- one
+        graph serves every set of lengths.  Allocated here, before the capture: the host writes it between replays, so it must not
+        come from the graph's pool."""
         dev = _require_hip(torch.device(device) if device is not None else params.tensors()[0].device, type(self).__name__, "the MAC cell")
         d = int(get(config, "memDim"))
         self.config, self.params = config, params
@@ -205,20 +241,29 @@ class _CellInputs:
         self.knowledgeBase = torch.zeros(B, N, d, device=dev, requires_grad=requires_grad)
         if train:
             self.d_memory = torch.zeros(B, d, device=dev)
+        if kb_lengths:
+            self.kb_lengths = torch.full((B,), N, dtype=torch.int32, device=dev)
         return dev
 
     def _randomise(self, seed):
-        """N(0, 1) inputs for the self-check"""
+        """N(0, 1) inputs for the self-check; with kb_lengths: one question at N, one at 1, the rest random (the device-read path)"""
         g = torch.Generator().manual_seed(seed)
         with torch.no_grad():
             for t in (self.vecQuestions, self.words, self.knowledgeBase) + (() if self.d_memory is None else (self.d_memory,)):
                 t.copy_(torch.randn(t.shape, generator=g).to(t.device))
+            if self.kb_lengths is not None:
+                self.kb_lengths.copy_(_draw_lengths(g, *self.knowledgeBase.shape[:2]))
 
-    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory=None):
+    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory=None, kb_lengths=None, check_ids=True):
         """Copy a batch into the captured run's input tensors (or write into .knowledgeBase etc. directly and skip this);
-        d_memory: the training classes' [B, d] gradient of the final memory, and theirs only"""
+        d_memory: the training classes' [B, d] gradient of the final memory, and theirs only;
+        kb_lengths: the [B] integer sizes of a class built with kb_lengths=True, and of such a class only; check_ids tests
+        1 <= kb_lengths <= N on the host first (synchronises; unchecked values are clamped by the kernel)"""
         if (d_memory is None) != (self.d_memory is None):
             raise TypeError("%s.load() takes %s d_memory" % (type(self).__name__, "no" if self.d_memory is None else "a"))
+        _lengths_argument(type(self).__name__, "kb_lengths", kb_lengths is not None, self.kb_lengths is not None)
+        if kb_lengths is not None:
+            _check_lengths(kb_lengths, *self.knowledgeBase.shape[:2], check_ids, "kb_lengths")
         with torch.no_grad():
             self.vecQuestions.copy_(vecQuestions)
             self.words.copy_(words)
@@ -226,11 +271,15 @@ class _CellInputs:
             self.knowledgeBase.copy_(knowledgeBase)
             if d_memory is not None:
                 self.d_memory.copy_(d_memory)
+            if kb_lengths is not None:
+                self.kb_lengths.copy_(kb_lengths)
 
     def _make_cell(self, train):
         """evaluation: no dropout, no seed, no word; training: the config's keep values, seed, b0 and the mask word"""
         keep = [float(get(self.config, k)) if train else 1.0 for k in ("memoryDropout", "readDropout", "writeDropout")]
         drawn = dict(seed=self.seed, b0=self.b0, mask_word=self.mask_word) if train else {}
+        if self.kb_lengths is not None:               # (None: the cell's call of before)
+            drawn["kb_lengths"] = self.kb_lengths
         return MACCell(vecQuestions=self.vecQuestions, questionWords=self.words, questionCntxWords=self.words,
                        questionLengths=self.lengths, knowledgeBase=self.knowledgeBase, memoryDropout=keep[0], readDropout=keep[1],
                        writeDropout=keep[2], batchSize=self.vecQuestions.shape[0], train=train, config=self.config,
@@ -240,9 +289,9 @@ class _CellInputs:
 class CapturedForward(_Captured, _CellInputs):
     _WHAT = ("run", "run")
 
-    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True, check_every=0):
+    def __init__(self, config, params, B, S, N, device=None, netLength=None, warmup=2, verify=True, check_every=0, kb_lengths=False):
         self.check_every = int(check_every)
-        dev = self._alloc_inputs(config, params, B, S, N, device, netLength)
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, kb_lengths=kb_lengths)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
         self._self_check(verify)
@@ -269,8 +318,8 @@ class CapturedForward(_Captured, _CellInputs):
         self._count_replay()
         return self.memory
 
-    def __call__(self, vecQuestions, words, lengths, knowledgeBase):
-        self.load(vecQuestions, words, lengths, knowledgeBase)
+    def __call__(self, vecQuestions, words, lengths, knowledgeBase, kb_lengths=None):
+        self.load(vecQuestions, words, lengths, knowledgeBase, kb_lengths=kb_lengths)
         return self.replay()
 
 
@@ -301,10 +350,11 @@ class CapturedTrainStep(_Captured, _CellInputs, _MaskWord):
     `verify=True` replays three times against the eager step on random inputs and falls back to eager launches when a replay
     differs in any gradient (`captured` False, a warning says so)."""
 
-    def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True, check_every=0):
+    def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True, check_every=0,
+                 kb_lengths=False):
         self.seed, self.b0 = int(seed), int(b0)
         self.check_every = int(check_every)
-        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, requires_grad=True)
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, requires_grad=True, kb_lengths=kb_lengths)
         self._alloc_mask_word(dev)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)], before=self._clear_grads)
@@ -377,8 +427,8 @@ class CapturedDPTrainStep(_Captured, _CellInputs, _MaskWord, TwoPhaseStep):
     """
 
     def __init__(self, config, params, bucket, B, S, N, global_batch, seed=0, b0=0, device=None, netLength=None, warmup=2, capture=True,
-                 check_every=0):
-        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True)
+                 check_every=0, kb_lengths=False):
+        dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, kb_lengths=kb_lengths)
         if bucket.flat.data_ptr() != params.grad_buffer().data_ptr():
             raise ValueError("the bucket must be built over params' own flat gradient buffer (OverlappedBuckets(params) / "
                              "GradBucket(params.tensors(), params=params))")
@@ -482,17 +532,39 @@ def _random_tower_inputs(gen, B, S, vocab, shape_images, answers, dev):
 class _TowerInputs:
     """the static input tensors of a captured tower and load() into them"""
 
-    G, image_index = None, None            # questions that share images (CapturedTowerForward(images=G)): see _alloc_inputs
+    G, image_index = None, None            # questions that share images (images=G): see _alloc_inputs
+    kb_lengths, image_lengths = None, None # knowledge bases of per-question / per-image size: see _alloc_inputs
 
-    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev, images=None):
+    @staticmethod
+    def _check_options(net, who, images, kb_lengths, image_lengths, train):
+        """what a constructor refuses before it asks for the device"""
+        if image_lengths and images is None:
+            raise ValueError("%s(image_lengths=True) needs images=G: the sizes belong to shared images (one image per question: "
+                             "kb_lengths=True)" % who)
+        if image_lengths and kb_lengths:
+            raise ValueError("%s: image_lengths and kb_lengths both given: with image_lengths the per-question sizes are made on the "
+                             "device (image_lengths[image_index])" % who)
+        if images is not None and train and hasattr(net, "stem"):       # the eager path's ValueError for a stem that drops (stem.check_image_index)
+            from .stem import check_image_index
+            check_image_index(torch.zeros(1, dtype=torch.int32), 1, True, net.stem)
+
+    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev, images=None, kb_lengths=False, image_lengths=False):
         """images: None (one image per question), or G: the static image tensor holds G images and a static [B] int32
-        `image_index`, read by the captured gather kernel at replay time, says which one each question looks at"""
+        `image_index`, read by the captured gather kernel at replay time, says which one each question looks at.
+        kb_lengths: a static [B] int32 `kb_lengths` (all N), read by the cell's attention kernel at replay time.
+        image_lengths (with images=G): a static [G] int32 `image_lengths` (all N), read by the captured gather (macx_kb_gather_l),
+        which makes the cell's per-question lengths on the device.  Both are allocated here, before the capture."""
         self.B, self.S, self.H, self.W, self.imageInDim = int(B), int(S), int(H), int(W), int(imageInDim)
+        self.N = net.stem.out_hw[0] * net.stem.out_hw[1]
+        if kb_lengths:
+            self.kb_lengths = torch.full((self.B,), self.N, dtype=torch.int32, device=dev)
         if images is not None:
             if int(images) < 1:
                 raise ValueError("images = %r: the number of distinct images of a batch is at least 1" % (images,))
             self.G = int(images)
             self.image_index = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            if image_lengths:
+                self.image_lengths = torch.full((self.G,), self.N, dtype=torch.int32, device=dev)
         if (net.stem.H, net.stem.W, net.stem.inDim) != (self.H, self.W, self.imageInDim):
             raise ValueError("the net's stem was built for %d x %d x %d image features, not %d x %d x %d"
                              % (net.stem.H, net.stem.W, net.stem.inDim, self.H, self.W, self.imageInDim))
@@ -500,7 +572,30 @@ class _TowerInputs:
         self.questions = torch.zeros(self.B, self.S, dtype=torch.int32, device=dev)
         self.lengths = torch.full((self.B,), self.S, dtype=torch.int32, device=dev)
 
-    def _load_inputs(self, images, questions, lengths, check_ids, image_index=None):
+    def _net_arguments(self):
+        """the keyword arguments of the net's call that the static tensors stand for ({}: the call of before)"""
+        named = (("image_index", self.image_index), ("kb_lengths", self.kb_lengths), ("image_lengths", self.image_lengths))
+        return {k: t for k, t in named if t is not None}
+
+    def _random_groups(self, gen):
+        """(image_index, kb_lengths, image_lengths) for the self-checks, None where the class has none: an index with repeats and
+        (G > 1) one image that no question names; lengths with one N and one 1"""
+        index = None
+        if self.G is not None:
+            index = torch.randint(0, max(self.G - 1, 1), (self.B,), generator=gen, dtype=torch.int32)
+            index[-1] = index[0]
+        kbl = None if self.kb_lengths is None else _draw_lengths(gen, self.B, self.N)
+        iml = None if self.image_lengths is None else _draw_lengths(gen, self.G, self.N)
+        return index, kbl, iml
+
+    def _load_inputs(self, images, questions, lengths, check_ids, image_index=None, kb_lengths=None, image_lengths=None):
+        who = type(self).__name__
+        _lengths_argument(who, "kb_lengths", kb_lengths is not None, self.kb_lengths is not None)
+        _lengths_argument(who, "image_lengths", image_lengths is not None, self.image_lengths is not None)
+        if kb_lengths is not None:
+            _check_lengths(kb_lengths, self.B, self.N, check_ids, "kb_lengths")
+        if image_lengths is not None:
+            _check_lengths(image_lengths, self.G, self.N, check_ids, "image_lengths")
         if self.G is None and image_index is not None:
             raise ValueError("this graph was captured with one image per question (images=None): it takes no image_index")
         if self.G is not None:
@@ -526,6 +621,10 @@ class _TowerInputs:
             self.lengths.copy_(lengths)
             if self.G is not None:
                 self.image_index.copy_(image_index)
+            if kb_lengths is not None:
+                self.kb_lengths.copy_(kb_lengths)
+            if image_lengths is not None:
+                self.image_lengths.copy_(image_lengths)
 
 
 class CapturedTowerForward(_Captured, _TowerInputs):
@@ -543,6 +642,13 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         fwd = macx.CapturedTowerForward(net, B=64, S=50, images=7)
         logits = fwd(images7, questions, lengths, image_index=index)      # question b looks at images7[index[b]]
 
+    Knowledge bases of different sizes: `kb_lengths=True` (a static [B] `fwd.kb_lengths`, MACNet.forward's kb_lengths) or, with
+    images=G, `image_lengths=True` (a static [G] `fwd.image_lengths`: the captured gather is macx_kb_gather_l, which zeroes each
+    question's padded rows and makes the per-question lengths on the device).  Both are read at replay time and loaded like the index:
+
+        fwd = macx.CapturedTowerForward(net, B=64, S=50, images=7, image_lengths=True)
+        logits = fwd(images7, questions, lengths, image_index=index, image_lengths=sizes)
+
     Evaluation only (train=False: no dropout, nothing kept for a backward pass).  Parameters are read at replay time: an optimizer
     step or a checkpoint load between calls is seen; changing a parameter's storage needs a new capture.  `load()` validates ids
     and lengths on the host as QuestionEncoder.forward does (check_ids=False skips the synchronisation); the graph itself runs
@@ -551,11 +657,13 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     state and attentions are views of its `saved` buffer."""
     _WHAT = ("tower", "forward")
 
-    def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None):
+    def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None, kb_lengths=False,
+                 image_lengths=False):
+        self._check_options(net, "CapturedTowerForward", images, kb_lengths, image_lengths, train=False)
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
-        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
         self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
@@ -564,8 +672,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     @torch.no_grad()
     def _eager(self):
         from .output import _AnswerLoss
-        group = {} if self.G is None else {"image_index": self.image_index}
-        logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **group)
+        logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **self._net_arguments())
         self.cell = self.net.last_cell                      # (status(): the latest run's buffers)
         _, pred = _AnswerLoss.apply(logits, self._no_answers)          # addPredOp's argmax (first maximum), one kernel
         return logits, pred
@@ -577,18 +684,15 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     def _replays_match_eager(self, replays=3):
         g = torch.Generator().manual_seed(20240521)
         images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, self.images.device)
-        index = None
-        if self.G is not None:                              # repeats, and (G > 1) one image that no question names
-            index = torch.randint(0, max(self.G - 1, 1), (self.B,), generator=g, dtype=torch.int32)
-            index[-1] = index[0]
-        self._load_inputs(images, q, lengths, False, index)
+        self._load_inputs(images, q, lengths, False, *self._random_groups(g))
         want = self._eager_on_captured([], lambda: [t.clone() for t in self._eager()])
         return self._compare_replays(replays, lambda: [("logits", self.logits), ("pred", self.pred)], want)
 
-    def load(self, images, questions, lengths, check_ids=True, image_index=None):
+    def load(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
         """image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
-        validated with the ids (check_ids)"""
-        self._load_inputs(images, questions, lengths, check_ids, image_index)
+        validated with the ids (check_ids).  kb_lengths [B] / image_lengths [G]: the integer sizes of a graph captured with
+        kb_lengths=True / image_lengths=True (required there, refused otherwise); 1 <= size <= N is validated with the ids"""
+        self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
 
     def replay(self):
         if self.captured:
@@ -598,8 +702,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         self._count_replay()
         return self.logits
 
-    def __call__(self, images, questions, lengths, check_ids=True, image_index=None):
-        self.load(images, questions, lengths, check_ids, image_index)
+    def __call__(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
+        self.load(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
         return self.replay()
 
 
@@ -626,6 +730,10 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     here (CapturedDPTrainStep is the cell-level route).  `opt` must be built over bucket.tensors(), `bucket` with
     fused_gather=True.
 
+    images=G / kb_lengths=True / image_lengths=True: CapturedTowerForward's (load() takes image_index / kb_lengths / image_lengths
+    accordingly).  With images=G the stem runs once per image and the gather and its backward (macx_kb_gather[_l] / _bwd[_l]) are
+    part of the graph; a stem that drops (stemDropout < 1) is refused at construction with the eager path's ValueError.
+
     verify=True replays three times against the eager step on random inputs -- loss, logits, pred, norm, the flat gradient, every
     parameter, m, v, ema -- each time from the same restored state, and falls back to eager launches when anything differs
     (`captured` False, a RuntimeWarning; `verify_report` lists what differed).  Parameters, m, v, ema and t are restored
@@ -635,7 +743,9 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     adopts each returned gradient as the parameter's .grad without a copy as long as nobody else holds it (the module functions
     return fresh tensors), and sums the two gradients of vecQuestions with a kernel."""
 
-    def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0):
+    def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0, images=None,
+                 kb_lengths=False, image_lengths=False):
+        self._check_options(net, "CapturedTowerTrainStep", images, kb_lengths, image_lengths, train=True)
         dev = _require_fused_tower(net, "CapturedTowerTrainStep")
         if not getattr(bucket, "fused_gather", False):
             raise ValueError("CapturedTowerTrainStep needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
@@ -648,7 +758,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
                              "bucket.flat as it is")
         self.net, self.opt, self.bucket, self.seed = net, opt, bucket, int(seed)
         self.check_every = int(check_every)
-        self._alloc_inputs(net, B, S, H, W, imageInDim, dev)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
         self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._alloc_mask_word(dev)
         self.norm = opt.norm
@@ -690,7 +800,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         """the step's launches on the current stream (opt.advance() is the caller's: it is not part of the graph)"""
         self._clear_grads()
         net, B = self.net, self.B
-        logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word)
+        logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
+                     **self._net_arguments())
         self.cell = net.last_cell
         loss, pred = net.loss_and_pred(logits, self.answers)
         self.bucket.begin_step(B, B)
@@ -715,7 +826,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         g = torch.Generator().manual_seed(20240522)
         images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers,
                                                        self.images.device)
-        self._load_inputs(images, q, lengths, False)
+        self._load_inputs(images, q, lengths, False, *self._random_groups(g))
         self.answers.copy_(ans)
         self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
 
@@ -728,8 +839,9 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped())
         return self._compare_replays(replays, written, want, before=from_state)
 
-    def load(self, images, questions, lengths, answers, check_ids=True):
-        self._load_inputs(images, questions, lengths, check_ids)
+    def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
+        """image_index / kb_lengths / image_lengths: CapturedTowerForward.load's"""
+        self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
         with torch.no_grad():
             self.answers.copy_(answers)
 

@@ -15,7 +15,7 @@ from .encoder import QuestionEncoder
 from .options import UnsupportedOptions, freeze, fresh_seed, get
 from .output import OutputClassifier, answer_loss_and_pred
 from .params import MACCellParams
-from .stem import Stem, check_image_index, kb_gather
+from .stem import Stem, check_image_index, check_image_lengths, kb_gather
 
 
 class MACNetCore(torch.nn.Module):
@@ -45,8 +45,13 @@ class MACNetCore(torch.nn.Module):
 
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
                 questionWords=None, mask_word=None, image_index=None, check_index=False, kb_lengths=None,
-                check_kb_lengths=False):
-        """kb_lengths: None, or a [B] integer device tensor, ALWAYS per question: question b's knowledge base is the first
+                check_kb_lengths=False, image_lengths=None):
+        """image_lengths: None, or a [G] integer device tensor for a batch whose questions share images (it needs image_index; passing
+        kb_lengths as well is a ValueError): image g's knowledge base is the first image_lengths[g] of the stem's N cells.  The gather
+        (macx_kb_gather_l) writes +0 into every question's padded rows, whatever the stem computed there, and makes the per-question
+        kb_lengths the cell receives on the device: nothing is indexed on the host, so a captured graph follows rewritten lengths.
+        check_kb_lengths=True tests 1 <= image_lengths <= N on the host first, as for kb_lengths.
+        kb_lengths: None, or a [B] integer device tensor, ALWAYS per question: question b's knowledge base is the first
         kb_lengths[b] of the stem's N output cells (MACCell's kb_lengths: object features padded to a common N, grids of mixed
         sizes).  With image_index the caller passes lengths_per_image[image_index].  check_kb_lengths=True tests
         1 <= kb_lengths <= N on the host first (synchronises) and raises ValueError; unchecked values are clamped by the kernel.
@@ -60,6 +65,9 @@ class MACNetCore(torch.nn.Module):
         [0, G) gives that question a NaN knowledge base; check_index=True tests the range on the host first (synchronises)."""
         cfg = self.config
         image_index = check_image_index(image_index, vecQuestions.shape[0], train, self.stem, images, host_check=check_index)
+        if image_lengths is not None:
+            check_image_lengths(image_lengths, image_index, kb_lengths, images, self.stem.out_hw[0] * self.stem.out_hw[1],
+                                host_check=check_kb_lengths)
         if mask_word is not None and not isinstance(self.cell, MACCellParams):
             raise UnsupportedOptions("a run's mask word over the whole tower needs the fused cell (MACCellParams); this option set "
                                      "runs the cell on the generic path")
@@ -73,7 +81,10 @@ class MACNetCore(torch.nn.Module):
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}               # (None: the modules' calls of before)
         kb = self.stem(images, train=train, seed=seed, b0=b0, **word)               # model.py:791
-        if image_index is not None:
+        if image_lengths is not None:
+            kb, kb_lengths = kb_gather(kb, image_index.to(kb.device), image_lengths.to(kb.device))
+            check_kb_lengths = False                                                 # (clamped by the gather; the host check is done)
+        elif image_index is not None:
             kb = kb_gather(kb, image_index.to(kb.device))
         batch = images.shape[0] if image_index is None else vecQuestions.shape[0]
         lens = {} if kb_lengths is None else {"kb_lengths": kb_lengths}             # (None: the cell's call of before)
@@ -106,10 +117,14 @@ class MACNet(MACNetCore):
         return self.enc.tensors() + super().tensors()
 
     def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None,
-                image_index=None, check_index=False, kb_lengths=None):
-        """image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B]).
+                image_index=None, check_index=False, kb_lengths=None, image_lengths=None):
+        """image_lengths: MACNetCore.forward's (live knowledge-base cells per IMAGE of a batch with image_index).
+        image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B]).
         kb_lengths: MACNetCore.forward's (live knowledge-base cells per question); check_ids=True also tests its range on the host."""
         check_image_index(image_index, questions.shape[0], train, self.stem, images, host_check=check_index)
+        if image_lengths is not None:
+            check_image_lengths(image_lengths, image_index, kb_lengths, images, self.stem.out_hw[0] * self.stem.out_hw[1],
+                                host_check=check_ids)
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}
         words, vecQ = self.enc(questions, questionLengths, train=train, seed=seed, b0=b0, check_ids=check_ids, **word)   # model.py:783-788
@@ -121,4 +136,5 @@ class MACNet(MACNetCore):
                 raise ValueError("Dimensions must be equal: without --controlContextual the question words are wrdEmbDim = %d wide, "
                                  "the control state ctrlDim = %d (mac_cell.py:154)" % (raw.shape[-1], get(self.config, "ctrlDim")))
         return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw,
-                               image_index=image_index, kb_lengths=kb_lengths, check_kb_lengths=check_ids, **word)
+                               image_index=image_index, kb_lengths=kb_lengths, check_kb_lengths=check_ids and image_lengths is None, **word,
+                               **({} if image_lengths is None else {"image_lengths": image_lengths}))

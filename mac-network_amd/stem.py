@@ -430,6 +430,70 @@ class _KBGather(torch.autograd.Function):
         return out, None
 
 
-def kb_gather(kb_images, image_index):
-    """[G, N, d] stem output -> the [B, N, d] knowledge base of B questions (differentiable in kb_images)"""
-    return _KBGather.apply(kb_images, image_index)
+def check_image_lengths(image_lengths, image_index, kb_lengths, images=None, N=None, host_check=False):
+    """The validation of model.MACNet(Core).forward's image_lengths (a [G] integer tensor: image g's knowledge base is the first
+    image_lengths[g] of the stem's N cells), done before anything asks for the device.  Returns None for None.  host_check (with N):
+    also 1 <= length <= N on the host (synchronises)."""
+    if image_lengths is None:
+        return None
+    if image_index is None:
+        raise ValueError("image_lengths are the sizes of shared images: they need image_index (one image per question: kb_lengths)")
+    if kb_lengths is not None:
+        raise ValueError("image_lengths and kb_lengths both given: with image_lengths the per-question sizes are made on the device "
+                         "(image_lengths[image_index])")
+    G = None if images is None else images.shape[0]
+    if not torch.is_tensor(image_lengths) or image_lengths.dim() != 1 or (G is not None and image_lengths.shape[0] != G):
+        raise ValueError("image_lengths must be a [%s] tensor, one size per image; got %s"
+                         % ("G" if G is None else G, tuple(image_lengths.shape) if torch.is_tensor(image_lengths) else type(image_lengths).__name__))
+    if image_lengths.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError("image_lengths must have an integer dtype, not %s" % image_lengths.dtype)
+    if host_check and N is not None and image_lengths.numel():
+        lo, hi = int(image_lengths.min()), int(image_lengths.max())
+        if lo < 1 or hi > N:
+            raise ValueError("image_lengths must lie in [1, %d] (the knowledge base's cells); got %d .. %d" % (N, lo, hi))
+    return image_lengths
+
+
+class _KBGatherL(torch.autograd.Function):
+    """(kb, kb_lengths) = macx_kb_gather_l(kb_images, index, lengths): question b's block is its image's first L rows and +0 behind
+    them, kb_lengths[b] = L, L = clamp(lengths[index[b]], 1, N); backward: macx_kb_gather_bwd_l (zeros in every image's padded rows).
+    index [B] and lengths [G]: int32 on the device, read when the kernels run."""
+
+    @staticmethod
+    def forward(ctx, kb_images, index, lengths):
+        kb_images = generic._dev(kb_images, "the stem's output")
+        generic._require_device(index, "image_index")
+        generic._require_device(lengths, "image_lengths")
+        if index.dtype != torch.int32 or not index.is_contiguous():
+            index = index.to(torch.int32).contiguous()
+        if lengths.dtype != torch.int32 or not lengths.is_contiguous():
+            lengths = lengths.to(torch.int32).contiguous()
+        G, N, d = kb_images.shape
+        if lengths.shape != (G,):
+            raise ValueError("image_lengths must be [%d], one size per image" % G)
+        B = index.shape[0]
+        kb = torch.empty(B, N, d, dtype=torch.float32, device=kb_images.device)
+        kb_lengths = torch.empty(B, dtype=torch.int32, device=kb_images.device)
+        _lib.check(_lib.lib().macx_kb_gather_l(generic._p(kb_images), generic._p(index), generic._p(lengths), G, B, N, d, generic._p(kb),
+                                               generic._p(kb_lengths), generic._st(kb)), "macx_kb_gather_l")
+        ctx.index, ctx.lengths, ctx.G = index, lengths, G
+        ctx.mark_non_differentiable(kb_lengths)
+        return kb, kb_lengths
+
+    @staticmethod
+    def backward(ctx, dkb, _):
+        dkb = dkb.contiguous()
+        B, N, d = dkb.shape
+        out = torch.empty(ctx.G, N, d, dtype=torch.float32, device=dkb.device)
+        _lib.check(_lib.lib().macx_kb_gather_bwd_l(generic._p(dkb), generic._p(ctx.index), generic._p(ctx.lengths), ctx.G, B, N, d,
+                                                   generic._p(out), generic._st(out)), "macx_kb_gather_bwd_l")
+        return out, None, None
+
+
+def kb_gather(kb_images, image_index, image_lengths=None):
+    """[G, N, d] stem output -> the [B, N, d] knowledge base of B questions (differentiable in kb_images).
+    image_lengths: None, or a [G] integer device tensor, the live cells of each image; then returns (kb, kb_lengths): the padded
+    rows of kb are +0 whatever the stem's output holds there, kb_lengths [B] int32 is what the cell takes (made on the device)."""
+    if image_lengths is None:
+        return _KBGather.apply(kb_images, image_index)
+    return _KBGatherL.apply(kb_images, image_index, image_lengths)
