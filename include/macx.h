@@ -297,6 +297,37 @@ int macx_cell_backward_phase(const macx_opts*, const macx_shapes*, const macx_dr
                        const float* d_memory, const float* d_control,
                        const macx_param_grads*, const macx_input_grads*, int phase, void* stream);
 
+/* Gradients that a loss sends to the run's attention maps and step states themselves (attention supervision, entropy
+ * regularisers, per-step heads): dL/d of the viewable segments of `saved`, in the layouts of the MACX_SEG_* segments.  Every
+ * field may be NULL = zero.  They are ADDED to what arrives through the final state: d_memory / d_control keep their meaning
+ * (slot p of the histories takes both).  d_att_self needs write_self_att, d_att_gate needs write_gate: MACX_EINVAL otherwise,
+ * before anything is launched.  There is no d_infos.
+ * Contract, as for the padded rows of the knowledge base (macx_inputs.kbLengths): the values must be FINITE.  The softmax
+ * backward multiplies them by the attention, so entries at masked words and padded cells (att == 0) contribute exact zeros and the
+ * gradients there stay exact zeros -- but 0 * NaN or 0 * Inf would poison the whole row's sum. */
+typedef struct macx_state_grads {
+  const float* d_controls;      /* [p+1,B,d]  dL/d controls history (slot 0 = initial control)  */
+  const float* d_memories;      /* [p+1,B,d]  dL/d memories history                              */
+  const float* d_att_question;  /* [p,B,S]                                                       */
+  const float* d_att_kb;        /* [p,B,N]                                                       */
+  const float* d_att_self;      /* [p,B,p]    row i uses entries 0..i; only with write_self_att  */
+  const float* d_att_gate;      /* [p,B,d]    only with write_gate                               */
+} macx_state_grads;
+/* macx_cell_backward / macx_cell_backward_phase with those gradients.  A NULL struct, or one whose fields are all NULL, IS the
+ * plain call: the same launches, the same arithmetic order, bit-identical results (the plain exports forward here with NULL).
+ * A non-NULL d_memories costs one small launch per step where the option set has neither self attention nor a gate (the
+ * step's dL/dm_{i-1} is accumulated into its slot instead of written); the other fields ride launches that run anyway. */
+int macx_cell_backward_x(const macx_opts*, const macx_shapes*, const macx_dropout*, const macx_params*,
+                       const macx_inputs*, const float* saved, size_t saved_floats,
+                       float* ws, size_t ws_floats,
+                       const float* d_memory, const float* d_control,
+                       const macx_param_grads*, const macx_input_grads*, const macx_state_grads*, void* stream);
+int macx_cell_backward_phase_x(const macx_opts*, const macx_shapes*, const macx_dropout*, const macx_params*,
+                       const macx_inputs*, const float* saved, size_t saved_floats,
+                       float* ws, size_t ws_floats,
+                       const float* d_memory, const float* d_control,
+                       const macx_param_grads*, const macx_input_grads*, const macx_state_grads*, int phase, void* stream);
+
 /* ---- output unit + classifier (consumer of the final memory) ------------------ */
 /* outputOp (model.py:512-528, --outQuestion) + classifier (model.py:547-576 -> ops.FCLayer
  * ops.py:349-359) for outClassifierDims = [hidden]:

@@ -131,6 +131,15 @@ class MacxInputGrads(C.Structure):
     _fields_ = [("vecQuestions", C.c_void_p), ("words", C.c_void_p), ("knowledgeBase", C.c_void_p)]
 
 
+STATE_GRAD_FIELDS = ("d_controls", "d_memories", "d_att_question", "d_att_kb", "d_att_self", "d_att_gate")
+
+
+class MacxStateGrads(C.Structure):
+    """macx_state_grads: gradients a loss sends to the run's histories and attention maps themselves (device pointers in the layouts
+    of the MACX_SEG_* segments; NULL = zero).  Finite values only (include/macx.h)."""
+    _fields_ = [(n, C.c_void_p) for n in STATE_GRAD_FIELDS]
+
+
 EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats", "macx_ws_floats",
            "macx_saved_segment", "macx_cell_begin", "macx_cell_step", "macx_cell_forward", "macx_cell_backward",
            "macx_cell_backward_phase",
@@ -149,7 +158,8 @@ EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats
            "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest",
            "macx_encoder_forward_w", "macx_encoder_backward_w", "macx_stem_forward_w", "macx_stem_backward_w",
            "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat",
-           "macx_kb_gather", "macx_kb_gather_bwd", "macx_kb_gather_l", "macx_kb_gather_bwd_l", "macx_read_fwd_l")
+           "macx_kb_gather", "macx_kb_gather_bwd", "macx_kb_gather_l", "macx_kb_gather_bwd_l", "macx_read_fwd_l",
+           "macx_cell_backward_x", "macx_cell_backward_phase_x")
 
 _lib = None
 
@@ -204,6 +214,10 @@ def lib():
     L.macx_cell_forward.argtypes = common + [C.c_int, C.c_void_p]
     L.macx_cell_backward.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), C.c_void_p]
     L.macx_cell_backward_phase.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), C.c_int, C.c_void_p]
+    # (... + macx_state_grads* behind the input gradients; NULL = the plain call)
+    L.macx_cell_backward_x.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), P(MacxStateGrads), C.c_void_p]
+    L.macx_cell_backward_phase_x.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), P(MacxStateGrads),
+                                                      C.c_int, C.c_void_p]
     L.macx_linear.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                               C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.macx_pack_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

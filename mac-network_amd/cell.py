@@ -19,6 +19,7 @@ libmacx.so or without a HIP device every entry point raises.
 """
 import collections
 import ctypes as C
+import weakref
 
 import torch
 
@@ -69,7 +70,13 @@ class _Run:
     """One cell run: shapes, frozen options, buffers, and the ctypes structs that describe them."""
 
     def __init__(self, cell, keep_activations):
-        self.cell = cell
+        # the cell's device tensors this run's structs point at, held here: the backward pass of this run may outlive the cell.  NOT
+        # the cell itself -- the cell holds the outputs of this run's autograd node (its differentiable histories and attention
+        # maps), the node holds the run, and a reference back would close a cycle through the autograd graph that the garbage
+        # collector cannot see: every run's `saved` buffer would stay allocated
+        self.vecQuestions, self.words, self.knowledgeBase = cell.vecQuestions, cell.words, cell.knowledgeBase
+        self.questionLengths, self.mask_word = cell.questionLengths, cell.mask_word
+        self._cell_ref = weakref.ref(cell)      # (weak: only to tell the cell that this run's backward pass is over)
         self.keep = int(bool(keep_activations))
         self.L = _lib.lib()
         self.opts = cell.opts
@@ -143,7 +150,10 @@ class _Run:
     def forward(self):
         _lib.check(self.L.macx_cell_forward(*self._common(), self.keep, self.stream), "macx_cell_forward")
 
-    def segment(self, name, shape):
+    def segment(self, name, shape, alias=False):
+        """a viewable segment of `saved` as a tensor of `shape`.  alias=True: a tensor of its own on the same memory instead of a
+        view of `saved` (no copy, no launch) -- what the autograd node returns: autograd tracks in-place writes per base tensor, and
+        a torch-level write anywhere into `saved` (the status words, say) would otherwise invalidate every output of the node."""
         off, cnt = C.c_size_t(0), C.c_size_t(0)
         _lib.check(self.L.macx_saved_segment(C.byref(self.opts), C.byref(self.shapes), self.keep, _lib.SEG[name],
                                              C.byref(off), C.byref(cnt)), "macx_saved_segment")
@@ -152,14 +162,43 @@ class _Run:
             n *= x
         if n > cnt.value:
             raise ValueError("segment %s holds %d floats, view wants %d" % (name, cnt.value, n))
+        if alias:
+            t = torch.empty(0, dtype=torch.float32, device=self.saved.device)
+            return t.set_(self.saved.untyped_storage(), self.saved.storage_offset() + off.value, tuple(shape))
         return self.saved[off.value: off.value + n].view(*shape)
 
-    def backward_begin(self, d_control, d_memory):
-        """Buffers and argument block of this run's backward pass: (args of macx_cell_backward[_phase] without the trailing phase /
-        stream, {field: gradient view}, (d vecQuestions, d words, d knowledgeBase), the flat gradient buffer, keep-alive list)."""
+    def state_grad_shapes(self):
+        """{macx_state_grads field: shape} of this run (the layouts of the viewable segments of `saved`)"""
+        s = self.shapes
+        return {"d_controls": (s.p + 1, s.B, s.d), "d_memories": (s.p + 1, s.B, s.d), "d_att_question": (s.p, s.B, s.S),
+                "d_att_kb": (s.p, s.B, s.N), "d_att_self": (s.p, s.B, s.p), "d_att_gate": (s.p, s.B, s.d)}
+
+    def _state_grads(self, state_grads):
+        """{field: tensor | None} -> (MacxStateGrads | None, tensors kept alive).  None when no gradient arrived: the plain call."""
+        given = {k: v for k, v in (state_grads or {}).items() if v is not None}
+        if not given:
+            return None, []
+        shapes = self.state_grad_shapes()
+        sg, held = _lib.MacxStateGrads(), []
+        for k, t in given.items():
+            if k not in shapes:
+                raise KeyError("no state gradient %r (have %s)" % (k, sorted(shapes)))
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError("%s must be %s, got %s" % (k, shapes[k], tuple(t.shape)))
+            t = _f32c(t, k)
+            held.append(t)
+            setattr(sg, k, t.data_ptr())
+        return sg, held
+
+    def backward_begin(self, d_control, d_memory, state_grads=None):
+        """Buffers and argument block of this run's backward pass: (args of macx_cell_backward[_phase]_x without the trailing phase /
+        stream, {field: gradient view}, (d vecQuestions, d words, d knowledgeBase), the flat gradient buffer, keep-alive list).
+        state_grads: None, or {macx_state_grads field: tensor | None} -- gradients a loss sends to the run's histories and attention
+        maps themselves (shapes: state_grad_shapes(); finite values).  None / all None passes a NULL struct: the plain call."""
         if not self.keep:
             raise RuntimeError("this run did not keep its activations (train=False / no_grad)")
         dev = self.saved.device
+        sg, sg_held = self._state_grads(state_grads)
         ws_floats = self.L.macx_ws_floats(C.byref(self.opts), C.byref(self.shapes), 1)
         ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
         gstruct = _lib.MacxParamGrads()
@@ -185,26 +224,25 @@ class _Run:
             off += n
         for f in _lib.PARAM_FIELDS:
             setattr(gstruct, f, grads[f].data_ptr() if f in grads else None)
-        cell = self.cell
-        gi_vq = torch.empty_like(cell.vecQuestions)
-        gi_words = torch.empty_like(cell.words)
-        gi_kb = torch.empty_like(cell.knowledgeBase)
+        gi_vq = torch.empty_like(self.vecQuestions)
+        gi_words = torch.empty_like(self.words)
+        gi_kb = torch.empty_like(self.knowledgeBase)
         gistruct = _lib.MacxInputGrads(vecQuestions=gi_vq.data_ptr(), words=gi_words.data_ptr(),
                                        knowledgeBase=gi_kb.data_ptr())
         dm = _f32c(d_memory, "d_memory") if d_memory is not None else None
         dc = _f32c(d_control, "d_control") if d_control is not None else None
         args = (C.byref(self.opts), C.byref(self.shapes), C.byref(self.drop), C.byref(self.pstruct), C.byref(self.inputs),
                 _ptr(self.saved), C.c_size_t(self.saved_floats), _ptr(ws), C.c_size_t(ws_floats), _ptr(dm), _ptr(dc),
-                C.byref(gstruct), C.byref(gistruct))
-        return args, grads, (gi_vq, gi_words, gi_kb), flat, (ws, gstruct, gistruct, dm, dc)
+                C.byref(gstruct), C.byref(gistruct), C.byref(sg) if sg is not None else None)
+        return args, grads, (gi_vq, gi_words, gi_kb), flat, (ws, gstruct, gistruct, dm, dc, sg, sg_held)
 
     def backward_phase(self, args, phase):
-        """macx_cell_backward_phase on torch's CURRENT stream (1: everything but the read unit's deferred contractions, 2: those)"""
+        """macx_cell_backward_phase_x on torch's CURRENT stream (1: everything but the read unit's deferred contractions, 2: those)"""
         stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
-        _lib.check(self.L.macx_cell_backward_phase(*args, int(phase), stream), "macx_cell_backward_phase(%d)" % phase)
+        _lib.check(self.L.macx_cell_backward_phase_x(*args, int(phase), stream), "macx_cell_backward_phase_x(%d)" % phase)
 
-    def backward(self, d_control, d_memory):
-        args, grads, (gi_vq, gi_words, gi_kb), flat, _keep = self.backward_begin(d_control, d_memory)
+    def backward(self, d_control, d_memory, state_grads=None):
+        args, grads, (gi_vq, gi_words, gi_kb), flat, _keep = self.backward_begin(d_control, d_memory, state_grads)
         stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
         hook = getattr(self.params, "after_backward_phase1", None)
         if hook is not None and flat is getattr(self.params, "_grad_flat", None):
@@ -213,7 +251,7 @@ class _Run:
             hook(flat)
             self.backward_phase(args, 2)
         else:
-            _lib.check(self.L.macx_cell_backward(*args, stream), "macx_cell_backward")
+            _lib.check(self.L.macx_cell_backward_x(*args, stream), "macx_cell_backward_x")
         return grads, gi_vq, gi_words, gi_kb
 
 
@@ -230,17 +268,43 @@ class _CellFunction(torch.autograd.Function):
         # freshly filled zeros tensor: one fill and one copy launch less per step -- macx_cell_backward takes NULL for it
         ctx.set_materialize_grads(False)
         p = run.shapes.p
-        controls = run.segment("controls", (p + 1, run.shapes.B, run.shapes.d))
-        memories = run.segment("memories", (p + 1, run.shapes.B, run.shapes.d))
-        # views of the run's own `saved` buffer (nothing writes it after the forward pass): no copy launches
-        return controls[p], memories[p]
+        # all on the run's own `saved` buffer (nothing writes it after the forward pass): no copy launches.  The final state stays
+        # an output of its own, so that a plain training step differentiates exactly what it always did; behind it the histories
+        # and the attention maps, in the order of _state_segments -- a loss on any of them arrives in backward() as that output's
+        # gradient, an unused one as None
+        outs = [run.segment(seg, shape, alias=True) for seg, shape in zip(_state_segments(run), _state_shapes(run))]
+        final = [run.segment(seg, (p + 1, run.shapes.B, run.shapes.d))[p] for seg in ("controls", "memories")]
+        return tuple(final) + tuple(outs)
 
     @staticmethod
-    def backward(ctx, d_control, d_memory):
+    def backward(ctx, d_control, d_memory, *d_state):
         run = ctx.run
-        grads, gvq, gwords, gkb = run.backward(d_control, d_memory)
+        fields = ["d_" + seg for seg in _state_segments(run)]
+        grads, gvq, gwords, gkb = run.backward(d_control, d_memory, dict(zip(fields, d_state)))
         pgrads = tuple(grads[f] for f in run.params.fields)
+        # the pass is over: a cell that still publishes this run's differentiable maps goes back to plain views, so that it does not
+        # keep the finished autograd graph -- and with it the AccumulateGrad nodes of the parameters -- alive until its next run.
+        # (A captured step keeps its cell; nodes that outlive the capture's side stream cost every later eager backward pass a
+        # stream synchronisation per parameter.)
+        cell = run._cell_ref()
+        if cell is not None and cell._run is run:
+            cell._drop_graph()
         return (None, None, gvq, gwords, gkb) + pgrads
+
+
+def _state_segments(run):
+    """the viewable segments a run's autograd node returns behind the final state (the macx_state_grads fields without `d_`)"""
+    segs = ["controls", "memories", "att_question", "att_kb"]
+    if run.opts.write_self_att:
+        segs.append("att_self")
+    if run.opts.write_gate:
+        segs.append("att_gate")
+    return segs
+
+
+def _state_shapes(run):
+    shapes = run.state_grad_shapes()
+    return [shapes["d_" + seg] for seg in _state_segments(run)]
 
 
 def _begin_and_forward(self):
@@ -269,6 +333,13 @@ class MACCell:
              (zeros) when gradients are taken; their own gradient is exactly 0.  The padded rows are still computed.
     gemm     kernel family of the knowledge-base GEMMs of THIS cell: "h2" | "split" | "native" (None: the process default)
     tune     {key: value} for macx_opts.tune, the per-call A/B hooks (_lib.TUNE; measurement only, never needed for results)
+    Auxiliary losses.  When the run keeps its activations (train / grad enabled), attentions["kb" | "question" | "self" | "gate"][i],
+    controls and memories carry the autograd edge after run() or after the LAST __call__ of the per-step loop, as the reference's
+    graph nodes do: attention supervision, entropy regularisers, per-step heads train the network (macx_cell_backward_x).  In the
+    per-step loop the autograd node exists only after the last step: a tensor fetched before it is a constant, so read them
+    after the loop.  Their incoming gradients must be finite.  infos is a constant.  The captured-graph classes take no such loss.
+    Once the run's backward pass is over the cell publishes plain views again (the finished graph is not kept alive): build the
+    whole loss from tensors fetched BEFORE backward(); with retain_graph=True those keep working, tensors fetched afterwards are constants.
     """
 
     def __new__(cls, *args, config=None, gemm=None, **kw):
@@ -356,15 +427,33 @@ class MACCell:
         srcs = [self._vq_src, self._words_src, self._kb_src] + self.params.tensors()
         return any(t.requires_grad for t in srcs)
 
-    def _views(self):
+    def _views(self, node_outputs=None):
+        """the histories and attention maps as views of the run's `saved`; node_outputs: what the run's autograd node returned behind
+        the final state -- the same views WITH the autograd edge (a loss on them reaches the inputs and the parameters)"""
         run, s = self._run, self._run.shapes
-        self._controls_all = run.segment("controls", (s.p + 1, s.B, s.d))
-        self._memories_all = run.segment("memories", (s.p + 1, s.B, s.d))
+        if node_outputs is not None:
+            out = dict(zip(_state_segments(run), node_outputs))
+        else:
+            out = {seg: run.segment(seg, shape) for seg, shape in zip(_state_segments(run), _state_shapes(run))}
+        self._controls_all = out["controls"]
+        self._memories_all = out["memories"]
         self._infos_all = run.segment("infos", (s.p, s.B, s.d))
-        self._att_q = run.segment("att_question", (s.p, s.B, s.S))
-        self._att_kb = run.segment("att_kb", (s.p, s.B, s.N))
-        self._att_self = run.segment("att_self", (s.p, s.B, s.p)) if self.opts.write_self_att else None
-        self._att_gate = run.segment("att_gate", (s.p, s.B, s.d)) if self.opts.write_gate else None
+        # per step: ONE unbind per map (a single autograd node where the map carries the edge) instead of p slices
+        self._att_q = out["att_question"].unbind(0)
+        self._att_kb = out["att_kb"].unbind(0)
+        self._att_self = out["att_self"].unbind(0) if "att_self" in out else None
+        self._att_gate = out["att_gate"].unbind(0) if "att_gate" in out else None
+
+    def _republish(self):
+        for k in self.attentions:
+            del self.attentions[k][:]
+        for j in range(self._steps_done):
+            self._publish_step(j)
+
+    def _drop_graph(self):
+        """back to plain views of `saved` (same lists, entries replaced): called when the run's backward pass is over"""
+        self._views()
+        self._republish()
 
     # ---- zero_state (mac_cell.py:539-592)
     @property
@@ -386,7 +475,7 @@ class MACCell:
         self.attentions["question"].append(self._att_q[i])
         self.attentions["kb"].append(self._att_kb[i])
         if self._att_self is not None:      # [B, i+1]: initial state + steps 0..i-1 (mac_cell.py:324-329)
-            self.attentions["self"].append(self._att_self[i, :, : i + 1])
+            self.attentions["self"].append(self._att_self[i][:, : i + 1])
         if self._att_gate is not None:
             self.attentions["gate"].append(self._att_gate[i])
 
@@ -401,8 +490,10 @@ class MACCell:
 
     @property
     def infos(self):
+        """[B, steps+1, d].  A CONSTANT on the fused path: no gradient flows from a loss on it (there is no d_infos in the C ABI);
+        controls, memories and the attention maps carry the autograd edge."""
         # the reference seeds `infos` with the initial MEMORY (mac_cell.py:551)
-        return torch.cat([self._memories_all[:1], self._infos_all[: self._steps_done]], dim=0).transpose(0, 1)
+        return torch.cat([self._memories_all[:1].detach(), self._infos_all[: self._steps_done]], dim=0).transpose(0, 1)
 
     # ---- one step (mac_cell.py:420-480)
     def __call__(self, inputs, state, scope=None):
@@ -416,9 +507,13 @@ class MACCell:
         self._publish_step(i)
         control, memory = self._controls_all[i + 1], self._memories_all[i + 1]
         if i == self.netLength - 1 and self._run.keep:
-            # the final state carries the autograd edge of the whole run
-            control, memory = _CellFunction.apply(self._run, "adopt", self._vq_src, self._words_src, self._kb_src,
-                                                  *self.params.tensors())
+            # the final state carries the autograd edge of the whole run, and from here on so do the histories and the attention
+            # maps: the node exists only now, so the entries published by the earlier steps are replaced in place (a tensor FETCHED
+            # before the last step stays a constant)
+            control, memory, *outs = _CellFunction.apply(self._run, "adopt", self._vq_src, self._words_src, self._kb_src,
+                                                         *self.params.tensors())
+            self._views(outs)
+            self._republish()
         return self.none, MACCellTuple(control, memory)
 
     # ---- macx_run_status of the latest run
@@ -443,13 +538,14 @@ class MACCell:
     def run(self):
         self._run = _Run(self, keep_activations=self._needs_grad())
         self.attentions = {"kb": [], "question": [], "self": [], "gate": []}
+        outs = None
         if self._run.keep:
-            control, memory = _CellFunction.apply(self._run, "run", self._vq_src, self._words_src, self._kb_src,
-                                                  *self.params.tensors())
+            control, memory, *outs = _CellFunction.apply(self._run, "run", self._vq_src, self._words_src, self._kb_src,
+                                                         *self.params.tensors())
         else:
             self._run.forward()
             control = memory = None
-        self._views()
+        self._views(outs)
         self._steps_done = self.netLength
         for i in range(self.netLength):
             self._publish_step(i)
@@ -543,7 +639,15 @@ class PaddedMACCell:
 
     none = property(lambda self: self.inner.none)
     iteration = property(lambda self: self.inner.iteration, lambda self, v: setattr(self.inner, "iteration", v))
-    attentions = property(lambda self: self.inner.attentions)
+    @property
+    def attentions(self):
+        """the inner cell's maps.  Without a gate: the inner cell's own dict.  With one, the gate -- the one map as wide as the state --
+        is cropped to the logical width by ordinary slicing (the autograd edge of the inner tensors is kept): then this is a NEW
+        dict with a new gate list on every access, so fetch it once, and do not expect a change made to it to last."""
+        a = self.inner.attentions
+        if not a["gate"]:
+            return a
+        return {k: ([t[..., :self.d] for t in v] if k == "gate" else v) for k, v in a.items()}
 
     @property
     def state_size(self):

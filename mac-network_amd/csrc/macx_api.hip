@@ -1329,6 +1329,9 @@ struct CellBwd : CellRun {
   ChainDkbP dkb_q;
   RowsumBatch rs;               // bias-gradient row sums of this call: one launch at the end of each phase
   SmallWgradBatch wb;           // weight gradients of the [B,d] linears: one launch at the end of phase 1
+  // gradients that arrive at the run's attention maps and step states themselves (macx_cell_backward_x): all null = none, and
+  // then every launch below is the one a plain backward call issues
+  macx_state_grads sg{};
   CellBwd(const macx_opts* o_, const macx_shapes* s_, const macx_dropout* dp_, const macx_params* P_, const macx_inputs* in_,
           const float* saved_, float* ws_, const macx_param_grads* GP_, const macx_input_grads* GI_, void* stream)
       : CellRun(o_, s_, dp_, P_, in_, const_cast<float*>(saved_), 1, stream), ws(ws_), W(make_bwd(o_, s_)), wT(saved_ + L.bwd_packs),
@@ -1368,17 +1371,25 @@ int CellBwd::check_bwd_buffers(size_t saved_floats, size_t ws_floats, int phase)
   return MACX_OK;
 }
 
-// DM / DC: zeros, the incoming gradients in the last slabs
+// DM / DC: zeros (or the gradients a loss sends to the histories themselves, sg.d_memories / sg.d_controls), the incoming
+// gradients of the final state added to the last slabs
 int CellBwd::init_state_grads(const float* d_memory, const float* d_control) {
-  if (DC == DM + (size_t)(p + 1) * Bd && !misaligned(d_memory) && !misaligned(d_control)) {
+  const size_t hist = (size_t)(p + 1) * Bd;
+  if (DC == DM + hist && !misaligned(d_memory) && !misaligned(d_control)) {
     // (adjacent in the workspace: one launch)
-    hipLaunchKernelGGL(bwd_init_kernel, dim3(fill_grid(2 * (size_t)(p + 1) * Bd)), dim3(256), 0, st, DM, Bd, p, d_memory, d_control, 0);
+    hipLaunchKernelGGL(bwd_init_kernel, dim3(fill_grid(2 * hist)), dim3(256), 0, st, DM, Bd, p, d_memory, d_control, 0,
+                       sg.d_memories, sg.d_controls);
     CK(hipGetLastError());
   } else {
-    CK(dev_zero(DM, (size_t)(p + 1) * Bd * sizeof(float), st));
-    CK(dev_zero(DC, (size_t)(p + 1) * Bd * sizeof(float), st));
-    if (d_memory) CK(dev_copy(DM + (size_t)p * Bd, d_memory, Bd * sizeof(float), st));
-    if (d_control) CK(dev_copy(DC + (size_t)p * Bd, d_control, Bd * sizeof(float), st));
+    const float* fin[2] = {d_memory, d_control};
+    const float* his[2] = {sg.d_memories, sg.d_controls};
+    float* dst[2] = {DM, DC};
+    for (int k = 0; k < 2; ++k) {
+      if (his[k]) CK(dev_copy(dst[k], his[k], hist * sizeof(float), st));
+      else CK(dev_zero(dst[k], hist * sizeof(float), st));
+      if (fin[k] && his[k]) CK(axpy(fin[k], Bd, dst[k] + (size_t)p * Bd, st));
+      else if (fin[k]) CK(dev_copy(dst[k] + (size_t)p * Bd, fin[k], Bd * sizeof(float), st));
+    }
   }
   return MACX_OK;
 }
@@ -1420,7 +1431,7 @@ int CellBwd::write_unit_bwd(int i) {
     mnew_out = saved + L.mnew + (size_t)i * Bd;
     float* dzpre = ws + W.dzpre + (size_t)i * Bd;
     hipLaunchKernelGGL(gate_bwd_kernel, dim3(64), dim3(256), 0, st, dm_i, z, mnew_out, memories() + (size_t)i * Bd, Bd,
-                       ws + W.tmpBd[2], ws + W.tmpBd[3], dzpre);
+                       ws + W.tmpBd[2], ws + W.tmpBd[3], dzpre, sg.d_att_gate ? sg.d_att_gate + (size_t)i * Bd : nullptr);
     CK(hipGetLastError());
     dmnew = ws + W.tmpBd[2];
     // dL/dc_i += dzpre Wg^T
@@ -1451,6 +1462,7 @@ int CellBwd::write_unit_bwd(int i) {
     q.dsc = ws + W.dsc + (size_t)i * Bd;
     q.dw_part = ws + W.dws_part + (size_t)i * Bd;
     q.db_part = ws + W.dbs_part + (size_t)i * B;
+    if (sg.d_att_self) q.g_att = sg.d_att_self + (size_t)i * B * p;
     hipLaunchKernelGGL(self_attend_bwd_kernel, dim3(B), dim3(256), 0, st, q);
     CK(hipGetLastError());
   }
@@ -1591,7 +1603,7 @@ int CellBwd::read_bwd_f32(int i) {
 int CellBwd::read_unit_bwd(int i) {
   const int R = B * N;
   hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo.at(i), dinfo.ld, in->knowledgeBase, B, N, d,
-                     ws + W.da);
+                     ws + W.da, sg.d_att_kb ? sg.d_att_kb + (size_t)i * B * N : nullptr);
   CK(hipGetLastError());
   if (!h2) return read_bwd_f32(i);
   const size_t a = (size_t)i * L.act_stride;
@@ -1645,8 +1657,9 @@ int CellBwd::dy_linear_bwd(int i, bool with_write) {
     hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dy_part), (h2 ? SBH_CW / 2 : 2) * d / 128, Bd, DYi);
     CK(hipGetLastError());
   }
-  // with self attention DM[i] already holds the parts later steps sent to this memory: accumulate
-  const bool acc_prev = with_write && (o->write_self_att || o->write_gate);
+  // with self attention DM[i] already holds the parts later steps sent to this memory, with a loss on the memories history the
+  // part that loss sent: accumulate
+  const bool acc_prev = with_write && (o->write_self_att || o->write_gate || sg.d_memories);
   LinP l = lin_basic(DYi, d, d, B, wT + W.wyT, nullptr, d, MACX_ACT_NON, acc_prev ? ws + W.tmpBd[0] : dm_prev, d);
   l.use_drop = 1; l.drop_ld = dlog_of(s);
   l.d1 = o->memory_variational_dropout ? make_drop(dp->keep_memory, dp, SITE_MEM_VAR, 0)
@@ -1686,6 +1699,7 @@ int CellBwd::control_step_bwd(int i) {
   c.dcc = ws + W.dcc + (size_t)i * Bd; c.z_dcc = 0;
   c.dwords = GI->words; c.acc_words = 1;
   c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part + (size_t)i * B;
+  if (sg.d_att_question) c.g_att = sg.d_att_question + (size_t)i * B * S;
   hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, 1), dim3(256), 0, st, c);
   hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
   CK(hipGetLastError());
@@ -1782,6 +1796,7 @@ int CellBwd::control_bwd_tail() {
     c.dcc = ws + W.dcc; c.z_dcc = Bd;
     c.dwords = GI->words; c.acc_words = 0;
     c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part;
+    c.g_att = sg.d_att_question; c.z_g = (size_t)B * S;
     hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, p), dim3(256), 0, st, c);
     hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
     CK(hipGetLastError());
@@ -1972,16 +1987,19 @@ int CellBwd::read_weight_contractions() {
 }
 }  // namespace
 
-int macx_cell_backward_phase(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
-                             const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
-                             const float* d_memory, const float* d_control, const macx_param_grads* GP,
-                             const macx_input_grads* GI, int phase, void* stream) {
+int macx_cell_backward_phase_x(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
+                               const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
+                               const float* d_memory, const float* d_control, const macx_param_grads* GP,
+                               const macx_input_grads* GI, const macx_state_grads* SG, int phase, void* stream) {
   ModeScope ms(o);
   if (phase < 0 || phase > 2) return MACX_EINVAL;
   CKI(check_impl(o, s));
   if (!dp || !P || !in || !saved || !ws || !GP || !GI) return MACX_EINVAL;
   if (!GI->knowledgeBase || !GI->words || !GI->vecQuestions) return MACX_EINVAL;
+  // a gradient for an attention map this option set does not have: refused before anything is launched
+  if (SG && ((SG->d_att_self && !o->write_self_att) || (SG->d_att_gate && !o->write_gate))) return MACX_EINVAL;
   CellBwd r(o, s, dp, P, in, saved, ws, GP, GI, stream);
+  if (SG) r.sg = *SG;
   CKI(r.check_bwd_buffers(saved_floats, ws_floats, phase));
   if (phase != 2) {
     CKI(r.init_state_grads(d_memory, d_control));
@@ -2011,11 +2029,25 @@ int macx_cell_backward_phase(const macx_opts* o, const macx_shapes* s, const mac
   return phase == 1 ? MACX_OK : r.read_weight_contractions();
 }
 
+int macx_cell_backward_phase(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
+                             const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
+                             const float* d_memory, const float* d_control, const macx_param_grads* GP,
+                             const macx_input_grads* GI, int phase, void* stream) {
+  return macx_cell_backward_phase_x(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, d_memory, d_control, GP, GI, nullptr, phase, stream);
+}
+
+int macx_cell_backward_x(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
+                         const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
+                         const float* d_memory, const float* d_control, const macx_param_grads* GP,
+                         const macx_input_grads* GI, const macx_state_grads* SG, void* stream) {
+  return macx_cell_backward_phase_x(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, d_memory, d_control, GP, GI, SG, 0, stream);
+}
+
 int macx_cell_backward(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
                        const macx_inputs* in, const float* saved, size_t saved_floats, float* ws, size_t ws_floats,
                        const float* d_memory, const float* d_control, const macx_param_grads* GP,
                        const macx_input_grads* GI, void* stream) {
-  return macx_cell_backward_phase(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, d_memory, d_control, GP, GI, 0, stream);
+  return macx_cell_backward_x(o, s, dp, P, in, saved, saved_floats, ws, ws_floats, d_memory, d_control, GP, GI, nullptr, stream);
 }
 
 // =================================================================================================

@@ -244,8 +244,10 @@ __global__ void init_states_kernel(int mode_c, const float* __restrict__ prm_c, 
 
 // start of a backward pass: the running gradients DM / DC [p + 1][rows * d] are zero except their last slab, which takes the
 // incoming dL/dm_p / dL/dc_p (null: zero).  One launch instead of a fill and two copies.  DM and DC adjacent
-// (DC == DM + (p + 1) n); `tail` more words after DC are zeroed too.
-__global__ void bwd_init_kernel(float* DM, size_t slab, int p, const float* __restrict__ d_memory, const float* __restrict__ d_control, int tail) {
+// (DC == DM + (p + 1) n); `tail` more words after DC are zeroed too.  g_mem / g_ctrl (macx_state_grads.d_memories / d_controls,
+// [p + 1][slab] each, null: zero): a loss on the histories -- slab i starts from them instead of 0, the last one takes both.
+__global__ void bwd_init_kernel(float* DM, size_t slab, int p, const float* __restrict__ d_memory, const float* __restrict__ d_control, int tail,
+                                const float* __restrict__ g_mem = nullptr, const float* __restrict__ g_ctrl = nullptr) {
   const size_t per = (size_t)(p + 1) * slab, total = 2 * per + (size_t)tail;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     float v = 0.f;
@@ -255,6 +257,8 @@ __global__ void bwd_init_kernel(float* DM, size_t slab, int p, const float* __re
         const float* src = i >= per ? d_control : d_memory;
         if (src) v = src[w - (size_t)p * slab];
       }
+      const float* g = i >= per ? g_ctrl : g_mem;
+      if (g) v += g[w];
     }
     DM[i] = v;
   }
@@ -459,6 +463,7 @@ struct CtrlBwdP {
   int acc_words;                        // recurrent control: steps are differentiated one launch at a time
   float* dw_part;                       // [B][d]      out (sum over steps)
   float* db_part;                       // [nz*B]      out
+  const float* g_att = nullptr; size_t z_g = 0;   // [z][B][S]  dL/d(att) from a loss on the attention itself, or null
 };
 
 __global__ __launch_bounds__(256) void control_bwd_dl_kernel(CtrlBwdP p) {
@@ -469,6 +474,7 @@ __global__ __launch_bounds__(256) void control_bwd_dl_kernel(CtrlBwdP p) {
   const float* words = p.words + (size_t)b * p.S * p.d;
   const float* dc = p.dcontrol + (size_t)z * p.z_dc + (size_t)b * p.d;
   const float* att = p.att + (size_t)z * p.z_att + (size_t)b * p.S;
+  const float* g_att = p.g_att ? p.g_att + (size_t)z * p.z_g + (size_t)b * p.S : nullptr;
   for (int s0 = wave; s0 < p.S; s0 += 4 * CA_U) {       // (CA_U words per batch of loads, as in control_attend_kernel)
     float part[CA_U];
 #pragma unroll
@@ -485,7 +491,7 @@ __global__ __launch_bounds__(256) void control_bwd_dl_kernel(CtrlBwdP p) {
     for (int u = 0; u < CA_U; ++u) {
       const int s = s0 + 4 * u;
       const float t = wave_sum(part[u]);
-      if (lane == 0 && s < p.S) s_da[s] = t;
+      if (lane == 0 && s < p.S) s_da[s] = g_att ? t + g_att[s] : t;
     }
   }
   __syncthreads();
@@ -663,9 +669,11 @@ __global__ __launch_bounds__(KA_THREADS) void kb_attend_kernel(KbAttP p) {
   }
 }
 
-// backward, part 1: da[b][n] = dr[b] . KB[b][n]   (one wave per knowledge-base cell)
+// backward, part 1: da[b][n] = dr[b] . KB[b][n] (+ g[b][n])   (one wave per knowledge-base cell)
+// g_att: dL/d(att) from a loss on the attention itself ([B][N], null: none).  A padded cell (kbLengths) has att == 0, so whatever
+// FINITE value it holds there drops out of the softmax backward of every consumer of `da`.
 __global__ __launch_bounds__(256) void kb_att_da_kernel(const float* __restrict__ dr, int ld_dr, const float* __restrict__ kb,
-                                                        int B, int N, int d, float* da) {
+                                                        int B, int N, int d, float* da, const float* __restrict__ g_att = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t row = (size_t)blockIdx.x * 4 + wave;
   if (row >= (size_t)B * N) return;
@@ -677,7 +685,7 @@ __global__ __launch_bounds__(256) void kb_att_da_kernel(const float* __restrict_
     part += v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3];
   }
   part = wave_sum(part);
-  if (lane == 0) da[row] = part;
+  if (lane == 0) da[row] = g_att ? part + g_att[row] : part;
 }
 
 // backward, part 2: softmax backward + everything elementwise between the logits and I2
@@ -783,12 +791,14 @@ __global__ void gate_mix_kernel(const float* __restrict__ mnew, const float* __r
     out[i] = mnew[i] * z[i] + mprev[i] * (1.0f - z[i]);
 }
 __global__ void gate_bwd_kernel(const float* __restrict__ dm, const float* __restrict__ z, const float* __restrict__ mnew,
-                                const float* __restrict__ mprev, size_t n, float* dmnew, float* dprev, float* dzpre) {
+                                const float* __restrict__ mprev, size_t n, float* dmnew, float* dprev, float* dzpre,
+                                const float* __restrict__ g_z = nullptr) {   // g_z: dL/dz from a loss on the gate itself
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float g = dm[i], zz = z[i];
     dmnew[i] = g * zz;
     dprev[i] = g * (1.0f - zz);
-    dzpre[i] = g * (mnew[i] - mprev[i]) * zz * (1.0f - zz);   // through the sigmoid
+    dzpre[i] = g_z ? (g * (mnew[i] - mprev[i]) + g_z[i]) * zz * (1.0f - zz)
+                   : g * (mnew[i] - mprev[i]) * zz * (1.0f - zz);   // through the sigmoid
   }
 }
 
@@ -851,6 +861,7 @@ struct SelfAttBwdP {
   float* dsc;                      // [B][d]      written
   float* dw_part;                  // [B][d]      written
   float* db_part;                  // [B]         written
+  const float* g_att = nullptr;    // [B][ld_att] dL/d(att) from a loss on the attention itself (entries 0..nh-1), or null
 };
 
 __global__ __launch_bounds__(256) void self_attend_bwd_kernel(SelfAttBwdP p) {
@@ -868,7 +879,10 @@ __global__ __launch_bounds__(256) void self_attend_bwd_kernel(SelfAttBwdP p) {
       part += mv[0] * gv[0] + mv[1] * gv[1] + mv[2] * gv[2] + mv[3] * gv[3];
     }
     part = wave_sum(part);
-    if (lane == 0) { s_dl[j] = part; s_att[j] = p.att[(size_t)b * p.ld_att + j]; }
+    if (lane == 0) {
+      s_dl[j] = p.g_att ? part + p.g_att[(size_t)b * p.ld_att + j] : part;
+      s_att[j] = p.att[(size_t)b * p.ld_att + j];
+    }
   }
   __syncthreads();
   if (tid == 0) {

@@ -46,7 +46,10 @@ class MACNetCore(torch.nn.Module):
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
                 questionWords=None, mask_word=None, image_index=None, check_index=False, kb_lengths=None,
                 check_kb_lengths=False, image_lengths=None):
-        """image_lengths: None, or a [G] integer device tensor for a batch whose questions share images (it needs image_index; passing
+        """Auxiliary losses: after the call `self.last_cell` is the cell of this pass.  Its attentions["kb" | "question" | "self" |
+        "gate"][i], controls and memories carry the autograd edge (train / grad enabled), so a loss such as
+        CE + lam * (net.last_cell.attentions["kb"][i] * target).sum() trains the stem, the encoder and the cell; infos is a constant.
+        image_lengths: None, or a [G] integer device tensor for a batch whose questions share images (it needs image_index; passing
         kb_lengths as well is a ValueError): image g's knowledge base is the first image_lengths[g] of the stem's N cells.  The gather
         (macx_kb_gather_l) writes +0 into every question's padded rows, whatever the stem computed there, and makes the per-question
         kb_lengths the cell receives on the device: nothing is indexed on the host, so a captured graph follows rewritten lengths.
