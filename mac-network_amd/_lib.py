@@ -6,6 +6,8 @@ module raises, and every op built on it fails loudly.
 import ctypes as C
 import os
 
+import torch
+
 from . import build as _build
 
 ABI_VERSION = 5
@@ -140,26 +142,165 @@ class MacxStateGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in STATE_GRAD_FIELDS]
 
 
-EXPORTS = ("macx_abi_version", "macx_strerror", "macx_check", "macx_saved_floats", "macx_ws_floats",
-           "macx_saved_segment", "macx_cell_begin", "macx_cell_step", "macx_cell_forward", "macx_cell_backward",
-           "macx_cell_backward_phase",
-           "macx_linear", "macx_pack_weight", "macx_kb_project", "macx_control_attend", "macx_dropout_mask", "macx_dropout_mask_w", "macx_wgrad_splits",
-           "macx_wgrad", "macx_output_saved_floats", "macx_output_ws_floats",
-           "macx_output_forward", "macx_output_backward", "macx_adam_ema_step",
-           "macx_stem_saved_floats", "macx_stem_ws_floats", "macx_stem_forward", "macx_stem_backward",
-           "macx_encoder_saved_floats", "macx_encoder_ws_floats", "macx_encoder_forward", "macx_encoder_backward",
-           "macx_images_to_nhwc", "macx_gemm_mode", "macx_h2_floats", "macx_h2_from_f32", "macx_h2_to_f32", "macx_h2_gemm",
-           "macx_h2_pack_weight", "macx_h2_gemm_planes", "macx_op_act", "macx_op_act_bwd", "macx_op_binary", "macx_op_reduce",
-           "macx_op_softmax", "macx_op_softmax_bwd", "macx_op_dropout", "macx_op_dropout_w", "macx_kb_attend_fwd", "macx_kb_attend_fwd_l", "macx_kb_attend_bwd",
-           "macx_kb_attend_bwd_ws_floats", "macx_answer_loss", "macx_workspace_bytes", "macx_embed_lookup", "macx_embed_lookup_bwd", "macx_control_attend_bwd",
-           "macx_control_attend_bwd_ws_floats", "macx_read_fwd", "macx_read_bwd",
-           "macx_write_fwd", "macx_write_bwd", "macx_read_chain_time", "macx_cell_forward_chain_time", "macx_saved_activation", "macx_ctrl_inputs_ws_floats",
-           "macx_ctrl_inputs_fwd", "macx_ctrl_inputs_bwd", "macx_conv2d_ws_floats", "macx_conv2d_fwd", "macx_conv2d_bwd_data",
-           "macx_conv2d_wgrad", "macx_run_status", "macx_run_status_reset", "macx_handoff_selftest",
-           "macx_encoder_forward_w", "macx_encoder_backward_w", "macx_stem_forward_w", "macx_stem_backward_w",
-           "macx_output_forward_w", "macx_output_backward_w", "macx_adam_ema_step_p", "macx_gather_flat",
-           "macx_kb_gather", "macx_kb_gather_bwd", "macx_kb_gather_l", "macx_kb_gather_bwd_l", "macx_read_fwd_l",
-           "macx_cell_backward_x", "macx_cell_backward_phase_x")
+# ---------------------------------------------------------------------------------------------------------------------------
+# The binding: export -> (restype, argtypes), in the order and under the section titles of include/macx.h.  This table is the ONE
+# place an export is declared on the Python side; lib() applies it and nothing else sets a restype or argtypes.  It is plain data
+# (importable without libmacx.so), and tests/test_abi_host.py holds it to the header: every prototype's arity and every
+# parameter's class (pointer | int | uint32 | size_t | float), every struct's size and field offsets.
+# A pointer is POINTER(Struct) where callers pass byref(struct) / None, c_void_p where they pass addresses (tensor.data_ptr()).
+# ---------------------------------------------------------------------------------------------------------------------------
+_P = C.POINTER
+_I, _U, _Z, _F, _V = C.c_int, C.c_uint32, C.c_size_t, C.c_float, C.c_void_p
+
+
+def _masked(sig):
+    """the `_w` twin of an entry point: the plain signature + the device mask word in front of the stream"""
+    restype, a = sig
+    return restype, a[:-1] + (_V, a[-1])
+
+
+_OS = (_P(MacxOpts), _P(MacxShapes))
+# what every call on a cell run starts with: opts, shapes, dropout, params, inputs, saved, saved_floats, ws, ws_floats
+_RUN = _OS + (_P(MacxDropout), _P(MacxParams), _P(MacxInputs), _V, _Z, _V, _Z)
+# ... and a backward call goes on with: d_memory, d_control, parameter gradients, input gradients
+_BWD = _RUN + (_V, _V, _P(MacxParamGrads), _P(MacxInputGrads))
+# a single unit (read / write) starts with: opts, shapes, dropout, params
+_UNIT = _OS + (_P(MacxDropout), _P(MacxParams))
+_STEM = (_P(MacxStemShapes), _I, _F, _U, _P(MacxStemParams))        # shapes, act, keep, seed, params
+_OUT = (_P(MacxOutShapes), _I, _F, _U, _P(MacxOutParams))
+_ENC = (_P(MacxEncShapes), _F, _F, _U, _P(MacxEncParams))           # shapes, keep_input, keep_question, seed, params
+_GATHER = (_V, _V, _I, _I, _I, _I, _V, _V)                          # source, index, G, B, N, d, destination, stream
+
+TABLE = {}
+# ---- sizing
+TABLE.update(
+    macx_saved_floats=(_Z, _OS + (_I,)),
+    macx_ws_floats=(_Z, _OS + (_I,)),
+    macx_saved_segment=(_I, _OS + (_I, _I, _P(_Z), _P(_Z))),
+    macx_check=(_I, _OS))
+# ---- did the run's in-launch hand-offs complete?
+TABLE.update(
+    macx_run_status=(_I, _OS + (_I, _V, _Z, _V, _P(_U), _P(C.c_int32))),
+    macx_run_status_reset=(_I, _OS + (_I, _V, _Z, _V)),
+    macx_handoff_selftest=(_I, (_V, _P(_U))))
+# ---- the cell
+TABLE.update(
+    macx_cell_begin=(_I, _RUN + (_I, _V)),
+    macx_cell_step=(_I, _RUN + (_I, _I, _V)),
+    macx_cell_forward=(_I, _RUN + (_I, _V)),
+    macx_cell_backward=(_I, _BWD + (_V,)),
+    macx_cell_backward_phase=(_I, _BWD + (_I, _V)),
+    # (... + macx_state_grads* behind the input gradients; NULL = the plain call)
+    macx_cell_backward_x=(_I, _BWD + (_P(MacxStateGrads), _V)),
+    macx_cell_backward_phase_x=(_I, _BWD + (_P(MacxStateGrads), _I, _V)))
+# ---- output unit + classifier
+TABLE.update(
+    macx_output_saved_floats=(_Z, (_P(MacxOutShapes),)),
+    macx_output_ws_floats=(_Z, (_P(MacxOutShapes),)),
+    macx_output_forward=(_I, _OUT + (_V, _V, _V, _V, _Z, _V)),
+    macx_output_backward=(_I, _OUT + (_V, _V, _V, _Z, _V, _Z, _V, _P(MacxOutGrads), _V, _V, _V)))
+TABLE.update(macx_output_forward_w=_masked(TABLE["macx_output_forward"]),
+             macx_output_backward_w=_masked(TABLE["macx_output_backward"]))
+# ---- stem CNN
+TABLE.update(
+    macx_stem_saved_floats=(_Z, (_P(MacxStemShapes),)),
+    macx_stem_ws_floats=(_Z, (_P(MacxStemShapes),)),
+    macx_stem_forward=(_I, _STEM + (_V, _V, _V, _Z, _V)),
+    macx_stem_backward=(_I, _STEM + (_V, _V, _Z, _V, _Z, _V, _P(MacxStemGrads), _V)))
+TABLE.update(macx_stem_forward_w=_masked(TABLE["macx_stem_forward"]),
+             macx_stem_backward_w=_masked(TABLE["macx_stem_backward"]))
+# ---- general convolution
+TABLE.update(
+    macx_conv2d_ws_floats=(_Z, (_P(MacxConvShapes),)),
+    macx_conv2d_fwd=(_I, (_P(MacxConvShapes), _V, _V, _V, _V, _V)),
+    macx_conv2d_bwd_data=(_I, (_P(MacxConvShapes), _V, _V, _V, _V)),
+    macx_conv2d_wgrad=(_I, (_P(MacxConvShapes), _V, _V, _V, _V, _Z, _V)),
+    macx_images_to_nhwc=(_I, (_V, _I, _I, _I, _V, _V)))
+# ---- question encoder
+TABLE.update(
+    macx_encoder_saved_floats=(_Z, (_P(MacxEncShapes),)),
+    macx_encoder_ws_floats=(_Z, (_P(MacxEncShapes),)),
+    macx_encoder_forward=(_I, _ENC + (_V, _V, _V, _V, _V, _Z, _V)),
+    macx_encoder_backward=(_I, _ENC + (_V, _V, _V, _Z, _V, _Z, _V, _V, _P(MacxEncGrads), _V)))
+TABLE.update(macx_encoder_forward_w=_masked(TABLE["macx_encoder_forward"]),
+             macx_encoder_backward_w=_masked(TABLE["macx_encoder_backward"]))
+# ---- optimizer step
+TABLE.update(
+    macx_adam_ema_step=(_I, (_Z, _V, _V, _V, _V, _V, _F, _F, _F, _F, _I, _F, _F, _V, _V, _V)),
+    # (the rate in device memory instead of lr and step)
+    macx_adam_ema_step_p=(_I, (_Z, _V, _V, _V, _V, _V, _V, _F, _F, _F, _F, _F, _V, _V, _V)))
+# ---- flat gather
+TABLE.update(macx_gather_flat=(_I, (_V, _I, _V, _V)))             # (the table of MacxGatherEntry rows lives in device memory)
+# ---- questions that share images
+TABLE.update(
+    macx_kb_gather=(_I, _GATHER),
+    macx_kb_gather_bwd=(_I, _GATHER),
+    # (the sizes per image, [G] int32 or NULL, behind the index; the forward call also writes kb_lengths_out [B] in front of the stream)
+    macx_kb_gather_l=(_I, _GATHER[:2] + (_V,) + _GATHER[2:-1] + (_V, _GATHER[-1])),
+    macx_kb_gather_bwd_l=(_I, _GATHER[:2] + (_V,) + _GATHER[2:]))
+# ---- unit-level entry points
+TABLE.update(
+    macx_linear=(_I, (_V, _I, _V, _I, _I, _V, _V, _F, _I, _I, _V, _V)),
+    macx_pack_weight=(_I, (_V, _I, _I, _I, _V, _V)),
+    macx_gemm_mode=(_I, (_I,)))
+# ---- the H2 tensor format
+TABLE.update(
+    macx_h2_floats=(_Z, (_Z, _Z)),
+    macx_h2_from_f32=(_I, (_V, _I, _I, _I, _V, _V)),
+    macx_h2_to_f32=(_I, (_V, _I, _I, _V, _V)),
+    macx_h2_pack_weight=(_I, (_V, _I, _I, _I, _V, _V)),
+    macx_h2_gemm_planes=(_I, (_V, _I, _I, _I, _V, _I, _V, _I, _V, _V)),
+    macx_h2_gemm=(_I, (_V, _I, _I, _I, _V, _I, _V, _I, _V, _V, _Z, _V)),
+    macx_read_chain_time=(_I, _RUN[:7] + (_I, _I, _P(_F), _V)),
+    macx_cell_forward_chain_time=(_I, _RUN + (_P(_F), _V)),
+    macx_saved_activation=(_I, _OS + (_I, _I, _V, _Z, _V, _V)),
+    macx_ctrl_inputs_ws_floats=(_Z, _OS),
+    macx_ctrl_inputs_fwd=(_I, _OS + (_P(MacxParams), _V, _V, _V, _V, _Z, _V)),
+    macx_ctrl_inputs_bwd=(_I, _OS + (_P(MacxParams), _V, _V, _V, _P(MacxParamGrads), _V, _V, _Z, _V)),
+    macx_kb_project=(_I, (_P(MacxShapes), _P(MacxDropout), _I, _V, _V, _V, _V, _V, _V)),
+    macx_control_attend=(_I, (_P(MacxShapes),) + (_V,) * 8),
+    macx_control_attend_bwd_ws_floats=(_Z, (_P(MacxShapes),)),
+    macx_control_attend_bwd=(_I, (_P(MacxShapes),) + (_V,) * 6 + (_Z,) + (_V,) * 5),
+    macx_dropout_mask=(_I, (_U, _U, _U, _F, _U, _Z, _V, _V)),
+    macx_dropout_mask_w=(_I, (_U, _U, _U, _F, _U, _Z, _V, _V, _V)),          # (the word in front of `out`)
+    macx_wgrad_splits=(_I, (_I, _I, _I)),
+    macx_wgrad=(_I, (_V, _I, _V, _I, _I, _I, _I, _V, _V, _V)))
+# ---- answer loss and prediction
+TABLE.update(macx_answer_loss=(_I, (_V, _V, _I, _I, _V, _V, _V, _F, _V)))
+# ---- the knowledge-base attention unit on its own
+TABLE.update(
+    macx_kb_attend_fwd=(_I, (_I, _I, _I) + (_V,) * 6),
+    macx_kb_attend_fwd_l=(_I, (_I, _I, _I) + (_V,) * 7),                       # (+ kb_lengths behind kb)
+    macx_kb_attend_bwd_ws_floats=(_Z, (_I, _I, _I)),
+    macx_kb_attend_bwd=(_I, (_I, _I, _I) + (_V,) * 5 + (_I, _V, _Z, _V)))
+# ---- the read unit and the write unit as wholes
+TABLE.update(
+    macx_workspace_bytes=(_Z, _OS + (_I,)),
+    macx_read_fwd=(_I, _UNIT + (_V, _V, _V, _V, _Z, _V, _V, _V)),
+    macx_read_fwd_l=(_I, _UNIT + (_V, _V, _V, _V, _V, _Z, _V, _V, _V)),      # (+ kb_lengths behind knowledgeBase)
+    macx_read_bwd=(_I, _UNIT + (_V, _V, _Z, _V, _Z, _V, _P(MacxParamGrads), _V, _V, _V, _V)),
+    macx_write_fwd=(_I, _UNIT + (_V, _V, _V, _V, _Z, _V, _V)),
+    macx_write_bwd=(_I, _UNIT + (_V, _Z, _V, _Z, _V, _P(MacxParamGrads), _V, _V, _V, _V)))
+# ---- embedding lookup on its own
+TABLE.update(
+    macx_embed_lookup=(_I, (_V, _V, _I, _I, _I, _F, _U, _U, _V, _V)),
+    macx_embed_lookup_bwd=(_I, (_V, _V, _I, _I, _I, _I, _F, _U, _U, _V, _V)))
+# ---- the ops.py primitives as single kernels
+TABLE.update(
+    macx_op_act=(_I, (_I, _V, _V, _Z, _I, _V, _V)),
+    macx_op_act_bwd=(_I, (_I, _V, _V, _V, _Z, _I, _V, _V, _V)),
+    macx_op_binary=(_I, (_I, _I, _V, _V, _Z, _I, _I, _F, _V, _V)),
+    macx_op_reduce=(_I, (_I, _V, _Z, _I, _I, _V, _V, _V)),
+    macx_op_softmax=(_I, (_V, _V, _I, _Z, _I, _V, _V)),
+    macx_op_softmax_bwd=(_I, (_V, _V, _Z, _I, _V, _V)),
+    macx_op_dropout=(_I, (_V, _Z, _U, _U, _U, _F, _U, _V, _V)),
+    macx_op_dropout_w=(_I, (_V, _Z, _U, _U, _U, _F, _U, _V, _V, _V)))         # (the word in front of `out`)
+# ---- (the header's tail)
+TABLE.update(
+    macx_strerror=(C.c_char_p, (_I,)),
+    macx_abi_version=(_I, ()))
+
+EXPORTS = tuple(TABLE)
 
 _lib = None
 
@@ -195,150 +336,23 @@ def lib():
     missing = [n for n in EXPORTS if not hasattr(L, n)]
     if missing:
         raise ImportError("libmacx.so lacks symbols: %s" % missing)
-    L.macx_abi_version.restype = C.c_int
     if L.macx_abi_version() != ABI_VERSION:
         raise ImportError("libmacx.so ABI %d != binding ABI %d" % (L.macx_abi_version(), ABI_VERSION))
-    L.macx_strerror.restype = C.c_char_p
-    L.macx_strerror.argtypes = [C.c_int]
-    P = C.POINTER
-    L.macx_check.argtypes = [P(MacxOpts), P(MacxShapes)]
-    L.macx_saved_floats.restype = C.c_size_t
-    L.macx_saved_floats.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int]
-    L.macx_ws_floats.restype = C.c_size_t
-    L.macx_ws_floats.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int]
-    L.macx_saved_segment.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_int, P(C.c_size_t), P(C.c_size_t)]
-    common = [P(MacxOpts), P(MacxShapes), P(MacxDropout), P(MacxParams), P(MacxInputs), C.c_void_p, C.c_size_t,
-              C.c_void_p, C.c_size_t]
-    L.macx_cell_begin.argtypes = common + [C.c_int, C.c_void_p]
-    L.macx_cell_step.argtypes = common + [C.c_int, C.c_int, C.c_void_p]
-    L.macx_cell_forward.argtypes = common + [C.c_int, C.c_void_p]
-    L.macx_cell_backward.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), C.c_void_p]
-    L.macx_cell_backward_phase.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), C.c_int, C.c_void_p]
-    # (... + macx_state_grads* behind the input gradients; NULL = the plain call)
-    L.macx_cell_backward_x.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), P(MacxStateGrads), C.c_void_p]
-    L.macx_cell_backward_phase_x.argtypes = common + [C.c_void_p, C.c_void_p, P(MacxParamGrads), P(MacxInputGrads), P(MacxStateGrads),
-                                                      C.c_int, C.c_void_p]
-    L.macx_linear.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                              C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_pack_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_kb_project.argtypes = [P(MacxShapes), P(MacxDropout), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]
-    L.macx_control_attend.argtypes = [P(MacxShapes)] + [C.c_void_p] * 8
-    L.macx_dropout_mask.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_size_t, C.c_void_p,
-                                    C.c_void_p]
-    L.macx_dropout_mask_w.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-    L.macx_read_chain_time.argtypes = [P(MacxOpts), P(MacxShapes), P(MacxDropout), P(MacxParams), P(MacxInputs), C.c_void_p, C.c_size_t,
-                                       C.c_int, C.c_int, P(C.c_float), C.c_void_p]
-    L.macx_cell_forward_chain_time.argtypes = common + [P(C.c_float), C.c_void_p]
-    L.macx_saved_activation.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.macx_ctrl_inputs_ws_floats.restype = C.c_size_t
-    L.macx_ctrl_inputs_ws_floats.argtypes = [P(MacxOpts), P(MacxShapes)]
-    L.macx_ctrl_inputs_fwd.argtypes = [P(MacxOpts), P(MacxShapes), P(MacxParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                       C.c_void_p]
-    L.macx_ctrl_inputs_bwd.argtypes = [P(MacxOpts), P(MacxShapes), P(MacxParams), C.c_void_p, C.c_void_p, C.c_void_p, P(MacxParamGrads),
-                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_gemm_mode.argtypes = [C.c_int]
-    L.macx_adam_ema_step.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                     C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_adam_ema_step.restype = C.c_int
-    L.macx_stem_saved_floats.restype = C.c_size_t
-    L.macx_stem_saved_floats.argtypes = [P(MacxStemShapes)]
-    L.macx_stem_ws_floats.restype = C.c_size_t
-    L.macx_stem_ws_floats.argtypes = [P(MacxStemShapes)]
-    L.macx_stem_forward.restype = C.c_int
-    L.macx_stem_forward.argtypes = [P(MacxStemShapes), C.c_int, C.c_float, C.c_uint32, P(MacxStemParams), C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_stem_backward.restype = C.c_int
-    L.macx_stem_backward.argtypes = [P(MacxStemShapes), C.c_int, C.c_float, C.c_uint32, P(MacxStemParams), C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, P(MacxStemGrads), C.c_void_p]
-    L.macx_output_saved_floats.restype = C.c_size_t
-    L.macx_output_saved_floats.argtypes = [P(MacxOutShapes)]
-    L.macx_output_ws_floats.restype = C.c_size_t
-    L.macx_output_ws_floats.argtypes = [P(MacxOutShapes)]
-    L.macx_output_forward.argtypes = [P(MacxOutShapes), C.c_int, C.c_float, C.c_uint32, P(MacxOutParams), C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_output_backward.argtypes = [P(MacxOutShapes), C.c_int, C.c_float, C.c_uint32, P(MacxOutParams), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, P(MacxOutGrads), C.c_void_p,
-                                       C.c_void_p, C.c_void_p]
-    L.macx_wgrad_splits.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.macx_wgrad.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                             C.c_void_p]
-    for n in EXPORTS:
+    for n, (restype, argtypes) in TABLE.items():
         f = getattr(L, n)
-        if f.restype is C.c_int or n in ("macx_check",):
-            f.restype = C.c_int
-    L.macx_run_status.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_uint32), P(C.c_int32)]
-    L.macx_run_status_reset.argtypes = [P(MacxOpts), P(MacxShapes), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_handoff_selftest.argtypes = [C.c_void_p, P(C.c_uint32)]
-    L.macx_conv2d_ws_floats.argtypes = [P(MacxConvShapes)]
-    L.macx_conv2d_fwd.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_conv2d_bwd_data.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_conv2d_wgrad.argtypes = [P(MacxConvShapes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_images_to_nhwc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_encoder_saved_floats.argtypes = [P(MacxEncShapes)]
-    L.macx_encoder_ws_floats.argtypes = [P(MacxEncShapes)]
-    L.macx_encoder_forward.argtypes = [P(MacxEncShapes), C.c_float, C.c_float, C.c_uint32, P(MacxEncParams), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_encoder_backward.argtypes = [P(MacxEncShapes), C.c_float, C.c_float, C.c_uint32, P(MacxEncParams), C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(MacxEncGrads),
-                                        C.c_void_p]
-    L.macx_h2_floats.argtypes = [C.c_size_t, C.c_size_t]
-    L.macx_h2_from_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_h2_to_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_h2_pack_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_h2_gemm_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_h2_gemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                               C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_answer_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-    P_, V_ = C.c_void_p, C.c_void_p
-    L.macx_embed_lookup.argtypes = [V_, V_, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_uint32, V_, V_]
-    L.macx_embed_lookup_bwd.argtypes = [V_, V_, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_uint32, V_, V_]
-    L.macx_control_attend_bwd_ws_floats.restype = C.c_size_t
-    L.macx_control_attend_bwd_ws_floats.argtypes = [P_]
-    L.macx_control_attend_bwd.argtypes = [P_] + [V_] * 6 + [C.c_size_t] + [V_] * 5
-    L.macx_workspace_bytes.restype = C.c_size_t
-    L.macx_workspace_bytes.argtypes = [P_, P_, C.c_int]
-    L.macx_read_fwd.argtypes = [P_] * 4 + [V_] * 3 + [V_, C.c_size_t, V_, V_, V_]
-    L.macx_read_fwd_l.argtypes = [P_] * 4 + [V_] * 4 + [V_, C.c_size_t, V_, V_, V_]          # (+ kb_lengths behind knowledgeBase)
-    L.macx_read_bwd.argtypes = [P_] * 4 + [V_, V_, C.c_size_t, V_, C.c_size_t, V_, P_, V_, V_, V_, V_]
-    L.macx_write_fwd.argtypes = [P_] * 4 + [V_] * 3 + [V_, C.c_size_t, V_, V_]
-    L.macx_write_bwd.argtypes = [P_] * 4 + [V_, C.c_size_t, V_, C.c_size_t, V_, P_, V_, V_, V_, V_]
-    L.macx_kb_attend_fwd.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
-    L.macx_kb_attend_fwd_l.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
-    L.macx_kb_attend_bwd_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.macx_kb_attend_bwd.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.macx_op_act.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_op_act_bwd.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_op_binary.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    L.macx_op_reduce.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_op_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_op_softmax_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_op_dropout.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
-                                  C.c_void_p]
-    L.macx_op_dropout_w.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-    # the entry points under a run's mask word: the plain signature + the device word in front of the stream
-    for n in ("macx_encoder_forward", "macx_encoder_backward", "macx_stem_forward", "macx_stem_backward", "macx_output_forward",
-              "macx_output_backward"):
-        a = getattr(L, n).argtypes
-        getattr(L, n + "_w").argtypes = list(a[:-1]) + [C.c_void_p, a[-1]]
-    L.macx_adam_ema_step_p.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.macx_gather_flat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    # (block source, index [B] int32, G, B, N, d, destination, stream): forward images -> questions, backward questions -> images
-    L.macx_kb_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.macx_kb_gather_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    # (..., index, lengths [G] int32 or NULL, G, B, N, d, destination, [kb_lengths_out [B] int32,] stream)
-    L.macx_kb_gather_l.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3
-    L.macx_kb_gather_bwd_l.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2
-    for n in EXPORTS:
-        if n.endswith("_floats"):
-            getattr(L, n).restype = C.c_size_t
-        elif n not in ("macx_strerror",):
-            getattr(L, n).restype = C.c_int
+        f.restype, f.argtypes = restype, list(argtypes)
     _lib = L
     return L
+
+
+def ptr(t):
+    """a tensor's device address as a ctypes argument; None -> NULL"""
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def stream_of(where):
+    """torch's CURRENT stream on a tensor's device (or on a device) as a ctypes argument -- read it where the call is made"""
+    return C.c_void_p(torch.cuda.current_stream(getattr(where, "device", where)).cuda_stream)
 
 
 def check(code, where):

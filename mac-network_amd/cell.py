@@ -30,10 +30,6 @@ from .params import MACCellParams
 MACCellTuple = collections.namedtuple("MACCellTuple", ("control", "memory"))   # mac_cell.py:8
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def _f32c(t, name):
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32" % name)
@@ -106,7 +102,7 @@ class _Run:
                                       knowledgeBase=cell.knowledgeBase.data_ptr(),
                                       kbLengths=cell.kb_lengths.data_ptr() if cell.kb_lengths is not None else None)
         self.kb_lengths = cell.kb_lengths          # held here: the backward pass of this run may outlive the cell
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self.stream = _lib.stream_of(dev)
         # the hand-off status words of `saved` are sticky (macx_run_status): zero them once, here.  Not inside a graph capture -- the
         # status must survive replays -- so a run allocated under capture is reset by its capturer afterwards (graph.py)
         self.status_reset_pending = torch.cuda.is_current_stream_capturing()
@@ -114,11 +110,11 @@ class _Run:
             self.reset_status()
 
     def _status_args(self):
-        return (C.byref(self.opts), C.byref(self.shapes), self.keep, _ptr(self.saved), C.c_size_t(self.saved_floats))
+        return (C.byref(self.opts), C.byref(self.shapes), self.keep, _lib.ptr(self.saved), C.c_size_t(self.saved_floats))
 
     def reset_status(self):
         """zero the run's hand-off status words: asynchronous, on torch's current stream (the run's own when it is allocated)"""
-        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        stream = _lib.stream_of(self.saved)
         _lib.check(self.L.macx_run_status_reset(*self._status_args(), stream), "macx_run_status_reset")
         self.status_reset_pending = False
 
@@ -126,7 +122,7 @@ class _Run:
         """(bits, first_step) of macx_run_status: (0, -1) when every in-launch hand-off of the runs on this buffer completed.
         Synchronises torch's current stream."""
         bits, first = C.c_uint32(0), C.c_int32(-1)
-        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        stream = _lib.stream_of(self.saved)
         rc = self.L.macx_run_status(*self._status_args(), stream, C.byref(bits), C.byref(first))
         if rc not in (_lib.MACX_OK, _lib.MACX_EWAIT):
             raise _lib.MacxError(rc, "macx_run_status")
@@ -139,7 +135,7 @@ class _Run:
 
     def _common(self):
         return (C.byref(self.opts), C.byref(self.shapes), C.byref(self.drop), C.byref(self.pstruct), C.byref(self.inputs),
-                _ptr(self.saved), C.c_size_t(self.saved_floats), _ptr(self.ws_fwd), C.c_size_t(self.ws_fwd.numel()))
+                _lib.ptr(self.saved), C.c_size_t(self.saved_floats), _lib.ptr(self.ws_fwd), C.c_size_t(self.ws_fwd.numel()))
 
     def begin(self):
         _lib.check(self.L.macx_cell_begin(*self._common(), self.keep, self.stream), "macx_cell_begin")
@@ -232,18 +228,18 @@ class _Run:
         dm = _f32c(d_memory, "d_memory") if d_memory is not None else None
         dc = _f32c(d_control, "d_control") if d_control is not None else None
         args = (C.byref(self.opts), C.byref(self.shapes), C.byref(self.drop), C.byref(self.pstruct), C.byref(self.inputs),
-                _ptr(self.saved), C.c_size_t(self.saved_floats), _ptr(ws), C.c_size_t(ws_floats), _ptr(dm), _ptr(dc),
+                _lib.ptr(self.saved), C.c_size_t(self.saved_floats), _lib.ptr(ws), C.c_size_t(ws_floats), _lib.ptr(dm), _lib.ptr(dc),
                 C.byref(gstruct), C.byref(gistruct), C.byref(sg) if sg is not None else None)
         return args, grads, (gi_vq, gi_words, gi_kb), flat, (ws, gstruct, gistruct, dm, dc, sg, sg_held)
 
     def backward_phase(self, args, phase):
         """macx_cell_backward_phase_x on torch's CURRENT stream (1: everything but the read unit's deferred contractions, 2: those)"""
-        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        stream = _lib.stream_of(self.saved)
         _lib.check(self.L.macx_cell_backward_phase_x(*args, int(phase), stream), "macx_cell_backward_phase_x(%d)" % phase)
 
     def backward(self, d_control, d_memory, state_grads=None):
         args, grads, (gi_vq, gi_words, gi_kb), flat, _keep = self.backward_begin(d_control, d_memory, state_grads)
-        stream = C.c_void_p(torch.cuda.current_stream(self.saved.device).cuda_stream)
+        stream = _lib.stream_of(self.saved)
         hook = getattr(self.params, "after_backward_phase1", None)
         if hook is not None and flat is getattr(self.params, "_grad_flat", None):
             # every gradient except the read unit's big contractions is final: let the data-parallel layer start on it
@@ -262,7 +258,7 @@ class _CellFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, run, mode, vecQ, words, kb, *params):
         if mode == "run":
-            run.begin_and_forward()
+            run.forward()
         ctx.run = run
         # an output nobody differentiates (the final control, when only the memory feeds the classifier) arrives as None instead of a
         # freshly filled zeros tensor: one fill and one copy launch less per step -- macx_cell_backward takes NULL for it
@@ -305,13 +301,6 @@ def _state_segments(run):
 def _state_shapes(run):
     shapes = run.state_grad_shapes()
     return [shapes["d_" + seg] for seg in _state_segments(run)]
-
-
-def _begin_and_forward(self):
-    self.forward()
-
-
-_Run.begin_and_forward = _begin_and_forward
 
 
 class MACCell:

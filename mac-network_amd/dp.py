@@ -8,7 +8,6 @@ gradient buffer (cell only: 2.1 M + p * 0.26 M parameters = 21 MB at p = 12).  E
 the MEAN loss over its shard (model.py:596); shard gradients are combined weighted by shard size so
 that the result equals the full-batch gradient.
 """
-import ctypes as C
 
 import torch
 import torch.distributed as dist
@@ -302,8 +301,7 @@ class TowerBuckets:
                 table = torch.tensor(flatrows, dtype=torch.int64).to(self.flat.device)
                 self._tables[(lo, hi)] = [flatrows, table]
             table = self._tables[(lo, hi)][1]
-        st = C.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
-        _lib.check(_lib.lib().macx_gather_flat(C.c_void_p(table.data_ptr()), len(rows), C.c_void_p(base), st), "macx_gather_flat")
+        _lib.check(_lib.lib().macx_gather_flat(_lib.ptr(table), len(rows), base, _lib.stream_of(self.flat)), "macx_gather_flat")
 
     def reserve_tables(self, k):
         """k more spare device tables for gathers issued under a capture; call it outside any capture"""

@@ -25,7 +25,7 @@ REF_NAMES = {"emb": "qEmbeddings/emb",
 class _EncoderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, keep_in, keep_q, seed, b0, word, questions, lengths, *params):
-        # word: None (macx_encoder_forward / _backward) or the run's mask word, a 1-element int32 device tensor (the _w entry points)
+        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_encoder_forward / _backward pass on
         L = _lib.lib()
         B, S = questions.shape
         sh = _lib.MacxEncShapes(B=B, S=S, V=mod.vocab, E=mod.E, h=mod.h, b0=b0)
@@ -37,13 +37,9 @@ class _EncoderFunction(torch.autograd.Function):
         words = torch.empty(B, S, 2 * mod.h, dtype=torch.float32, device=dev)
         vecQ = torch.empty(B, 2 * mod.h, dtype=torch.float32, device=dev)
         ps = _lib.MacxEncParams(*[p.data_ptr() for p in params])
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        args = (C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(), words.data_ptr(),
-                vecQ.data_ptr(), saved.data_ptr(), n_saved)
-        if word is None:
-            _lib.check(L.macx_encoder_forward(*args, st), "macx_encoder_forward")
-        else:
-            _lib.check(L.macx_encoder_forward_w(*args, word.data_ptr(), st), "macx_encoder_forward_w")
+        _lib.check(L.macx_encoder_forward_w(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(),
+                                            words.data_ptr(), vecQ.data_ptr(), saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(dev)),
+                   "macx_encoder_forward_w")
         ctx.stuff = (mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params, word)
         if torch.cuda.is_current_stream_capturing():
             # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
@@ -63,13 +59,10 @@ class _EncoderFunction(torch.autograd.Function):
         ps = _lib.MacxEncParams(*[p.data_ptr() for p in params])
         d_words = saved.new_zeros((sh.B, sh.S, 2 * sh.h)) if d_words is None else d_words.contiguous()
         d_vecQ = saved.new_zeros((sh.B, 2 * sh.h)) if d_vecQ is None else d_vecQ.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        args = (C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(), saved.data_ptr(),
-                n_saved, ws.data_ptr(), n_ws, d_words.data_ptr(), d_vecQ.data_ptr(), C.byref(gs))
-        if word is None:
-            _lib.check(L.macx_encoder_backward(*args, st), "macx_encoder_backward")
-        else:                                   # the word the forward pass hashed with
-            _lib.check(L.macx_encoder_backward_w(*args, word.data_ptr(), st), "macx_encoder_backward_w")
+        _lib.check(L.macx_encoder_backward_w(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(),
+                                             saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_words.data_ptr(), d_vecQ.data_ptr(), C.byref(gs),
+                                             _lib.ptr(word), _lib.stream_of(dev)),                      # (the word the forward pass hashed with)
+                   "macx_encoder_backward_w")
         if not mod.emb.requires_grad:
             grads[0] = None
         return (None,) * 8 + tuple(grads)

@@ -16,7 +16,6 @@ reference checkpoint loads by name (GenericParams.load_reference_dict) whatever 
 Not covered (UnsupportedOptions, never a silent fallback): dimensions that are not multiples of 128.
 """
 import collections
-import ctypes as C
 import math
 from contextlib import contextmanager
 from types import SimpleNamespace
@@ -24,6 +23,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from ._lib import ptr, stream_of
 from .options import UnsupportedOptions, fresh_seed, get, reject_like_reference, DEFAULTS
 
 MACCellTuple = collections.namedtuple("MACCellTuple", ("control", "memory"))
@@ -34,14 +34,6 @@ R_MID, R_LAST, R_ROWS = 0, 1, 2
 ACT_PRELU = 16
 ACT_RSQRT_EPS = 17
 SITE_MEM_VAR, SITE_MEM, SITE_READ_KB, SITE_READ_MEM, SITE_READ_ATT, SITE_WRITE_INFO = 1, 2, 3, 4, 5, 6
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _require_device(t, name):
@@ -66,7 +58,7 @@ def _L():
 # -------------------------------------------------------------------------------------------------------------------
 def k_binary(op, bmode, a, b, mid, inner, scale=1.0):
     out = torch.empty_like(a)
-    _lib.check(_L().macx_op_binary(op, bmode, _p(a), _p(b), a.numel(), mid, inner, scale, _p(out), _st(a)), "macx_op_binary")
+    _lib.check(_L().macx_op_binary(op, bmode, ptr(a), ptr(b), a.numel(), mid, inner, scale, ptr(out), stream_of(a)), "macx_op_binary")
     return out
 
 
@@ -74,20 +66,20 @@ def k_reduce(mode, x, outer, mid, inner):
     shape = {R_MID: (outer, inner), R_LAST: (outer,), R_ROWS: (inner,)}[mode]
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
     ws = torch.empty(64 * inner, dtype=torch.float32, device=x.device) if mode == R_ROWS else None
-    _lib.check(_L().macx_op_reduce(mode, _p(x), outer, mid, inner, _p(out), _p(ws), _st(x)), "macx_op_reduce")
+    _lib.check(_L().macx_op_reduce(mode, ptr(x), outer, mid, inner, ptr(out), ptr(ws), stream_of(x)), "macx_op_reduce")
     return out
 
 
 def k_act(act, x, alpha):
     out = torch.empty_like(x)
-    _lib.check(_L().macx_op_act(act, _p(x), _p(alpha), x.numel(), x.shape[-1], _p(out), _st(x)), "macx_op_act")
+    _lib.check(_L().macx_op_act(act, ptr(x), ptr(alpha), x.numel(), x.shape[-1], ptr(out), stream_of(x)), "macx_op_act")
     return out
 
 
 def k_act_bwd(act, x, alpha, g):
     dx = torch.empty_like(x)
     de = torch.empty_like(x) if act == ACT_PRELU else None          # (ACT_RSQRT_EPS: alpha holds eps, no gradient)
-    _lib.check(_L().macx_op_act_bwd(act, _p(x), _p(alpha), _p(g), x.numel(), x.shape[-1], _p(dx), _p(de), _st(x)), "macx_op_act_bwd")
+    _lib.check(_L().macx_op_act_bwd(act, ptr(x), ptr(alpha), ptr(g), x.numel(), x.shape[-1], ptr(dx), ptr(de), stream_of(x)), "macx_op_act_bwd")
     return dx, de
 
 
@@ -96,22 +88,22 @@ def k_softmax(x, lengths):
     rows = x.numel() // n
     out = torch.empty_like(x)
     rpl = rows // lengths.numel() if lengths is not None else 1
-    _lib.check(_L().macx_op_softmax(_p(x), _p(lengths), rpl, rows, n, _p(out), _st(x)), "macx_op_softmax")
+    _lib.check(_L().macx_op_softmax(ptr(x), ptr(lengths), rpl, rows, n, ptr(out), stream_of(x)), "macx_op_softmax")
     return out
 
 
 def k_softmax_bwd(a, g):
     n = a.shape[-1]
     dx = torch.empty_like(a)
-    _lib.check(_L().macx_op_softmax_bwd(_p(a), _p(g), a.numel() // n, n, _p(dx), _st(a)), "macx_op_softmax_bwd")
+    _lib.check(_L().macx_op_softmax_bwd(ptr(a), ptr(g), a.numel() // n, n, ptr(dx), stream_of(a)), "macx_op_softmax_bwd")
     return dx
 
 
 def k_dropout(x, seed, site, step, keep, first, mask_word=None):
     """mask_word: macx_dropout.mask_word (1-element int32 device tensor XORed into the site key when the kernel runs) or None"""
     out = torch.empty_like(x)
-    _lib.check(_L().macx_op_dropout_w(_p(x), x.numel(), seed, site, step, keep, first, _p(mask_word) if mask_word is not None else None,
-                                      _p(out), _st(x)), "macx_op_dropout")
+    _lib.check(_L().macx_op_dropout_w(ptr(x), x.numel(), seed, site, step, keep, first, ptr(mask_word), ptr(out),
+                                      stream_of(x)), "macx_op_dropout")
     return out
 
 
@@ -139,26 +131,26 @@ def k_matmul(x, W, b, big):
         B, N = big
         nws = L.macx_h2_floats(rows, K) + L.macx_h2_floats(rows, n) + K * n + 64
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-        _lib.check(L.macx_h2_gemm(_p(x), B, N, K, _p(W), n, _p(bias), 0, _p(out), _p(ws), nws, _st(x)), "macx_h2_gemm")
+        _lib.check(L.macx_h2_gemm(ptr(x), B, N, K, ptr(W), n, ptr(bias), 0, ptr(out), ptr(ws), nws, stream_of(x)), "macx_h2_gemm")
     else:
         wp = torch.empty(K * n, dtype=torch.float32, device=x.device)
-        _lib.check(L.macx_pack_weight(_p(W), K, n, _lib.PACK_F32MFMA, _p(wp), _st(x)), "macx_pack_weight")
-        _lib.check(L.macx_linear(_p(x), K, None, 0, rows, _p(wp), _p(bias), 0.0, n, 0, _p(out), _st(x)), "macx_linear")
+        _lib.check(L.macx_pack_weight(ptr(W), K, n, _lib.PACK_F32MFMA, ptr(wp), stream_of(x)), "macx_pack_weight")
+        _lib.check(L.macx_linear(ptr(x), K, None, 0, rows, ptr(wp), ptr(bias), 0.0, n, 0, ptr(out), stream_of(x)), "macx_linear")
     return out
 
 
 def k_embed(ids, emb, E, ld, keep, seed, first_row):
     """rows of the zero-padded embedding table for `ids` [rows] int32, through the input dropout: [rows, ld] (columns >= E zero)."""
     out = torch.empty((ids.numel(), ld), dtype=torch.float32, device=emb.device)
-    _lib.check(_L().macx_embed_lookup(_p(ids), _p(emb), ids.numel(), E, ld, keep, seed & 0xFFFFFFFF, first_row, _p(out), _st(emb)),
+    _lib.check(_L().macx_embed_lookup(ptr(ids), ptr(emb), ids.numel(), E, ld, keep, seed & 0xFFFFFFFF, first_row, ptr(out), stream_of(emb)),
                "macx_embed_lookup")
     return out
 
 
 def k_embed_bwd(ids, dx, E, V, keep, seed, first_row):
     d_emb = torch.empty((V, E), dtype=torch.float32, device=dx.device)
-    _lib.check(_L().macx_embed_lookup_bwd(_p(ids), _p(dx), ids.numel(), E, dx.shape[1], V, keep, seed & 0xFFFFFFFF, first_row,
-                                          _p(d_emb), _st(dx)), "macx_embed_lookup_bwd")
+    _lib.check(_L().macx_embed_lookup_bwd(ptr(ids), ptr(dx), ids.numel(), E, dx.shape[1], V, keep, seed & 0xFFFFFFFF, first_row,
+                                          ptr(d_emb), stream_of(dx)), "macx_embed_lookup_bwd")
     return d_emb
 
 
@@ -173,7 +165,7 @@ def k_wgrad(x2, g2):
         return k_wgrad(pad(x2, (0, Kp - K)).contiguous(), pad(g2, (0, np_ - n)).contiguous())[:K, :n].contiguous()
     dW = torch.empty((K, n), dtype=torch.float32, device=g2.device)
     ws = torch.empty(L.macx_wgrad_splits(rows, K, n) * K * n, dtype=torch.float32, device=g2.device)
-    _lib.check(L.macx_wgrad(_p(x2), K, _p(g2), n, rows, K, n, _p(dW), _p(ws), _st(g2)), "macx_wgrad")
+    _lib.check(L.macx_wgrad(ptr(x2), K, ptr(g2), n, rows, K, n, ptr(dW), ptr(ws), stream_of(g2)), "macx_wgrad")
     return dW
 
 

@@ -92,19 +92,15 @@ class FlatAdamEMA:
             raise ValueError("flat_grad holds %d floats, this optimizer's layout %d (segments padded to 4 floats, parameters in "
                              "the order given at construction)" % (flat_grad.numel(), self.flat.numel()))
         L = _lib.lib()
-        dev = self.flat.device
-        p_ = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        ptr = _lib.ptr
+        head = (self.flat.numel(), ptr(self.flat), ptr(flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema))
+        tail = (self.clip_norm, self.ema_decay, ptr(self.ws), ptr(self.norm), _lib.stream_of(self.flat))
+        # (two calls, not one with a suffix: for the plain one the LIBRARY computes the bias-corrected rate from lr and the step count)
         if device_lr:
-            _lib.check(L.macx_adam_ema_step_p(self.flat.numel(), p_(self.flat), p_(flat_grad), p_(self.m), p_(self.v), p_(self.ema),
-                                              p_(self.lr_t), self.beta1, self.beta2, self.eps, self.clip_norm, self.ema_decay, p_(self.ws),
-                                              p_(self.norm), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "macx_adam_ema_step_p")
-            if self.grad_owner is not None:
-                self.grad_owner.release_grad_buffer()
-            return self.norm
-        self.t += 1
-        _lib.check(L.macx_adam_ema_step(self.flat.numel(), p_(self.flat), p_(flat_grad), p_(self.m), p_(self.v), p_(self.ema), self.lr,
-                                        self.beta1, self.beta2, self.eps, self.t, self.clip_norm, self.ema_decay, p_(self.ws),
-                                        p_(self.norm), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "macx_adam_ema_step")
+            _lib.check(L.macx_adam_ema_step_p(*head, ptr(self.lr_t), self.beta1, self.beta2, self.eps, *tail), "macx_adam_ema_step_p")
+        else:
+            self.t += 1
+            _lib.check(L.macx_adam_ema_step(*head, self.lr, self.beta1, self.beta2, self.eps, self.t, *tail), "macx_adam_ema_step")
         if self.grad_owner is not None:
             self.grad_owner.release_grad_buffer()          # the step's gradients are consumed: the next backward may claim the buffer
         return self.norm

@@ -13,10 +13,6 @@ import torch
 from . import _lib
 from .options import UnsupportedOptions, _resolve_act, fresh_seed
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 REF_NAMES = {
     "outQuestion_W": "outputUnit/linearLayeroutQuestion/weights/weight",
     "outQuestion_b": "outputUnit/linearLayeroutQuestion/biases/bias",
@@ -38,13 +34,10 @@ class _OutFunction(torch.autograd.Function):
         saved = torch.empty(n_saved, dtype=torch.float32, device=memory.device)
         logits = torch.empty(B, mod.answers, dtype=torch.float32, device=memory.device)
         memory, vecQ = memory.contiguous(), vecQ.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(memory.device).cuda_stream)
-        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(), logits.data_ptr(),
-                saved.data_ptr(), n_saved)
-        if word is None:
-            _lib.check(L.macx_output_forward(*args, st), "macx_output_forward")
-        else:                                   # the run's mask word (1-element int32 device tensor)
-            _lib.check(L.macx_output_forward_w(*args, word.data_ptr(), st), "macx_output_forward_w")
+        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_output_forward passes on
+        _lib.check(L.macx_output_forward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
+                                           logits.data_ptr(), saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(memory)),
+                   "macx_output_forward_w")
         ctx.stuff = (mod, keep, seed, sh, saved, n_saved, memory, vecQ, params, word)
         if torch.cuda.is_current_stream_capturing():
             # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
@@ -63,13 +56,10 @@ class _OutFunction(torch.autograd.Function):
         ps = _lib.MacxOutParams(*[p.data_ptr() for p in params])
         dmem, dvq = torch.empty_like(memory), torch.empty_like(vecQ)
         d_logits = d_logits.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(memory.device).cuda_stream)
-        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(), saved.data_ptr(), n_saved,
-                ws.data_ptr(), n_ws, d_logits.data_ptr(), C.byref(gs), dmem.data_ptr(), dvq.data_ptr())
-        if word is None:
-            _lib.check(L.macx_output_backward(*args, st), "macx_output_backward")
-        else:                                   # the word the forward pass hashed with
-            _lib.check(L.macx_output_backward_w(*args, word.data_ptr(), st), "macx_output_backward_w")
+        _lib.check(L.macx_output_backward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
+                                            saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_logits.data_ptr(), C.byref(gs), dmem.data_ptr(),
+                                            dvq.data_ptr(), _lib.ptr(word), _lib.stream_of(memory)),    # (the word the forward pass hashed with)
+                   "macx_output_backward_w")
         return (None, None, None, None, None, dmem, dvq) + tuple(grads)
 
 
@@ -270,8 +260,8 @@ class _AnswerLoss(torch.autograd.Function):
         rows = torch.empty(B, dtype=torch.float32, device=lg.device)
         pred = torch.empty(B, dtype=torch.int32, device=lg.device)
         dl = torch.empty_like(lg)
-        st = C.c_void_p(torch.cuda.current_stream(lg.device).cuda_stream)
-        _lib.check(L.macx_answer_loss(_ptr(lg), _ptr(ans), B, A, _ptr(rows), _ptr(pred), _ptr(dl), 1.0 / B, st), "macx_answer_loss")
+        ptr = _lib.ptr
+        _lib.check(L.macx_answer_loss(ptr(lg), ptr(ans), B, A, ptr(rows), ptr(pred), ptr(dl), 1.0 / B, _lib.stream_of(lg)), "macx_answer_loss")
         ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(pred)
         return rows, pred

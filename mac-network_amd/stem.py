@@ -36,12 +36,9 @@ class _StemFunction(torch.autograd.Function):
         saved = torch.empty(n_saved, dtype=torch.float32, device=images.device)
         kb = torch.empty(B, mod.H * mod.W, mod.outDim, dtype=torch.float32, device=images.device)
         ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
-        st = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), images.data_ptr(), kb.data_ptr(), saved.data_ptr(), n_saved)
-        if word is None:
-            _lib.check(L.macx_stem_forward(*args, st), "macx_stem_forward")
-        else:                                   # the run's mask word (1-element int32 device tensor)
-            _lib.check(L.macx_stem_forward_w(*args, word.data_ptr(), st), "macx_stem_forward_w")
+        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_stem_forward passes on
+        _lib.check(L.macx_stem_forward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), images.data_ptr(), kb.data_ptr(),
+                                         saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(images)), "macx_stem_forward_w")
         ctx.stuff = (mod, keep, seed, sh, saved, n_saved, kb, params, word)
         if torch.cuda.is_current_stream_capturing():
             # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
@@ -59,13 +56,9 @@ class _StemFunction(torch.autograd.Function):
         gs = _lib.MacxStemGrads(*[g.data_ptr() for g in grads])
         ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
         d_kb = d_kb.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(kb.device).cuda_stream)
-        args = (C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), kb.data_ptr(), saved.data_ptr(), n_saved, ws.data_ptr(), n_ws,
-                d_kb.data_ptr(), C.byref(gs))
-        if word is None:
-            _lib.check(L.macx_stem_backward(*args, st), "macx_stem_backward")
-        else:
-            _lib.check(L.macx_stem_backward_w(*args, word.data_ptr(), st), "macx_stem_backward_w")
+        _lib.check(L.macx_stem_backward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), kb.data_ptr(), saved.data_ptr(), n_saved,
+                                          ws.data_ptr(), n_ws, d_kb.data_ptr(), C.byref(gs), _lib.ptr(word), _lib.stream_of(kb)),
+                   "macx_stem_backward_w")
         return (None, None, None, None, None, None) + tuple(grads)     # image features are inputs, not trained (extract_features.py)
 
 
@@ -125,9 +118,8 @@ class Stem(torch.nn.Module):
         if images.dim() == 4 and images.shape[1] == self.inDim and tuple(images.shape[2:]) == (self.H, self.W):
             src = images.contiguous()
             images = torch.empty(src.shape[0], self.H * self.W, self.inDim, dtype=torch.float32, device=src.device)
-            st = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
-            _lib.check(_lib.lib().macx_images_to_nhwc(src.data_ptr(), src.shape[0], self.inDim, self.H * self.W, images.data_ptr(), st),
-                       "macx_images_to_nhwc")
+            _lib.check(_lib.lib().macx_images_to_nhwc(src.data_ptr(), src.shape[0], self.inDim, self.H * self.W, images.data_ptr(),
+                                                      _lib.stream_of(src)), "macx_images_to_nhwc")
         elif images.dim() == 4:
             images = images.reshape(images.shape[0], self.H * self.W, self.inDim)
         keep = self.keep if train else 1.0
@@ -215,7 +207,7 @@ def k_conv_fwd(x, w, b, stride):
     k, Cout = w.shape[0], w.shape[3]
     sh = _lib.MacxConvShapes(B, H, W, Cin, Cout, k, stride)
     y = torch.empty(B, out_dim(H, stride), out_dim(W, stride), Cout, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().macx_conv2d_fwd(C.byref(sh), generic._p(x), generic._p(w), generic._p(b), generic._p(y), generic._st(x)),
+    _lib.check(_lib.lib().macx_conv2d_fwd(C.byref(sh), _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), _lib.stream_of(x)),
                "macx_conv2d_fwd")
     return y
 
@@ -225,7 +217,7 @@ def k_conv_bwd_data(dy, w, x_shape, stride):
     k, Cout = w.shape[0], w.shape[3]
     sh = _lib.MacxConvShapes(B, H, W, Cin, Cout, k, stride)
     dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy.device)
-    _lib.check(_lib.lib().macx_conv2d_bwd_data(C.byref(sh), generic._p(dy), generic._p(w), generic._p(dx), generic._st(dy)),
+    _lib.check(_lib.lib().macx_conv2d_bwd_data(C.byref(sh), _lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), _lib.stream_of(dy)),
                "macx_conv2d_bwd_data")
     return dx
 
@@ -238,14 +230,14 @@ def k_conv_wgrad(x, dy, w_shape, stride):
     n_ws = L.macx_conv2d_ws_floats(C.byref(sh))
     ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=x.device)
     dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
-    _lib.check(L.macx_conv2d_wgrad(C.byref(sh), generic._p(x), generic._p(dy), generic._p(dw), generic._p(ws), n_ws, generic._st(x)),
+    _lib.check(L.macx_conv2d_wgrad(C.byref(sh), _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(ws), n_ws, _lib.stream_of(x)),
                "macx_conv2d_wgrad")
     return dw
 
 
 def k_nchw_to_nhwc(src, C_, HW):
     out = torch.empty(src.shape[0], HW, C_, dtype=torch.float32, device=src.device)
-    _lib.check(_lib.lib().macx_images_to_nhwc(src.data_ptr(), src.shape[0], C_, HW, out.data_ptr(), generic._st(src)),
+    _lib.check(_lib.lib().macx_images_to_nhwc(src.data_ptr(), src.shape[0], C_, HW, out.data_ptr(), _lib.stream_of(src)),
                "macx_images_to_nhwc")
     return out
 
@@ -402,34 +394,6 @@ def check_image_index(image_index, B, train, stem, images=None, host_check=False
     return image_index
 
 
-class _KBGather(torch.autograd.Function):
-    """kb[b] = kb_images[index[b]] (macx_kb_gather); backward: the fixed-order sum of macx_kb_gather_bwd.  index: [B] int32 on the
-    device, read when the kernels run."""
-
-    @staticmethod
-    def forward(ctx, kb_images, index):
-        kb_images = generic._dev(kb_images, "the stem's output")
-        generic._require_device(index, "image_index")
-        if index.dtype != torch.int32 or not index.is_contiguous():
-            index = index.to(torch.int32).contiguous()
-        G, N, d = kb_images.shape
-        B = index.shape[0]
-        kb = torch.empty(B, N, d, dtype=torch.float32, device=kb_images.device)
-        _lib.check(_lib.lib().macx_kb_gather(generic._p(kb_images), generic._p(index), G, B, N, d, generic._p(kb), generic._st(kb)),
-                   "macx_kb_gather")
-        ctx.index, ctx.G = index, G
-        return kb
-
-    @staticmethod
-    def backward(ctx, dkb):
-        dkb = dkb.contiguous()
-        B, N, d = dkb.shape
-        out = torch.empty(ctx.G, N, d, dtype=torch.float32, device=dkb.device)
-        _lib.check(_lib.lib().macx_kb_gather_bwd(generic._p(dkb), generic._p(ctx.index), ctx.G, B, N, d, generic._p(out), generic._st(out)),
-                   "macx_kb_gather_bwd")
-        return out, None
-
-
 def check_image_lengths(image_lengths, image_index, kb_lengths, images=None, N=None, host_check=False):
     """The validation of model.MACNet(Core).forward's image_lengths (a [G] integer tensor: image g's knowledge base is the first
     image_lengths[g] of the stem's N cells), done before anything asks for the device.  Returns None for None.  host_check (with N):
@@ -454,30 +418,35 @@ def check_image_lengths(image_lengths, image_index, kb_lengths, images=None, N=N
     return image_lengths
 
 
-class _KBGatherL(torch.autograd.Function):
-    """(kb, kb_lengths) = macx_kb_gather_l(kb_images, index, lengths): question b's block is its image's first L rows and +0 behind
-    them, kb_lengths[b] = L, L = clamp(lengths[index[b]], 1, N); backward: macx_kb_gather_bwd_l (zeros in every image's padded rows).
+class _KBGather(torch.autograd.Function):
+    """(kb, kb_lengths) = macx_kb_gather_l(kb_images, index, lengths); backward: the fixed-order sum of macx_kb_gather_bwd_l.
+    lengths None (NULL; the plain macx_kb_gather / _bwd, which the library forwards to): kb[b] = kb_images[index[b]], kb_lengths None.
+    Else question b's block is its image's first L rows and +0 behind them, kb_lengths[b] = L, L = clamp(lengths[index[b]], 1, N),
+    and the backward pass writes zeros into every image's padded rows.
     index [B] and lengths [G]: int32 on the device, read when the kernels run."""
 
     @staticmethod
     def forward(ctx, kb_images, index, lengths):
         kb_images = generic._dev(kb_images, "the stem's output")
         generic._require_device(index, "image_index")
-        generic._require_device(lengths, "image_lengths")
         if index.dtype != torch.int32 or not index.is_contiguous():
             index = index.to(torch.int32).contiguous()
-        if lengths.dtype != torch.int32 or not lengths.is_contiguous():
-            lengths = lengths.to(torch.int32).contiguous()
         G, N, d = kb_images.shape
-        if lengths.shape != (G,):
-            raise ValueError("image_lengths must be [%d], one size per image" % G)
         B = index.shape[0]
+        kb_lengths = None
+        if lengths is not None:
+            generic._require_device(lengths, "image_lengths")
+            if lengths.dtype != torch.int32 or not lengths.is_contiguous():
+                lengths = lengths.to(torch.int32).contiguous()
+            if lengths.shape != (G,):
+                raise ValueError("image_lengths must be [%d], one size per image" % G)
+            kb_lengths = torch.empty(B, dtype=torch.int32, device=kb_images.device)
+            ctx.mark_non_differentiable(kb_lengths)
         kb = torch.empty(B, N, d, dtype=torch.float32, device=kb_images.device)
-        kb_lengths = torch.empty(B, dtype=torch.int32, device=kb_images.device)
-        _lib.check(_lib.lib().macx_kb_gather_l(generic._p(kb_images), generic._p(index), generic._p(lengths), G, B, N, d, generic._p(kb),
-                                               generic._p(kb_lengths), generic._st(kb)), "macx_kb_gather_l")
+        ptr = _lib.ptr
+        _lib.check(_lib.lib().macx_kb_gather_l(ptr(kb_images), ptr(index), ptr(lengths), G, B, N, d, ptr(kb), ptr(kb_lengths),
+                                               _lib.stream_of(kb)), "macx_kb_gather_l")
         ctx.index, ctx.lengths, ctx.G = index, lengths, G
-        ctx.mark_non_differentiable(kb_lengths)
         return kb, kb_lengths
 
     @staticmethod
@@ -485,8 +454,9 @@ class _KBGatherL(torch.autograd.Function):
         dkb = dkb.contiguous()
         B, N, d = dkb.shape
         out = torch.empty(ctx.G, N, d, dtype=torch.float32, device=dkb.device)
-        _lib.check(_lib.lib().macx_kb_gather_bwd_l(generic._p(dkb), generic._p(ctx.index), generic._p(ctx.lengths), ctx.G, B, N, d,
-                                                   generic._p(out), generic._st(out)), "macx_kb_gather_bwd_l")
+        ptr = _lib.ptr
+        _lib.check(_lib.lib().macx_kb_gather_bwd_l(ptr(dkb), ptr(ctx.index), ptr(ctx.lengths), ctx.G, B, N, d, ptr(out),
+                                                   _lib.stream_of(out)), "macx_kb_gather_bwd_l")
         return out, None, None
 
 
@@ -494,6 +464,5 @@ def kb_gather(kb_images, image_index, image_lengths=None):
     """[G, N, d] stem output -> the [B, N, d] knowledge base of B questions (differentiable in kb_images).
     image_lengths: None, or a [G] integer device tensor, the live cells of each image; then returns (kb, kb_lengths): the padded
     rows of kb are +0 whatever the stem's output holds there, kb_lengths [B] int32 is what the cell takes (made on the device)."""
-    if image_lengths is None:
-        return _KBGather.apply(kb_images, image_index)
-    return _KBGatherL.apply(kb_images, image_index, image_lengths)
+    kb, kb_lengths = _KBGather.apply(kb_images, image_index, image_lengths)
+    return kb if image_lengths is None else (kb, kb_lengths)

@@ -201,3 +201,25 @@ def test_kb_gather_function_with_lengths(macx, dev):
     assert bits_equal(kb.detach(), want) and torch.equal(kbl, want_len) and bits_equal(x.grad, want_grad)
     assert torch.equal(kbl.cpu(), torch.tensor(clamp(lengths, N), dtype=torch.int32)[torch.tensor(index)])
     assert type(macx.stem.kb_gather(x.detach(), idx32)) is torch.Tensor          # without lengths: the call of before
+
+
+@pytest.mark.parametrize("N, d", [(2, 4), (2, 6)])
+def test_kb_gather_function_without_lengths_is_the_plain_export(macx, dev, N, d):
+    """stem.kb_gather(kb_images, index) -- one autograd function on macx_kb_gather_l / _bwd_l with NULL lengths -- against
+    macx_kb_gather / macx_kb_gather_bwd called directly: the same bits forward and backward.  The smallest shape with a repeated
+    (1) and an unused (0) image; d = 6: N * d % 4 == 0 with d % 4 != 0, which the plain exports take and the call must still take."""
+    G, B = 2, 3
+    L = macx._lib.lib()
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(G, N, d, generator=g).to(dev).requires_grad_(True)
+    dout = torch.randn(B, N, d, generator=g).to(dev)
+    idx = torch.tensor([1, 1, 1], dtype=torch.int32, device=dev)
+    kb = macx.stem.kb_gather(x, idx)
+    assert type(kb) is torch.Tensor
+    kb.backward(dout)
+    want, want_grad = torch.full((B, N, d), float("nan"), device=dev), torch.full((G, N, d), float("nan"), device=dev)
+    assert L.macx_kb_gather(p_(x.detach()), p_(idx), G, B, N, d, p_(want), None) == 0
+    assert L.macx_kb_gather_bwd(p_(dout), p_(idx), G, B, N, d, p_(want_grad), None) == 0
+    torch.cuda.synchronize()
+    assert bits_equal(kb.detach(), want) and bits_equal(x.grad, want_grad)
+    assert bool((x.grad[0].view(torch.int32) == 0).all())
