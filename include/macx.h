@@ -632,6 +632,26 @@ int macx_wgrad(const float* A, int lda, const float* G, int ldg, int M, int Kd, 
 int macx_answer_loss(const float* logits, const int32_t* answers, int B, int A, float* loss_rows, int32_t* pred,
                      float* dlogits, float grad_scale, void* stream);
 
+/* ---- a loss on a run's attention maps (attention supervision, entropy regularisers) --------------------------------
+ * One launch turns a stacked map `att` [p,B,n] (a viewable segment of `saved`: MACX_SEG_ATT_KB, n = N; MACX_SEG_ATT_QUESTION,
+ * n = S) into loss rows [p,B] and the gradient d_att [p,B,n] (may be NULL: rows only) in the layout macx_state_grads takes, so the
+ * call can sit between macx_cell_forward and macx_cell_backward[_phase]_x -- inside a captured graph as well.
+ * With w = scale * step_weights[i] * row_weights[b] (NULL weights = 1) and L = clamp(lengths[b], 1, n) (NULL = n; the clamp of
+ * macx_kb_attend_fwd_l):
+ *   MACX_ATT_LOSS_CE       loss_rows[i,b] = -w sum_{j<L} t[j] log(a[j] + eps);   d_att[i,b,j] = -w t[j] / (a[j] + eps)
+ *                          t = target[b] ([B,n], target_steps 0) or target[i,b] ([p,B,n], target_steps 1)
+ *   MACX_ATT_LOSS_ENTROPY  loss_rows[i,b] =  w sum_{j<L} a[j] log(a[j] + eps)   (the NEGATIVE entropy: the sign of `scale` chooses);
+ *                          d_att[i,b,j] = w (log(a[j] + eps) + a[j] / (a[j] + eps));   target is not read (NULL)
+ * d_att[i,b,j >= L] = +0.0f and neither att nor target is read there (they may hold NaN); a row with w == 0 (row_weights[b] = 0: the
+ * question is unsupervised) is exactly 0 with an all +0.0f d_att row, whatever att and target hold -- the finite-gradient contract
+ * of macx_state_grads.  (A live cell with t[j] == 0 gets CE's -0.0f under w > 0: +0.0f is promised for j >= L and w == 0 only.)  lengths (int32), step_weights [p] and row_weights [B] are device memory read when the kernel runs; eps and
+ * scale travel by value.  Identical calls give identical bits (fixed-order reduction, no atomics).
+ * MACX_EINVAL, and nothing is launched: eps <= 0 or not finite, an unknown kind, kind CE without a target. */
+enum { MACX_ATT_LOSS_CE = 0, MACX_ATT_LOSS_ENTROPY = 1 };
+int macx_att_loss(const float* att, const float* target, const int32_t* lengths, const float* step_weights,
+                  const float* row_weights, int p, int B, int n, int kind, int target_steps, float eps, float scale,
+                  float* loss_rows, float* d_att, void* stream);
+
 /* ---- the knowledge-base attention unit on its own (mac_cell.py:266-272: inter2att's softmax + att2Smry) ------------
  * The fused cell's own kernels behind a per-unit contract, so that the unit is testable in isolation:
  *   macx_kb_attend_fwd   att[B,N] = softmax_n(logits[B,N] + bias[0]);  info[B,d] = sum_n att KB        (ops.py:140-150)

@@ -298,6 +298,9 @@ def _state_segments(run):
     return segs
 
 
+STATE_TENSORS = ("controls", "memories", "att_question", "att_kb", "att_self", "att_gate")      # MACCell.state_tensor's names
+
+
 def _state_shapes(run):
     shapes = run.state_grad_shapes()
     return [shapes["d_" + seg] for seg in _state_segments(run)]
@@ -326,7 +329,8 @@ class MACCell:
     controls and memories carry the autograd edge after run() or after the LAST __call__ of the per-step loop, as the reference's
     graph nodes do: attention supervision, entropy regularisers, per-step heads train the network (macx_cell_backward_x).  In the
     per-step loop the autograd node exists only after the last step: a tensor fetched before it is a constant, so read them
-    after the loop.  Their incoming gradients must be finite.  infos is a constant.  The captured-graph classes take no such loss.
+    after the loop.  Their incoming gradients must be finite.  infos is a constant.  state_tensor(name) is the stacked tensor behind
+    each of them.  Inside a replayed graph: the captured training steps' att_loss= / aux_loss= (graph.py).
     Once the run's backward pass is over the cell publishes plain views again (the finished graph is not kept alive): build the
     whole loss from tensors fetched BEFORE backward(); with retain_graph=True those keep working, tensors fetched afterwards are constants.
     """
@@ -424,6 +428,7 @@ class MACCell:
             out = dict(zip(_state_segments(run), node_outputs))
         else:
             out = {seg: run.segment(seg, shape) for seg, shape in zip(_state_segments(run), _state_shapes(run))}
+        self._stacked = out
         self._controls_all = out["controls"]
         self._memories_all = out["memories"]
         self._infos_all = run.segment("infos", (s.p, s.B, s.d))
@@ -443,6 +448,21 @@ class MACCell:
         """back to plain views of `saved` (same lists, entries replaced): called when the run's backward pass is over"""
         self._views()
         self._republish()
+
+    def state_tensor(self, name):
+        """The STACKED output of the run's autograd node in the layout of macx_state_grads: "controls" / "memories" [p + 1, B, d],
+        "att_question" [p, B, S], "att_kb" [p, B, N], "att_self" [p, B, p] (row i: its first i + 1 entries), "att_gate" [p, B, d].
+        The rules of `attentions`: it carries the autograd edge while the run's graph is alive (after run() / the last step of the
+        loop) and is a plain view of the run's buffer afterwards.  A loss on it sends ONE gradient tensor to macx_cell_backward_x;
+        the same loss over attentions[...][i] goes through unbind's backward pass, which stacks p slices first
+        (losses.attention_loss takes this tensor)."""
+        if self._run is None:
+            raise RuntimeError("no run yet: call zero_state() or run() first")
+        if name not in STATE_TENSORS:
+            raise KeyError("no state tensor %r (have %s)" % (name, ", ".join(STATE_TENSORS)))
+        if name not in self._stacked:
+            raise KeyError("this cell has no %s (the option set runs without it)" % name)
+        return self._stacked[name]
 
     # ---- zero_state (mac_cell.py:539-592)
     @property
@@ -667,6 +687,12 @@ class PaddedMACCell:
 
     def reset_status(self):
         return self.inner.reset_status()
+
+    def state_tensor(self, name):
+        """MACCell.state_tensor; what is as wide as the state (controls, memories, att_gate) cropped to the logical width by
+        ordinary slicing, as the lists are"""
+        t = self.inner.state_tensor(name)
+        return t[..., :self.d] if name in ("controls", "memories", "att_gate") else t
 
     controls = property(lambda self: self.inner.controls[..., :self.d])
     memories = property(lambda self: self.inner.memories[..., :self.d])

@@ -21,6 +21,7 @@
 #include "macx_ops.hip.h"
 #include "macx_conv.hip.h"
 #include "macx_kb_gather.hip.h"
+#include "macx_att_loss.hip.h"
 
 using namespace macx;
 
@@ -2313,6 +2314,23 @@ int macx_answer_loss(const float* logits, const int32_t* answers, int B, int A, 
   if (!logits || !answers || !loss_rows || !pred || B < 1 || A < 1) return MACX_EINVAL;
   hipLaunchKernelGGL(answer_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, answers, B, A, loss_rows, pred,
                      dlogits, grad_scale);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// ---- a loss on a run's attention maps: rows [p,B] and d_att [p,B,n] in one launch (macx_att_loss.hip.h) ------------------------
+int macx_att_loss(const float* att, const float* target, const int32_t* lengths, const float* step_weights, const float* row_weights,
+                  int p, int B, int n, int kind, int target_steps, float eps, float scale, float* loss_rows, float* d_att, void* stream) {
+  if (!att || !loss_rows || p < 1 || B < 1 || n < 1) return MACX_EINVAL;
+  if (!(eps > 0.f && eps < INFINITY)) return MACX_EINVAL;          // (NaN fails both comparisons)
+  if (kind != ATT_LOSS_CE && kind != ATT_LOSS_ENTROPY) return MACX_EINVAL;
+  if (kind == ATT_LOSS_CE && !target) return MACX_EINVAL;
+  AttLossP q;
+  q.att = att; q.target = target; q.lengths = lengths; q.step_weights = step_weights; q.row_weights = row_weights;
+  q.p = p; q.B = B; q.n = n; q.target_steps = target_steps != 0; q.eps = eps; q.scale = scale; q.loss_rows = loss_rows; q.d_att = d_att;
+  const dim3 grid((unsigned)(((size_t)p * B + 3) / 4));
+  if (kind == ATT_LOSS_CE) hipLaunchKernelGGL(att_loss_kernel<ATT_LOSS_CE>, grid, dim3(256), 0, (hipStream_t)stream, q);
+  else hipLaunchKernelGGL(att_loss_kernel<ATT_LOSS_ENTROPY>, grid, dim3(256), 0, (hipStream_t)stream, q);
   CK(hipGetLastError());
   return MACX_OK;
 }

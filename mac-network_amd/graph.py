@@ -46,12 +46,17 @@ Five classes, one protocol, written once in `_Captured`: warm up on a side strea
 the eager run and fall back (`_self_check`, `_eager_on_captured`, `_compare_replays`), report the status.  A class adds its static
 inputs (`_CellInputs`, `_TowerInputs`; the training classes' mask word: `_MaskWord`), `_eager()` -- its launches on the current
 stream -- and `_issue()`, which publishes what they return: the body of the capture and the eager fallback of `replay()`.
+
+Losses on the run's own attention maps and states (attention supervision, entropy regularisers, per-step heads): the three training
+classes take `att_loss=dict(...)` -- one launch of the library (macx_att_loss) between the forward and the backward launches, its
+target and weights static tensors read at replay time -- and, where autograd runs, `aux_loss=callable` (`_AttLoss`;
+CapturedTrainStep documents both).
 """
 import warnings
 
 import torch
 
-from .cell import MACCell, _Run
+from .cell import MACCell, MACCellTuple, _Run
 from .dp import TwoPhaseStep
 from .options import UnsupportedOptions, get
 from .params import MACCellParams
@@ -112,7 +117,13 @@ class _Captured:
         """use the capture unless `verify` and its replays do not reproduce the eager run (_replays_match_eager(*args))"""
         self._captured_cell = self.cell              # the run whose buffers the graph replays on
         self.captured = True
-        if verify and not self._replays_match_eager(*args):
+        try:
+            matched = not verify or self._replays_match_eager(*args)
+        finally:
+            # the check drew a target and weights into the static att_loss= tensors: back to what a constructed step documents
+            # (target zeros, weights ones), whether or not the replays matched -- load() does not force the weights
+            getattr(self, "_reset_att_loss", lambda: None)()
+        if not matched:
             self.captured = False
             warnings.warn("%s: replays of the captured %s do not reproduce the eager %s in this process; "
                           "falling back to eager launches" % ((type(self).__name__,) + self._WHAT), RuntimeWarning)
@@ -214,15 +225,133 @@ def _check_lengths(t, n, N, check, name):
         raise ValueError("%s must lie in [1, %d] (the knowledge base's cells); got %d .. %d" % (name, N, int(t.min()), int(t.max())))
 
 
-def _lengths_argument(who, name, given, built):
-    """load() takes `name` exactly when the class was built with it (as d_memory)"""
+def _lengths_argument(who, name, given, built, how=None):
+    """load() takes `name` exactly when the class was built with it (as d_memory); how: the constructor argument that builds it"""
     if given != built:
-        raise TypeError("%s.load() %s %s: the graph was captured %s %s=True"
-                        % (who, "needs" if built else "takes no", name, "with" if built else "without", name))
+        raise TypeError("%s.load() %s %s: the graph was captured %s %s"
+                        % (who, "needs" if built else "takes no", name, "with" if built else "without", how or name + "=True"))
 
 
-class _CellInputs:
-    """the static input tensors of a captured cell, load() into them and the cell built on them"""
+# ---------------------------------------------------------------------------------------------------------------------------
+# a loss on the run's attention maps inside the captured step (att_loss=) and losses written in torch ops (aux_loss=)
+# ---------------------------------------------------------------------------------------------------------------------------
+_ATT_LOSS_KEYS = {"on": "kb", "kind": "ce", "weight": 1.0, "eps": 1e-8, "per_step_target": False}
+
+
+def _att_loss_spec(who, spec):
+    """att_loss=None | dict(on="kb" | "question", kind="ce" | "entropy", weight=lambda, eps=1e-8, per_step_target=False) -> the
+    dict with every key, validated (before anything asks for the device)"""
+    if spec is None:
+        return None
+    from .losses import check_scalars
+    if not isinstance(spec, dict):
+        raise TypeError("%s: att_loss is None or a dict(on=, kind=, weight=, eps=, per_step_target=), not %r" % (who, spec))
+    unknown = sorted(set(spec) - set(_ATT_LOSS_KEYS))
+    if unknown:
+        raise ValueError("%s: att_loss has no key %s (have %s)" % (who, ", ".join(map(repr, unknown)), ", ".join(sorted(_ATT_LOSS_KEYS))))
+    out = dict(_ATT_LOSS_KEYS, **spec)
+    if out["on"] not in ("kb", "question"):
+        raise ValueError('%s: att_loss on=%r: the supervised map is "kb" or "question" (the self-attention and the gate are reached '
+                         "through aux_loss= and cell.state_tensor)" % (who, out["on"]))
+    _, out["eps"], out["weight"] = check_scalars(out["kind"], out["eps"], out["weight"])
+    out["per_step_target"] = bool(out["per_step_target"])
+    if out["per_step_target"] and out["kind"] != "ce":
+        raise ValueError('%s: att_loss per_step_target=True belongs to kind "ce": kind "entropy" has no target' % who)
+    return out
+
+
+class _AttLoss:
+    """What the three captured training steps share for att_loss= / aux_loss=: the static tensors (allocated with the other inputs,
+    BEFORE the capture: DESIGN 8), load() into them, the draw of the self-checks (undone behind the check: _Captured._self_check puts
+    the target back to zeros and the weights to ones, what a constructed step documents), and the launch.
+
+    The auxiliary loss is  weight * sum(rows) / (p * B)  with B the class's own batch -- a data-parallel shard takes the mean over its
+    shard, like the loss whose d_memory the caller hands it; weight / (p * B) travels into the launch by value, everything else
+    (target, row weights, step weights, lengths) is device data read when the kernel runs."""
+
+    att_loss, aux_loss = None, None
+    att_target, att_row_weights, att_step_weights, aux_rows = None, None, None, None
+
+    def _alloc_att_loss(self, spec, p, B, S, N, dev):
+        self.att_loss = _att_loss_spec(type(self).__name__, spec)
+        if self.att_loss is None:
+            return
+        n = N if self.att_loss["on"] == "kb" else S
+        self._att_segment = "att_" + self.att_loss["on"]
+        self._att_shape = (int(p), int(B), int(n))
+        self._att_scale = self.att_loss["weight"] / float(p * B)
+        if self.att_loss["kind"] == "ce":
+            self.att_target = torch.zeros(self._att_shape if self.att_loss["per_step_target"] else self._att_shape[1:], device=dev)
+        self.att_row_weights = torch.ones(B, device=dev)
+        self.att_step_weights = torch.ones(p, device=dev)
+        self.aux_rows = torch.zeros(p, B, device=dev)
+
+    def _check_att_loss(self, att_target, att_row_weights, att_step_weights):
+        """load()'s refusals: att_target exactly when built for kind "ce", the weights only when built with att_loss, shapes"""
+        who = type(self).__name__
+        _lengths_argument(who, "att_target", att_target is not None, self.att_target is not None, 'att_loss=dict(kind="ce")')
+        for name, t in (("att_row_weights", att_row_weights), ("att_step_weights", att_step_weights)):
+            if t is not None:
+                _lengths_argument(who, name, True, self.att_loss is not None, "att_loss=")
+        for name, t, buf in (("att_target", att_target, self.att_target), ("att_row_weights", att_row_weights, self.att_row_weights),
+                             ("att_step_weights", att_step_weights, self.att_step_weights)):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != tuple(buf.shape) or not t.dtype.is_floating_point):
+                raise ValueError("%s must be a %s floating-point tensor" % (name, list(buf.shape)))
+
+    def _copy_att_loss(self, att_target, att_row_weights, att_step_weights):
+        """... and its copies (None keeps what the buffer holds)"""
+        with torch.no_grad():
+            for t, buf in ((att_target, self.att_target), (att_row_weights, self.att_row_weights), (att_step_weights, self.att_step_weights)):
+                if t is not None:
+                    buf.copy_(t)
+
+    def _randomise_att_loss(self, gen, live):
+        """the self-check's draw: target = softmax of N(0,1) over each question's live cells (live: [B] sizes on the host, None = all;
+        zeros behind them), row weights in [0.5, 1.5] with the last question unsupervised (B > 1), step weights in [0.5, 1.5]"""
+        if self.att_loss is None:
+            return
+        p, B, n = self._att_shape
+        with torch.no_grad():
+            if self.att_target is not None:
+                dead = torch.zeros(B, n, dtype=torch.bool) if live is None else torch.arange(n).unsqueeze(0) >= live.clamp(1, n).unsqueeze(1)
+                logits = torch.randn(self.att_target.shape, generator=gen).masked_fill(dead.expand(self.att_target.shape), float("-inf"))
+                self.att_target.copy_(torch.softmax(logits, dim=-1))
+            rw = 0.5 + torch.rand(B, generator=gen)
+            if B > 1:
+                rw[-1] = 0.0
+            self.att_row_weights.copy_(rw)
+            self.att_step_weights.copy_(0.5 + torch.rand(p, generator=gen))
+
+    def _reset_att_loss(self):
+        """the static tensors as construction leaves them: target zeros, row and step weights ones, rows zeros"""
+        with torch.no_grad():
+            for t, value in ((self.att_target, 0.0), (self.att_row_weights, 1.0), (self.att_step_weights, 1.0), (self.aux_rows, 0.0)):
+                if t is not None:
+                    t.fill_(value)
+
+    def _att_lengths(self, cell):
+        """the lengths the supervised map was computed under: the cell's own device tensors (kb: None when every question has N)"""
+        cell = getattr(cell, "inner", cell)          # (a zero-padded cell wraps the real one)
+        return cell.kb_lengths if self.att_loss["on"] == "kb" else cell.questionLengths
+
+    def _att_loss_rows(self, cell):
+        """attention_loss on the cell's stacked map, the rows written into the static `aux_rows`: [p, B] with the autograd edge"""
+        from .losses import attention_loss
+        a = self.att_loss
+        return attention_loss(cell.state_tensor(self._att_segment), self.att_target, self._att_lengths(cell), self.att_step_weights,
+                              self.att_row_weights, kind=a["kind"], eps=a["eps"], scale=self._att_scale, _rows_out=self.aux_rows)
+
+    def _aux_terms(self, cell, state):
+        """the scalars the step differentiates besides its own loss: [] for a class built without att_loss / aux_loss"""
+        terms = [] if self.att_loss is None else [self._att_loss_rows(cell).sum()]
+        if self.aux_loss is not None:
+            terms.append(self.aux_loss(cell, state))
+        return terms
+
+
+class _CellInputs(_AttLoss):
+    """the static input tensors of a captured cell (the training classes' att_loss= tensors among them: _AttLoss), load() into them
+    and the cell built on them"""
 
     d_memory = None                                  # [B, d] gradient of the final memory: the training classes
     kb_lengths = None                                # [B] int32 live knowledge-base cells per question: kb_lengths=True
@@ -251,19 +380,29 @@ class _CellInputs:
         with torch.no_grad():
             for t in (self.vecQuestions, self.words, self.knowledgeBase) + (() if self.d_memory is None else (self.d_memory,)):
                 t.copy_(torch.randn(t.shape, generator=g).to(t.device))
+            live = None
             if self.kb_lengths is not None:
-                self.kb_lengths.copy_(_draw_lengths(g, *self.knowledgeBase.shape[:2]))
+                live = _draw_lengths(g, *self.knowledgeBase.shape[:2])
+                self.kb_lengths.copy_(live)
+        if self.att_loss is not None:
+            self._randomise_att_loss(g, live if self.att_loss["on"] == "kb" else self.lengths.cpu())
 
-    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory=None, kb_lengths=None, check_ids=True):
+    def load(self, vecQuestions, words, lengths, knowledgeBase, d_memory=None, kb_lengths=None, check_ids=True, att_target=None,
+             att_row_weights=None, att_step_weights=None):
         """Copy a batch into the captured run's input tensors (or write into .knowledgeBase etc. directly and skip this);
         d_memory: the training classes' [B, d] gradient of the final memory, and theirs only;
         kb_lengths: the [B] integer sizes of a class built with kb_lengths=True, and of such a class only; check_ids tests
-        1 <= kb_lengths <= N on the host first (synchronises; unchecked values are clamped by the kernel)"""
+        1 <= kb_lengths <= N on the host first (synchronises; unchecked values are clamped by the kernel);
+        att_target: the target distribution of a training class built with att_loss=dict(kind="ce"), and of such a class only
+        ([B, n], or [p, B, n] with per_step_target); att_row_weights [B] / att_step_weights [p]: a class built with att_loss= (None
+        keeps what .att_row_weights / .att_step_weights hold: ones after construction)"""
         if (d_memory is None) != (self.d_memory is None):
             raise TypeError("%s.load() takes %s d_memory" % (type(self).__name__, "no" if self.d_memory is None else "a"))
         _lengths_argument(type(self).__name__, "kb_lengths", kb_lengths is not None, self.kb_lengths is not None)
         if kb_lengths is not None:
             _check_lengths(kb_lengths, *self.knowledgeBase.shape[:2], check_ids, "kb_lengths")
+        self._check_att_loss(att_target, att_row_weights, att_step_weights)
+        self._copy_att_loss(att_target, att_row_weights, att_step_weights)
         with torch.no_grad():
             self.vecQuestions.copy_(vecQuestions)
             self.words.copy_(words)
@@ -348,13 +487,40 @@ class CapturedTrainStep(_Captured, _CellInputs, _MaskWord):
     measurement wants.  The eager step behind `_eager()` reads the same word, so verification compares like with like.
 
     `verify=True` replays three times against the eager step on random inputs and falls back to eager launches when a replay
-    differs in any gradient (`captured` False, a warning says so)."""
+    differs in any gradient (`captured` False, a warning says so).
+
+    Losses on the run's own maps and states, inside the graph (the gradient of such a loss depends on the forward pass of the SAME
+    replay, so it cannot be a static input):
+
+    att_loss=dict(on="kb" | "question", kind="ce" | "entropy", weight=lam, eps=1e-8, per_step_target=False) adds
+    lam * sum(rows) / (p * B) of losses.attention_loss on cell.state_tensor("att_kb" | "att_question") to what the step
+    differentiates -- one launch (macx_att_loss) between the forward and the backward launches.  Static tensors, allocated before
+    the capture and read when the kernel runs: `att_target` ([B, n], [p, B, n] with per_step_target; kind "ce" only),
+    `att_row_weights` [B] and `att_step_weights` [p] (ones; a row weight of 0: that question is unsupervised), written by
+    load(..., att_target=, att_row_weights=, att_step_weights=) or directly; the output `aux_rows` [p, B].  on="kb" masks by the
+    class's kb_lengths, on="question" by the question lengths.  The self-check draws all of them and afterwards puts the target
+    back to zeros and the weights back to ones: None in load() keeps ones until the caller writes others.
+
+        step = macx.CapturedTrainStep(cfg, params, B=64, S=50, N=196, att_loss=dict(on="kb", kind="ce", weight=0.1))
+        step.load(vecQuestions, words, lengths, knowledgeBase, d_memory, att_target=boxes_as_distribution)
+        step.replay(); aux = step.aux_rows.sum()
+
+    aux_loss=callable(cell, state) -> scalar tensor: a loss written in torch ops on cell.state_tensor(...) (per-step heads on
+    "memories", the self-attention, the gate), evaluated inside the step and therefore inside the graph.  It must not synchronise
+    with the host (no .item(), no printing of values, no data-dependent Python branches), and every tensor it reads that the HOST
+    writes between replays must be allocated by the caller BEFORE this class is constructed (a tensor allocated inside the callable
+    comes from the graph's pool).  A head's own parameters take their gradients as any leaf does, but the step does not clear
+    them: their .grad is allocated by the warm-up and every replay ADDS to it in place -- zero it in place (grad.zero_(), never
+    grad = None) before a replay whose gradient is to be read alone."""
 
     def __init__(self, config, params, B, S, N, seed=0, device=None, netLength=None, b0=0, warmup=2, verify=True, check_every=0,
-                 kb_lengths=False):
+                 kb_lengths=False, att_loss=None, aux_loss=None):
         self.seed, self.b0 = int(seed), int(b0)
         self.check_every = int(check_every)
+        att_loss = _att_loss_spec(type(self).__name__, att_loss)
         dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, requires_grad=True, kb_lengths=kb_lengths)
+        self._alloc_att_loss(att_loss, self.netLength, B, S, N, dev)
+        self.aux_loss = aux_loss
         self._alloc_mask_word(dev)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)], before=self._clear_grads)
@@ -371,7 +537,8 @@ class CapturedTrainStep(_Captured, _CellInputs, _MaskWord):
         self._clear_grads()
         self.cell = self._make_cell(train=True)   # (status(): the latest run's buffers)
         state = self.cell.run()
-        torch.autograd.backward([state.memory], [self.d_memory])
+        aux = self._aux_terms(self.cell, state)
+        torch.autograd.backward([state.memory] + aux, [self.d_memory] + [None] * len(aux))
         return state.memory.detach()
 
     def _issue(self):
@@ -387,8 +554,10 @@ class CapturedTrainStep(_Captured, _CellInputs, _MaskWord):
         self.set_mask_word(0x5bd1e995)          # a non-trivial word: the check covers the device-read path as well
         self._randomise(20240520)
         memory, grads = self.eager_reference()
-        written = lambda: enumerate([self.memory] + [t.grad for t in self._leaves()])     # labels: the index into [memory] + leaves
-        return self._compare_replays(replays, written, [memory] + grads)
+        extra = [] if self.aux_rows is None else [self.aux_rows.clone()]                  # (the eager run wrote the static buffer)
+        # labels: the index into [memory] + leaves (+ aux_rows)
+        written = lambda: enumerate([self.memory] + [t.grad for t in self._leaves()] + ([] if self.aux_rows is None else [self.aux_rows]))
+        return self._compare_replays(replays, written, [memory] + grads + extra)
 
     def replay(self, iteration=None):
         """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration)"""
@@ -424,11 +593,25 @@ class CapturedDPTrainStep(_Captured, _CellInputs, _MaskWord, TwoPhaseStep):
         step = macx.CapturedDPTrainStep(cfg, params, bucket, B=shard, S=50, N=196, global_batch=64, seed=1234, b0=lo)
         step.load(vecQ[lo:hi], words[lo:hi], lengths[lo:hi], kb[lo:hi], d_memory[lo:hi])
         step.step(iteration=it)              # params' .grad = the all-reduced full-batch gradient; step.memory: [shard, d]
+
+    att_loss=: CapturedTrainStep's, with B the shard -- lam * sum(rows) / (p * shard), the mean over the shard that the bucket then
+    weights like the loss behind d_memory.  There is no autograd here: behind the forward pass, phase A launches macx_att_loss on
+    the run's stacked map (a segment of `saved`), which writes `aux_rows` and a static d_att buffer that the backward pass's
+    macx_state_grads points at -- in both graphs' capture and on the uncaptured route alike.  aux_loss= (a loss in torch ops)
+    needs autograd and is refused: att_loss= is this class's route, CapturedTrainStep takes callables.
     """
 
     def __init__(self, config, params, bucket, B, S, N, global_batch, seed=0, b0=0, device=None, netLength=None, warmup=2, capture=True,
-                 check_every=0, kb_lengths=False):
+                 check_every=0, kb_lengths=False, att_loss=None, aux_loss=None):
+        if aux_loss is not None:
+            raise TypeError("CapturedDPTrainStep takes no aux_loss: its two phases are the library's calls themselves, without autograd, "
+                            "so a loss written in torch ops has nothing to differentiate it.  Losses on the attention maps go through "
+                            "att_loss= (one launch of the library inside phase A); CapturedTrainStep takes aux_loss=")
+        att_loss = _att_loss_spec(type(self).__name__, att_loss)
         dev = self._alloc_inputs(config, params, B, S, N, device, netLength, train=True, kb_lengths=kb_lengths)
+        self._alloc_att_loss(att_loss, self.netLength, B, S, N, dev)
+        if self.att_loss is not None:
+            self._d_att = torch.zeros(self._att_shape, device=dev)      # macx_state_grads.d_att_kb / d_att_question of every run
         if bucket.flat.data_ptr() != params.grad_buffer().data_ptr():
             raise ValueError("the bucket must be built over params' own flat gradient buffer (OverlappedBuckets(params) / "
                              "GradBucket(params.tensors(), params=params))")
@@ -454,7 +637,13 @@ class CapturedDPTrainStep(_Captured, _CellInputs, _MaskWord, TwoPhaseStep):
             cell = self._make_cell(train=True)
             run = _Run(cell, True)
             run.forward()
-            args, grads, gi, flat, keep = run.backward_begin(None, self.d_memory)
+            state_grads = None
+            if self.att_loss is not None:
+                from .losses import KINDS, launch
+                launch(run.segment(self._att_segment, self._att_shape), self.att_target, self._att_lengths(cell), self.att_step_weights,
+                       self.att_row_weights, KINDS[self.att_loss["kind"]], self.att_loss["eps"], self._att_scale, self.aux_rows, self._d_att)
+                state_grads = {"d_" + self._att_segment: self._d_att}
+            args, grads, gi, flat, keep = run.backward_begin(None, self.d_memory, state_grads)
             if flat.data_ptr() != self.bucket.flat.data_ptr():
                 raise RuntimeError("the backward pass did not receive the parameters' flat gradient buffer (is a gradient still attached?)")
             run.backward_phase(args, 1)
@@ -529,8 +718,8 @@ def _random_tower_inputs(gen, B, S, vocab, shape_images, answers, dev):
     return images.to(dev), q.to(dev), lengths.to(dev), ans.to(dev)
 
 
-class _TowerInputs:
-    """the static input tensors of a captured tower and load() into them"""
+class _TowerInputs(_AttLoss):
+    """the static input tensors of a captured tower (the training step's att_loss= tensors among them: _AttLoss) and load() into them"""
 
     G, image_index = None, None            # questions that share images (images=G): see _alloc_inputs
     kb_lengths, image_lengths = None, None # knowledge bases of per-question / per-image size: see _alloc_inputs
@@ -739,13 +928,23 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     (`captured` False, a RuntimeWarning; `verify_report` lists what differed).  Parameters, m, v, ema and t are restored
     afterwards: a constructed step has not trained.
 
+    att_loss= / aux_loss=: CapturedTrainStep's, on net.last_cell.  The loss the step trains on becomes CE + aux with
+    aux = lam * sum(aux_rows) / (p * B) (+ aux_loss(cell, state)): `step.loss` is the total, `step.ce` the mean cross-entropy,
+    `step.aux` the auxiliary part (None for a class built without either; then loss is ce).  on="kb" masks by the lengths the cell ran
+    under: the static kb_lengths, or with image_lengths=True the per-question tensor the captured gather makes on the device.
+    load(..., att_target=, att_row_weights=, att_step_weights=) as CapturedTrainStep.load.  Optimizer, bucket and the restore logic
+    are the same; a weight of 0 trains exactly as the class without att_loss.
+
     Copies on the captured path: none issued by the library or by this class.  What autograd adds is torch's own business: it
     adopts each returned gradient as the parameter's .grad without a copy as long as nobody else holds it (the module functions
     return fresh tensors), and sums the two gradients of vecQuestions with a kernel."""
 
+    aux = None
+
     def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0, images=None,
-                 kb_lengths=False, image_lengths=False):
+                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None):
         self._check_options(net, "CapturedTowerTrainStep", images, kb_lengths, image_lengths, train=True)
+        att_loss = _att_loss_spec("CapturedTowerTrainStep", att_loss)
         dev = _require_fused_tower(net, "CapturedTowerTrainStep")
         if not getattr(bucket, "fused_gather", False):
             raise ValueError("CapturedTowerTrainStep needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
@@ -760,6 +959,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         self.check_every = int(check_every)
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
         self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._alloc_att_loss(att_loss, net.netLength, self.B, self.S, self.N, dev)
+        self.aux_loss = aux_loss
         self._alloc_mask_word(dev)
         self.norm = opt.norm
         state = self._state()
@@ -803,15 +1004,24 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
                      **self._net_arguments())
         self.cell = net.last_cell
-        loss, pred = net.loss_and_pred(logits, self.answers)
+        ce, pred = net.loss_and_pred(logits, self.answers)
+        loss, aux = ce, None
+        if self.att_loss is not None or self.aux_loss is not None:
+            cell, p = self.cell, net.netLength
+            state = MACCellTuple(cell.state_tensor("controls")[p], cell.state_tensor("memories")[p])      # the run's final state
+            terms = self._aux_terms(cell, state)
+            aux = terms[0] if len(terms) == 1 else terms[0] + terms[1]
+            loss = ce + aux
         self.bucket.begin_step(B, B)
         loss.backward()
         self.bucket.allreduce_(B, B)                        # one process: the gather; nothing is exchanged
         self.opt.step(flat_grad=self.bucket.flat, device_lr=True)
+        self._parts = (ce.detach(), None if aux is None else aux.detach())
         return loss.detach(), logits.detach(), pred
 
     def _issue(self):
         self.loss, self.logits, self.pred = self._eager()
+        self.ce, self.aux = self._parts
 
     def _stepped(self):
         """what a step writes besides its outputs"""
@@ -820,14 +1030,23 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     def _eager_reference(self):
         """the eager step from the optimizer's state as it is: clones of loss, logits, pred and _stepped(); the captured `.grad`
         tensors and `cell` are put back (CapturedTrainStep.eager_reference)"""
-        return self._eager_on_captured(self.bucket.tensors(), lambda: [t.clone() for t in list(self._eager()) + self._stepped()])
+        return self._eager_on_captured(self.bucket.tensors(),
+                                       lambda: [t.clone() for t in list(self._eager()) + self._stepped() + self._aux_written(self._parts[1])])
+
+    def _aux_written(self, aux):
+        """what a step with an auxiliary loss writes besides: the auxiliary part, and the rows of att_loss"""
+        return ([] if aux is None else [aux]) + ([] if self.aux_rows is None else [self.aux_rows])
 
     def _replays_match_eager(self, state, replays=3):
         g = torch.Generator().manual_seed(20240522)
         images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers,
                                                        self.images.device)
-        self._load_inputs(images, q, lengths, False, *self._random_groups(g))
+        index, kbl, iml = self._random_groups(g)
+        self._load_inputs(images, q, lengths, False, index, kbl, iml)
         self.answers.copy_(ans)
+        if self.att_loss is not None:
+            live = kbl if iml is None else iml[index.long()]     # the per-question sizes the gather makes on the device
+            self._randomise_att_loss(g, live if self.att_loss["on"] == "kb" else lengths.cpu())
         self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
 
         def from_state():                                   # the eager step and every replay start from the same state
@@ -836,12 +1055,17 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         from_state()
         want = self._eager_reference()
         names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
-        written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped())
+        names += ([] if self.aux is None else ["aux"]) + ([] if self.aux_rows is None else ["aux_rows"])
+        written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped() + self._aux_written(self.aux))
         return self._compare_replays(replays, written, want, before=from_state)
 
-    def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
-        """image_index / kb_lengths / image_lengths: CapturedTowerForward.load's"""
+    def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None,
+             att_target=None, att_row_weights=None, att_step_weights=None):
+        """image_index / kb_lengths / image_lengths: CapturedTowerForward.load's; att_target / att_row_weights / att_step_weights:
+        CapturedTrainStep.load's (a class built with att_loss=)"""
+        self._check_att_loss(att_target, att_row_weights, att_step_weights)
         self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
+        self._copy_att_loss(att_target, att_row_weights, att_step_weights)
         with torch.no_grad():
             self.answers.copy_(answers)
 
