@@ -652,6 +652,33 @@ int macx_att_loss(const float* att, const float* target, const int32_t* lengths,
                   const float* row_weights, int p, int B, int n, int kind, int target_steps, float eps, float scale,
                   float* loss_rows, float* d_att, void* stream);
 
+/* ---- the answer loss under per-question weights: partial batches, re-weighted samples, evaluation totals ----------
+ * macx_answer_loss with a weight per question that is DEVICE data, read when the kernel runs -- a captured graph of batch size B
+ * serves n < B questions (weights of 0 behind them) and any re-weighting, one graph for all of them.  (It stands behind
+ * macx_att_loss here, not beside macx_answer_loss, which it leaves as it is: the binding table follows the header's order.)
+ * weights: [B] fp32 or NULL (= all ones).  Question b is LIVE iff weights[b] > 0; everything else -- 0, negative, NaN -- is weight 0.
+ * W = sum of the live weights, summed in fp64 in one fixed order.
+ *   live row   loss_rows[b] = -log softmax(logits[b])[answers[b]], UNWEIGHTED: the bits macx_answer_loss writes; pred[b] = argmax (first
+ *              maximum); dlogits[b] = grad_scale * (w_b / W) * (softmax - onehot).  A label outside [0, A): NaN loss row, zero
+ *              gradient row, as in macx_answer_loss; that NaN reaches loss_out and totals.
+ *   dead row   neither logits[b] nor answers[b] is read (they may hold NaN or garbage): loss_rows[b] = +0.0f, pred[b] = -1,
+ *              dlogits[b] all +0.0f -- downstream the finite-gradient contract macx_att_loss states for w == 0.
+ *   loss_out   (may be NULL) loss_out[0] = sum_live w_b loss_rows[b] / W, the products and the sum in fp64, rounded once; W == 0: +0.0f,
+ *              and every gradient is +0.0f -- no division by zero, no NaN.
+ *   totals     (may be NULL) three doubles in device memory to which the call ADDS sum w_b loss_rows[b], sum w_b [pred[b] == answers[b]]
+ *              and W: fp64 products and sums in a fixed order, added by one thread with a plain load and store -- no atomics.  They
+ *              run on across calls and graph replays until the host clears them; calls that share a `totals` must be stream-ordered.
+ *   dlogits    (may be NULL) rows, pred, loss_out and totals only.
+ * With weights == NULL, W = B: rows and pred are macx_answer_loss's bit for bit; dlogits * B is its dlogits at grad_scale 1 within
+ * 2 ulp per entry (one division and one product in fp32; bit for bit when B is a power of two).
+ * One workgroup walks the batch, 16 questions per pass: no hand-off between workgroups.  Any B >= 1 is accepted and correct; the
+ * intended range is a training or evaluation batch, B up to a few hundred (4 passes at B = 64), and the time grows with B / 16, so a
+ * loss over many thousands of rows belongs in several calls.  W is rounded once to fp32 for w_b / W.  Identical calls give identical bits.
+ * MACX_EINVAL, and nothing is launched: B < 1, A < 1, a NULL logits, answers, loss_rows or pred. */
+int macx_answer_loss_weighted(const float* logits, const int32_t* answers, const float* weights, int B, int A,
+                              float* loss_rows, int32_t* pred, float* dlogits, float* loss_out, double* totals,
+                              float grad_scale, void* stream);
+
 /* ---- the knowledge-base attention unit on its own (mac_cell.py:266-272: inter2att's softmax + att2Smry) ------------
  * The fused cell's own kernels behind a per-unit contract, so that the unit is testable in isolation:
  *   macx_kb_attend_fwd   att[B,N] = softmax_n(logits[B,N] + bias[0]);  info[B,d] = sum_n att KB        (ops.py:140-150)

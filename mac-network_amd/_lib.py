@@ -271,6 +271,9 @@ TABLE.update(macx_answer_loss=(_I, (_V, _V, _I, _I, _V, _V, _V, _F, _V)))
 # (att, target, lengths, step_weights, row_weights; p, B, n, kind, target_steps; eps, scale; loss_rows, d_att, stream)
 TABLE.update(macx_att_loss=(_I, (_V,) * 5 + (_I,) * 5 + (_F, _F) + (_V, _V, _V)))
 ATT_LOSS_KINDS = {"ce": 0, "entropy": 1}                                      # MACX_ATT_LOSS_*
+# ---- the answer loss under per-question device weights
+# (logits, answers, weights; B, A; loss_rows, pred, dlogits, loss_out, totals; grad_scale; stream)
+TABLE.update(macx_answer_loss_weighted=(_I, (_V,) * 3 + (_I, _I) + (_V,) * 5 + (_F, _V)))
 # ---- the knowledge-base attention unit on its own
 TABLE.update(
     macx_kb_attend_fwd=(_I, (_I, _I, _I) + (_V,) * 6),

@@ -2335,6 +2335,17 @@ int macx_att_loss(const float* att, const float* target, const int32_t* lengths,
   return MACX_OK;
 }
 
+// ---- the answer loss under per-question device weights, its weighted mean and an evaluation loop's running totals ---------------
+// (contract: include/macx.h; one workgroup of AW_WAVES waves, answer_loss_weighted_kernel in macx_ops.hip.h)
+int macx_answer_loss_weighted(const float* logits, const int32_t* answers, const float* weights, int B, int A, float* loss_rows,
+                              int32_t* pred, float* dlogits, float* loss_out, double* totals, float grad_scale, void* stream) {
+  if (!logits || !answers || !loss_rows || !pred || B < 1 || A < 1) return MACX_EINVAL;
+  hipLaunchKernelGGL(answer_loss_weighted_kernel, dim3(1), dim3(AW_WAVES * 64), 0, (hipStream_t)stream, logits, answers, weights, B, A,
+                     loss_rows, pred, dlogits, loss_out, totals, grad_scale);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
 // ---- the knowledge-base attention unit on its own (the fused cell's kernels behind a per-unit contract) -----------------
 // forward: att = softmax_n(logits + bias), info = sum_n att KB       (ops.inter2att :140-146 + ops.att2Smry :149-150)
 int macx_kb_attend_fwd(int B, int N, int d, const float* logits, const float* bias, const float* kb, float* att, float* info,

@@ -187,6 +187,99 @@ __global__ __launch_bounds__(256) void answer_loss_kernel(const float* logits, c
   }
 }
 
+// The weighted twin of answer_loss_kernel (macx_answer_loss_weighted, include/macx.h): per-question weights read from device memory
+// when the kernel runs, the weighted-mean loss and the running totals of an evaluation loop.  ONE workgroup of AW_WAVES waves walks
+// the batch, one wave per question and AW_WAVES questions at a time, so every sum over the batch stays inside the workgroup: nothing
+// is handed from one workgroup to another, nothing is atomic, and every order is fixed by (B, A) alone.
+//   W      every wave sums the live weights itself, lanes strided over b, in fp64, combined by the fixed xor tree: the same bits in
+//          every wave (fp32 weights summed in fp64: B = 64 ones give exactly 64)
+//   live   the row code of answer_loss_kernel, expression for expression (the same loss row and pred bits), the gradient scaled by
+//          scale * (w / W)
+//   dead   !(w > 0): left before the first load of logits[b] or answers[b]
+//   sums   each wave adds w * loss and w * [pred == answer] of its questions in fp64, in the order it walks them; thread 0 adds the
+//          AW_WAVES partial sums in wave order, writes loss_out and adds to totals with plain loads and stores
+constexpr int AW_WAVES = 16;
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(AW_WAVES * 64) void answer_loss_weighted_kernel(const float* logits, const int32_t* answers, const float* weights,
+                                                                             int B, int A, float* loss_rows, int32_t* pred, float* dlogits,
+                                                                             float* loss_out, double* totals, float scale) {
+  __shared__ double part_loss[AW_WAVES], part_hit[AW_WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double wl = 0.0;
+  for (int b = lane; b < B; b += 64) {
+    const float w = weights ? weights[b] : 1.f;
+    if (w > 0.f) wl += (double)w;                         // (NaN and negative weights fail the comparison: weight 0)
+  }
+  const double W = wave_sum_f64(wl);
+  const float Wf = (float)W;
+  double sum_loss = 0.0, sum_hit = 0.0;
+  for (int b = wave; b < B; b += AW_WAVES) {              // wave-uniform: a whole wave is live or dead
+    const float w = weights ? weights[b] : 1.f;
+    if (!(w > 0.f)) {                                     // dead: out before any load of the row
+      if (lane == 0) {
+        loss_rows[b] = 0.f;
+        pred[b] = -1;
+      }
+      if (dlogits)
+        for (int c = lane; c < A; c += 64) dlogits[(size_t)b * A + c] = 0.f;
+      continue;
+    }
+    const float* p = logits + (size_t)b * A;
+    float m = -INFINITY;
+    int am = 0x7FFFFFFF;
+    for (int c = lane; c < A; c += 64) {
+      const float v = p[c];
+      if (v > m) { m = v; am = c; }                       // strict: keeps the first maximum of this lane's columns
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+      const float om = __shfl_xor(m, s, 64);
+      const int oa = __shfl_xor(am, s, 64);
+      if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+    }
+    float z = 0.f;
+    for (int c = lane; c < A; c += 64) z += expf(p[c] - m);
+    z = wave_sum(z);
+    const int ans = answers[b];
+    const bool valid = ans >= 0 && ans < A;               // an out-of-range label: NaN loss row, no gradient (answer_loss_kernel)
+    const float loss = valid ? (m + logf(z)) - p[ans] : NAN;
+    if (lane == 0) {
+      loss_rows[b] = loss;
+      pred[b] = am;
+    }
+    if (dlogits) {
+      const float inv = 1.0f / z;
+      const float k = scale * (w / Wf);
+      for (int c = lane; c < A; c += 64)
+        dlogits[(size_t)b * A + c] = valid ? (expf(p[c] - m) * inv - (c == ans ? 1.f : 0.f)) * k : 0.f;
+    }
+    sum_loss += (double)w * (double)loss;
+    if (am == ans) sum_hit += (double)w;
+  }
+  if (lane == 0) {
+    part_loss[wave] = sum_loss;
+    part_hit[wave] = sum_hit;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double L = 0.0, H = 0.0;
+    for (int k = 0; k < AW_WAVES; ++k) {
+      L += part_loss[k];
+      H += part_hit[k];
+    }
+    if (loss_out) loss_out[0] = W > 0.0 ? (float)(L / W) : 0.f;
+    if (totals) {
+      totals[0] = totals[0] + L;
+      totals[1] = totals[1] + H;
+      totals[2] = totals[2] + W;
+    }
+  }
+}
+
 // dKB[b][n][c] (+)= att[b][n] * dinfo[b][c]: the knowledge-base gradient of ops.att2Smry
 __global__ __launch_bounds__(256) void kb_attend_dkb_kernel(const float* att, const float* dinfo, size_t n, int N, int d, int accumulate,
                                                             float* dkb) {

@@ -51,6 +51,12 @@ Losses on the run's own attention maps and states (attention supervision, entrop
 classes take `att_loss=dict(...)` -- one launch of the library (macx_att_loss) between the forward and the backward launches, its
 target and weights static tensors read at replay time -- and, where autograd runs, `aux_loss=callable` (`_AttLoss`;
 CapturedTrainStep documents both).
+
+Per-question answer weights and partial batches (the tower's two classes): `CapturedTowerTrainStep(weights=True)` and
+`CapturedTowerForward(score=True)` put macx_answer_loss_weighted in the place of macx_answer_loss -- a static [B] `weights` read when the
+kernel runs, a weighted-mean loss, optional running totals (output.AnswerTotals) -- and their load() takes n <= B questions: the slots
+behind them become copies of slot 0 with weight 0 (`_pad_slots`, `_TowerInputs._load_inputs`).  Built without, the classes issue the
+launches of before and refuse a batch of any other size than B.  The cell-level classes are out of this: their caller owns d_memory.
 """
 import warnings
 
@@ -225,6 +231,15 @@ def _check_lengths(t, n, N, check, name):
         raise ValueError("%s must lie in [1, %d] (the knowledge base's cells); got %d .. %d" % (name, N, int(t.min()), int(t.max())))
 
 
+def _pad_slots(buf, t, n, axis=0):
+    """the padding rule of a short batch: along `axis` slots 0 .. n-1 of the static tensor `buf` become `t`, slots n .. copies of slot 0
+    -- finite and in range whatever the batch holds, and the same launches for every n"""
+    live, rest = buf.narrow(axis, 0, n), buf.narrow(axis, n, buf.shape[axis] - n)
+    live.copy_(t)
+    if rest.shape[axis]:
+        rest.copy_(buf.narrow(axis, 0, 1).expand_as(rest))
+
+
 def _lengths_argument(who, name, given, built, how=None):
     """load() takes `name` exactly when the class was built with it (as d_memory); how: the constructor argument that builds it"""
     if given != built:
@@ -286,21 +301,36 @@ class _AttLoss:
         self.att_step_weights = torch.ones(p, device=dev)
         self.aux_rows = torch.zeros(p, B, device=dev)
 
-    def _check_att_loss(self, att_target, att_row_weights, att_step_weights):
-        """load()'s refusals: att_target exactly when built for kind "ce", the weights only when built with att_loss, shapes"""
+    def _check_att_loss(self, att_target, att_row_weights, att_step_weights, n=None):
+        """load()'s refusals: att_target exactly when built for kind "ce", the weights only when built with att_loss, shapes.
+        n: None, or the questions of a short batch (a tower class built with weights=True): the per-question axis is n long"""
         who = type(self).__name__
         _lengths_argument(who, "att_target", att_target is not None, self.att_target is not None, 'att_loss=dict(kind="ce")')
         for name, t in (("att_row_weights", att_row_weights), ("att_step_weights", att_step_weights)):
             if t is not None:
                 _lengths_argument(who, name, True, self.att_loss is not None, "att_loss=")
-        for name, t, buf in (("att_target", att_target, self.att_target), ("att_row_weights", att_row_weights, self.att_row_weights),
-                             ("att_step_weights", att_step_weights, self.att_step_weights)):
-            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != tuple(buf.shape) or not t.dtype.is_floating_point):
-                raise ValueError("%s must be a %s floating-point tensor" % (name, list(buf.shape)))
+        for name, t, buf, axis in (("att_target", att_target, self.att_target, -2), ("att_row_weights", att_row_weights, self.att_row_weights, 0),
+                                   ("att_step_weights", att_step_weights, self.att_step_weights, None)):
+            if t is None:
+                continue
+            want = list(buf.shape)
+            if n is not None and axis is not None:
+                want[axis] = n
+            if not torch.is_tensor(t) or list(t.shape) != want or not t.dtype.is_floating_point:
+                raise ValueError("%s must be a %s floating-point tensor" % (name, want))
 
-    def _copy_att_loss(self, att_target, att_row_weights, att_step_weights):
-        """... and its copies (None keeps what the buffer holds)"""
+    def _copy_att_loss(self, att_target, att_row_weights, att_step_weights, n=None):
+        """... and its copies (None keeps what the buffer holds).  n (a tower class built with weights=True): the target's slots behind
+        the n questions become copies of slot 0 (_pad_slots), the row weights there 0 -- and att_row_weights=None then means ones for
+        the n questions, not "keep": a longer batch after a shorter one would otherwise inherit its zeros"""
         with torch.no_grad():
+            if n is not None and self.att_loss is not None:
+                if att_target is not None:
+                    _pad_slots(self.att_target, att_target, n, axis=self.att_target.dim() - 2)
+                    att_target = None
+                self.att_row_weights[:n] = 1.0 if att_row_weights is None else att_row_weights
+                self.att_row_weights[n:] = 0.0
+                att_row_weights = None
             for t, buf in ((att_target, self.att_target), (att_row_weights, self.att_row_weights), (att_step_weights, self.att_step_weights)):
                 if t is not None:
                     buf.copy_(t)
@@ -723,6 +753,78 @@ class _TowerInputs(_AttLoss):
 
     G, image_index = None, None            # questions that share images (images=G): see _alloc_inputs
     kb_lengths, image_lengths = None, None # knowledge bases of per-question / per-image size: see _alloc_inputs
+    weights, totals, n = None, None, None  # per-question answer weights, running totals, questions of the last load: _alloc_weights
+    _WEIGHTS_HOW = "weights=True"          # the constructor argument that builds `weights`
+
+    def _alloc_weights(self, dev, totals):
+        """A static [B] float32 `weights` (all ones), which the answer-loss kernel (macx_answer_loss_weighted) reads when it runs: one
+        graph serves every n <= B questions (weights of 0 behind them) and every re-weighting.  totals: None, True (a new
+        output.AnswerTotals) or one to adopt.  Both are allocated here, before the capture: the host writes them between replays, so
+        they must not come from the graph's pool."""
+        from .output import AnswerTotals
+        self.weights = torch.ones(self.B, dtype=torch.float32, device=dev)
+        if totals is not None and totals is not False:
+            self.totals = AnswerTotals(dev) if totals is True else totals
+
+    @staticmethod
+    def _check_totals(who, weights, totals):
+        """what a constructor refuses about weights= / totals= before it asks for the device"""
+        from .output import AnswerTotals
+        if totals is not None and totals is not False and totals is not True and not isinstance(totals, AnswerTotals):
+            raise TypeError("%s: totals is None, True or a macx.output.AnswerTotals, not %r" % (who, totals))
+        if totals and not weights:
+            raise ValueError("%s: totals= belongs to the weighted answer loss: build the class with weights=True" % who)
+
+    def _loss_arguments(self):
+        """the keyword arguments of loss_and_pred that the static tensors stand for ({}: the call of before)"""
+        return {} if self.weights is None else {"weights": self.weights, "totals": self.totals}
+
+    def _draw_weights(self):
+        """the self-checks' weights: one 0 (the last question, B > 1), one fraction, the rest ones -- the device-read path, as
+        _draw_lengths for the lengths"""
+        if self.weights is not None:
+            w = torch.ones(self.B)
+            w[0] = 0.5
+            if self.B > 1:
+                w[-1] = 0.0
+            self.weights.copy_(w)
+
+    def _reset_weights(self):
+        """as construction leaves them: weights ones, totals cleared, a full batch"""
+        if self.weights is not None:
+            self.weights.fill_(1.0)
+            self.n = self.B
+        if self.totals is not None:
+            self.totals.reset()
+
+    def _refuse_other_size(self, questions):
+        """a class built without `weights` takes batches of B questions only (this used to be a reshape error, and n = 1 was broadcast
+        into every slot); load() raises it before any other complaint about the batch's shapes"""
+        if self.weights is None and torch.is_tensor(questions) and questions.dim() == 2 and questions.shape[0] != self.B:
+            raise ValueError("%s was captured for batches of %d questions and got %d: a class built with weights=True "
+                             "(CapturedTowerForward: score=True) takes any n <= %d" % (type(self).__name__, self.B, questions.shape[0], self.B))
+
+    def _batch(self, questions, weights, per_question):
+        """n, the questions of a load -- B, or with `weights` 1 <= n <= B -- and the refusals about it, raised before anything is
+        copied: per_question is the (name, tensor) list of the arguments that carry one entry per question"""
+        who = type(self).__name__
+        if weights is not None and self.weights is None:
+            raise TypeError("%s.load() takes no weights: the graph was captured without %s" % (who, self._WEIGHTS_HOW))
+        if not torch.is_tensor(questions) or questions.dim() != 2:
+            raise ValueError("questions must be a [n, %d] integer tensor" % self.S)
+        n = int(questions.shape[0])
+        self._refuse_other_size(questions)
+        if not 1 <= n <= self.B:
+            raise ValueError("%s was captured for batches of %d questions: load() takes 1 <= n <= %d of them, got %d" % (who, self.B, self.B, n))
+        for name, t in per_question:
+            if t is not None and (not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] != n):
+                raise ValueError("%s must have the leading size %d of questions (one entry per question)" % (name, n))
+        if weights is not None:
+            if not torch.is_tensor(weights) or weights.dtype != torch.float32:
+                raise TypeError("weights must be a float32 tensor")
+            if tuple(weights.shape) != (n,):
+                raise ValueError("weights must be [%d] (one per question), got %s" % (n, list(weights.shape)))
+        return n
 
     @staticmethod
     def _check_options(net, who, images, kb_lengths, image_lengths, train):
@@ -744,6 +846,7 @@ class _TowerInputs(_AttLoss):
         image_lengths (with images=G): a static [G] int32 `image_lengths` (all N), read by the captured gather (macx_kb_gather_l),
         which makes the cell's per-question lengths on the device.  Both are allocated here, before the capture."""
         self.B, self.S, self.H, self.W, self.imageInDim = int(B), int(S), int(H), int(W), int(imageInDim)
+        self.n = self.B
         self.N = net.stem.out_hw[0] * net.stem.out_hw[1]
         if kb_lengths:
             self.kb_lengths = torch.full((self.B,), self.N, dtype=torch.int32, device=dev)
@@ -777,24 +880,45 @@ class _TowerInputs(_AttLoss):
         iml = None if self.image_lengths is None else _draw_lengths(gen, self.G, self.N)
         return index, kbl, iml
 
-    def _load_inputs(self, images, questions, lengths, check_ids, image_index=None, kb_lengths=None, image_lengths=None):
+    def _load_inputs(self, images, questions, lengths, check_ids, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
+                     weights=None):
+        """A batch into the static tensors.  A class built with `weights` takes n <= B questions (n = questions.shape[0]; with
+        images=G also g <= G images): every per-question argument -- lengths, answers, images (one image per question), image_index,
+        kb_lengths; the training step's att_target and att_row_weights: _check_att_loss -- must have that leading size (ValueError
+        naming it).
+        Slots n .. B-1 of every per-question static tensor become copies of slot 0 (_pad_slots: finite and in range), their weights 0;
+        image slots g .. G-1 copies of image 0 and of image_lengths[0].  A class built without `weights` refuses n != B."""
         who = type(self).__name__
         _lengths_argument(who, "kb_lengths", kb_lengths is not None, self.kb_lengths is not None)
         _lengths_argument(who, "image_lengths", image_lengths is not None, self.image_lengths is not None)
+        per_question = [("lengths", lengths), ("answers", answers), ("image_index", image_index), ("kb_lengths", kb_lengths)]
+        # (images: with one image per question, and in a class built with `weights` only -- a class built without keeps taking any
+        # tensor with the static tensor's element count, e.g. [B * N, C], as it always did)
+        n = self._batch(questions, weights, per_question + ([("images", images)] if self.G is None and self.weights is not None else []))
+        g = n if self.G is None else self.G
+        if self.G is not None and self.weights is not None:
+            g = int(images.shape[0]) if torch.is_tensor(images) and images.dim() else 0
+            if not 1 <= g <= self.G:
+                raise ValueError("images: this graph was captured for %d shared images: load() takes 1 <= g <= %d of them, got %d"
+                                 % (self.G, self.G, g))
         if kb_lengths is not None:
-            _check_lengths(kb_lengths, self.B, self.N, check_ids, "kb_lengths")
+            _check_lengths(kb_lengths, n, self.N, check_ids, "kb_lengths")
         if image_lengths is not None:
-            _check_lengths(image_lengths, self.G, self.N, check_ids, "image_lengths")
+            _check_lengths(image_lengths, g, self.N, check_ids, "image_lengths")
         if self.G is None and image_index is not None:
             raise ValueError("this graph was captured with one image per question (images=None): it takes no image_index")
         if self.G is not None:
             if image_index is None:
                 raise ValueError("this graph was captured for %d shared images (images=%d): load() needs the [%d] image_index"
-                                 % (self.G, self.G, self.B))
-            if tuple(image_index.shape) != (self.B,) or image_index.dtype.is_floating_point or image_index.dtype == torch.bool:
-                raise ValueError("image_index must be a [%d] integer tensor" % self.B)
-            if check_ids and (int(image_index.max()) >= self.G or int(image_index.min()) < 0):
-                raise IndexError("image_index outside [0, %d)" % self.G)
+                                 % (self.G, self.G, n))
+            if tuple(image_index.shape) != (n,) or image_index.dtype.is_floating_point or image_index.dtype == torch.bool:
+                raise ValueError("image_index must be a [%d] integer tensor" % n)
+            if check_ids and (int(image_index.max()) >= g or int(image_index.min()) < 0):
+                raise IndexError("image_index outside [0, %d)" % g)
+        if self.weights is None and torch.is_tensor(images) and images.numel() != self.images.numel():
+            # (any layout with the static tensor's element count is taken, as always; anything else used to be a reshape error)
+            raise ValueError("images: this graph was captured for %s image features and got %s: a class built with weights=True "
+                             "(CapturedTowerForward: score=True) takes fewer images" % (list(self.images.shape), list(images.shape)))
         if check_ids:                          # the encoder's own validation (host synchronisation), outside the graph
             vocab = self.net.enc.vocab
             if int(questions.max()) > vocab or int(questions.min()) < 0:
@@ -805,15 +929,22 @@ class _TowerInputs(_AttLoss):
             if images.dim() == 4 and images.shape[1] == self.imageInDim and tuple(images.shape[2:]) == (self.H, self.W):
                 from .stem import k_nchw_to_nhwc          # the feed-dict layout [B, C, H, W]: transposed on the device
                 images = k_nchw_to_nhwc(images.to(self.images.device).contiguous(), self.imageInDim, self.H * self.W)
-            self.images.copy_(images.reshape(self.images.shape))
-            self.questions.copy_(questions)
-            self.lengths.copy_(lengths)
+            _pad_slots(self.images, images.reshape((g,) + tuple(self.images.shape[1:])), g)
+            _pad_slots(self.questions, questions, n)
+            _pad_slots(self.lengths, lengths, n)
             if self.G is not None:
-                self.image_index.copy_(image_index)
+                _pad_slots(self.image_index, image_index, n)
             if kb_lengths is not None:
-                self.kb_lengths.copy_(kb_lengths)
+                _pad_slots(self.kb_lengths, kb_lengths, n)
             if image_lengths is not None:
-                self.image_lengths.copy_(image_lengths)
+                _pad_slots(self.image_lengths, image_lengths, g)
+            if answers is not None:
+                _pad_slots(self.answers, answers, n)
+            if self.weights is not None:
+                self.weights[:n] = 1.0 if weights is None else weights
+                self.weights[n:] = 0.0
+        self.n = n
+        return n
 
 
 class CapturedTowerForward(_Captured, _TowerInputs):
@@ -845,43 +976,84 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     Copies on the captured path: none -- every module writes into outputs it allocates from the graph's pool, the cell's final
     state and attentions are views of its `saved` buffer."""
     _WHAT = ("tower", "forward")
+    _WEIGHTS_HOW = "score=True"
+    answers, loss = None, None
 
     def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None, kb_lengths=False,
-                 image_lengths=False):
+                 image_lengths=False, score=False):
+        """score=True: the graph scores its answers -- static int32 [B] `answers`, float32 [B] `weights` (ones) and an
+        output.AnswerTotals `totals`, allocated with the other inputs; the argmax launch becomes macx_answer_loss_weighted without a
+        gradient, which adds every replay's weighted loss, correct count and weight to `totals`.  load() / __call__ then take
+        answers= (required) and weights=, and n <= B questions (g <= G images) by _load_inputs' padding rule; __call__ returns
+        logits[:n] (a view, valid until the next call), `fwd.pred` holds -1 behind the n questions, `fwd.loss` the batch's weighted
+        mean, `fwd.n` is n.  An evaluation loop synchronises once per epoch:
+
+            fwd.totals.reset()
+            for images, questions, lengths, answers in batches: fwd(images, questions, lengths, answers=answers)
+            result = fwd.totals.read()                # {"loss": .., "accuracy": .., "weight": ..}
+
+        Out of scope: several processes (the totals are this process's), question length S and cell count N other than the
+        capture's, and towers with generic modules (capture stays refused; the eager net.loss_and_pred(logits, answers, weights=,
+        totals=) works for them, because it only sees logits).  Without score the class is what it was."""
         self._check_options(net, "CapturedTowerForward", images, kb_lengths, image_lengths, train=False)
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
-        self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if score:
+            self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self._alloc_weights(dev, True)
+        else:
+            self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
-        self._self_check(verify)
+        try:
+            self._self_check(verify)
+        finally:
+            self._reset_weights()                           # warm-up and verification scored their inputs: the totals start cleared
 
     @torch.no_grad()
     def _eager(self):
         from .output import _AnswerLoss
         logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **self._net_arguments())
         self.cell = self.net.last_cell                      # (status(): the latest run's buffers)
+        if self.weights is not None:                        # score=True: the weighted call, dlogits = NULL (no_grad), one kernel
+            loss, pred = self.net.loss_and_pred(logits, self.answers, **self._loss_arguments())
+            return logits, pred, loss
         _, pred = _AnswerLoss.apply(logits, self._no_answers)          # addPredOp's argmax (first maximum), one kernel
         return logits, pred
 
     def _issue(self):
-        self.logits, self.pred = self._eager()
+        out = self._eager()
+        self.logits, self.pred = out[:2]
+        if self.weights is not None:
+            self.loss = out[2]
         self.attentions = self.cell.attentions
 
     def _replays_match_eager(self, replays=3):
         g = torch.Generator().manual_seed(20240521)
-        images, q, lengths, _ = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, 2, self.images.device)
-        self._load_inputs(images, q, lengths, False, *self._random_groups(g))
-        want = self._eager_on_captured([], lambda: [t.clone() for t in self._eager()])
-        return self._compare_replays(replays, lambda: [("logits", self.logits), ("pred", self.pred)], want)
+        answers = 2 if self.weights is None else self.net.out.answers
+        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, answers, self.images.device)
+        self._load_inputs(images, q, lengths, False, *self._random_groups(g), answers=None if self.weights is None else ans)
+        self._draw_weights()
+        written = lambda: [("logits", self.logits), ("pred", self.pred)]
+        clear = None
+        if self.weights is not None:                        # every run adds to the totals: each starts from cleared ones
+            written = lambda: [("logits", self.logits), ("pred", self.pred), ("loss", self.loss), ("totals", self.totals.tensor)]
+            clear = self.totals.reset
+            clear()
+        want = self._eager_on_captured([], lambda: [t.clone() for t in list(self._eager()) + ([] if clear is None else [self.totals.tensor])])
+        return self._compare_replays(replays, written, want, before=clear)
 
-    def load(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
+    def load(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
+             weights=None):
         """image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
         validated with the ids (check_ids).  kb_lengths [B] / image_lengths [G]: the integer sizes of a graph captured with
-        kb_lengths=True / image_lengths=True (required there, refused otherwise); 1 <= size <= N is validated with the ids"""
-        self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
+        kb_lengths=True / image_lengths=True (required there, refused otherwise); 1 <= size <= N is validated with the ids.
+        answers [n] / weights [n] (float32, default ones): a graph captured with score=True, and such a graph only; it takes
+        n <= B questions (the constructor's docstring)"""
+        _lengths_argument(type(self).__name__, "answers", answers is not None, self.answers is not None, "score=True")
+        return self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
 
     def replay(self):
         if self.captured:
@@ -889,10 +1061,11 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         else:                                               # (module docstring: slower where the host is slow, never wrong)
             self._issue()
         self._count_replay()
-        return self.logits
+        return self.logits if self.weights is None else self.logits[:self.n]
 
-    def __call__(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None):
-        self.load(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
+    def __call__(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
+                 weights=None):
+        self.load(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
         return self.replay()
 
 
@@ -937,14 +1110,36 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
 
     Copies on the captured path: none issued by the library or by this class.  What autograd adds is torch's own business: it
     adopts each returned gradient as the parameter's .grad without a copy as long as nobody else holds it (the module functions
-    return fresh tensors), and sums the two gradients of vecQuestions with a kernel."""
+    return fresh tensors), and sums the two gradients of vecQuestions with a kernel.
+
+    weights=True: per-question answer weights and partial batches from the ONE graph.  A static float32 [B] `step.weights` (ones) is
+    allocated with the other inputs and read by the loss kernel when it runs (macx_answer_loss_weighted in the place of
+    macx_answer_loss: one launch for one launch, no timing is claimed); the step trains on the weighted mean
+    sum_live w_b l_b / sum_live w_b -- all ones: the mean.  load(..., weights=) takes n <= B questions (n = questions.shape[0]; with
+    images=G also g <= G images): slots n .. B-1 of every per-question static tensor become copies of slot 0, so they stay finite and in
+    range and the graph runs the same launches, and their weights become 0 -- the loss kernel does not read a dead question's logits or
+    answer and writes an all +0 gradient row, every backward consumer is linear in that row, so no parameter gradient, loss or
+    prediction depends on what the dead slots hold.  `step.loss` / `step.ce` are the weighted means, `step.pred` holds -1 in
+    dead slots, `step.n` is n.  With att_loss the att_row_weights of the dead slots become 0 and att_row_weights=None means ones for the
+    n questions; the attention loss keeps its p * B normaliser (a short batch's auxiliary part is not rescaled to n).
+    totals=True (or an output.AnswerTotals to adopt): every replay adds its weighted loss, correct count and weight to `step.totals`,
+    read with one synchronisation per epoch (totals.read()); construction leaves it cleared.
+    The self-check draws weights too (one 0, one fraction, the rest ones).  Built without weights the class issues the launches it
+    always issued and refuses n != B.  Out of scope: several processes (with global_batch != B the weighted mean would need W summed over
+    the ranks: a bucket that spans more than one process is refused with weights=True), the cell-level classes (their caller owns
+    d_memory), S and N other than the capture's, and towers with generic modules (capture stays refused as it is; the eager
+    net.loss_and_pred(logits, answers, weights=) works for them, because it only sees logits)."""
 
     aux = None
 
     def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0, images=None,
-                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None):
+                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None, weights=False, totals=None):
         self._check_options(net, "CapturedTowerTrainStep", images, kb_lengths, image_lengths, train=True)
         att_loss = _att_loss_spec("CapturedTowerTrainStep", att_loss)
+        self._check_totals("CapturedTowerTrainStep", weights, totals)
+        if weights and getattr(bucket, "_active", lambda: False)():
+            raise ValueError("CapturedTowerTrainStep(weights=True): the bucket spans more than one process; the weighted mean over a "
+                             "global batch needs the weights summed over the ranks, which the step does not do")
         dev = _require_fused_tower(net, "CapturedTowerTrainStep")
         if not getattr(bucket, "fused_gather", False):
             raise ValueError("CapturedTowerTrainStep needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
@@ -959,6 +1154,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         self.check_every = int(check_every)
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
         self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if weights:
+            self._alloc_weights(dev, totals)
         self._alloc_att_loss(att_loss, net.netLength, self.B, self.S, self.N, dev)
         self.aux_loss = aux_loss
         self._alloc_mask_word(dev)
@@ -970,7 +1167,10 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
             opt.advance()
             self._eager()
         self._capture(dev, warmup, warm, [(self.graph, self._issue)], before=self._clear_grads)
-        self._self_check(verify, state)
+        try:
+            self._self_check(verify, state)
+        finally:
+            self._reset_weights()                           # ... and scored them: weights back to ones, the totals cleared
         self._restore(state)                                # warm-up (and verification) trained on zeros: undo
 
     def _after_capture(self):
@@ -1004,7 +1204,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
                      **self._net_arguments())
         self.cell = net.last_cell
-        ce, pred = net.loss_and_pred(logits, self.answers)
+        ce, pred = net.loss_and_pred(logits, self.answers, **self._loss_arguments())
         loss, aux = ce, None
         if self.att_loss is not None or self.aux_loss is not None:
             cell, p = self.cell, net.netLength
@@ -1034,8 +1234,10 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
                                        lambda: [t.clone() for t in list(self._eager()) + self._stepped() + self._aux_written(self._parts[1])])
 
     def _aux_written(self, aux):
-        """what a step with an auxiliary loss writes besides: the auxiliary part, and the rows of att_loss"""
-        return ([] if aux is None else [aux]) + ([] if self.aux_rows is None else [self.aux_rows])
+        """what a step with an auxiliary loss writes besides: the auxiliary part, and the rows of att_loss; what a step with totals
+        adds to"""
+        return (([] if aux is None else [aux]) + ([] if self.aux_rows is None else [self.aux_rows])
+                + ([] if self.totals is None else [self.totals.tensor]))
 
     def _replays_match_eager(self, state, replays=3):
         g = torch.Generator().manual_seed(20240522)
@@ -1048,26 +1250,35 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
             live = kbl if iml is None else iml[index.long()]     # the per-question sizes the gather makes on the device
             self._randomise_att_loss(g, live if self.att_loss["on"] == "kb" else lengths.cpu())
         self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
+        self._draw_weights()
 
         def from_state():                                   # the eager step and every replay start from the same state
             self._restore(state)
             self.opt.advance()
+            if self.totals is not None:
+                self.totals.reset()
         from_state()
         want = self._eager_reference()
         names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
         names += ([] if self.aux is None else ["aux"]) + ([] if self.aux_rows is None else ["aux_rows"])
+        names += [] if self.totals is None else ["totals"]
         written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped() + self._aux_written(self.aux))
         return self._compare_replays(replays, written, want, before=from_state)
 
     def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None,
-             att_target=None, att_row_weights=None, att_step_weights=None):
+             att_target=None, att_row_weights=None, att_step_weights=None, weights=None):
         """image_index / kb_lengths / image_lengths: CapturedTowerForward.load's; att_target / att_row_weights / att_step_weights:
-        CapturedTrainStep.load's (a class built with att_loss=)"""
-        self._check_att_loss(att_target, att_row_weights, att_step_weights)
-        self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths)
-        self._copy_att_loss(att_target, att_row_weights, att_step_weights)
-        with torch.no_grad():
-            self.answers.copy_(answers)
+        CapturedTrainStep.load's (a class built with att_loss=).
+        weights: a class built with weights=True, and such a class only: [n] float32 (default ones).  Such a class takes n <= B
+        questions -- every per-question argument (lengths, answers, images or image_index, kb_lengths, att_target, att_row_weights)
+        with that leading size -- by the padding rule of the class docstring; a class built without refuses n != B.  Returns n."""
+        self._refuse_other_size(questions)                  # (ahead of the att_* shapes: a short batch is the first thing to say)
+        short = self.weights is not None and torch.is_tensor(questions) and questions.dim() == 2
+        n = int(questions.shape[0]) if short else None
+        self._check_att_loss(att_target, att_row_weights, att_step_weights, n)
+        n = self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
+        self._copy_att_loss(att_target, att_row_weights, att_step_weights, n if self.weights is not None else None)
+        return n
 
     def replay(self, iteration=None):
         """iteration: None keeps the current mask word; an int draws the masks of word mix32(iteration).  Counts the optimizer's

@@ -105,8 +105,12 @@ class MACNetCore(torch.nn.Module):
         return self.out(state.memory, vecQuestions, train=train, seed=seed, b0=b0, **word)   # model.py:805-809
 
     @staticmethod
-    def loss_and_pred(logits, answers):
-        return answer_loss_and_pred(logits, answers)                                 # model.py:812-813
+    def loss_and_pred(logits, answers, weights=None, totals=None):
+        """weights / totals: output.answer_loss_and_pred's (per-question device weights with the weighted-mean loss, an
+        output.AnswerTotals the launch adds to); both None is the call of before"""
+        if weights is None and totals is None:
+            return answer_loss_and_pred(logits, answers)                             # model.py:812-813
+        return answer_loss_and_pred(logits, answers, weights=weights, totals=totals)
 
 
 class MACNet(MACNetCore):

@@ -273,8 +273,100 @@ class _AnswerLoss(torch.autograd.Function):
         return dl * (g_rows * dl.shape[0]).unsqueeze(1), None
 
 
-def answer_loss_and_pred(logits, answers):
+class AnswerTotals:
+    """The running totals of macx_answer_loss_weighted: three doubles in device memory -- sum of w * loss, sum of w * [pred == answer],
+    sum of w -- to which every call that is handed this object ADDS, replays of a captured graph included, until reset().
+
+        totals = macx.output.AnswerTotals(device)
+        for batch in loader: ... net.loss_and_pred(logits, answers, weights, totals=totals)       # no host synchronisation
+        totals.read()                                  # {"loss": .., "accuracy": .., "weight": ..}: the one synchronisation
+
+    `tensor` is the buffer ([3] float64).  A captured class allocates it before its capture: the host clears it outside the graph
+    (DESIGN 8)."""
+
+    def __init__(self, device):
+        self.tensor = torch.zeros(3, dtype=torch.float64, device=device)
+
+    def reset(self):
+        self.tensor.zero_()
+
+    def read(self):
+        """dict(loss = sum w l / W, accuracy = sum w [correct] / W, weight = W); both ratios are 0 when W == 0.  Synchronises."""
+        loss, hit, w = self.tensor.tolist()
+        return dict(loss=loss / w if w > 0 else 0.0, accuracy=hit / w if w > 0 else 0.0, weight=w)
+
+
+def _answer_weights(weights, B):
+    """the weights= argument, in the style of losses._device_f32: a [B] float32 tensor on the HIP device (None: all ones)"""
+    if weights is None:
+        return None
+    if not torch.is_tensor(weights) or weights.dtype != torch.float32:
+        raise TypeError("weights must be a float32 tensor")
+    if tuple(weights.shape) != (B,):
+        raise ValueError("weights must be [%d] (one per question), got %s" % (B, list(weights.shape)))
+    if not weights.is_cuda:
+        raise RuntimeError("weights must live on the HIP device: the loss has no CPU path")
+    return weights.detach().contiguous()
+
+
+def _answer_totals(totals):
+    if totals is None:
+        return None
+    if not isinstance(totals, AnswerTotals):
+        raise TypeError("totals is None or a macx.output.AnswerTotals, not %r" % (totals,))
+    if not totals.tensor.is_cuda:
+        raise RuntimeError("totals must live on the HIP device: the loss has no CPU path")
+    return totals.tensor
+
+
+class _WeightedAnswerLoss(torch.autograd.Function):
+    """macx_answer_loss_weighted: the weighted-mean cross-entropy (a 0-dim tensor the kernel wrote), argmax with -1 in dead rows, and
+    the gradient of that mean from the same launch; the backward pass returns the stored dlogits times the incoming scalar.  Weights
+    and totals are data: no gradient flows to them.  Without a gradient to compute (no_grad, constant logits) dlogits is NULL."""
+
+    @staticmethod
+    def forward(ctx, logits, answers, weights, totals):
+        if not logits.is_cuda:
+            raise RuntimeError("logits must live on the HIP device: the loss has no CPU path")
+        L = _lib.lib()
+        lg = logits.detach().contiguous()
+        B, A = lg.shape
+        ans = answers.to(device=lg.device, dtype=torch.int32).contiguous()
+        rows = torch.empty(B, dtype=torch.float32, device=lg.device)
+        pred = torch.empty(B, dtype=torch.int32, device=lg.device)
+        loss = torch.empty((), dtype=torch.float32, device=lg.device)
+        dl = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
+        ptr = _lib.ptr
+        _lib.check(L.macx_answer_loss_weighted(ptr(lg), ptr(ans), ptr(weights), B, A, ptr(rows), ptr(pred), ptr(dl), ptr(loss), ptr(totals),
+                                               1.0, _lib.stream_of(lg)), "macx_answer_loss_weighted")
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(pred, rows)
+        return loss, pred, rows
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_pred, _g_rows):
+        (dl,) = ctx.saved_tensors
+        return dl * g_loss, None, None, None
+
+
+def answer_loss_and_pred(logits, answers, weights=None, totals=None):
     """addAnswerLossOp (model.py:593-599) + addPredOp (model.py:603-612): mean sparse CE, int32 argmax -- one HIP kernel
-    (macx_answer_loss) for both and for the gradient."""
-    rows, pred = _AnswerLoss.apply(logits, answers)
-    return rows.mean(), pred
+    (macx_answer_loss) for both and for the gradient.
+
+    weights / totals (both None: the call above, launch for launch): one launch of macx_answer_loss_weighted instead.
+    weights: a [B] float32 tensor on the HIP device, read when the kernel runs; question b is live iff weights[b] > 0.  The loss becomes
+    the weighted mean  sum_live w_b l_b / W,  W = sum_live w_b  (0 when no question is live), differentiable with respect to logits;
+    pred is -1 in dead rows, whose logits and answers are never read (a partial batch pads with anything) and whose gradient rows are
+    exactly +0.  None with totals given: all ones.  totals: an AnswerTotals to which the launch adds its weighted loss, correct count
+    and weight.  TypeError / ValueError / RuntimeError for anything else; no CPU path.
+    The call only sees logits, so it serves every tower, the ones with generic modules included (whose capture stays refused:
+    graph.CapturedTowerTrainStep).  Out of scope: several processes -- the weighted mean over a global batch needs W summed over the
+    ranks, which this call does not do; the cell-level captured classes, whose caller owns d_memory and so the loss."""
+    if weights is None and totals is None:
+        rows, pred = _AnswerLoss.apply(logits, answers)
+        return rows.mean(), pred
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError("logits must be a [B, answers] tensor")
+    weights, totals = _answer_weights(weights, logits.shape[0]), _answer_totals(totals)
+    loss, pred, _ = _WeightedAnswerLoss.apply(logits, answers, weights, totals)
+    return loss, pred
