@@ -61,6 +61,23 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += dpp_mov_f<0x121>(v);      // row_ror:1
   return v;
 }
+// row16_sum of NV independent values, step by step across all of them: a DPP move waits on the VALU write of its source, and a
+// lone chain fills those wait states with s_nop -- side by side the other chains fill them.  Per value the same rotation tree.
+template <int CTRL, int NV>
+__device__ __forceinline__ void row16_step_n(float (&v)[NV]) {
+  float t[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) t[i] = dpp_mov_f<CTRL>(v[i]);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] += t[i];
+}
+template <int NV>
+__device__ __forceinline__ void row16_sum_n(float (&v)[NV]) {
+  row16_step_n<0x128>(v);
+  row16_step_n<0x124>(v);
+  row16_step_n<0x122>(v);
+  row16_step_n<0x121>(v);
+}
 
 // sum over the 8 lanes 8 k .. 8 k + 7; every lane of the group receives the same value
 __device__ __forceinline__ float row8_sum(float v) {
@@ -483,17 +500,18 @@ struct ChainCtx {
   __device__ __forceinline__ void colsum(const f32x4 (&acc)[RT][CT], float* part) const {
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
+      float s[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        float s = acc[0][c][q];
+        s[q] = acc[0][c][q];
 #pragma unroll
-        for (int t = 1; t < RT; ++t) s += acc[t][c][q];
-        s = colred_sum(s);
-        if (col_writer()) {
-          const int col = acol(c) + q;
-          if (NWR == 1) part[col] = s;
-          else sCol[wr * D + col] = s;
-        }
+        for (int t = 1; t < RT; ++t) s[q] += acc[t][c][q];
+      }
+      row16_sum_n(s);                          // the group's four columns side by side
+      if (col_writer()) {
+        float* dst = NWR == 1 ? part : sCol + wr * D;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dst[acol(c) + q] = s[q];
       }
     }
   }
@@ -523,6 +541,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
     const bool drop1 = p.thr1 < (1u << 24), drop2 = p.thr2 < (1u << 24);
     const uint32_t key1 = run_key(k1, p.word), key2 = run_key(k2, p.word);
     const size_t Rp2 = (size_t)M + H2_PAD_ROWS;
+    const uint32_t cvm = lane_mask(x.cvalid);
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
       const int kg = x.ckg(j);
@@ -530,7 +549,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
       const float* src = p.kb + min(x.cgrow, (size_t)M - 1) * D + kg * 8;
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { v[j][q] = x.cvalid ? a0[q] : 0.f; v[j][4 + q] = x.cvalid ? a1[q] : 0.f; }
+      for (int q = 0; q < 4; ++q) { v[j][q] = mask_f(a0[q], cvm); v[j][4 + q] = mask_f(a1[q], cvm); }
     }
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
@@ -541,7 +560,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
 #pragma unroll
         for (int q = 0; q < 8; q += 2) byte |= keep_pair(e0 + q, key1, p.thr1) << q;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[j][q] = ((byte >> q) & 1u) ? v[j][q] * p.inv1 : 0.f;
+        for (int q = 0; q < 8; ++q) v[j][q] = mask_f(v[j][q] * p.inv1, bit_mask(byte, q));
         if (bits1 && x.cvalid) bits1[x.cgrow * KG + kg] = (uint8_t)byte;
       }
       if (drop2) {
@@ -652,6 +671,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
     x.load_tile(p.X, x.sE);
   }
   if (p.dbg & 1) return;
+  MACX_MARK("fwd 0");                        // stage 0 done
 
   f32x4 acc[RT][CT];
   // x = act(acc * 2^-(eA[row] + eW) + bias), left in acc
@@ -683,6 +703,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
   if (p.mode != 1) {
     x.zero_acc(acc);
     x.template kloop<KV>(acc, p.Wx.planes);
+    MACX_MARK("fwd 1");                      // X product done
     bias_act(std::integral_constant<int, ACT_NON>{}, x.sE, *p.Wx.exp, p.bx);
     x.rowmax(acc);
     __syncthreads();                       // every wave is done reading P; sMax is complete
@@ -691,11 +712,13 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
     __syncthreads();
   }
   if (p.dbg & 2) return;
+  MACX_MARK("fwd 2");                        // X epilogue done
 
   // =====================================================================================================================
   // stage 2: H1 = act(X W1b + (X * y) W1a + b1)
   x.zero_acc(acc);
   x.template kloop<KV>(acc, p.W1b.planes);
+  MACX_MARK("fwd 3");                        // X W1b done
   constexpr bool YCOH = D == 512;                 // y may come from this launch's fillers (ChainPreP): agent-scope loads
   if constexpr (YCOH) {
     MACX_STAMP((int)blockIdx.x == p.pre.nfill, 9);
@@ -761,7 +784,9 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
         for (int q = 0; q < 4; ++q) acc[t][c][q] = ldexpf(acc[t][c][q], k);
     }
   }
+  MACX_MARK("fwd 4");                        // X * y conversion done
   x.template kloop<KV>(acc, p.W1a.planes);
+  MACX_MARK("fwd 5");                        // (X * y) W1a done
   bias_act_any(p.act1, x.sE2, *p.W1a.exp, p.b1);
   x.rowmax(acc);
   __syncthreads();
@@ -769,15 +794,18 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
   x.publish_rows(x.sE, C::PASS_EPI, p.H1);
   __syncthreads();
   if (p.dbg & 4) return;
+  MACX_MARK("fwd 6");                        // H1 epilogue done
 
   // =====================================================================================================================
   // stage 3: I2 = H1 W2 + b2 ; logits = dropout(act(I2 * c)) . w_k
   x.zero_acc(acc);
   x.template kloop<KV>(acc, p.W2.planes);
+  MACX_MARK("fwd 7");                        // H1 W2 done
   bias_act(std::integral_constant<int, ACT_NON>{}, x.sE, *p.W2.exp, p.b2);
   x.rowmax(acc);
   {
     const bool drop2 = p.thr2 < (1u << 24);
+    const float inv2 = drop2 ? p.inv2 : 1.0f;
     auto logit_pass = [&](auto act_c) __attribute__((always_inline)) {
       constexpr int ACT = decltype(act_c)::value;
 #pragma unroll
@@ -794,7 +822,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float g = chain_act(ACT, acc[t][c][q] * cv[q]);
-            if (drop2) g = ((kb >> q) & 1u) ? g * p.inv2 : 0.f;
+            g = mask_f(g * inv2, bit_mask(kb, q));      // keep bit ? g / keep : 0 (no dropout: every bit set, times one)
             part = fmaf(g, wv[q], part);
           }
         }
@@ -821,6 +849,7 @@ __global__ __launch_bounds__(512) void chain_fwd_kernel(const ChainFwdP p) {
     for (int w = 1; w < C::NWC; ++w) s += x.sPart[(w0 + w) * R + x.tid];          // fixed order
     p.logits[x.grow0 + x.tid] = ygave ? handoff_poison() : s;
   }
+  MACX_MARK("fwd 8");                        // I2 epilogue and logits done
 }
 
 // e0 / e1 (both or neither): HIP events that receive the KERNEL's own start and stop timestamps (hipExtLaunchKernelGGL: the dispatch
@@ -1039,8 +1068,13 @@ __global__ __launch_bounds__(512) void chain_dkb_rest_kernel(const ChainDkbP q, 
 
 // A2: readCtrlAct as a compile-time constant -- one kernel per activation (chain_bwd_launch_t); several arms in one kernel met in one
 // register allocation (two arms: 86 spilled registers; a per-value run-time switch: 102-104).
-template <int D_, int KV = 0, int A2 = -1, int R_ = 64>
+// TWO: N >= tile rows, so a tile touches at most two questions (what dkb_fill_plan relies on): stage B0 and the dy sums carry two
+// per-question accumulator sets instead of three and tell the two apart by one all-ones / zero word per row block (lane_mask)
+// instead of a compare and a select per value.  A second kernel, chosen by the launcher from N, for the same reason as A2: both
+// forms behind a uniform branch in one kernel met in one register allocation and spilled 59 - 72 registers.
+template <int D_, int KV = 0, int A2 = -1, int R_ = 64, bool TWO = false>
 __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
+  static_assert(!TWO || R_ == 64, "two-question tiles: the 64-row tile only (the short tiles serve small N and B)");
   using C = ChainCtx<D_, R_>;
   constexpr int D = C::D, R = C::R, KG = C::KG, CB = C::CB, CT = C::CT, RT = C::RT, IT = C::IT;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1056,9 +1090,9 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
     }
   }
 #ifdef MACX_FILL_PROF
-#define MACX_BSTAMP(k) do { if (p.dkb.prof && p.dkb.step == 5 && blockIdx.x == 0 && x.tid == 0) p.dkb.prof[PROF_BWD_OFF + (k)] = (uint32_t)__builtin_readcyclecounter(); } while (0)
+#define MACX_BSTAMP(k) do { MACX_MARK("bwd " #k); if (p.dkb.prof && p.dkb.step == 5 && blockIdx.x == 0 && x.tid == 0) p.dkb.prof[PROF_BWD_OFF + (k)] = (uint32_t)__builtin_readcyclecounter(); } while (0)
 #else
-#define MACX_BSTAMP(k) do { } while (0)
+#define MACX_BSTAMP(k) MACX_MARK("bwd " #k)
 #endif
   MACX_BSTAMP(0);
 
@@ -1167,10 +1201,19 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
         dlr[sb] = 8 * sb + r8 < x.nvalid ? a_r[sb] * (d_r[sb] - sDot[seg[sb]]) : 0.f;
       }
     };
-    float a_dw[8], a_db[8], a_dc[3][8];
+    constexpr int NSEG = TWO ? 2 : 3;                  // per-question accumulator sets
+    // TWO: the second question's rows and the rows past the end are told by one all-ones / zero word each per row block (lane_mask)
+    // and bit operations per value instead of selects, and the keep factor comes from a bit-field extract instead of a compare and
+    // a select.  With three questions the mask forms spilled 8 - 13 registers at every width: the selects stay there
+    float a_dw[8], a_db[8], a_dc[NSEG][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) a_dw[e] = a_db[e] = a_dc[0][e] = a_dc[1][e] = a_dc[2][e] = 0.f;
+    for (int e = 0; e < 8; ++e) {
+      a_dw[e] = a_db[e] = 0.f;
+#pragma unroll
+      for (int k = 0; k < NSEG; ++k) a_dc[k][e] = 0.f;
+    }
     const f32x4 w0 = *reinterpret_cast<const f32x4*>(x.sW + kg * 8), w1 = *reinterpret_cast<const f32x4*>(x.sW + kg * 8 + 4);
+    const uint32_t inv2b = __float_as_uint(p.inv2);
     auto block = [&](auto act_c, auto sb_c) __attribute__((always_inline)) {
       constexpr int ACTC = decltype(act_c)::value;
       const int ACT = ACTC >= 0 ? ACTC : p.act2;
@@ -1180,14 +1223,17 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
       float i2[8];
       h2_join8(raw[sb][0], raw[sb][1], inv[sb], i2);
       const bool rv = 8 * sb + r8 < x.nvalid;
+      const uint32_t rvm = lane_mask(rv);                     // TWO: the row exists
+      const uint32_t kbits = bits[sb] | bits_or;
+      const uint32_t second = lane_mask(seg[sb] != 0);       // TWO: the row belongs to the tile's second question
       float o[8];
       float m = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        i2[e] = rv ? i2[e] : 0.f;            // (pad rows hold anything, NaN included: select, do not multiply by zero)
+        i2[e] = TWO ? mask_f(i2[e], rvm) : (rv ? i2[e] : 0.f);       // (pad rows hold anything, NaN included: mask or select, do not multiply by zero)
         const float cv = e < 4 ? c0[e & 3] : c1[e & 3], wv = e < 4 ? w0[e & 3] : w1[e & 3];
         const float g = chain_act(ACT, i2[e] * cv);
-        const float f = (((bits[sb] | bits_or) >> e) & 1u) ? p.inv2 : 0.f;
+        const float f = TWO ? __uint_as_float(bit_mask(kbits, e) & inv2b) : (((kbits >> e) & 1u) ? p.inv2 : 0.f);       // keep bit ? 1 / keep : 0
         const float dz = (dlr[sb] * wv) * f * act_grad_from_out(ACT, g);
         const float ov = dz * cv;
         o[e] = ov;
@@ -1195,9 +1241,14 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
         a_dw[e] = fmaf(dlr[sb], g * f, a_dw[e]);              // dw_k += dl * dropped(G)
         a_db[e] += ov;
         const float t = dz * i2[e];                            // dc += dZ * I2, per question of the row
-        a_dc[0][e] += seg[sb] == 0 ? t : 0.f;
-        a_dc[1][e] += seg[sb] == 1 ? t : 0.f;
-        a_dc[2][e] += seg[sb] == 2 ? t : 0.f;
+        if constexpr (TWO) {
+          const float t1 = mask_f(t, second);
+          a_dc[0][e] += __uint_as_float(__float_as_uint(t) ^ __float_as_uint(t1));      // t where the mask is zero, else +0
+          a_dc[1][e] += t1;
+        } else {
+#pragma unroll
+          for (int k = 0; k < NSEG; ++k) a_dc[k][e] += seg[sb] == k ? t : 0.f;
+        }
       }
       mx[sb] = m;
       x.blk_park(kg, 8 * sb + r8, o);
@@ -1240,7 +1291,7 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
         a_dw[e] = row8_sum(a_dw[e]);
         a_db[e] = row8_sum(a_db[e]);
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
+        for (int k = 0; k < NSEG; ++k)
           if (k < nq) a_dc[k][e] = row8_sum(a_dc[k][e]);
       }
       if (r8 == 0) {
@@ -1249,7 +1300,7 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
         *reinterpret_cast<f32x4*>(db) = f32x4{a_db[0], a_db[1], a_db[2], a_db[3]};
         *reinterpret_cast<f32x4*>(db + 4) = f32x4{a_db[4], a_db[5], a_db[6], a_db[7]};
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
+        for (int k = 0; k < NSEG; ++k)
           if (k < nq) {
             *reinterpret_cast<f32x4*>(dc + k * D) = f32x4{a_dc[k][0], a_dc[k][1], a_dc[k][2], a_dc[k][3]};
             *reinterpret_cast<f32x4*>(dc + k * D + 4) = f32x4{a_dc[k][4], a_dc[k][5], a_dc[k][6], a_dc[k][7]};
@@ -1341,37 +1392,44 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
       sr[t] = h2_unscale(x.sE[x.arow(t)], eW);
     }
     float* stage = x.sW;                                 // [NWR][3][D] when the rows are split over two wave groups (sW and sC are idle)
+    {
+      constexpr int NSEG = TWO ? 2 : 3;                  // sums per column: one per question the tile can touch
+      // (the conditions stay selects here: they compile to the scalar-pair form, and row masks held in vector registers through
+      // the column loop spilled 14 registers in the d = 512 kernel)
 #pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      const int kg = x.akg(c);
-      float xv[RT][4];
-#pragma unroll
-      for (int t = 0; t < RT; ++t) {
-        const char* src = p.X.base + ((size_t)kg * Rp + gr[t]) * 16 + x.ahalf();
-        const u32x2 hh = *reinterpret_cast<const u32x2*>(src), hl = *reinterpret_cast<const u32x2*>(src + xpb);
-        h2_join4(hh, hl, h2_pow2(-(int)p.X.exps()[gr[t] * CB + (kg >> 4)]), xv[t]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float s3[3] = {0.f, 0.f, 0.f};
+      for (int c = 0; c < CT; ++c) {
+        const int kg = x.akg(c);
+        float xv[RT][4];
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
-          // (rows past the end read the last row again: select, their accumulators are zero but X need not be finite there)
-          const float v = x.arow(t) < x.nvalid ? acc[t][c][q] * sr[t] * xv[t][q] : 0.f;
-          s3[0] += sg[t] == 0 ? v : 0.f;
-          s3[1] += sg[t] == 1 ? v : 0.f;
-          s3[2] += sg[t] == 2 ? v : 0.f;
+          const char* src = p.X.base + ((size_t)kg * Rp + gr[t]) * 16 + x.ahalf();
+          const u32x2 hh = *reinterpret_cast<const u32x2*>(src), hl = *reinterpret_cast<const u32x2*>(src + xpb);
+          h2_join4(hh, hl, h2_pow2(-(int)p.X.exps()[gr[t] * CB + (kg >> 4)]), xv[t]);
         }
-        const int col = x.acol(c) + q;
+        float s[4 * NSEG];                               // [q][k]
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          if (k < nq) {
-            const float sum = x.colred_sum(s3[k]);
-            if (x.col_writer()) {
-              if (C::NWR == 1) p.dy_part[(tile * 3 + k) * D + col] = sum;
-              else stage[(x.wr * 3 + k) * D + col] = sum;
-            }
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+          for (int k = 0; k < NSEG; ++k) s[q * NSEG + k] = 0.f;
+#pragma unroll
+          for (int t = 0; t < RT; ++t) {
+            // (rows past the end read the last row again: select, their accumulators are zero but X need not be finite there)
+            const float v = x.arow(t) < x.nvalid ? acc[t][c][q] * sr[t] * xv[t][q] : 0.f;
+#pragma unroll
+            for (int k = 0; k < NSEG; ++k) s[q * NSEG + k] += sg[t] == k ? v : 0.f;
           }
+        }
+        // the column group's sums reduce side by side (a question the tile does not touch sums zeros and is not stored)
+        row16_sum_n(s);
+        if (x.col_writer()) {
+#pragma unroll
+          for (int k = 0; k < NSEG; ++k)
+            if (k < nq) {
+              float* dst = C::NWR == 1 ? p.dy_part + (tile * 3 + k) * D : stage + (x.wr * 3 + k) * D;
+#pragma unroll
+              for (int q = 0; q < 4; ++q) dst[x.acol(c) + q] = s[q * NSEG + k];
+            }
+        }
       }
     }
   }
@@ -1413,15 +1471,25 @@ __global__ __launch_bounds__(512) void chain_bwd_kernel(const ChainBwdP p) {
   }
 }
 
-template <int D_, int KV, int A2, int R_ = 64>
-inline hipError_t chain_bwd_launch_a(const ChainBwdP& p, hipStream_t st) {
-  auto kern = chain_bwd_kernel<D_, KV, A2, R_>;
+template <int D_, int KV, int A2, int R_, bool TWO>
+inline hipError_t chain_bwd_launch_k(const ChainBwdP& p, hipStream_t st) {
+  auto kern = chain_bwd_kernel<D_, KV, A2, R_, TWO>;
   constexpr size_t lds = ChainGeo<D_, R_>::LDS;
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);
   if (e != hipSuccess) return e;
   const int nfill = (D_ == 512 && R_ == 64 && p.dkb.njobs > 0) ? p.dkb.nfill : 0;
   hipLaunchKernelGGL(kern, dim3((p.M + R_ - 1) / R_ + nfill), dim3(512), lds, st, p);
   return hipGetLastError();
+}
+// a 64-row tile of questions of N >= 64 rows touches at most two of them: the two-question kernel (uniform per launch)
+template <int D_, int KV, int A2, int R_ = 64>
+inline hipError_t chain_bwd_launch_a(const ChainBwdP& p, hipStream_t st) {
+  // (not for the identity activation: its short B0 body is packed to the register cap already, and the two-question form of it
+  // spilled 11 - 16 registers where the general one spills 8 - 9)
+  if constexpr (R_ == 64 && A2 != ACT_NON) {
+    if (p.N >= R_) return chain_bwd_launch_k<D_, KV, A2, R_, true>(p, st);
+  }
+  return chain_bwd_launch_k<D_, KV, A2, R_, false>(p, st);
 }
 
 // One kernel per readCtrlAct (round 5).  The run-time variant (A2 = -1: a per-value switch inside stage B0's 64-value body) met

@@ -183,6 +183,34 @@ __device__ __forceinline__ float act_grad_from_out(int act, float o) {
   }
 }
 
+// stage markers: assembler comments that delimit a kernel's stages in a -S listing (tools/stage_insts.py counts instruction
+// classes between them).  Only in a build with -DMACX_STAGE_MARKS: the product build has none.
+#ifdef MACX_STAGE_MARKS
+#define MACX_MARK(name) asm volatile("; MACX_STAGE " name)
+#else
+#define MACX_MARK(name) do { } while (0)
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// selects as bit masks.  `c ? v : 0.f` over a 64-value body costs a compare plus a v_cndmask per value (through VCC: 22.8 cycles
+// each, profiles/r04_valu_probe.txt); where the condition belongs to a ROW (a lane's row block), it is turned once into an
+// all-ones / zero word and every value is ANDed with it (2.4 cycles).  The AND is the select bit for bit -- NaN and infinity
+// included, which a multiply by 0 / 1 is not.
+// ---------------------------------------------------------------------------------------------
+// (opaque: the optimiser would otherwise fold "and with a sign-extended condition" straight back into the select)
+__device__ __forceinline__ uint32_t lane_mask(bool c) {
+  uint32_t m = c ? ~0u : 0u;
+  asm("" : "+v"(m));
+  return m;
+}
+__device__ __forceinline__ float mask_f(float v, uint32_t m) { return __uint_as_float(__float_as_uint(v) & m); }
+// bit e of `bits` spread over a word (one sign-extending bit-field extract)
+__device__ __forceinline__ uint32_t bit_mask(uint32_t bits, int e) {
+  uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)bits, (uint32_t)e, 1u);
+  asm("" : "+v"(m));
+  return m;
+}
+
 // ---------------------------------------------------------------------------------------------
 // wave64 reductions
 // ---------------------------------------------------------------------------------------------
