@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .options import freeze, fresh_seed, get
-from .params import MACCellParams
+from .params import FlatLayout, MACCellParams
 
 MACCellTuple = collections.namedtuple("MACCellTuple", ("control", "memory"))   # mac_cell.py:8
 
@@ -198,9 +198,8 @@ class _Run:
         ws_floats = self.L.macx_ws_floats(C.byref(self.opts), C.byref(self.shapes), 1)
         ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
         gstruct = _lib.MacxParamGrads()
-        grads = {}
         present = [f for f in self.params.fields if f in self._ptensors]
-        sizes = [(self._ptensors[f].numel() + 3) & ~3 for f in present]          # 16-byte aligned views
+        layout = FlatLayout([self._ptensors[f] for f in present])
         # the parameters' persistent flat gradient buffer (one fill instead of one per parameter; the views below become the
         # parameters' .grad, so a flat all-reduce / optimizer needs no gather) -- only for a registered flat consumer and only
         # once per step: a second cell run inside the same backward pass (micro-batches, two towers on one device), or a
@@ -209,15 +208,11 @@ class _Run:
         if hasattr(self.params, "claim_grad_buffer") and present == list(self.params.fields):
             if all(getattr(self.params, f).grad is None for f in present):
                 buf = self.params.claim_grad_buffer()          # None: no flat consumer, or already handed out this step
-                if buf is not None and buf.numel() == sum(sizes):
+                if buf is not None and buf.numel() == layout.total:
                     flat = buf
         if flat is None:
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-        off = 0
-        for f, n in zip(present, sizes):
-            t = self._ptensors[f]
-            grads[f] = flat[off: off + t.numel()].view(t.shape)
-            off += n
+            flat = torch.zeros(layout.total, dtype=torch.float32, device=dev)
+        grads = {f: layout.view(flat, i) for i, f in enumerate(present)}
         for f in _lib.PARAM_FIELDS:
             setattr(gstruct, f, grads[f].data_ptr() if f in grads else None)
         gi_vq = torch.empty_like(self.vecQuestions)
@@ -240,8 +235,8 @@ class _Run:
     def backward(self, d_control, d_memory, state_grads=None):
         args, grads, (gi_vq, gi_words, gi_kb), flat, _keep = self.backward_begin(d_control, d_memory, state_grads)
         stream = _lib.stream_of(self.saved)
-        hook = getattr(self.params, "after_backward_phase1", None)
-        if hook is not None and flat is getattr(self.params, "_grad_flat", None):
+        hook = self.params.after_backward_phase1
+        if hook is not None and self.params.grad_buffer_state(flat):
             # every gradient except the read unit's big contractions is final: let the data-parallel layer start on it
             self.backward_phase(args, 1)
             hook(flat)
@@ -584,6 +579,7 @@ def _pad_blocks(t, d, dp):
 class _PaddedParams:
     """The zero-padded image of a MACCellParams: same fields, every width d -> dp.  The padded tensors are autograd results of
     the logical parameters (torch.nn.functional.pad), so gradients arrive at the logical tensors, sliced, on their own."""
+    after_backward_phase1 = None          # owns no flat gradient buffer (no claim_grad_buffer): its backward pass is never split
 
     def __init__(self, params, d, dp):
         self.fields = list(params.fields)

@@ -9,8 +9,12 @@ the MEAN loss over its shard (model.py:596); shard gradients are combined weight
 that the result equals the full-batch gradient.
 """
 
+import contextlib
+
 import torch
 import torch.distributed as dist
+
+from .params import FlatLayout
 
 
 def tower_slice(batch_size, rank, world):
@@ -21,6 +25,10 @@ def tower_slice(batch_size, rank, world):
     return start, end
 
 
+def _world(group):
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
 class GradBucket:
     """Flat gradient buffer reused across steps; one all-reduce (sum) per step.
 
@@ -28,6 +36,8 @@ class GradBucket:
     receives pointers into it, and autograd hands the views through as `.grad`).  When every gradient is found to be a
     view of that buffer at its expected offset the all-reduce runs on it in place -- no gather copy; anything else (a
     gradient produced elsewhere, accumulated, or absent) falls back to one gather kernel into the buffer."""
+
+    tensors = property(lambda self: self._tensors)          # (TowerBuckets: a method -- what its optimizer is built over)
 
     def __init__(self, tensors, flat=None, params=None):
         """params: the MACCellParams whose grad_buffer() `flat` is -- registers this bucket as its flat consumer (the backward
@@ -37,56 +47,110 @@ class GradBucket:
             if flat is None:
                 flat = params.grad_buffer()
             params.register_grad_buffer_user()
-        self.tensors = list(tensors)
-        self.sizes = [t.numel() for t in self.tensors]
-        self.offsets, off = [], 0
-        for n in self.sizes:
-            self.offsets.append(off)
-            off += (n + 3) & ~3                      # 16-byte aligned segments (what the kernels write through)
+        self._tensors = list(tensors)
+        self.layout = FlatLayout(self._tensors)
+        self.sizes, self.offsets = self.layout.sizes, self.layout.offsets
         if flat is None:
-            flat = torch.zeros(off, dtype=torch.float32, device=self.tensors[0].device)
-        if flat.numel() < off:
-            raise ValueError("flat buffer holds %d floats, the gradients need %d" % (flat.numel(), off))
+            flat = torch.zeros(self.layout.total, dtype=torch.float32, device=self._tensors[0].device)
+        if flat.numel() < self.layout.total:
+            raise ValueError("flat buffer holds %d floats, the gradients need %d" % (flat.numel(), self.layout.total))
         self.flat = flat
         self.zero_copy_steps = 0
 
-    def _in_place(self):
-        base = self.flat.data_ptr()
-        for t, o in zip(self.tensors, self.offsets):
-            g = t.grad
-            if g is None or not g.is_contiguous() or g.data_ptr() != base + 4 * o:
-                return False
-        return True
+    def begin_step(self, shard_size, global_size):
+        """One bucket: nothing to prepare.  (The two-bucket classes take the shard weight here: their phase-1 hook needs it.)"""
+
+    def _in_place(self, lo, hi):
+        return all(self.layout.is_view(self.flat, i, self._tensors[i].grad) for i in range(lo, hi))
+
+    def _gather(self, lo, hi):
+        for i in range(lo, hi):
+            g, dst = self._tensors[i].grad, self.layout.view(self.flat, i)
+            if g is None:
+                dst.zero_()
+            elif not self.layout.is_view(self.flat, i, g):
+                dst.copy_(g)
 
     def allreduce_(self, shard_size, global_size, group=None):
         """grads <- sum_r (shard_r / global) * grads_r  == gradient of the full-batch mean loss."""
-        w = float(shard_size) / float(global_size)
-        if self._in_place():
+        if self._in_place(0, len(self._tensors)):
             self.zero_copy_steps += 1
         else:
-            for t, o, n in zip(self.tensors, self.offsets, self.sizes):
-                dst = self.flat[o:o + n]
-                if t.grad is None:
-                    dst.zero_()
-                else:
-                    dst.copy_(t.grad.reshape(-1))
+            self._gather(0, len(self._tensors))
+        return self._reduce_all(float(shard_size) / float(global_size), group)
+
+    def _reduce_all(self, w, group):
         if w != 1.0:
             self.flat.mul_(w)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        if _world(group) > 1:
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
-        for t, o, n in zip(self.tensors, self.offsets, self.sizes):            # gradients are views of the reduced buffer
-            t.grad = self.flat[o:o + n].view_as(t)
-        self._release()
-        return self.flat
+        return self._publish()
 
-    def _release(self):
-        """The step's gradients are final: the next backward pass may take the persistent buffer again (the caller drops the
-        .grad views -- zero_grad / an optimizer step -- before it runs, as with any accumulate-free training loop)."""
+    def _publish(self):
+        """The step's gradients are final: every .grad is a view of the reduced buffer, and the next backward pass may take the
+        persistent buffer again (the caller drops the .grad views -- zero_grad / an optimizer step -- before it runs, as with any
+        accumulate-free training loop)."""
+        for i, t in enumerate(self._tensors):
+            t.grad = self.layout.view(self.flat, i)
         if self.owner is not None:
             self.owner.release_grad_buffer()
+        return self.flat
 
 
-class OverlappedBuckets(GradBucket):
+class _TwoBuckets(GradBucket):
+    """What OverlappedBuckets and TowerBuckets share: flat[:early] is final when the cell's backward pass calls
+    `after_backward_phase1`, and is scaled and all-reduced from there -- on a side stream on the GPU -- while the rest of the
+    backward pass still runs; allreduce_() after backward() exchanges flat[early:] and joins.  A subclass says which range is
+    early, when its hook may start it (_phase1 -> _start_early), and what it falls back to (allreduce_ -> _finish only when
+    _early_done)."""
+
+    def _two_buckets(self, cell, early, group):
+        self.owner, self.early, self.group = cell, early, group
+        self.weight = 1.0
+        self._early_work, self._early_started = None, False
+        self.side = torch.cuda.Stream(device=self.flat.device) if self.flat.is_cuda else None
+        self.overlapped_steps = 0
+        cell.after_backward_phase1 = self._phase1
+
+    def _active(self):
+        return _world(self.group) > 1
+
+    def begin_step(self, shard_size, global_size):
+        self.weight = float(shard_size) / float(global_size)
+        self._early_started, self._early_work = False, None
+
+    def _start_early(self):
+        part = self.flat[:self.early]
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream(self.flat.device))
+        with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+            if self.weight != 1.0:
+                part.mul_(self.weight)
+            self._early_work = dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+        self._early_started = True
+
+    def _early_done(self, w, lo, hi, whose):
+        done = self._early_started and w == self.weight and self._in_place(lo, hi)
+        if self._early_started and not done:
+            raise RuntimeError("the early bucket is already in flight but %s gradients are not views of the flat buffer" % whose)
+        return done
+
+    def _finish(self, w):
+        late = self.flat[self.early:]
+        if w != 1.0:
+            late.mul_(w)
+        if late.numel():
+            dist.all_reduce(late, op=dist.ReduceOp.SUM, group=self.group)
+        if self._early_work is not None:
+            self._early_work.wait()
+        if self.side is not None:
+            torch.cuda.current_stream(self.flat.device).wait_stream(self.side)
+        self._early_started = False
+        self.overlapped_steps += 1
+        return self._publish()
+
+
+class OverlappedBuckets(_TwoBuckets):
     """Two buckets over MACCellParams.grad_buffer(), the first in flight while the backward pass is still running.
 
     The cell's backward pass produces its gradients in two parts (macx_cell_backward_phase): everything except the read
@@ -105,61 +169,18 @@ class OverlappedBuckets(GradBucket):
 
     def __init__(self, params, group=None):
         super().__init__(params.tensors(), flat=params.grad_buffer(), params=params)
-        self.early = params.early_floats()
-        self.group = group
-        self.weight = 1.0
-        self._early_work = None
-        self._early_started = False
-        self.side = torch.cuda.Stream(device=self.flat.device) if self.flat.is_cuda else None
-        self.overlapped_steps = 0
-        params.after_backward_phase1 = self._phase1
-
-    def _active(self):
-        return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-
-    def begin_step(self, shard_size, global_size):
-        self.weight = float(shard_size) / float(global_size)
-        self._early_started = False
-        self._early_work = None
+        self._two_buckets(params, params.early_floats(), group)
 
     def _phase1(self, flat):
-        if not self._active() or flat.data_ptr() != self.flat.data_ptr() or self.early == 0:
-            return
-        part = self.flat[: self.early]
-        if self.side is not None:
-            self.side.wait_stream(torch.cuda.current_stream(self.flat.device))
-            with torch.cuda.stream(self.side):
-                if self.weight != 1.0:
-                    part.mul_(self.weight)
-                self._early_work = dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        else:
-            if self.weight != 1.0:
-                part.mul_(self.weight)
-            self._early_work = dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        self._early_started = True
+        if self._active() and flat.data_ptr() == self.flat.data_ptr() and self.early != 0:
+            self._start_early()
 
     def allreduce_(self, shard_size, global_size, group=None):
         w = float(shard_size) / float(global_size)
-        if not (self._early_started and w == self.weight and self._in_place()):
-            if self._early_started:
-                raise RuntimeError("the early bucket is already in flight but the gradients are not views of the flat buffer")
+        if not self._early_done(w, 0, len(self._tensors), "the"):
             return super().allreduce_(shard_size, global_size, group if group is not None else self.group)
-        late = self.flat[self.early:]
-        if w != 1.0:
-            late.mul_(w)
-        if late.numel():
-            dist.all_reduce(late, op=dist.ReduceOp.SUM, group=self.group)
-        if self._early_work is not None:
-            self._early_work.wait()
-        if self.side is not None:
-            torch.cuda.current_stream(self.flat.device).wait_stream(self.side)
-        self._early_started = False
-        self.overlapped_steps += 1
         self.zero_copy_steps += 1
-        for t, o, n in zip(self.tensors, self.offsets, self.sizes):
-            t.grad = self.flat[o:o + n].view_as(t)
-        self._release()
-        return self.flat
+        return self._finish(w)
 
 
 class TwoPhaseStep:
@@ -182,19 +203,18 @@ class TwoPhaseStep:
 
     def exchange_step(self):
         b = self.bucket
-        if hasattr(b, "begin_step"):
-            b.begin_step(self.shard, self.global_batch)
+        b.begin_step(self.shard, self.global_batch)
         grads = self.run_part_a()
         for f, g in grads.items():                       # (views of the flat buffer at the bucket's offsets: its zero-copy path)
             getattr(self.params, f).grad = g
-        hook = getattr(self.params, "after_backward_phase1", None)
+        hook = self.params.after_backward_phase1
         if hook is not None:
             hook(b.flat)                                 # early bucket: scale + all-reduce (side stream on the GPU)
         self.run_part_b()
         return b.allreduce_(self.shard, self.global_batch)      # late bucket (or the one bucket), join; releases the flat buffer
 
 
-class TowerBuckets:
+class TowerBuckets(_TwoBuckets):
     """Data parallelism for the WHOLE tower the reference builds per GPU (model.py:775-826: embeddings, question encoder, stem,
     MAC cell, output unit + classifier -- 57 MB of fp32 gradients at p = 12), two buckets over ONE flat buffer:
 
@@ -205,7 +225,7 @@ class TowerBuckets:
     early fields are final after its phase 1 (macx_cell_backward_phase), so that range is all-reduced on a side stream from the
     cell's phase-1 hook while phase 2 -- and then the stem's and the encoder's backward passes, which need the cell's input
     gradients -- still run; the rest follows after backward().  The cell's gradient buffer IS its range of the flat buffer
-    (MACCellParams.grad_buffer() is pointed at it), the other modules' gradients are gathered into theirs.  Clipping comes
+    (MACCellParams.adopt_grad_buffer), the other modules' gradients are gathered into theirs.  Clipping comes
     after the exchange, as in model.py:645-650: hand `flat` to optim.FlatAdamEMA(bucket.tensors()).step(flat_grad=bucket.flat).
 
         bucket = TowerBuckets(net); opt = FlatAdamEMA(bucket.tensors(), ...)
@@ -223,7 +243,7 @@ class TowerBuckets:
     """
 
     def __init__(self, net, group=None, fused_gather=False):
-        self.net, self.group = net, group
+        self.net = net
         self.fused_gather = bool(fused_gather)
         self._tables = {}                    # (lo, hi) -> [host rows, device table]: the eager gathers
         self._captured_tables = []           # [host rows, device table, uploaded]: one per gather issued under a capture
@@ -234,29 +254,11 @@ class TowerBuckets:
                             "GradBucket(net.tensors())")
         enc = list(net.enc.tensors()) if hasattr(net, "enc") else []
         groups = [list(net.out.tensors()), list(cell.tensors()), list(net.stem.tensors()), enc]
-        self._tensors = [t for g in groups for t in g]
-        self.sizes = [t.numel() for t in self._tensors]
-        self.offsets, off = [], 0
-        for n in self.sizes:
-            self.offsets.append(off)
-            off += (n + 3) & ~3
-        dev = self._tensors[0].device
-        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
-        n_out = len(groups[0])
-        self.cell_lo = self.offsets[n_out]
-        cell_floats = sum((t.numel() + 3) & ~3 for t in groups[1])
-        self.cell_hi = self.cell_lo + cell_floats
-        # the cell's backward pass writes straight into its range
-        object.__setattr__(cell, "_grad_flat", self.flat[self.cell_lo:self.cell_hi])
-        cell.register_grad_buffer_user()
-        cell.after_backward_phase1 = self._phase1
-        self.early = self.cell_lo + cell.early_floats()
-        self.n_out = n_out
-        self.n_cell = len(groups[1])
-        self.weight = 1.0
-        self._early_work, self._early_started = None, False
-        self.side = torch.cuda.Stream(device=dev) if self.flat.is_cuda else None
-        self.overlapped_steps = 0
+        super().__init__([t for g in groups for t in g])
+        self.n_out, self.n_cell = len(groups[0]), len(groups[1])
+        self.cell_lo, self.cell_hi = self.layout.prefix(self.n_out), self.layout.prefix(self.n_out + self.n_cell)
+        cell.adopt_grad_buffer(self.flat[self.cell_lo:self.cell_hi])      # the cell's backward pass writes straight into its range
+        self._two_buckets(cell, self.cell_lo + cell.early_floats(), group)
         self.allreduce_ms = None
         if self.fused_gather:
             self.reserve_tables(4)
@@ -264,13 +266,6 @@ class TowerBuckets:
     def tensors(self):
         """the parameters in the flat buffer's order (what optim.FlatAdamEMA must be built over to take `flat` as it is)"""
         return list(self._tensors)
-
-    def _active(self):
-        return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-
-    def begin_step(self, shard_size, global_size):
-        self.weight = float(shard_size) / float(global_size)
-        self._early_started, self._early_work = False, None
 
     def _gather_fused(self, lo, hi):
         from . import _lib
@@ -318,14 +313,7 @@ class TowerBuckets:
                 slot[2] = True
 
     def _gather(self, lo, hi):
-        if self.fused_gather:
-            return self._gather_fused(lo, hi)
-        for t, o, n in zip(self._tensors[lo:hi], self.offsets[lo:hi], self.sizes[lo:hi]):
-            dst = self.flat[o:o + n]
-            if t.grad is None:
-                dst.zero_()
-            elif t.grad.data_ptr() != dst.data_ptr():
-                dst.copy_(t.grad.reshape(-1))
+        return self._gather_fused(lo, hi) if self.fused_gather else super()._gather(lo, hi)
 
     def _phase1(self, flat):
         if flat.data_ptr() != self.flat.data_ptr() + 4 * self.cell_lo:
@@ -335,44 +323,13 @@ class TowerBuckets:
         if not self._active():
             return                                    # single process: allreduce_ gathers and scales the WHOLE buffer (like OverlappedBuckets)
         self._gather(0, self.n_out)
-        part = self.flat[:self.early]
-        cur = torch.cuda.current_stream(self.flat.device) if self.side is not None else None
-        if self.side is not None:
-            self.side.wait_stream(cur)
-            with torch.cuda.stream(self.side):
-                if self.weight != 1.0:
-                    part.mul_(self.weight)
-                self._early_work = dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        else:
-            if self.weight != 1.0:
-                part.mul_(self.weight)
-            self._early_work = dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        self._early_started = True
+        self._start_early()
 
     def allreduce_(self, shard_size, global_size):
         w = float(shard_size) / float(global_size)
-        cell_ok = all(t.grad is not None and t.grad.data_ptr() == self.flat.data_ptr() + 4 * o
-                      for t, o in zip(self._tensors[self.n_out:self.n_out + self.n_cell], self.offsets[self.n_out:self.n_out + self.n_cell]))
-        early_done = self._early_started and w == self.weight and cell_ok
-        if self._early_started and not early_done:
-            raise RuntimeError("the early bucket is already in flight but the cell's gradients are not views of the flat buffer")
-        lo = self.early if early_done else 0
+        n = self.n_out + self.n_cell
+        early_done = self._early_done(w, self.n_out, n, "the cell's")
         if not early_done:
-            self._gather(0, self.n_out + self.n_cell)
-        self._gather(self.n_out + self.n_cell, len(self._tensors))
-        late = self.flat[lo:]
-        if w != 1.0:
-            late.mul_(w)
-        if self._active():
-            dist.all_reduce(late, op=dist.ReduceOp.SUM, group=self.group)
-            if self._early_work is not None:
-                self._early_work.wait()
-        if self.side is not None and early_done:
-            torch.cuda.current_stream(self.flat.device).wait_stream(self.side)
-        if early_done:
-            self.overlapped_steps += 1
-        self._early_started = False
-        for t, o, n in zip(self._tensors, self.offsets, self.sizes):
-            t.grad = self.flat[o:o + n].view_as(t)
-        self.net.cell.release_grad_buffer()
-        return self.flat
+            self._gather(0, n)
+        self._gather(n, len(self._tensors))
+        return self._finish(w) if early_done else self._reduce_all(w, self.group)

@@ -10,6 +10,7 @@ import math
 import torch
 
 from . import _lib
+from .params import FlatLayout, grad_buffer_owner
 
 
 class FlatAdamEMA:
@@ -24,18 +25,15 @@ class FlatAdamEMA:
         self.params = [p for p in params]
         if not self.params or not self.params[0].is_cuda:
             raise RuntimeError("FlatAdamEMA needs parameters on the HIP device")
-        self.sizes = [p.numel() for p in self.params]
-        # 16-byte aligned segments: the layout of MACCellParams.grad_buffer() and dp.GradBucket.flat, so that either can be
-        # handed to step(flat_grad=...) as it is (pad floats stay zero: gradient, moments and update)
-        self.offsets, n = [], 0
-        for k in self.sizes:
-            self.offsets.append(n)
-            n += (k + 3) & ~3
+        # the layout of MACCellParams.grad_buffer() and dp.GradBucket.flat, so that either can be handed to step(flat_grad=...) as
+        # it is (pad floats stay zero: gradient, moments and update)
+        self.layout = FlatLayout(self.params)
+        self.sizes, self.offsets, n = self.layout.sizes, self.layout.offsets, self.layout.total
         dev = self.params[0].device
         self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        for p, k, off in zip(self.params, self.sizes, self.offsets):          # parameters become views of the flat buffer
-            self.flat[off:off + k].copy_(p.data.reshape(-1))
-            p.data = self.flat[off:off + k].view_as(p.data)
+        for i, p in enumerate(self.params):                                   # parameters become views of the flat buffer
+            self.layout.view(self.flat, i).copy_(p.data)
+            p.data = self.layout.view(self.flat, i)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m = torch.zeros(n, dtype=torch.float32, device=dev)
         self.v = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -68,25 +66,24 @@ class FlatAdamEMA:
         """device_lr: False -- the step of before: t += 1 here, lr and t travel by value (macx_adam_ema_step).  True -- this call only
         ENQUEUES the update (macx_adam_ema_step_p): the kernel reads the rate advance() wrote, t is not touched; the pair
         advance(); step(device_lr=True) gives the bits of step().  What a captured graph holds (graph.CapturedTowerTrainStep).
-        flat_grad: an already flat gradient in THIS layout -- the parameters in order, each segment padded to a multiple of
-        4 floats: dp.GradBucket.flat / TowerBuckets.flat after the all-reduce, or MACCellParams.grad_buffer() for a cell-only
-        optimizer built with grad_owner= (without a registered consumer the backward pass does not write into that buffer: a
-        stale or zero gradient would be stepped on -- refused below; a dp bucket over the parameters is such a consumer).  A buffer of any other size is rejected.  Without
-        flat_grad the .grad of every parameter is gathered."""
-        if flat_grad is not None and self.grad_owner is None and getattr(flat_grad, "_macx_cell_grad_buffer", False):
-            # the buffer is only ever written for a REGISTERED consumer: a dp bucket built over it (GradBucket(params=...),
+        flat_grad: an already flat gradient in THIS layout (params.FlatLayout over the parameters in order): dp.GradBucket.flat /
+        TowerBuckets.flat after the all-reduce, or MACCellParams.grad_buffer() for a cell-only optimizer built with grad_owner=
+        (without a registered consumer the backward pass does not write into that buffer: a stale or zero gradient would be
+        stepped on -- refused below; a dp bucket over the parameters is such a consumer).  A buffer of any other size is
+        rejected.  Without flat_grad the .grad of every parameter is gathered."""
+        if flat_grad is not None and self.grad_owner is None:
+            # a cell's own buffer is only ever written for a REGISTERED consumer: a dp bucket built over it (GradBucket(params=...),
             # OverlappedBuckets) is one, and hands its `flat` -- this very tensor -- over after the exchange
-            owner = getattr(flat_grad, "_macx_cell_grad_owner", None)
-            owner = owner() if owner is not None else None
-            if owner is None or not getattr(owner, "_grad_flat_registered", False):
+            owner = grad_buffer_owner(flat_grad)
+            if owner is not None and not owner.grad_buffer_state(flat_grad):
                 raise ValueError("this is a MACCellParams.grad_buffer() nobody is registered for: build the optimizer with "
                                  "grad_owner=params (or a dp bucket over the parameters) so that the backward pass writes into it")
         if flat_grad is None:
-            for p, k, off in zip(self.params, self.sizes, self.offsets):
+            for i, p in enumerate(self.params):
                 if p.grad is None:
-                    self.grad[off:off + k].zero_()
+                    self.layout.view(self.grad, i).zero_()
                 else:
-                    self.grad[off:off + k].copy_(p.grad.reshape(-1))
+                    self.layout.view(self.grad, i).copy_(p.grad)
             flat_grad = self.grad
         elif flat_grad.numel() != self.flat.numel() or flat_grad.dtype != torch.float32:
             raise ValueError("flat_grad holds %d floats, this optimizer's layout %d (segments padded to 4 floats, parameters in "
@@ -107,4 +104,4 @@ class FlatAdamEMA:
 
     def ema_state(self):
         """{index: tensor} views of the EMA shadow, shaped like the parameters (what emaSaver restores, main.py:711-729)."""
-        return [self.ema[off:off + k].view_as(p) for p, k, off in zip(self.params, self.sizes, self.offsets)]
+        return [self.layout.view(self.ema, i) for i in range(len(self.params))]

@@ -80,8 +80,46 @@ def shapes(config, p):
     return sh
 
 
+class FlatLayout:
+    """THE layout of every flat fp32 buffer here (gradient buffers, dp buckets, the flat optimizer's parameters and moments):
+    the tensors in order, each segment padded to a multiple of 4 floats -- 16-byte aligned, what the kernels write through; the
+    pad floats stay zero.  Built from tensors or from plain sizes."""
+
+    def __init__(self, tensors):
+        self.shapes = [tuple(t.shape) if torch.is_tensor(t) else (int(t),) for t in tensors]
+        self.sizes = [math.prod(s) for s in self.shapes]
+        self.offsets, self.total = [], 0
+        for n in self.sizes:
+            self.offsets.append(self.total)
+            self.total += (n + 3) & ~3
+
+    def prefix(self, k):
+        """padded floats of the first k segments == where segment k starts"""
+        return self.offsets[k] if k < len(self.offsets) else self.total
+
+    def view(self, flat, i):
+        """segment i of `flat`, shaped like tensor i"""
+        return flat[self.offsets[i]: self.offsets[i] + self.sizes[i]].view(self.shapes[i])
+
+    def is_view(self, flat, i, t):
+        """is `t` (a gradient, or None) a contiguous view of `flat` at segment i"""
+        return t is not None and t.is_contiguous() and t.data_ptr() == flat.data_ptr() + 4 * self.offsets[i]
+
+
+_OWNERS = weakref.WeakValueDictionary()          # data_ptr of an allocated MACCellParams.grad_buffer() -> that MACCellParams
+
+
+def grad_buffer_owner(flat):
+    """The live MACCellParams that allocated `flat` as its grad_buffer(), or None (any other tensor)."""
+    owner = _OWNERS.get(flat.data_ptr())
+    return owner if owner is not None and owner.grad_buffer_state(flat) is not None else None
+
+
 class MACCellParams(torch.nn.Module):
     """Trainable parameters of the cell.  One tensor per macx_params field."""
+    # the persistent flat gradient buffer (grad_buffer()), whether a flat consumer registered for it, whether this step's backward
+    # pass holds it; and the hook a data-parallel bucket sets: called with the buffer between the two phases of the backward pass
+    _grad_flat, _grad_flat_registered, _grad_flat_busy, after_backward_phase1 = None, False, False, None
 
     def __init__(self, config, netLength=None, device=None, generator=None, dtype=torch.float32):
         super().__init__()
@@ -108,47 +146,57 @@ class MACCellParams(torch.nn.Module):
                     lim = math.sqrt(6.0 / (shape[-2] + shape[-1]))
                 t = (torch.rand(shape, generator=gen, dtype=torch.float64) * 2 - 1) * lim
             self.register_parameter(f, torch.nn.Parameter(t.to(dtype).to(device) if device else t.to(dtype)))
+        self.layout = FlatLayout(self.tensors())
 
     def tensors(self):
         return [getattr(self, f) for f in self.fields]
 
     def early_floats(self):
         """Floats of grad_buffer() in front of the first LATE_FIELDS segment: complete after phase 1 of the backward pass."""
-        return sum((getattr(self, f).numel() + 3) & ~3 for f in self.fields if f not in LATE_FIELDS)
+        return self.layout.prefix(sum(f not in LATE_FIELDS for f in self.fields))
 
     def grad_buffer(self):
-        """Persistent flat fp32 buffer the backward pass writes the parameter gradients into (16-byte aligned segments in
-        `fields` order): the gradients autograd hands out are views of it, so a data-parallel all-reduce (macx.dp.GradBucket)
-        or a flat optimizer over exactly these tensors (optim.FlatAdamEMA(..., grad_owner=params) uses the same padded layout)
-        can run on it without a gather copy.  Allocated on first use; the backward pass only writes into it for a registered
-        consumer (register_grad_buffer_user), once per step, until the consumer releases it (release_grad_buffer)."""
+        """Persistent flat fp32 buffer the backward pass writes the parameter gradients into (`layout`: FlatLayout over
+        `fields`): the gradients autograd hands out are views of it, so a data-parallel all-reduce (macx.dp.GradBucket) or a
+        flat optimizer over exactly these tensors (optim.FlatAdamEMA(..., grad_owner=params)) can run on it without a gather
+        copy.  Allocated on first use; the backward pass only writes into it for a registered consumer
+        (register_grad_buffer_user), once per step, until the consumer releases it (release_grad_buffer)."""
         dev = self.tensors()[0].device
-        n = sum((t.numel() + 3) & ~3 for t in self.tensors())
-        buf = getattr(self, "_grad_flat", None)
-        if buf is None or buf.numel() != n or buf.device != dev:
-            buf = torch.zeros(n, dtype=torch.float32, device=dev)
-            buf._macx_cell_grad_buffer = True          # optim.FlatAdamEMA.step refuses it while NOBODY is registered as its consumer
-            buf._macx_cell_grad_owner = weakref.ref(self)
-            object.__setattr__(self, "_grad_flat", buf)
+        buf = self._grad_flat
+        if buf is None or buf.numel() != self.layout.total or buf.device != dev:
+            buf = self._grad_flat = torch.zeros(self.layout.total, dtype=torch.float32, device=dev)
+            _OWNERS[buf.data_ptr()] = self
         return buf
+
+    def adopt_grad_buffer(self, flat):
+        """`flat` -- layout.total floats of somebody else's buffer (dp.TowerBuckets: the cell's range of the tower's) -- IS
+        grad_buffer() from now on, and its provider the registered consumer."""
+        if flat.numel() != self.layout.total or flat.dtype != torch.float32 or flat.device != self.tensors()[0].device:
+            raise ValueError("the cell's gradient buffer is %d fp32 on the parameters' device" % self.layout.total)
+        self._grad_flat = flat
+        self.register_grad_buffer_user()
+
+    def grad_buffer_state(self, flat):
+        """None: `flat` is not this cell's gradient buffer.  Else whether a consumer is registered for it -- only then does the
+        backward pass write into it (and split in two phases around after_backward_phase1)."""
+        return self._grad_flat_registered if flat is self._grad_flat else None
 
     def register_grad_buffer_user(self):
         """A flat consumer (dp.GradBucket / OverlappedBuckets, a flat optimizer) announces itself: from now on the backward pass
         writes into grad_buffer() -- once per step; the consumer calls release_grad_buffer() when it is done with the step's
         gradients.  Without a registered consumer every backward pass gets a buffer of its own (two cell runs in one backward,
         torch.autograd.grad results that must survive the next call)."""
-        object.__setattr__(self, "_grad_flat_registered", True)
-        object.__setattr__(self, "_grad_flat_busy", False)
+        self._grad_flat_registered, self._grad_flat_busy = True, False
 
     def claim_grad_buffer(self):
         """The persistent buffer, zeroed, if a consumer registered and this step's buffer has not been handed out yet; else None."""
-        if not getattr(self, "_grad_flat_registered", False) or getattr(self, "_grad_flat_busy", False):
+        if not self._grad_flat_registered or self._grad_flat_busy:
             return None
-        object.__setattr__(self, "_grad_flat_busy", True)
+        self._grad_flat_busy = True
         return self.grad_buffer().zero_()
 
     def release_grad_buffer(self):
-        object.__setattr__(self, "_grad_flat_busy", False)
+        self._grad_flat_busy = False
 
     def to_reference_dict(self):
         """{TF variable name: tensor} with the reference's shapes (scalar biases are 0-d)."""

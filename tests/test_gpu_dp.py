@@ -205,6 +205,32 @@ def test_flat_optimizer_takes_a_cell_buckets_flat_buffer(macx, dev, kind):
     assert torch.equal(train(False), train(True))
 
 
+def test_backward_bucket_and_optimizer_share_one_layout(macx, dev):
+    """The zero-copy path end to end: one backward pass with OverlappedBuckets(prm) leaves every .grad at its FlatLayout segment of
+    bucket.flat, the flat optimizer over the same tensors has the same offsets, and it takes bucket.flat as it is."""
+    B, S, N, d, p = 2, 3, 16, 128, 2
+    cfg = macx.configs.flag_file_config("args", netLength=p, memDim=d, ctrlDim=d, attDim=d)
+    vq, words, lengths, kb = [t.to(dev) for t in macx.configs.synthetic_inputs(B, S, N, d, seed=3)]
+    params = macx.MACCellParams(cfg, p, generator=torch.Generator().manual_seed(7)).to(dev)
+    bucket = macx.dp.OverlappedBuckets(params)
+    opt = macx.optim.FlatAdamEMA(params.tensors(), lr=1e-2)
+    layout = macx.params.FlatLayout(params.tensors())
+    cell = macx.MACCell(vq, words, words, lengths, kb, cfg.memoryDropout, cfg.readDropout, cfg.writeDropout, B, True,
+                        config=cfg, params=params, seed=5)
+    bucket.begin_step(B, B)
+    cell.run().memory.square().sum().backward()
+    base = bucket.flat.data_ptr()
+    assert [t.grad.data_ptr() for t in params.tensors()] == [base + 4 * o for o in layout.offsets]
+    assert opt.offsets == bucket.offsets == layout.offsets and opt.flat.numel() == bucket.flat.numel() == layout.total
+    bucket.allreduce_(B, B)
+    assert bucket.zero_copy_steps == 1
+    assert [t.grad.data_ptr() for t in params.tensors()] == [base + 4 * o for o in layout.offsets]
+    before = opt.flat.clone()
+    opt.step(bucket.flat)                                 # accepted: the bucket is the buffer's registered consumer
+    torch.cuda.synchronize()
+    assert opt.t == 1 and bool(torch.isfinite(opt.flat).all()) and not torch.equal(opt.flat, before)
+
+
 def test_tower_buckets_single_process_shard_weight(macx, dev):
     """One process, shard != global (shard emulation): TowerBuckets must scale EVERY gradient by shard / global -- the classifier's
     and the cell's early fields too (round 4 marked them 'already exchanged' in the phase-1 hook and left them unscaled)."""
