@@ -420,7 +420,9 @@ int macx_images_to_nhwc(const float* nchw, int B, int C, int HW, float* nhwc, vo
  * bidirectional BasicLSTMCell(h = encDim/2) under tf.nn.bidirectional_dynamic_rnn semantics,
  * questionCntxWords = concat(fw, bw) [B,S,2h], vecQuestions = dropout(concat(final h), qDropout).
  * Variables: qEmbeddings/emb [V,E]; encoder/birnnLayer/bidirectional_rnn/{fw,bw}/basic_lstm_cell/
- * {kernel [E+h,4h], bias [4h]} (gate order i, j, f, o; forget bias 1).  h % 128 == 0. */
+ * {kernel [E+h,4h], bias [4h]} (gate order i, j, f, o; forget bias 1).  h % 128 == 0 (else MACX_EINVAL) and h <= 512:
+ * the backward step holds the gate gradients of 16 questions in LDS, (16 (4h + 4) + 4608) * 4 bytes, which passes a CU's
+ * 160 KB (163,840 B) at h = 640.  A wider h is MACX_EUNSUPPORTED in every call below, and both sizing calls return 0. */
 typedef struct macx_enc_shapes { int32_t B, S, V, E, h, b0; } macx_enc_shapes;   /* V rows in emb (ids 1..V) */
 typedef struct macx_enc_params { const float* emb; const float* fw_kernel; const float* fw_bias; const float* bw_kernel; const float* bw_bias; } macx_enc_params;
 typedef struct macx_enc_grads { float* emb; float* fw_kernel; float* fw_bias; float* bw_kernel; float* bw_bias; } macx_enc_grads;

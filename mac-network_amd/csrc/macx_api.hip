@@ -2950,8 +2950,12 @@ EncBwdLayout make_enc_bwd(const macx_enc_shapes* s) {
   L.total = off;
   return L;
 }
+constexpr size_t ENC_LDS_MAX = 160 * 1024;      // LDS of one CU (gfx950)
 int enc_check(const macx_enc_shapes* s) {
   if (!s || s->B < 1 || s->S < 1 || s->V < 1 || s->E < 1 || s->h < 128 || s->h % 128) return MACX_EINVAL;
+  // the backward step keeps the gate gradients of 16 questions x 4h columns in LDS: past one CU's 160 KB (h > 512) the
+  // forward pass would run and only the backward launch fail, so the shape is refused before anything is sized or launched
+  if (lstm_step_bwd_lds(s->h) > ENC_LDS_MAX) return MACX_EUNSUPPORTED;
   return MACX_OK;
 }
 }  // namespace

@@ -6,7 +6,6 @@
 #include <stdint.h>
 #include <mutex>
 #include <map>
-#include <set>
 #include <utility>
 #include "../../include/macx.h"
 
@@ -15,19 +14,22 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace macx {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per-device state, so the
-// cache is keyed by both (a process that drives several GPUs from one thread each must not skip the call on the second
-// device), and it is guarded for concurrent callers.
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) and size: the attribute is per-device state, so
+// the cache is keyed by both (a process that drives several GPUs from one thread each must not skip the call on the second
+// device), and it is guarded for concurrent callers.  The cache holds the LARGEST size set so far: a kernel whose dynamic LDS
+// grows with the shape (lstm_step_bwd_kernel: with h) raises the attribute when a larger request arrives and never lowers it;
+// a caller with one constant size sets it once.
 inline hipError_t lds_attr_once(const void* fn, size_t bytes) {
   static std::mutex mu;
-  static std::set<std::pair<const void*, int>> done;
+  static std::map<std::pair<const void*, int>, size_t> largest;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   std::lock_guard<std::mutex> lock(mu);
-  if (done.count({fn, dev})) return hipSuccess;
+  auto it = largest.find({fn, dev});
+  if (it != largest.end() && it->second >= bytes) return hipSuccess;
   e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) done.insert({fn, dev});
+  if (e == hipSuccess) largest[{fn, dev}] = bytes;
   return e;
 }
 

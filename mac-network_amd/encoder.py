@@ -20,6 +20,7 @@ REF_NAMES = {"emb": "qEmbeddings/emb",
              "fw_bias": "encoder/birnnLayer/bidirectional_rnn/fw/basic_lstm_cell/bias",
              "bw_kernel": "encoder/birnnLayer/bidirectional_rnn/bw/basic_lstm_cell/kernel",
              "bw_bias": "encoder/birnnLayer/bidirectional_rnn/bw/basic_lstm_cell/bias"}
+FUSED_H_MAX = 512       # widest direction macx_encoder_* accept (h <= 512, include/macx.h)
 
 
 class _EncoderFunction(torch.autograd.Function):
@@ -31,7 +32,7 @@ class _EncoderFunction(torch.autograd.Function):
         sh = _lib.MacxEncShapes(B=B, S=S, V=mod.vocab, E=mod.E, h=mod.h, b0=b0)
         n_saved = L.macx_encoder_saved_floats(C.byref(sh))
         if n_saved == 0:
-            raise ValueError("encoder: encDim/2 must be a multiple of 128")
+            raise ValueError("encoder: encDim/2 must be a multiple of 128, at most %d" % FUSED_H_MAX)
         dev = questions.device
         saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
         words = torch.empty(B, S, 2 * mod.h, dtype=torch.float32, device=dev)
@@ -80,6 +81,9 @@ def _check_fused(config):
         raise UnsupportedOptions("encoder: shared question/answer embeddings have no HIP path")
     if (int(g("encDim", 512)) // 2) % 128 or int(g("encDim", 512)) % 2:
         raise UnsupportedOptions("encoder: the fused kernels need 128 k units per direction (the generic path takes any multiple of 4)")
+    if int(g("encDim", 512)) // 2 > FUSED_H_MAX:
+        raise UnsupportedOptions("encoder: the fused backward step holds 16 questions' gate gradients in LDS, which fits up to %d units "
+                                 "per direction (macx_enc_shapes, include/macx.h); wider encoders run on the generic path" % FUSED_H_MAX)
 
 
 class QuestionEncoder(torch.nn.Module):

@@ -22,14 +22,14 @@ def make_questions(B, S, V, seed, min_len=1):
     return q, lengths
 
 
-def run_case(macx, dev, B, S, V, E, h, train, dtype=torch.float64, b0=0, fixed=False):
+def run_case(macx, dev, B, S, V, E, h, train, dtype=torch.float64, b0=0, fixed=False, min_len=1):
     cfg = mo.flag_file_config("args", ctrlDim=2 * h, memDim=2 * h, attDim=2 * h, encDim=2 * h, wrdEmbDim=E, wrdEmbFixed=fixed)
     enc = macx.QuestionEncoder(cfg, vocab=V, generator=torch.Generator().manual_seed(3)).to(dev)
     gb = torch.Generator().manual_seed(7)
     with torch.no_grad():
         enc.fw_bias.copy_(torch.rand(4 * h, generator=gb) - 0.5)
         enc.bw_bias.copy_(torch.rand(4 * h, generator=gb) - 0.5)
-    q, lengths = make_questions(B, S, V, seed=11)
+    q, lengths = make_questions(B, S, V, seed=11, min_len=min_len)     # min_len = 0: question 0 full, question 1 empty
     words, vecQ = enc(q.to(dev), lengths.to(dev), train=train, seed=9, b0=b0)
     g = torch.Generator().manual_seed(5)
     dW = torch.randn(B, S, 2 * h, generator=g) / B
