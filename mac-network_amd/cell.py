@@ -26,40 +26,9 @@ import torch
 from . import _lib
 from .options import freeze, fresh_seed, get
 from .params import FlatLayout, MACCellParams
+from .unit import _f32c, _kb_lengths, _mask_word
 
 MACCellTuple = collections.namedtuple("MACCellTuple", ("control", "memory"))   # mac_cell.py:8
-
-
-def _f32c(t, name):
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32" % name)
-    if not t.is_cuda:
-        raise RuntimeError("%s must live on the HIP device: the MAC cell has no CPU path" % name)
-    return t.contiguous()
-
-
-def _kb_lengths(t, batch):
-    """kb_lengths: None, or an integer tensor [batch] on the device -> contiguous int32 (what questionLengths goes through)"""
-    if t is None:
-        return None
-    if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool:
-        raise TypeError("kb_lengths must be an integer tensor")
-    if not t.is_cuda:
-        raise RuntimeError("kb_lengths must live on the HIP device: the MAC cell has no CPU path")
-    if t.shape != (batch,):
-        raise ValueError("kb_lengths must be [batchSize]")
-    return t.to(torch.int32).contiguous()
-
-
-def _mask_word(t, like):
-    """macx_dropout.mask_word: one 32-bit word in device memory (an int32 / uint32 tensor with one element), or None."""
-    if t is None:
-        return None
-    if not torch.is_tensor(t) or t.numel() != 1 or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
-        raise TypeError("mask_word must be a 1-element int32 tensor on the HIP device (the kernels read it when they run)")
-    if t.device != like.device:
-        raise ValueError("mask_word lives on %s, the cell on %s" % (t.device, like.device))
-    return t
 
 
 class _Run:

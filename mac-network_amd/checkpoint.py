@@ -22,7 +22,7 @@ def _modules(net):
     mods = []
     for attr in ("enc", "stem", "cell", "out"):
         m = getattr(net, attr, None)
-        if m is not None:
+        if hasattr(m, "to_reference_dict"):          # (a GenericQuestionEncoder's own .enc is a width)
             mods.append(m)
     if not mods:          # a single component (MACCellParams, Stem, ...)
         mods = [net]
@@ -86,12 +86,7 @@ def load_reference(net, d, use_ema=False, strict=True):
     for m in _modules(net):
         want = m.to_reference_dict()
         have = {k: (src[k] if k in src else want[k]) for k in want}
-        if hasattr(m, "load_reference_dict"):
-            m.load_reference_dict(have)
-        else:                                   # Stem / OutputClassifier: field -> name tables
-            names = m.REF_NAMES if hasattr(m, "REF_NAMES") else __import__(m.__module__, fromlist=["REF_NAMES"]).REF_NAMES
-            for f, n in names.items():
-                getattr(m, f).copy_(torch.as_tensor(have[n]).to(getattr(m, f).dtype).reshape(getattr(m, f).shape))
+        m.load_reference_dict(have)
     return missing
 
 

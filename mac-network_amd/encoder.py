@@ -7,12 +7,10 @@ questionCntxWords [B,S,encDim], vecQuestions = dropout(concat(final h_fw, h_bw),
     enc = QuestionEncoder(config, vocab=90).to(device)
     questionCntxWords, vecQuestions = enc(questions, lengths, train=True, seed=step)
 """
-import ctypes as C
-import math
-
 import torch
 
-from . import _lib
+from . import _lib, generic, unit
+from .generic import B_CHANNEL, B_ROW, B_SAME, OP_ADD, OP_MUL, GenericParams, _Act, _Binary, _Dropout, _Embed, _Linear, _Ops
 from .options import UnsupportedOptions, fresh_seed
 
 REF_NAMES = {"emb": "qEmbeddings/emb",
@@ -21,52 +19,6 @@ REF_NAMES = {"emb": "qEmbeddings/emb",
              "bw_kernel": "encoder/birnnLayer/bidirectional_rnn/bw/basic_lstm_cell/kernel",
              "bw_bias": "encoder/birnnLayer/bidirectional_rnn/bw/basic_lstm_cell/bias"}
 FUSED_H_MAX = 512       # widest direction macx_encoder_* accept (h <= 512, include/macx.h)
-
-
-class _EncoderFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, keep_in, keep_q, seed, b0, word, questions, lengths, *params):
-        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_encoder_forward / _backward pass on
-        L = _lib.lib()
-        B, S = questions.shape
-        sh = _lib.MacxEncShapes(B=B, S=S, V=mod.vocab, E=mod.E, h=mod.h, b0=b0)
-        n_saved = L.macx_encoder_saved_floats(C.byref(sh))
-        if n_saved == 0:
-            raise ValueError("encoder: encDim/2 must be a multiple of 128, at most %d" % FUSED_H_MAX)
-        dev = questions.device
-        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
-        words = torch.empty(B, S, 2 * mod.h, dtype=torch.float32, device=dev)
-        vecQ = torch.empty(B, 2 * mod.h, dtype=torch.float32, device=dev)
-        ps = _lib.MacxEncParams(*[p.data_ptr() for p in params])
-        _lib.check(L.macx_encoder_forward_w(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(),
-                                            words.data_ptr(), vecQ.data_ptr(), saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(dev)),
-                   "macx_encoder_forward_w")
-        ctx.stuff = (mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params, word)
-        if torch.cuda.is_current_stream_capturing():
-            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
-            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
-            mod._capture_keep = saved
-        return words, vecQ
-
-    @staticmethod
-    def backward(ctx, d_words, d_vecQ):
-        mod, keep_in, keep_q, seed, sh, saved, n_saved, questions, lengths, params, word = ctx.stuff
-        L = _lib.lib()
-        dev = saved.device
-        n_ws = L.macx_encoder_ws_floats(C.byref(sh))
-        ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
-        grads = [torch.empty_like(p) for p in params]
-        gs = _lib.MacxEncGrads(*[g.data_ptr() for g in grads])
-        ps = _lib.MacxEncParams(*[p.data_ptr() for p in params])
-        d_words = saved.new_zeros((sh.B, sh.S, 2 * sh.h)) if d_words is None else d_words.contiguous()
-        d_vecQ = saved.new_zeros((sh.B, 2 * sh.h)) if d_vecQ is None else d_vecQ.contiguous()
-        _lib.check(L.macx_encoder_backward_w(C.byref(sh), keep_in, keep_q, seed & 0xFFFFFFFF, C.byref(ps), questions.data_ptr(), lengths.data_ptr(),
-                                             saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_words.data_ptr(), d_vecQ.data_ptr(), C.byref(gs),
-                                             _lib.ptr(word), _lib.stream_of(dev)),                      # (the word the forward pass hashed with)
-                   "macx_encoder_backward_w")
-        if not mod.emb.requires_grad:
-            grads[0] = None
-        return (None,) * 8 + tuple(grads)
 
 
 def _check_fused(config):
@@ -86,19 +38,27 @@ def _check_fused(config):
                                  "per direction (macx_enc_shapes, include/macx.h); wider encoders run on the generic path" % FUSED_H_MAX)
 
 
-class QuestionEncoder(torch.nn.Module):
+def check_questions(questions, lengths, vocab, check_ids):
+    """lengths is [batchSize]; check_ids: word ids and lengths lie in range (a host synchronisation; off in the bench loop)"""
+    if lengths.shape != (questions.shape[0],):
+        raise ValueError("questionLengths must be [batchSize]")
+    if check_ids:
+        if int(questions.max()) > vocab or int(questions.min()) < 0:
+            raise IndexError("question word id outside [0, %d]" % vocab)
+        # tf.reverse_sequence / dynamic_rnn reject lengths beyond the padded length (InvalidArgumentError)
+        if int(lengths.max()) > questions.shape[1] or int(lengths.min()) < 0:
+            raise ValueError("question length outside [0, %d]" % questions.shape[1])
+
+
+class QuestionEncoder(unit.FusedUnit):
     """Mirrors `MACnet.embeddingsOp` + `MACnet.encoder` for the configuration every flag file uses
     (encType LSTM, --encBi, encNumLayers 1, encDim == ctrlDim so no projections) on the fused kernels.  Constructing it for
     another LSTM configuration -- no --encBi (the parser's default), --encProj, encDim != ctrlDim -- returns a
     GenericQuestionEncoder: the same interface on one HIP kernel per reference op."""
-
-    def __new__(cls, config=None, *args, **kw):
-        if cls is QuestionEncoder and config is not None:
-            try:
-                _check_fused(config)
-            except UnsupportedOptions:
-                return GenericQuestionEncoder(config, *args, **kw)
-        return super().__new__(cls)
+    FIELDS, REF_NAMES, ABI = _lib.ENC_FIELDS, REF_NAMES, "encoder"
+    SHAPES, PARAMS, GRADS = _lib.MacxEncShapes, _lib.MacxEncParams, _lib.MacxEncGrads
+    check_fused = staticmethod(_check_fused)
+    SIZE_ERROR = "encoder: encDim/2 must be a multiple of 128, at most %d" % FUSED_H_MAX
 
     def __init__(self, config, vocab, embInit=None, generator=None):
         super().__init__()
@@ -114,54 +74,47 @@ class QuestionEncoder(torch.nn.Module):
             if tuple(emb.shape) != (self.vocab, E):
                 raise ValueError("embInit must be [%d, %d]" % (self.vocab, E))
         self.emb = torch.nn.Parameter(emb.float(), requires_grad=not g("wrdEmbFixed", False))
-        lim = math.sqrt(6.0 / (E + h + 4 * h))        # glorot_uniform over [E+h, 4h]
         for d in ("fw", "bw"):
-            k = (torch.rand((E + h, 4 * h), generator=generator, dtype=torch.float64) * 2 - 1) * lim
-            self.register_parameter(d + "_kernel", torch.nn.Parameter(k.float()))
+            k = unit.xavier_uniform((E + h, 4 * h), E + h + 4 * h, generator)      # glorot_uniform over [E+h, 4h]
+            self.register_parameter(d + "_kernel", torch.nn.Parameter(k))
             self.register_parameter(d + "_bias", torch.nn.Parameter(torch.zeros(4 * h)))
-
-    def tensors(self):
-        return [getattr(self, f) for f in _lib.ENC_FIELDS]
-
-    def to_reference_dict(self):
-        return {REF_NAMES[f]: getattr(self, f).detach().clone() for f in _lib.ENC_FIELDS}
-
-    def load_reference_dict(self, d):
-        with torch.no_grad():
-            for f in _lib.ENC_FIELDS:
-                getattr(self, f).copy_(torch.as_tensor(d[REF_NAMES[f]]))
 
     def embed(self, questions):
         """embeddingsOp's `questionWords` (model.py:207-219, 783): the embedded question words [B,S,wrdEmbDim] WITHOUT the encoder's
         input dropout -- what the cell attends over when --controlContextual is off (mac_cell.py:570)."""
-        from .generic import _Embed
         B, S = questions.shape
-        return _Embed.apply(questions, self.emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
+        return generic._Embed.apply(questions, self.emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
 
     def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
         """questions [B,S] int32 (0 = pad), lengths [B] int32 -> (questionCntxWords [B,S,2h], vecQuestions [B,2h]).
         mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's): XORed into the keys of the input
         and the question dropout when the kernels run, so that one captured graph draws fresh masks per replay."""
-        if not questions.is_cuda:
-            raise RuntimeError("the question encoder has no CPU path")
+        unit.require_device(questions, "the question encoder")
         questions = questions.to(torch.int32).contiguous()
         lengths = lengths.to(device=questions.device, dtype=torch.int32).contiguous()
-        if lengths.shape != (questions.shape[0],):
-            raise ValueError("questionLengths must be [batchSize]")
-        if check_ids:                                                                         # host sync; off in the bench loop
-            if int(questions.max()) > self.vocab or int(questions.min()) < 0:
-                raise IndexError("question word id outside [0, %d]" % self.vocab)
-            # tf.reverse_sequence / dynamic_rnn reject lengths beyond the padded length (InvalidArgumentError)
-            if int(lengths.max()) > questions.shape[1] or int(lengths.min()) < 0:
-                raise ValueError("question length outside [0, %d]" % questions.shape[1])
-        keep_in = self.keep_in if train else 1.0
-        keep_q = self.keep_q if train else 1.0
-        from .cell import _mask_word
-        return _EncoderFunction.apply(self, keep_in, keep_q, fresh_seed(seed, train), int(b0), _mask_word(mask_word, questions),
-                                      questions, lengths, *self.tensors())
+        check_questions(questions, lengths, self.vocab, check_ids)
+        B, S = questions.shape
+        sh = self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=int(b0))
+        keeps = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
+        return self._call(sh, keeps, seed, train, mask_word, questions, lengths)
+
+    def _outputs(self, sh, inputs):
+        dev = inputs[0].device
+        words = torch.empty(sh.B, sh.S, 2 * sh.h, dtype=torch.float32, device=dev)
+        vecQ = torch.empty(sh.B, 2 * sh.h, dtype=torch.float32, device=dev)
+        return (words, vecQ), inputs
+
+    def _backward(self, sh, X, d_outs):
+        # an output nothing was computed from has no gradient: the kernels read zeros there
+        shapes = ((sh.B, sh.S, 2 * sh.h), (sh.B, 2 * sh.h))
+        d = tuple(torch.zeros(s, dtype=torch.float32, device=X[0].device) if g is None else g.contiguous() for s, g in zip(shapes, d_outs))
+        return d, (), (None, None)
+
+    def _param_grads(self, grads):
+        return [grads[0] if self.emb.requires_grad else None] + grads[1:]
 
 
-class GenericQuestionEncoder(torch.nn.Module):
+class GenericQuestionEncoder(generic.ParamsUnit, torch.nn.Module):
     """qEmbeddingsOp + encoder (model.py:207-219, 279-307 -> ops.RNNLayer -> biRNNLayer / fwRNNLayer, ops.py:798-950) for the
     LSTM configurations the fused kernels refuse -- a forward-only LSTM(encDim) (no --encBi: the parser's default), the output
     projections projCW / projQ (--encProj or encDim != ctrlDim, model.py:785-787, with --encProjQAct) -- as ONE HIP KERNEL PER
@@ -175,7 +128,6 @@ class GenericQuestionEncoder(torch.nn.Module):
 
     def __init__(self, config, vocab, embInit=None, generator=None, device=None):
         super().__init__()
-        from .generic import GenericParams, _Ops
         dflt = dict(encType="LSTM", encBi=False, encNumLayers=1, encVariationalDropout=False, encProj=False, encProjQAct="NON",
                     encDim=512, ctrlDim=512, wrdEmbDim=300, encInputDropout=0.85, qDropout=0.92, wrdEmbFixed=False, ansEmbMod="NON")
         g = lambda n: getattr(config, n, dflt[n])
@@ -248,27 +200,9 @@ class GenericQuestionEncoder(torch.nn.Module):
                     with vs.scope("basic_lstm_cell"):
                         yield d, vs.get("kernel", (self.E + self.hh, 4 * self.hh), "xavier"), vs.get("bias", (4 * self.hh,), "zeros")
 
-    def tensors(self):
-        return self.params.tensors()
-
-    def to_reference_dict(self):
-        return self.params.to_reference_dict()
-
-    def load_reference_dict(self, ref):
-        own = set(self.params.names)
-        self.params.load_reference_dict({k: v for k, v in ref.items() if k in own})
-        return self
-
-    def to(self, *a, **kw):
-        out = super().to(*a, **kw)
-        t = self.params.tensors()
-        self.params.device = t[0].device if t else self.params.device
-        return out
-
     def embed(self, questions):
         """embeddingsOp's `questionWords` (model.py:207-219, 783): the embedded question words [B,S,wrdEmbDim] without the input
         dropout -- what the cell attends over when --controlContextual is off (mac_cell.py:570)."""
-        from .generic import _Embed
         B, S = questions.shape
         with self.params.scope("qEmbeddings"):
             emb = self.params.get("emb", (self.vocab, self.E), "normal")
@@ -276,22 +210,12 @@ class GenericQuestionEncoder(torch.nn.Module):
 
     def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
         """questions [B,S] int (0 = pad), lengths [B] -> (questionCntxWords [B,S,w], vecQuestions [B,w]), w = ctrlDim when projected."""
-        if mask_word is not None:
-            raise UnsupportedOptions("encoder: a run's mask word is taken by the fused encoder only (macx_encoder_forward_w); the "
-                                     "generic encoder has no such path")
-        from . import generic as G
-        from .generic import B_CHANNEL, B_ROW, B_SAME, OP_ADD, OP_MUL, _Act, _Binary, _Dropout, _Embed, _Linear
-        G._require_device(questions, "questions")                       # no CPU path
+        unit.refuse_mask_word(mask_word, "encoder", "macx_encoder_forward_w")
+        generic._require_device(questions, "questions")                 # no CPU path
         dev = questions.device
         B, S = questions.shape
         lengths = lengths.to(device=dev)
-        if lengths.shape != (B,):
-            raise ValueError("questionLengths must be [batchSize]")
-        if check_ids:
-            if int(questions.max()) > self.vocab or int(questions.min()) < 0:
-                raise IndexError("question word id outside [0, %d]" % self.vocab)
-            if int(lengths.max()) > S or int(lengths.min()) < 0:
-                raise ValueError("question length outside [0, %d]" % S)
+        check_questions(questions, lengths, self.vocab, check_ids)
         keep_in, keep_q = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
         seed = fresh_seed(seed, train)
         E, hh = self.E, self.hh
@@ -341,3 +265,6 @@ class GenericQuestionEncoder(torch.nn.Module):
                 words = self.ops.linear(words.contiguous(), self.enc, self.ctrl, name="projCW")
                 vecQ = self.ops.linear(vecQ, self.enc, self.ctrl, act=self.proj_act, name="projQ")
         return words, vecQ
+
+
+QuestionEncoder.GENERIC = GenericQuestionEncoder

@@ -25,6 +25,7 @@ import torch
 from . import _lib
 from ._lib import ptr, stream_of
 from .options import UnsupportedOptions, fresh_seed, get, reject_like_reference, DEFAULTS
+from .unit import _kb_lengths, _mask_word
 
 MACCellTuple = collections.namedtuple("MACCellTuple", ("control", "memory"))
 
@@ -451,6 +452,28 @@ class GenericParams(torch.nn.Module):
         return self
 
 
+class ParamsUnit:
+    """Mixin of the modules that keep their variables in a GenericParams at self.params (GenericQuestionEncoder,
+    GenericOutputClassifier): what they show of it."""
+
+    def tensors(self):
+        return self.params.tensors()
+
+    def to_reference_dict(self):
+        return self.params.to_reference_dict()
+
+    def load_reference_dict(self, ref):
+        own = set(self.params.names)
+        self.params.load_reference_dict({k: v for k, v in ref.items() if k in own})
+        return self
+
+    def to(self, *a, **kw):
+        out = super().to(*a, **kw)
+        t = self.params.tensors()
+        self.params.device = t[0].device if t else self.params.device
+        return out
+
+
 # -------------------------------------------------------------------------------------------------------------------
 # eager layer helpers for the generic question encoder and output unit (encoder.py, output.py): a dense layer of the
 # "linearLayer<name>" family and the activation table, on the autograd nodes above
@@ -507,7 +530,6 @@ class GenericMACCell:
     def __init__(self, vecQuestions, questionWords, questionCntxWords, questionLengths, knowledgeBase,
                  memoryDropout, readDropout, writeDropout, batchSize, train, reuse=None, *, config=None, params=None,
                  netLength=None, seed=None, b0=0, mask_word=None, tune=None, kb_lengths=None):
-        from .cell import _mask_word, _kb_lengths
         del tune            # (the A/B hooks of macx_opts.tune select among FUSED kernels; this path has one kernel per op)
         self.mask_word = _mask_word(mask_word, knowledgeBase)
         # live cells per question: the read unit's softmax of the plan then runs behind the length mask (plan.compile_cell)

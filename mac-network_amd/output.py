@@ -5,12 +5,10 @@ identical answer argmax).  SURVEY.md 8f row 2.
     out = OutputClassifier(config, answerWordsNum=28).to(device)
     logits = out(memory, vecQuestions, train=True, seed=step)       # [B, answers], differentiable
 """
-import ctypes as C
-import math
-
 import torch
 
-from . import _lib
+from . import _lib, generic, unit
+from .generic import B_SAME, OP_MUL, GenericParams, _Binary, _Dropout, _Linear, _Ops
 from .options import UnsupportedOptions, _resolve_act, fresh_seed
 
 REF_NAMES = {
@@ -19,98 +17,6 @@ REF_NAMES = {
     "fc0_W": "classifier/linearLayerfc_0/weights/weight", "fc0_b": "classifier/linearLayerfc_0/biases/bias",
     "fc1_W": "classifier/linearLayerfc_1/weights/weight", "fc1_b": "classifier/linearLayerfc_1/biases/bias",
 }
-
-
-class _OutFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, keep, seed, b0, word, memory, vecQ, *params):
-        L = _lib.lib()
-        B, d = memory.shape
-        sh = _lib.MacxOutShapes(B=B, d=d, hidden=mod.hidden, answers=mod.answers, b0=b0)
-        ps = _lib.MacxOutParams(*[p.data_ptr() for p in params])
-        n_saved = L.macx_output_saved_floats(C.byref(sh))
-        if n_saved == 0:
-            raise ValueError("output unit: d and hidden must be multiples of 16")
-        saved = torch.empty(n_saved, dtype=torch.float32, device=memory.device)
-        logits = torch.empty(B, mod.answers, dtype=torch.float32, device=memory.device)
-        memory, vecQ = memory.contiguous(), vecQ.contiguous()
-        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_output_forward passes on
-        _lib.check(L.macx_output_forward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
-                                           logits.data_ptr(), saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(memory)),
-                   "macx_output_forward_w")
-        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, memory, vecQ, params, word)
-        if torch.cuda.is_current_stream_capturing():
-            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
-            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
-            mod._capture_keep = saved
-        return logits
-
-    @staticmethod
-    def backward(ctx, d_logits):
-        mod, keep, seed, sh, saved, n_saved, memory, vecQ, params, word = ctx.stuff
-        L = _lib.lib()
-        n_ws = L.macx_output_ws_floats(C.byref(sh))
-        ws = torch.empty(n_ws, dtype=torch.float32, device=memory.device)
-        grads = [torch.empty_like(p) for p in params]
-        gs = _lib.MacxOutGrads(*[g.data_ptr() for g in grads])
-        ps = _lib.MacxOutParams(*[p.data_ptr() for p in params])
-        dmem, dvq = torch.empty_like(memory), torch.empty_like(vecQ)
-        d_logits = d_logits.contiguous()
-        _lib.check(L.macx_output_backward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), memory.data_ptr(), vecQ.data_ptr(),
-                                            saved.data_ptr(), n_saved, ws.data_ptr(), n_ws, d_logits.data_ptr(), C.byref(gs), dmem.data_ptr(),
-                                            dvq.data_ptr(), _lib.ptr(word), _lib.stream_of(memory)),    # (the word the forward pass hashed with)
-                   "macx_output_backward_w")
-        return (None, None, None, None, None, dmem, dvq) + tuple(grads)
-
-
-class OutputClassifier(torch.nn.Module):
-    """Fused output unit (--outQuestion, one hidden layer).  Constructing it for any other legal option set returns a
-    GenericOutputClassifier: the same interface on one HIP kernel per reference op."""
-
-    def __new__(cls, config=None, *args, **kw):
-        if cls is OutputClassifier and config is not None:
-            try:
-                _check_fused(config)
-            except UnsupportedOptions:
-                return GenericOutputClassifier(config, *args, **kw)
-        return super().__new__(cls)
-
-    def __init__(self, config, answerWordsNum=None, generator=None):
-        super().__init__()
-        g = lambda n, dflt: getattr(config, n, dflt)
-        _check_fused(config)
-        dims = list(g("outClassifierDims", [512]))
-        d = g("memDim", 512)
-        self.d, self.hidden = d, dims[0]
-        self.answers = int(answerWordsNum if answerWordsNum is not None else g("answerWordsNum", 28))
-        self.act = _resolve_act(config, "RELU")          # FCLayer's default act (ops.py:349)
-        self.keep = float(g("outputDropout", 0.85))
-        shapes = {"outQuestion_W": (d, d), "outQuestion_b": (d,), "fc0_W": (2 * d, self.hidden), "fc0_b": (self.hidden,),
-                  "fc1_W": (self.hidden, self.answers), "fc1_b": (self.answers,)}
-        for f in _lib.OUT_FIELDS:
-            sh = shapes[f]
-            if f.endswith("_b"):
-                t = torch.zeros(sh, dtype=torch.float64)
-            else:
-                lim = math.sqrt(6.0 / (sh[0] + sh[1]))       # xavier-uniform, ops.py:20
-                t = (torch.rand(sh, generator=generator, dtype=torch.float64) * 2 - 1) * lim
-            self.register_parameter(f, torch.nn.Parameter(t.float()))
-
-    def tensors(self):
-        return [getattr(self, f) for f in _lib.OUT_FIELDS]
-
-    def to_reference_dict(self):
-        return {REF_NAMES[f]: getattr(self, f).detach().clone() for f in _lib.OUT_FIELDS}
-
-    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0, mask_word=None):
-        """mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's), XORed into the keys of both
-        layer-input dropouts when the kernels run."""
-        if not memory.is_cuda:
-            raise RuntimeError("the output unit has no CPU path")
-        keep = self.keep if train else 1.0          # model.py:118-125
-        from .cell import _mask_word
-        return _OutFunction.apply(self, keep, fresh_seed(seed, train), int(b0), _mask_word(mask_word, memory), memory, vecQuestions,
-                                  *self.tensors())
 
 
 def _check_fused(config):
@@ -125,13 +31,55 @@ def _check_fused(config):
         raise UnsupportedOptions("--relu PRM has no fused HIP path in the classifier")
 
 
+class OutputClassifier(unit.FusedUnit):
+    """Fused output unit (--outQuestion, one hidden layer).  Constructing it for any other legal option set returns a
+    GenericOutputClassifier: the same interface on one HIP kernel per reference op."""
+    FIELDS, REF_NAMES, ABI = _lib.OUT_FIELDS, REF_NAMES, "output"
+    SHAPES, PARAMS, GRADS = _lib.MacxOutShapes, _lib.MacxOutParams, _lib.MacxOutGrads
+    check_fused = staticmethod(_check_fused)
+    SIZE_ERROR = "output unit: d and hidden must be multiples of 16"
+
+    def __init__(self, config, answerWordsNum=None, generator=None):
+        super().__init__()
+        g = lambda n, dflt: getattr(config, n, dflt)
+        _check_fused(config)
+        dims = list(g("outClassifierDims", [512]))
+        d = g("memDim", 512)
+        self.d, self.hidden = d, dims[0]
+        self.answers = int(answerWordsNum if answerWordsNum is not None else g("answerWordsNum", 28))
+        self.act = _resolve_act(config, "RELU")          # FCLayer's default act (ops.py:349)
+        self.keep = float(g("outputDropout", 0.85))
+        shapes = {"outQuestion_W": (d, d), "outQuestion_b": (d,), "fc0_W": (2 * d, self.hidden), "fc0_b": (self.hidden,),
+                  "fc1_W": (self.hidden, self.answers), "fc1_b": (self.answers,)}
+        for f in self.FIELDS:
+            sh = shapes[f]
+            t = torch.zeros(sh) if f.endswith("_b") else unit.xavier_uniform(sh, sh[0] + sh[1], generator)      # ops.py:20
+            self.register_parameter(f, torch.nn.Parameter(t))
+
+    def forward(self, memory, vecQuestions, train=False, seed=None, b0=0, mask_word=None):
+        """mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's), XORed into the keys of both
+        layer-input dropouts when the kernels run."""
+        unit.require_device(memory, "the output unit")
+        B, d = memory.shape
+        sh = self.SHAPES(B=B, d=d, hidden=self.hidden, answers=self.answers, b0=int(b0))
+        keep = self.keep if train else 1.0          # model.py:118-125
+        return self._call(sh, (self.act, keep), seed, train, mask_word, memory, vecQuestions)
+
+    def _outputs(self, sh, inputs):
+        return (torch.empty(sh.B, self.answers, dtype=torch.float32, device=inputs[0].device),), inputs
+
+    def _backward(self, sh, X, d_outs):
+        d_inputs = tuple(torch.empty_like(x) for x in X)      # d_memory, d_vecQuestions
+        return (d_outs[0].contiguous(),), d_inputs, d_inputs
+
+
 def fc_site(layer):
     """Dropout site of the input of classifier layer `layer` on the stateless stream (macx_common.hip.h: 7, 8; 13, 14, ... for
     deeper classifiers)."""
     return 7 + layer if layer < 2 else 11 + layer
 
 
-class GenericOutputClassifier(torch.nn.Module):
+class GenericOutputClassifier(generic.ParamsUnit, torch.nn.Module):
     """outputOp (model.py:512-528) + classifier (model.py:547-576) for the legal option sets the fused kernels refuse --
     no --outQuestion, --outQuestionMul, any number of classifier layers, --relu PRM/STD -- as ONE HIP KERNEL PER REFERENCE
     OP (generic._Ops on macx_linear / macx_wgrad / macx_op_*), variables under the reference's names in its creation
@@ -141,7 +89,6 @@ class GenericOutputClassifier(torch.nn.Module):
 
     def __init__(self, config, answerWordsNum=None, generator=None, device=None):
         super().__init__()
-        from .generic import GenericParams, _Ops
         dflt = dict(outImage=False, answerMod="NON", outputBN=False, outputDropout=0.85, memDim=512, ctrlDim=512,
                     outClassifierDims=[512], outQuestion=False, outQuestionMul=False, relu="STD")        # config.py:196, 281-288
         g = lambda n: getattr(config, n, dflt[n])
@@ -184,30 +131,9 @@ class GenericOutputClassifier(torch.nn.Module):
                     with vs.scope("prelu", default=True):
                         vs.get("alpha", (dims[i + 1],), 0.25)
 
-    def tensors(self):
-        return self.params.tensors()
-
-    def to_reference_dict(self):
-        return self.params.to_reference_dict()
-
-    def load_reference_dict(self, ref):
-        own = set(self.params.names)
-        self.params.load_reference_dict({k: v for k, v in ref.items() if k in own})
-        return self
-
-    def to(self, *a, **kw):
-        out = super().to(*a, **kw)
-        t = self.params.tensors()
-        self.params.device = t[0].device if t else self.params.device
-        return out
-
     def forward(self, memory, vecQuestions, train=False, seed=None, b0=0, mask_word=None):
-        if mask_word is not None:
-            raise UnsupportedOptions("output unit: a run's mask word is taken by the fused output unit only (macx_output_forward_w); "
-                                     "the generic classifier has no such path")
-        from . import generic as G
-        from .generic import B_SAME, OP_MUL, _Binary, _Dropout, _Linear
-        G._require_device(memory, "memory")                              # no CPU path
+        unit.refuse_mask_word(mask_word, "output unit", "macx_output_forward_w", "classifier")
+        generic._require_device(memory, "memory")                        # no CPU path
         vs, ops, cfg = self.params, self.ops, self.config
         keep = self.keep if train else 1.0                               # model.py:118-125
         seed = fresh_seed(seed, train)
@@ -243,6 +169,9 @@ class GenericOutputClassifier(torch.nn.Module):
                 if not last:
                     features = ops.act("RELU", features)
         return features
+
+
+OutputClassifier.GENERIC = GenericOutputClassifier
 
 
 class _AnswerLoss(torch.autograd.Function):

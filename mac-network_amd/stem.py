@@ -12,54 +12,14 @@ MFMA), dropout / activation / bias-gradient kernels of the generic path between 
 for those option sets; --stemBN and --stemGridRnn raise what the reference raises (KeyError / NameError).
 """
 import ctypes as C
-import math
 
 import torch
 
-from . import _lib, generic
+from . import _lib, generic, unit
 from .options import UnsupportedOptions, _resolve_act, fresh_seed
 
 REF_NAMES = {"kernel0": "stem/cnnLayercnn_0/kernels/kernel", "bias0": "stem/cnnLayercnn_0/biases/bias",
              "kernel1": "stem/cnnLayercnn_1/kernels/kernel", "bias1": "stem/cnnLayercnn_1/biases/bias"}
-
-
-class _StemFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, keep, seed, b0, word, images, *params):
-        L = _lib.lib()
-        B = images.shape[0]
-        sh = _lib.MacxStemShapes(B=B, H=mod.H, W=mod.W, Cin=mod.inDim, Cmid=mod.midDim, Cout=mod.outDim, b0=b0)
-        n_saved = L.macx_stem_saved_floats(C.byref(sh))
-        if n_saved == 0:
-            raise ValueError("stem: channel counts must be multiples of 128")
-        images = images.contiguous()
-        saved = torch.empty(n_saved, dtype=torch.float32, device=images.device)
-        kb = torch.empty(B, mod.H * mod.W, mod.outDim, dtype=torch.float32, device=images.device)
-        ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
-        # word: the run's mask word (1-element int32 device tensor) or None == NULL == word 0: what macx_stem_forward passes on
-        _lib.check(L.macx_stem_forward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), images.data_ptr(), kb.data_ptr(),
-                                         saved.data_ptr(), n_saved, _lib.ptr(word), _lib.stream_of(images)), "macx_stem_forward_w")
-        ctx.stuff = (mod, keep, seed, sh, saved, n_saved, kb, params, word)
-        if torch.cuda.is_current_stream_capturing():
-            # under no_grad nothing holds `saved` once this call returns; inside a capture its block must not go back to the graph's
-            # pool, where a later buffer that is written from OUTSIDE the graph (the cell's sticky status words) could land on it
-            mod._capture_keep = saved
-        return kb
-
-    @staticmethod
-    def backward(ctx, d_kb):
-        mod, keep, seed, sh, saved, n_saved, kb, params, word = ctx.stuff
-        L = _lib.lib()
-        n_ws = L.macx_stem_ws_floats(C.byref(sh))
-        ws = torch.empty(n_ws, dtype=torch.float32, device=kb.device)
-        grads = [torch.empty_like(p) for p in params]
-        gs = _lib.MacxStemGrads(*[g.data_ptr() for g in grads])
-        ps = _lib.MacxStemParams(*[p.data_ptr() for p in params])
-        d_kb = d_kb.contiguous()
-        _lib.check(L.macx_stem_backward_w(C.byref(sh), mod.act, keep, seed & 0xFFFFFFFF, C.byref(ps), kb.data_ptr(), saved.data_ptr(), n_saved,
-                                          ws.data_ptr(), n_ws, d_kb.data_ptr(), C.byref(gs), _lib.ptr(word), _lib.stream_of(kb)),
-                   "macx_stem_backward_w")
-        return (None, None, None, None, None, None) + tuple(grads)     # image features are inputs, not trained (extract_features.py)
 
 
 def _check_fused(config):
@@ -70,17 +30,13 @@ def _check_fused(config):
         raise UnsupportedOptions("stem: the fused stem is stemNumLayers=2, stemKernelSize=3, stride 1 only")
 
 
-class Stem(torch.nn.Module):
+class Stem(unit.FusedUnit):
     """Fused stem (the default 2-layer 3x3 CNN).  Constructing it for any other option set returns a GenericStem: the same
     interface on one general convolution per layer."""
-
-    def __new__(cls, config=None, *args, **kw):
-        if cls is Stem and config is not None:
-            try:
-                _check_fused(config)
-            except UnsupportedOptions:
-                return GenericStem(config, *args, **kw)
-        return super().__new__(cls)
+    FIELDS, REF_NAMES, ABI = _lib.STEM_FIELDS, REF_NAMES, "stem"
+    SHAPES, PARAMS, GRADS = _lib.MacxStemShapes, _lib.MacxStemParams, _lib.MacxStemGrads
+    check_fused = staticmethod(_check_fused)
+    SIZE_ERROR = "stem: channel counts must be multiples of 128"
 
     def __init__(self, config, H=14, W=14, inDim=1024, generator=None):
         super().__init__()
@@ -92,39 +48,34 @@ class Stem(torch.nn.Module):
         self.keep = float(g("stemDropout", 0.82))
         shapes = {"kernel0": (3, 3, inDim, self.midDim), "bias0": (self.midDim,), "kernel1": (3, 3, self.midDim, self.outDim),
                   "bias1": (self.outDim,)}
-        for f in _lib.STEM_FIELDS:
+        for f in self.FIELDS:
             sh = shapes[f]
             if f.startswith("bias"):
-                t = torch.zeros(sh, dtype=torch.float64)
+                t = torch.zeros(sh)
             else:   # xavier-uniform over conv fans (ops.py:30): fan_in = 9*in, fan_out = 9*out
-                lim = math.sqrt(6.0 / (9 * sh[2] + 9 * sh[3]))
-                t = (torch.rand(sh, generator=generator, dtype=torch.float64) * 2 - 1) * lim
-            self.register_parameter(f, torch.nn.Parameter(t.float()))
+                t = unit.xavier_uniform(sh, 9 * sh[2] + 9 * sh[3], generator)
+            self.register_parameter(f, torch.nn.Parameter(t))
         self.out_hw = (H, W)
-
-    def tensors(self):
-        return [getattr(self, f) for f in _lib.STEM_FIELDS]
-
-    def to_reference_dict(self):
-        return {REF_NAMES[f]: getattr(self, f).detach().clone() for f in _lib.STEM_FIELDS}
 
     def forward(self, images, train=False, seed=None, b0=0, mask_word=None):
         """images: [B, H*W, inDim] / [B, H, W, inDim] (NHWC, what the graph sees after model.py:68) or the feed-dict layout
         [B, inDim, H, W] (h5 features, extract_features.py), which is transposed on the device first.
         mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's), XORed into both dropout keys when
         the kernels run."""
-        if not images.is_cuda:
-            raise RuntimeError("the stem has no CPU path")
+        unit.require_device(images, "the stem")
         if images.dim() == 4 and images.shape[1] == self.inDim and tuple(images.shape[2:]) == (self.H, self.W):
-            src = images.contiguous()
-            images = torch.empty(src.shape[0], self.H * self.W, self.inDim, dtype=torch.float32, device=src.device)
-            _lib.check(_lib.lib().macx_images_to_nhwc(src.data_ptr(), src.shape[0], self.inDim, self.H * self.W, images.data_ptr(),
-                                                      _lib.stream_of(src)), "macx_images_to_nhwc")
+            images = k_nchw_to_nhwc(images.contiguous(), self.inDim, self.H * self.W)
         elif images.dim() == 4:
             images = images.reshape(images.shape[0], self.H * self.W, self.inDim)
-        keep = self.keep if train else 1.0
-        from .cell import _mask_word
-        return _StemFunction.apply(self, keep, fresh_seed(seed, train), int(b0), _mask_word(mask_word, images), images, *self.tensors())
+        sh = self.SHAPES(B=images.shape[0], H=self.H, W=self.W, Cin=self.inDim, Cmid=self.midDim, Cout=self.outDim, b0=int(b0))
+        return self._call(sh, (self.act, self.keep if train else 1.0), seed, train, mask_word, images)
+
+    def _outputs(self, sh, inputs):
+        kb = torch.empty(sh.B, self.H * self.W, self.outDim, dtype=torch.float32, device=inputs[0].device)
+        return (kb,), (kb,)                                   # (the backward pass reads the knowledge base, not the images)
+
+    def _backward(self, sh, X, d_outs):
+        return (d_outs[0].contiguous(),), (), (None,)         # image features are inputs, not trained (extract_features.py)
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -295,11 +246,9 @@ class GenericStem(torch.nn.Module):
         for i, (k, s, cin, cout) in enumerate(self.layers):
             scope = "stem/linearLayer" if self.linear else "stem/cnnLayercnn_%d" % i
             shape = (cin, cout) if self.linear else (k, k, cin, cout)
-            fan = (cin + cout) * (1 if self.linear else k * k)
-            lim = math.sqrt(6.0 / fan)                # xavier-uniform (ops.py:18-33)
-            w = (torch.rand(shape, generator=generator, dtype=torch.float64) * 2 - 1) * lim
+            w = unit.xavier_uniform(shape, (cin + cout) * (1 if self.linear else k * k), generator)
             wname, bname = ("weights/weight", "biases/bias") if self.linear else ("kernels/kernel", "biases/bias")
-            self.register_parameter("kernel%d" % i, torch.nn.Parameter(w.float()))
+            self.register_parameter("kernel%d" % i, torch.nn.Parameter(w))
             self.register_parameter("bias%d" % i, torch.nn.Parameter(torch.zeros(cout)))
             self.names += [("kernel%d" % i, scope + "/" + wname), ("bias%d" % i, scope + "/" + bname)]
             hw = (out_dim(hw[0], s), out_dim(hw[1], s))
@@ -334,9 +283,7 @@ class GenericStem(torch.nn.Module):
     def forward(self, images, train=False, seed=None, b0=0, mask_word=None):
         """images: [B, H*W, inDim] / [B, H, W, inDim] (NHWC) or the feed-dict layout [B, inDim, H, W].
         Returns the knowledge base [B, Ho*Wo, memDim]."""
-        if mask_word is not None:
-            raise UnsupportedOptions("stem: a run's mask word is taken by the fused stem only (macx_stem_forward_w); the generic "
-                                     "stem has no such path")
+        unit.refuse_mask_word(mask_word, "stem", "macx_stem_forward_w")
         generic._require_device(images, "images")
         H, W, B = self.H, self.W, images.shape[0]
         if images.dim() == 4 and images.shape[1] == self.inDim and tuple(images.shape[2:]) == (H, W):
@@ -367,6 +314,8 @@ class GenericStem(torch.nn.Module):
             x = generic._Act.apply(_Conv.apply(x, w, getattr(self, "bias%d" % i), s), self.act, None)
         return x.reshape(B, self.N, self.outDim)
 
+
+Stem.GENERIC = GenericStem
 
 # -------------------------------------------------------------------------------------------------------------------
 # questions that share images: the stem runs once per image, every question gets a copy of its image's block
