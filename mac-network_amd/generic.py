@@ -3,8 +3,15 @@
 readMemAttType BL / ADD, relu = PRM, writeConcatMul, controlProj, controlConcatWords, unsharedCells, mulBias, ... -- runs
 as one HIP kernel per primitive of a PLAN that plan.compile_cell derives from the option set once (plan.py: variable table in
 the reference's creation order + a flat operation list per zero_state / step, executed and differentiated by plan.run_segment).
-This module holds what the plan stands on: the kernel calls (k_*), the variable store under the reference's names, the cell
-class that feeds the plan's segments, and the few eager layer helpers the generic question encoder / output unit use.
+This module holds what both stacks of the path stand on -- the plan's executor (plan._Exec: the cell) and the eager autograd
+nodes below (_Binary, _Act, _Linear, _Dropout, _Embed: the generic question encoder, output unit and stem):
+  * the kernel calls (k_*), the only place that touches libmacx.so;
+  * one RULE per primitive the two stacks share, directly under them: bin_bwd (backward of scale * (a op b) under the four
+    spreads), linear_fwd / linear_bwd, act_bwd, and the two routing decisions mid_of / big_of.  _Exec's "bin" / "linear" / "act"
+    branches and the eager nodes' forward / backward are calls of these, so a spread mode, a primitive or a fix exists once;
+  * act_code, the one table from config.py's activation names (and --relu) to kernel codes, raising what the reference raises;
+  * ScopeNames, the one TF scope namer, under the variable store (GenericParams) and under the plan's compiler;
+  * the cell class that feeds the plan's segments, and the layer helpers (_Ops) of the generic encoder / output unit.
 
 Every arithmetic step is a kernel of libmacx.so behind the C ABI (include/macx.h: macx_linear / macx_h2_gemm / macx_wgrad and
 the macx_op_* primitives); PyTorch owns the device memory, the stream, the concat / slice copies and the autograd tape that
@@ -13,7 +20,8 @@ orders the backward kernels -- plumbing.  There is no CPU path: tensors must liv
 Variables are created on first use under the reference's TF names (the same scope stacking as ops.py / mac_cell.py), so a
 reference checkpoint loads by name (GenericParams.load_reference_dict) whatever the option set.
 
-Not covered (UnsupportedOptions, never a silent fallback): dimensions that are not multiples of 128.
+Widths off the kernels' 128-column granule run zero-padded inside the products (k_matmul, k_wgrad).  Not covered
+(UnsupportedOptions, never a silent fallback): widths that are not multiples of 4.
 """
 import collections
 import math
@@ -171,7 +179,81 @@ def k_wgrad(x2, g2):
 
 
 # -------------------------------------------------------------------------------------------------------------------
-# autograd nodes: forward and backward are the kernels above
+# the rules of the primitives both stacks run -- the eager autograd nodes below and the plan's executor (plan._Exec) --
+# stated once, on the kernel calls above (looked up in this module's globals at call time: a test's swap reaches both stacks).
+# Tensors arrive contiguous; a gradient nobody wants is None and launches nothing.
+# -------------------------------------------------------------------------------------------------------------------
+def mid_of(bmode, a):
+    """the middle extent macx_op_binary spreads b over: a's second-to-last axis under B_MID, 1 otherwise"""
+    return a.shape[-2] if (bmode == B_MID and a.dim() >= 2) else 1
+
+
+def big_of(x):
+    """(B, N) when [B, N <= 1024, K] takes the knowledge-base GEMM (macx_h2_gemm), None for macx_linear"""
+    return (x.shape[0], x.shape[1]) if (x.dim() == 3 and x.shape[1] <= 1024) else None
+
+
+def bin_bwd(op, bmode, scale, g, a, b, mid, inner, want_a, want_b):
+    """backward of scale * (a op b), b spread over a by `bmode` -> (da, db); db summed over the spread, in b's shape"""
+    if op == OP_ADD:
+        full = g if scale == 1.0 else k_binary(OP_ADD, B_SAME, g, torch.zeros_like(g), 1, inner, scale)
+        da = full if want_a else None
+    else:
+        da = k_binary(OP_MUL, bmode, g, b, mid, inner, scale) if want_a else None
+        full = k_binary(OP_MUL, B_SAME, g, a, 1, inner, scale) if want_b else None
+    if not want_b:
+        return da, None
+    n = g.numel()
+    if bmode == B_SAME:
+        db = full
+    elif bmode == B_MID:
+        db = k_reduce(R_MID, full, n // (mid * inner), mid, inner)
+    elif bmode == B_CHANNEL:
+        db = k_reduce(R_ROWS, full, n // inner, 1, inner)
+    else:
+        db = k_reduce(R_LAST, full, n // inner, 1, inner)
+    return da, db.reshape(b.shape)
+
+
+def linear_fwd(x, W, b):
+    """x W (+ b) over the last axis -> (y, big); `big` goes back into linear_bwd"""
+    K, n = W.shape
+    big = big_of(x)
+    return k_matmul(x.reshape(-1, K), W, b, big).reshape(x.shape[:-1] + (n,)), big
+
+
+def linear_bwd(x, W, g, big, want_x, want_W, want_b):
+    """-> (dx, dW, db): backward-data on the forward's route, macx_wgrad, a fixed-order column sum"""
+    K, n = W.shape
+    g2 = g.reshape(-1, n)
+    dx = k_matmul(g2, W.t().contiguous(), None, big).reshape(x.shape) if want_x else None
+    dW = k_wgrad(x.reshape(-1, K), g2) if want_W else None
+    db = k_reduce(R_ROWS, g2, g2.shape[0], 1, n) if want_b else None
+    return dx, dW, db
+
+
+def act_bwd(code, x, alpha, g, want_alpha):
+    """-> (dx, dalpha); dalpha: the PReLU slope's per-element gradient summed over the rows"""
+    dx, de = k_act_bwd(code, x, alpha, g)
+    inner = x.shape[-1]
+    dalpha = k_reduce(R_ROWS, de, x.numel() // inner, 1, inner) if (de is not None and want_alpha) else None
+    return dx, dalpha
+
+
+def act_code(name, relu):
+    """config.py's activation name -> macx_op_act code; "RELU" is whatever --relu (`relu`) selects, ACT_PRELU for PRM, and
+    raises what ops.relu raises (ops.py:161-187): reluAlpha's flag is commented out, SELU has no branch"""
+    if name != "RELU":
+        return _lib.ACT[name]
+    if relu == "LKY":
+        raise AttributeError("'Config' object has no attribute 'reluAlpha'")
+    if relu == "SELU":
+        raise UnboundLocalError("local variable 'output' referenced before assignment")
+    return {"STD": _lib.ACT["RELU"], "ELU": _lib.ACT["ELU"], "PRM": ACT_PRELU}[relu]
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# autograd nodes: forward and backward are the kernels and rules above
 # -------------------------------------------------------------------------------------------------------------------
 class _Binary(torch.autograd.Function):
     """out = scale * (a op b); b broadcast by `bmode` (macx_op_binary).  a: [..., mid, inner] contiguous."""
@@ -179,75 +261,17 @@ class _Binary(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, op, bmode, scale):
         a, b = _dev(a), _dev(b)
-        inner = a.shape[-1]
-        mid = a.shape[-2] if (bmode == B_MID and a.dim() >= 2) else 1
-        ctx.meta = (op, bmode, scale, mid, inner, tuple(b.shape))
+        mid, inner = mid_of(bmode, a), a.shape[-1]
+        ctx.meta = (op, bmode, scale, mid, inner)
         ctx.save_for_backward(a, b)
         return k_binary(op, bmode, a, b, mid, inner, scale)
 
     @staticmethod
     def backward(ctx, g):
-        op, bmode, scale, mid, inner, bshape = ctx.meta
+        op, bmode, scale, mid, inner = ctx.meta
         a, b = ctx.saved_tensors
-        g = g.contiguous()
-        n = g.numel()
-        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        da = db = None
-        if op == OP_ADD:
-            gs = g if scale == 1.0 else k_binary(OP_ADD, B_SAME, g, torch.zeros_like(g), 1, inner, scale)
-            da, gb_full = (gs if need_a else None), gs
-        else:
-            if need_a:
-                da = k_binary(OP_MUL, bmode, g, b, mid, inner, scale)
-            gb_full = k_binary(OP_MUL, B_SAME, g, a, 1, inner, scale) if need_b else None
-        if need_b:
-            if bmode == B_SAME:
-                db = gb_full
-            elif bmode == B_MID:
-                db = k_reduce(R_MID, gb_full, n // (mid * inner), mid, inner)
-            elif bmode == B_CHANNEL:
-                db = k_reduce(R_ROWS, gb_full, n // inner, 1, inner)
-            else:
-                db = k_reduce(R_LAST, gb_full, n // inner, 1, inner)
-            db = db.reshape(bshape)
+        da, db = bin_bwd(op, bmode, scale, g.contiguous(), a, b, mid, inner, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return da, db, None, None, None
-
-
-class _Reduce(torch.autograd.Function):
-    """Sum over the middle axis of [B,N,d] (R_MID) or the last axis of [...,d] (R_LAST) (macx_op_reduce)."""
-
-    @staticmethod
-    def forward(ctx, x, mode):
-        x = _dev(x)
-        ctx.mode, ctx.shape = mode, tuple(x.shape)
-        if mode == R_MID:
-            B, N, d = x.shape
-            return k_reduce(R_MID, x, B, N, d)
-        d = x.shape[-1]
-        return k_reduce(R_LAST, x, x.numel() // d, 1, d).reshape(x.shape[:-1])
-
-    @staticmethod
-    def backward(ctx, g):
-        g = g.contiguous()
-        ones = torch.ones(ctx.shape, dtype=torch.float32, device=g.device)
-        if ctx.mode == R_MID:
-            return k_binary(OP_MUL, B_MID, ones, g, ctx.shape[1], ctx.shape[2]), None
-        return k_binary(OP_MUL, B_ROW, ones, g.reshape(-1), 1, ctx.shape[-1]), None
-
-
-class _RowSum(torch.autograd.Function):
-    """Sum over the rows of [rows, c] (macx_op_reduce ROWS): batch statistics."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = _dev(x)
-        ctx.shape = tuple(x.shape)
-        return k_reduce(R_ROWS, x, x.shape[0], 1, x.shape[1])
-
-    @staticmethod
-    def backward(ctx, g):
-        ones = torch.ones(ctx.shape, dtype=torch.float32, device=g.device)
-        return k_binary(OP_MUL, B_CHANNEL, ones, g.contiguous(), 1, ctx.shape[1])
 
 
 class _Act(torch.autograd.Function):
@@ -264,25 +288,8 @@ class _Act(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, al = ctx.saved_tensors
-        inner = x.shape[-1]
-        dx, de = k_act_bwd(ctx.act, x, al, g.contiguous())
-        dal = k_reduce(R_ROWS, de, x.numel() // inner, 1, inner) if de is not None else None
+        dx, dal = act_bwd(ctx.act, x, al, g.contiguous(), ctx.needs_input_grad[2])
         return dx, None, dal
-
-
-class _Softmax(torch.autograd.Function):
-    """softmax over the last axis, optionally behind ops.expMask (ops.py:243-247) (macx_op_softmax)."""
-
-    @staticmethod
-    def forward(ctx, x, lengths):
-        out = k_softmax(_dev(x), lengths)
-        ctx.save_for_backward(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (a,) = ctx.saved_tensors
-        return k_softmax_bwd(a, g.contiguous()), None
 
 
 class _Dropout(torch.autograd.Function):
@@ -305,22 +312,14 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b):
         x, W = _dev(x), _dev(W)
-        K, n = W.shape
-        x2 = x.reshape(-1, K)
-        big = (x.shape[0], x.shape[1]) if (x.dim() == 3 and x.shape[1] <= 1024) else None
-        ctx.big, ctx.xshape, ctx.has_b = big, tuple(x.shape), b is not None
-        ctx.save_for_backward(x2, W)
-        return k_matmul(x2, W, _dev(b) if b is not None else None, big).reshape(x.shape[:-1] + (n,))
+        y, ctx.big = linear_fwd(x, W, _dev(b) if b is not None else None)
+        ctx.save_for_backward(x, W)
+        return y
 
     @staticmethod
     def backward(ctx, g):
-        x2, W = ctx.saved_tensors
-        n = W.shape[1]
-        g2 = g.contiguous().reshape(-1, n)
-        dx = k_matmul(g2, W.t().contiguous(), None, ctx.big).reshape(ctx.xshape) if ctx.needs_input_grad[0] else None
-        dW = k_wgrad(x2, g2) if ctx.needs_input_grad[1] else None
-        db = k_reduce(R_ROWS, g2, g2.shape[0], 1, n) if ctx.has_b and ctx.needs_input_grad[2] else None
-        return dx, dW, db
+        x, W = ctx.saved_tensors
+        return linear_bwd(x, W, g.contiguous(), ctx.big, *ctx.needs_input_grad)
 
 
 class _Embed(torch.autograd.Function):
@@ -346,6 +345,38 @@ class _Embed(torch.autograd.Function):
 # -------------------------------------------------------------------------------------------------------------------
 # variables under the reference's names
 # -------------------------------------------------------------------------------------------------------------------
+class ScopeNames:
+    """TF variable scopes, names only: `with names("a"):` is tf.variable_scope("a"); default=True is
+    tf.variable_scope(None, default_name=name) -- `name`, then `name_1`, ... within one opening of the enclosing scope (ops.py:163;
+    the counts of a scope's children reset when it closes, as in TF).  The variable store below and the plan's compiler
+    (plan._Emitter) both name their variables through one of these."""
+
+    def __init__(self):
+        self.stack, self.opened = [], {}          # opened: full scope name -> times opened
+
+    @contextmanager
+    def __call__(self, name, default=False):
+        if default:
+            base = "/".join(self.stack + [name])
+            if self.opened.get(base, 0):
+                k = 1
+                while self.opened.get("%s_%d" % (base, k), 0):
+                    k += 1
+                name = "%s_%d" % (name, k)
+        self.stack.append(name)
+        full = "/".join(self.stack)
+        self.opened[full] = self.opened.get(full, 0) + 1
+        try:
+            yield
+        finally:
+            self.stack.pop()
+            for key in [k for k in self.opened if k.startswith(full + "/")]:
+                self.opened[key] = 0
+
+    def full(self, leaf):
+        return "/".join(self.stack + [leaf])
+
+
 class GenericParams(torch.nn.Module):
     """name -> Parameter, created on first use with the reference's initialisers (xavier-uniform weights ops.py:20, zero
     biases ops.py:40, N(0,1) state variables mac_cell.py:498-499, 0.25 PReLU slopes ops.py:172)."""
@@ -356,34 +387,18 @@ class GenericParams(torch.nn.Module):
         self.gen = generator
         self.table = torch.nn.ParameterDict()
         self.names = {}               # reference name -> ParameterDict key
-        self._stack = []
-        self._counts = {}             # full scope name -> times opened (default-name scopes: prelu, prelu_1, ...)
+        self.scopes = ScopeNames()
 
-    @contextmanager
     def scope(self, name, default=False):
-        """tf.variable_scope(name); default=True: tf.variable_scope(None, default_name=name) -- `name`, then `name_1`, ... within
-        one opening of the enclosing scope (ops.py:163; the counts of a scope's children reset when it closes, as in TF)."""
-        if default:
-            cur = "/".join(self._stack + [name])
-            if self._counts.get(cur, 0) > 0:
-                idx = 1
-                while self._counts.get("%s_%d" % (cur, idx), 0) > 0:
-                    idx += 1
-                name = "%s_%d" % (name, idx)
-        self._stack.append(name)
-        full = "/".join(self._stack)
-        self._counts[full] = self._counts.get(full, 0) + 1
-        try:
-            yield
-        finally:
-            self._stack.pop()
-            pre = full + "/"
-            for k in list(self._counts):
-                if k.startswith(pre):
-                    self._counts[k] = 0
+        """tf.variable_scope(name); default=True: tf.variable_scope(None, default_name=name) (ScopeNames)"""
+        return self.scopes(name, default)
 
     def get(self, name, shape, init):
-        key = "/".join(self._stack + [name])
+        """the variable `name` of the open scope"""
+        return self.ensure(self.scopes.full(name), shape, init)
+
+    def ensure(self, key, shape, init):
+        """the variable `key` (a complete scope path), created with `init` unless it exists (a loaded checkpoint)"""
         shape = tuple(shape)
         if key not in self.names:
             if init == "xavier":
@@ -401,14 +416,6 @@ class GenericParams(torch.nn.Module):
         if tuple(v.shape) != shape:
             raise ValueError("variable %s has shape %s, expected %s" % (key, tuple(v.shape), shape))
         return v
-
-    def ensure(self, full_name, shape, init):
-        """the variable `full_name` (a complete scope path), created with `init` unless it exists (a loaded checkpoint)"""
-        saved, self._stack = self._stack, []
-        try:
-            return self.get(full_name, shape, init)
-        finally:
-            self._stack = saved
 
     def _apply(self, fn, *a, **kw):
         """.to(device) / .cuda() on this module or on any module that holds it: variables created later follow."""
@@ -497,16 +504,11 @@ class _Ops:
         """config.py's activation names on macx_op_act; "RELU" is whatever --relu selects (ops.py:161-187)"""
         if name == "NON":
             return x
-        flavour = self.g("relu") if name == "RELU" else None
-        if flavour == "PRM":
+        code, alpha = act_code(name, self.g("relu")), None
+        if code == ACT_PRELU:
             with self.vs.scope("prelu", default=True):
-                return _Act.apply(x, ACT_PRELU, self.vs.get("alpha", (x.shape[-1],), 0.25))
-        if flavour == "LKY":
-            raise AttributeError("'Config' object has no attribute 'reluAlpha'")
-        if flavour == "SELU":
-            raise UnboundLocalError("local variable 'output' referenced before assignment")
-        code = {None: name, "ELU": "ELU", "STD": "RELU"}[flavour]
-        return _Act.apply(x, _lib.ACT[code], None)
+                alpha = self.vs.get("alpha", (x.shape[-1],), 0.25)
+        return _Act.apply(x, code, alpha)
 
     def linear(self, inp, inDim, outDim, dropout=None, act="NON", name=""):
         """[.., inDim] -> [.., outDim] under "linearLayer<name>" (ops.py:298-333): input dropout, x W + b, activation and -- with an

@@ -9,13 +9,16 @@ step is therefore ONE node of PyTorch's autograd graph (the interface the refere
 one node per reference op, and adjacent primitives are visible to a later fusion pass as data.
 
 Every primitive's arithmetic is a kernel of libmacx.so (generic.k_*: macx_linear / macx_h2_gemm / macx_wgrad / macx_op_*);
-PyTorch owns memory, streams, concat / stack copies.  What the option values mean is the reference's (mac_cell.py:133-375,
+PyTorch owns memory, streams, concat / stack copies.  What this stack has in common with the eager autograd nodes of generic.py
+lives there and is only called here: the rules of "bin", "linear" and "act" (generic.bin_bwd, linear_fwd / linear_bwd, act_bwd,
+mid_of, big_of), the activation table (generic.act_code) and the scope namer (generic.ScopeNames).  The primitives only the
+plan has (rowdot, wsum, blend, bn, ...) keep their rules in _Exec.  What the option values mean is the reference's (mac_cell.py:133-375,
 420-480, 539-592; ops.py:161-187, 298-333, 668-725) and is checked against it by executing the reference
 (tests/test_reference_exec.py -> oracle -> tests/test_generic_host.py, tests/test_gpu_generic.py); how it is organised --
 an option compiler emitting a dataflow plan, an interpreter with its own reverse sweep -- is not.
 """
 import collections
-from contextlib import ExitStack, contextmanager
+from contextlib import ExitStack
 
 import torch
 
@@ -27,36 +30,6 @@ Node = collections.namedtuple("Node", "op out ins attr")
 VarSpec = collections.namedtuple("VarSpec", "shape init")
 SITE = dict(mem_var=1, mem=2, read_kb=3, read_mem=4, read_att=5, write_info=6)
 NOGRAD_OPS = ("fill", "zeros", "bn_update")
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# naming: TF variable scopes, names only (default-name scopes count up within one opening of their parent)
-# ---------------------------------------------------------------------------------------------------------------------
-class ScopeNames:
-    def __init__(self):
-        self.stack, self.opened = [], {}
-
-    @contextmanager
-    def __call__(self, name, default=False):
-        if default:
-            base = "/".join(self.stack + [name])
-            if self.opened.get(base, 0):
-                k = 1
-                while self.opened.get("%s_%d" % (base, k), 0):
-                    k += 1
-                name = "%s_%d" % (name, k)
-        self.stack.append(name)
-        full = "/".join(self.stack)
-        self.opened[full] = self.opened.get(full, 0) + 1
-        try:
-            yield
-        finally:
-            self.stack.pop()
-            for key in [k for k in self.opened if k.startswith(full + "/")]:
-                self.opened[key] = 0
-
-    def full(self, leaf):
-        return "/".join(self.stack + [leaf])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -119,7 +92,7 @@ class _Emitter:
                   "out_words": "ctrlDim"}
 
     def __init__(self, config, plan):
-        self.cfg, self.plan, self.names, self.seg, self.w = config, plan, ScopeNames(), None, {}
+        self.cfg, self.plan, self.names, self.seg, self.w = config, plan, G.ScopeNames(), None, {}
         self.kb_lengths = False        # compile_cell(kb_lengths=True): the read unit's attention takes a "kb_lengths" feed
 
     def opt(self, key):
@@ -155,18 +128,12 @@ class _Emitter:
     def activation(self, kind, x):
         if kind == "NON":
             return x
-        if kind == "RELU":
-            flavour = self.opt("relu")
-            if flavour == "PRM":
-                with self.names("prelu", default=True):
-                    slope = self.variable("alpha", (self.w[x],), 0.25)
-                return self.emit(self.w[x], "act", x, slope, code=G.ACT_PRELU)
-            if flavour == "LKY":
-                raise AttributeError("'Config' object has no attribute 'reluAlpha'")
-            if flavour == "SELU":
-                raise UnboundLocalError("local variable 'output' referenced before assignment")
-            kind = "ELU" if flavour == "ELU" else "RELU"
-        return self.emit(self.w[x], "act", x, code=_lib.ACT[kind])
+        code = G.act_code(kind, self.opt("relu"))
+        if code != G.ACT_PRELU:
+            return self.emit(self.w[x], "act", x, code=code)
+        with self.names("prelu", default=True):
+            slope = self.variable("alpha", (self.w[x],), 0.25)
+        return self.emit(self.w[x], "act", x, slope, code=code)
 
     # -- a dense layer family member "linearLayer<tag>" (ops.py:298-333): K -> n (n = 1: a dot product per row), optional
     #    input dropout, activation, and -- when there is an activation -- the stacked "<tag>_2" layer
@@ -444,10 +411,6 @@ _SPREAD = {"same": G.B_SAME, "mid": G.B_MID, "channel": G.B_CHANNEL, "row": G.B_
 _OPC = {"add": G.OP_ADD, "mul": G.OP_MUL}
 
 
-def _ones_like(t):
-    return torch.ones_like(t)
-
-
 class _Exec:
     """the per-run context of a segment execution: dropout stream, mode, batch"""
 
@@ -460,12 +423,10 @@ class _Exec:
         op, a = nd.op, nd.attr
         if op == "linear":
             inp, W, b = x[0].contiguous(), x[1], (x[2] if len(x) > 2 else None)
-            K, n = W.shape
-            big = (inp.shape[0], inp.shape[1]) if (inp.dim() == 3 and inp.shape[1] <= 1024) else None
             if b is not None and a["const"] != 0.0:
                 b = G.k_binary(G.OP_ADD, G.B_SAME, b.contiguous(), torch.full_like(b, a["const"]), 1, b.shape[-1])
-            stash[nd.out] = big
-            return G.k_matmul(inp.reshape(-1, K), W, b, big).reshape(inp.shape[:-1] + (n,))
+            y, stash[nd.out] = G.linear_fwd(inp, W, b)               # (y, big: the route backward-data repeats)
+            return y
         if op == "rowdot":
             inp, w = x[0].contiguous(), x[1]
             c = inp.shape[-1]
@@ -478,10 +439,8 @@ class _Exec:
         if op == "act":
             return G.k_act(a["code"], x[0].contiguous(), x[1] if len(x) > 1 else None)
         if op == "bin":
-            p, q = x[0].contiguous(), x[1].contiguous()
-            inner = p.shape[-1]
-            mid = p.shape[-2] if (a["spread"] == "mid" and p.dim() >= 2) else 1
-            return G.k_binary(_OPC[a["op"]], _SPREAD[a["spread"]], p, q, mid, inner, a["scale"])
+            p, q, mode = x[0].contiguous(), x[1].contiguous(), _SPREAD[a["spread"]]
+            return G.k_binary(_OPC[a["op"]], mode, p, q, G.mid_of(mode, p), p.shape[-1], a["scale"])
         if op == "shift":
             p = x[0].contiguous()
             return G.k_binary(G.OP_ADD, G.B_CHANNEL, p, torch.full((p.shape[-1],), a["by"], device=p.device), 1, p.shape[-1])
@@ -507,7 +466,7 @@ class _Exec:
         if op == "blend":
             new, old, z = [t.contiguous() for t in x]
             inner = z.shape[-1]
-            ones = _ones_like(z)
+            ones = torch.ones_like(z)
             rest = G.k_binary(G.OP_ADD, G.B_SAME, G.k_binary(G.OP_MUL, G.B_SAME, z, ones, 1, inner, -1.0), ones, 1, inner)
             stash[nd.out] = rest
             return G.k_binary(G.OP_ADD, G.B_SAME, G.k_binary(G.OP_MUL, G.B_SAME, new, z, 1, inner), G.k_binary(G.OP_MUL, G.B_SAME, old, rest, 1, inner), 1, inner)
@@ -520,13 +479,7 @@ class _Exec:
         op, a = nd.op, nd.attr
         g = g.contiguous()
         if op == "linear":
-            inp, W = x[0].contiguous(), x[1]
-            K, n = W.shape
-            g2, big = g.reshape(-1, n), stash.get(nd.out)
-            dx = G.k_matmul(g2, W.t().contiguous(), None, big).reshape(inp.shape) if want[0] else None
-            dW = G.k_wgrad(inp.reshape(-1, K), g2) if want[1] else None
-            db = G.k_reduce(G.R_ROWS, g2, g2.shape[0], 1, n) if (len(x) > 2 and want[2]) else None
-            return [dx, dW, db][:len(x)]
+            return G.linear_bwd(x[0].contiguous(), x[1], g, stash.get(nd.out), want[0], want[1], len(x) > 2 and want[2])[:len(x)]
         if op == "rowdot":
             inp, w = x[0].contiguous(), x[1]
             c = inp.shape[-1]
@@ -539,37 +492,11 @@ class _Exec:
                 out.append(G.k_reduce(G.R_ROWS, g.reshape(-1, 1), rows, 1, 1).reshape(x[2].shape) if want[2] else None)
             return out
         if op == "act":
-            inp = x[0].contiguous()
             slope = x[1] if len(x) > 1 else None
-            dx, de = G.k_act_bwd(a["code"], inp, slope, g)
-            out = [dx]
-            if slope is not None:
-                c = inp.shape[-1]
-                out.append(G.k_reduce(G.R_ROWS, de, inp.numel() // c, 1, c) if (de is not None and want[1]) else None)
-            return out
+            return G.act_bwd(a["code"], x[0].contiguous(), slope, g, slope is not None and want[1])[:len(x)]
         if op == "bin":
-            p, q = x[0].contiguous(), x[1].contiguous()
-            inner, n = p.shape[-1], g.numel()
-            mid = p.shape[-2] if (a["spread"] == "mid" and p.dim() >= 2) else 1
-            mode, scale = _SPREAD[a["spread"]], a["scale"]
-            if a["op"] == "add":
-                gs = g if scale == 1.0 else G.k_binary(G.OP_ADD, G.B_SAME, g, torch.zeros_like(g), 1, inner, scale)
-                dp, full = (gs if want[0] else None), gs
-            else:
-                dp = G.k_binary(G.OP_MUL, mode, g, q, mid, inner, scale) if want[0] else None
-                full = G.k_binary(G.OP_MUL, G.B_SAME, g, p, 1, inner, scale) if want[1] else None
-            dq = None
-            if want[1]:
-                if mode == G.B_SAME:
-                    dq = full
-                elif mode == G.B_MID:
-                    dq = G.k_reduce(G.R_MID, full, n // (mid * inner), mid, inner)
-                elif mode == G.B_CHANNEL:
-                    dq = G.k_reduce(G.R_ROWS, full, n // inner, 1, inner)
-                else:
-                    dq = G.k_reduce(G.R_LAST, full, n // inner, 1, inner)
-                dq = dq.reshape(q.shape)
-            return [dp, dq]
+            p, q, mode = x[0].contiguous(), x[1].contiguous(), _SPREAD[a["spread"]]
+            return G.bin_bwd(_OPC[a["op"]], mode, a["scale"], g, p, q, G.mid_of(mode, p), p.shape[-1], want[0], want[1])
         if op == "shift":
             return [g]
         if op == "softmax":
@@ -600,7 +527,7 @@ class _Exec:
             d_old = G.k_binary(G.OP_MUL, G.B_SAME, g, rest, 1, inner) if want[1] else None
             d_z = None
             if want[2]:
-                diff = G.k_binary(G.OP_ADD, G.B_SAME, new, G.k_binary(G.OP_MUL, G.B_SAME, old, _ones_like(old), 1, inner, -1.0), 1, inner)
+                diff = G.k_binary(G.OP_ADD, G.B_SAME, new, G.k_binary(G.OP_MUL, G.B_SAME, old, torch.ones_like(old), 1, inner, -1.0), 1, inner)
                 d_z = G.k_binary(G.OP_MUL, G.B_SAME, g, diff, 1, inner)
             return [d_new, d_old, d_z]
         if op == "bn":

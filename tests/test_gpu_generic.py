@@ -221,3 +221,23 @@ def test_random_option_sets_on_the_gpu(macx, dev, seed):
     from test_generic_host import run_random_sets
     run_random_sets(macx, seed, dev=dev)
     torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_eager_nodes_and_plan_segments_agree_on_the_device(macx, dev):
+    """The eager autograd nodes (generic._Binary / _Act / _Linear) and one-node plan segments run the same rules on the same
+    kernels (tests/test_generic_rules_host.py: stacks_agree): outputs and every input gradient bit for bit.  [3, 10, 128] takes the
+    knowledge-base GEMM, [5, 128] macx_linear; 36 columns run zero-padded."""
+    from test_generic_rules_host import SPREADS, act_agrees, bin_agrees, linear_agrees, rand
+    for op in ("add", "mul"):
+        for spread in SPREADS:
+            for scale in (1.0, -0.5):
+                bin_agrees(macx, rand((3, 10, 128), 21, dev), op, spread, scale, dev)
+    y, (dx, dalpha) = act_agrees(macx, rand((3, 128), 22, dev), macx.generic.ACT_PRELU, dev)
+    assert dalpha.shape == (128,) and float(dalpha.abs().max()) > 0.0
+    for xshape in ((3, 10, 128), (5, 128)):
+        for n in (128, 36):
+            for bias in (True, False):
+                y, grads = linear_agrees(macx, rand(xshape, 23, dev), n, bias, dev)
+                assert y.shape == xshape[:-1] + (n,) and float(y.abs().max()) > 0.0
+    torch.cuda.synchronize()
