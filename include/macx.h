@@ -230,6 +230,42 @@ int macx_saved_segment(const macx_opts*, const macx_shapes*, int keep_activation
 /* validates an option/shape combination exactly as macx_cell_begin would */
 int macx_check(const macx_opts*, const macx_shapes*);
 
+/* The launch route of a fused-cell call: which of its kernels the library runs for these options, shapes and dropout on a device of
+ * `ncu` compute units, and how it sizes what they share.  The library plans this once per call, with the same function; this export
+ * only reads the plan (nothing is launched), for tests, tools and records.  Fields 0 / 1 unless a range is given. */
+typedef struct macx_route {
+  int32_t family;             /* kernel family the call runs on: MACX_GEMM_NATIVE / _SPLIT / _H2                               */
+  int32_t chain;              /* the read unit's products as ONE kernel per direction, chain_fwd / chain_bwd<d> (H2 family, d <= 512,
+                                 N >= 16, MACX_TUNE_CHAIN); 0: one launch per product                                             */
+  int32_t tile_rows, tiles;   /* chain: rows of a tile (16 | 32 | 64) and tiles of a launch; else 0                              */
+  int32_t chain_sums;         /* chain_bwd leaves per-tile partials of what is summed per question (N >= 32)                     */
+  int32_t sb_deferred;        /* dy from chain_bwd, S_b = X_b^T dI1_b of all steps in ONE launch at the end (MACX_TUNE_SB_DEFER); 0:
+                                 the S_b kernel once per step, which then also delivers dy                                        */
+  int32_t dy_in_linear;       /* sb_deferred: the dy linear sums the per-tile partials of dy itself (B <= 128, <= 6 tiles a question) */
+  int32_t dc_reduce_per_step; /* sb_deferred: ... or a reduction launch behind every chain_bwd launch does (a recurrent control unit
+                                 makes the whole-cell backward pass reduce per step whatever this says)                           */
+  int32_t sb_wide;            /* sb_deferred: the 128 x 256 S_b kernel (MACX_TUNE_SB_WIDE); 0: the 128 x 128 one                    */
+  int32_t sb_qpg, sb_groups;  /* questions per workgroup group of the S_b kernel in use, and groups per launch                   */
+  int32_t sb_slabs;           /* [d,d] partial slabs of dW1a (and of dW1b) the closing reduction sums                             */
+  int32_t wgrad_splits;       /* reduction splits the dW2 / dWx slabs are sized for                                              */
+  int32_t wgrad_kw;           /* H2 family: 128-column blocks per tile side (kw = jw) of those contractions, 1 | 2; else 0        */
+  int32_t db_rows, dwk_rows;  /* rows per step of the bias-gradient partials of dI1 / dX, and of dw_k / db2                       */
+  int32_t wfmt_plain, wfmt_ymix; /* internal pack format of a plain weight (0 f32 MFMA order | 1 bf16 planes | 3 fp16 planes +
+                                 exponent) and of one mixed with a per-question vector (0 | 2 fp32 k-major tiles)                */
+  /* what depends on `ncu` and on the dropout, never on anything above: work on the compute units a chain launch's tiles leave idle */
+  int32_t fwd_fillers;        /* filler workgroups of each chain_fwd launch of macx_cell_forward (MACX_TUNE_PRE_FILL); 0: none       */
+  int32_t fill_y;             /* ... they compute the step's y = md Wy + by                                                       */
+  int32_t fill_stage0;        /* ... and stage 0 (dropout(KB) -> fp16 planes) of the next step: keep_activations and keep_read < 1  */
+  int32_t fill_write;         /* ... and the previous step's write linear: no gate, no self-attention, no recurrent control, no write
+                                 dropout                                                                                          */
+  int32_t dkb_jobs, dkb_fillers, dkb_skip; /* dKB on chain_bwd's idle compute units (MACX_TUNE_DKB_FILL): jobs per filler workgroup
+                                 (0: the merged dKB launch), filler workgroups, tiles a launch leaves to the closing launch        */
+} macx_route;
+/* dropout NULL: no dropout.  ncu <= 0: the current device's compute units, exactly as a launch plans (0 without a device, hence no
+ * fillers); ncu > 0: plan for that many.  No field above the filler block depends on ncu or the dropout.  The step-wise and unit
+ * entry points follow the same route but never use forward fillers.  Returns what macx_check returns. */
+int macx_cell_route(const macx_opts*, const macx_shapes*, const macx_dropout*, int keep_activations, int ncu, macx_route* out);
+
 /* ---- did the run's in-launch hand-offs complete? ------------------------------------------------ */
 /* In the default d = 512 path (macx_cell_forward, MACX_TUNE_PRE_FILL) workgroups of ONE launch hand results to each other through
  * counters; the waits are bounded.  A workgroup whose wait runs out does not use the unfinished data: it computes on quiet NaNs, so

@@ -55,6 +55,14 @@ class MacxDropout(C.Structure):
                 ("mask_word", C.c_void_p)]
 
 
+class MacxRoute(C.Structure):
+    """macx_route: the launch route macx_cell_route reports (include/macx.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "family", "chain", "tile_rows", "tiles", "chain_sums", "sb_deferred", "dy_in_linear", "dc_reduce_per_step", "sb_wide", "sb_qpg",
+        "sb_groups", "sb_slabs", "wgrad_splits", "wgrad_kw", "db_rows", "dwk_rows", "wfmt_plain", "wfmt_ymix", "fwd_fillers", "fill_y",
+        "fill_stage0", "fill_write", "dkb_jobs", "dkb_fillers", "dkb_skip")]
+
+
 PARAM_FIELDS = (
     "initMem", "initCtrl", "qInput_W", "qInput_b", "qInputU_W", "qInputU_b", "ctrlLogits_w", "ctrlLogits_b",
     "contControl_W", "contControl_b", "contControl2_W", "contControl2_b", "projX_W", "projX_b", "projY_W", "projY_b",
@@ -177,7 +185,8 @@ TABLE.update(
     macx_saved_floats=(_Z, _OS + (_I,)),
     macx_ws_floats=(_Z, _OS + (_I,)),
     macx_saved_segment=(_I, _OS + (_I, _I, _P(_Z), _P(_Z))),
-    macx_check=(_I, _OS))
+    macx_check=(_I, _OS),
+    macx_cell_route=(_I, _OS + (_P(MacxDropout), _I, _I, _P(MacxRoute))))
 # ---- did the run's in-launch hand-offs complete?
 TABLE.update(
     macx_run_status=(_I, _OS + (_I, _V, _Z, _V, _P(_U), _P(C.c_int32))),

@@ -57,20 +57,7 @@ struct ModeScope {
   }
   ~ModeScope() { gemm_call_override() = saved; }
 };
-inline bool h2_mode() { return gemm_split_mode() == 2; }
-// the read unit's products as one kernel per direction (macx_chain_h2.hip.h); MACX_TUNE_CHAIN = 0 falls back to the per-product
-// launches that also serve d > 512 and N < 16
-inline int chain_mode() { return tune_get(MACX_TUNE_CHAIN, 1); }
-inline bool use_chain(int d, int N) { return h2_mode() && chain_mode() && chain_supported(d, N); }
-// dy from the chain kernel and S_b of all steps as one deferred launch; MACX_TUNE_SB_DEFER = 0: sb_h2 once per step (what N < 32 runs)
-inline int sb_defer_mode() { return tune_get(MACX_TUNE_SB_DEFER, 1); }
-// the deferred S_b contraction on 128 x 256 tiles with summation by parts (sb_h2w_kernel); MACX_TUNE_SB_WIDE = 0: the 128 x 128 kernel.
-// (Measured and removed: dW1a / dW1b as ONE dual-A contraction over X * y and X -- twice the matrix work, 392 against 345 us,
-// profiles/r05_dual_contraction_ab.txt; a side queue for the per-step dKB / dW2 contractions -- +8 % / +130 us per step,
-// profiles/r04_side_queue_ab.txt.)
-inline int sb_wide_mode() { return tune_get(MACX_TUNE_SB_WIDE, 1) ? 1 : 0; }
-inline int wfmt_plain() { return h2_mode() ? 3 : (gemm_split_mode() ? 1 : 0); }
-inline int wfmt_ymix() { return gemm_split_mode() ? 2 : 0; }
+inline bool h2_mode() { return gemm_split_mode() == 2; }      // (the fused cell asks its CellRoute instead)
 inline size_t wsize(size_t K, size_t n) { return K * n * 3 / 2; }     // covers format 1 (3/2) and format 3 (1 + the exponent)
 inline hipError_t wgrad_any(const TnP& t, hipStream_t st) {
   return (gemm_split_mode() && !(kb_gemm_dbg() & 128)) ? wgrad6_launch(t, st) : wgrad_tn_launch<A_PLAIN>(t, st);   // dbg 128: f32 TN kernel
@@ -124,6 +111,39 @@ inline int write_in_dim(const macx_opts* o, int d) {
   return dim;
 }
 
+// ---- the route of a fused-cell call ------------------------------------------------------------
+// Every choice among the cell's launch routes, taken ONCE per ABI call by plan_route() below (under the entry point's ModeScope) and
+// read by the two layouts, by CellRun / CellBwd and by macx_cell_route: no other code of the cell asks the kernel family, the tuning
+// table or the device.  (Launchers still pick their own kernel VARIANT from the tuning table in the kernel headers: chain_kv,
+// wgrad_pipe_mode, MACX_TUNE_ROW_TILES / _NATIVE_WAVES / _SB_CONT / _DKB_UNI and the kb_gemm_dbg phase masks.)
+struct CellRoute {
+  // ---- decided by (opts, shapes) alone: all that make_saved and make_bwd read (the sizing calls know no dropout and no device)
+  int family;                 // kernel family: 0 native f32 MFMA, 1 split-bf16, 2 H2 fp16 planes
+  bool h2;                    // ... is the H2 family
+  int wfmt_plain, wfmt_ymix;  // pack format of a plain weight / of one mixed with a per-question vector (B_YMIX_*) in that family
+  bool chain;                 // the read unit's products in the chain kernels, one launch per direction (else one launch per product)
+  int tile_rows, tile_shift;  // chain: rows of a tile (16 | 32 | 64) and their log2
+  size_t ntile;               // chain: tiles of a launch
+  bool chain_sums;            // the backward chain kernel leaves per-tile partials of dw_k / db2 / dc / db_k
+  bool sb_deferred;           // dy comes from the chain kernel: dI1 is kept per step and S_b of all steps is ONE launch at the end
+  bool dy_in_linear;          // ... and its per-tile partials are summed by the dy linear itself (small_linear PART form)
+  bool dc_reduce_per_step;    // ... or by a dc_reduce launch behind every chain_bwd launch (which then reduces dc / db_k too)
+  bool sb_wide;               // the deferred S_b contraction runs on sb_h2w_kernel (128 x 256 tiles, summation by parts)
+  int sb_qpg;                 // questions per workgroup group of the S_b kernel in use
+  size_t ngroup;              // ... and the groups of a launch
+  size_t nslab_sb;            // slabs of dW1a / dW1b the closing reduction sums
+  size_t ns_big;              // reduction splits the dW2 / dWx slabs are sized for
+  size_t db_rows;             // rows per step of db1_part / dbx_part
+  size_t dwk_rows;            // rows per step of dwk_part / db2_part
+  // ---- decided with the run's dropout and the device's compute units: what macx_cell_forward's and the backward loop's chain launches
+  // carry on the CUs their tile grids leave idle.  Never read by a layout.
+  int nfill;                  // filler workgroups of a chain_fwd launch (0: none)
+  bool fill_y;                // they compute the step's y = md Wy + by (PRE_YLIN)
+  bool fill_stage0;           // ... and stage 0 of the next step (PRE_STAGE0_NEXT / _DONE)
+  bool fill_write;            // ... and the previous step's write linear (PRE_WRITE_NEXT / _PREV)
+  DkbFillPlan dkb;            // dKB jobs on chain_bwd's idle CUs (njobs = 0: the merged dKB launch)
+};
+
 // ---- layout of `saved` ------------------------------------------------------------------------
 // The backward pass reads its weights in layouts of its own (transposes; H2 planes for the chain kernels): [wxT | w1aT | w1bT | w2T |
 // wyT | wmT | wqT | wqUT | wccT | wcc2T | wscT | wgT], the first region of the backward workspace layout (make_bwd).  A run that keeps
@@ -168,7 +188,7 @@ struct SavedLayout {
   size_t total;
 };
 
-SavedLayout make_saved(const macx_opts* o, const macx_shapes* s, int keep) {
+SavedLayout make_saved(const macx_opts* o, const macx_shapes* s, int keep, const CellRoute& R) {
   SavedLayout L;
   memset(&L, 0, sizeof(L));
   const size_t B = s->B, S = s->S, N = s->N, d = s->d, p = s->p;
@@ -215,13 +235,13 @@ SavedLayout make_saved(const macx_opts* o, const macx_shapes* s, int keep) {
   const size_t pk = keep ? p : 1;
   // h2 mode: activations are H2 tensors (4 bytes per element + exponents + pad rows); the attention keep bits are kept as
   // one byte per 8-column slot in slot order [d/8][Rp]
-  L.act_floats = h2_mode() ? al4(h2_floats(B * N, d)) : B * N * d;
+  L.act_floats = R.h2 ? al4(h2_floats(B * N, d)) : B * N * d;
   L.act_stride = keep ? L.act_floats : 0;
   L.X = take(pk * L.act_floats);
   L.H1 = take(pk * L.act_floats);
   L.I2 = take(pk * L.act_floats);
   L.KBd = take(pk * L.act_floats);
-  const size_t bits_floats = h2_mode() ? al4(((B * N + H2_PAD_ROWS) * (d / 8) + 3) / 4) : B * N * d / 32;
+  const size_t bits_floats = R.h2 ? al4(((B * N + H2_PAD_ROWS) * (d / 8) + 3) / 4) : B * N * d / 32;
   L.bits_stride = keep ? bits_floats : 0;
   L.kb_bits = take(pk * bits_floats);
   L.att_bits = take(pk * bits_floats);
@@ -253,8 +273,8 @@ inline int wgrad_splits(int M, int Kd, int Jd) {
   return ns;
 }
 // ... of the deferred H2 contractions (macx_wgrad_h2.hip.h: up to 256 x 256 output tiles)
-inline int wgrad_big_splits(int M, int Kd, int Jd) {
-  if (!h2_mode()) return wgrad_splits(M, Kd, Jd);
+inline int wgrad_big_splits(bool h2, int M, int Kd, int Jd) {
+  if (!h2) return wgrad_splits(M, Kd, Jd);
   int ns = 256 / wgrad_h2_tiles(Kd, Jd);
   const int max_by_rows = (M + 255) / 256;
   if (ns > max_by_rows) ns = max_by_rows;
@@ -264,16 +284,80 @@ inline int rows_per_split(int M, int ns) {
   int r = (M + ns - 1) / ns;
   return h2_mode() ? (r + 31) & ~31 : (r + 1) & ~1;       // H2: a 32-row stage never straddles two splits
 }
-inline int sb_qpg(int B, int N = 0) {   // questions per workgroup group in the S_b kernel: 16 tiles x groups ~ 256
+inline int sb_qpg(bool h2, int B, int N) {   // questions per workgroup group in the S_b kernel: 16 tiles x groups ~ 256
   int qpg = (B + 15) / 16;
   if (qpg < 1) qpg = 1;
-  if (h2_mode() && N > 0) {                 // the H2 kernel keeps one fp16 factor per (question, row) of a group in LDS
+  if (h2) {                                 // the H2 kernel keeps one fp16 factor per (question, row) of a group in LDS
     const int rows_q = ((N + 31) / 32) * 32;
     const int cap = SBH_MAXROWS / rows_q;
     if (qpg > cap) qpg = cap < 1 ? 1 : cap;
     if (qpg > SBH_MAXQ) qpg = SBH_MAXQ;
   }
   return qpg;
+}
+
+// The one place the cell's route is decided.  dp: the run's dropout (null: none -- the sizing calls); keep: the run keeps its
+// activations; ncu_: compute units to plan the fillers for, NCU_ASK: those of the current device (every launching call; 0 where
+// there is none, hence no fillers), NCU_NONE: no device is asked (the sizing calls: no layout depends on it).  Call under the entry
+// point's ModeScope: the family and the tuning table are the calling thread's.
+constexpr int NCU_ASK = 0, NCU_NONE = -1;
+CellRoute plan_route(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, int keep, int ncu_) {
+  const int B = s->B, N = s->N, d = s->d, p = s->p;
+  const int ncu = ncu_ == NCU_ASK ? device_cu_count() : ncu_;      // (cached per device)
+  const size_t M = (size_t)B * N;
+  CellRoute r;
+  // macx_opts.gemm_family where set, else the process default (macx_gemm_mode)
+  r.family = gemm_split_mode();
+  r.h2 = r.family == 2;
+  // plain weights: H2 planes + exponent (3) | bf16 planes (1) | f32 MFMA order (0); question-mixed ones: fp32 k-major tiles (2) | 0
+  r.wfmt_plain = r.h2 ? 3 : (r.family ? 1 : 0);
+  r.wfmt_ymix = r.family ? 2 : 0;
+  // the chain kernels (macx_chain_h2.hip.h) exist in the H2 family for d <= 512 and N >= 16; MACX_TUNE_CHAIN = 0 falls back to the
+  // per-product launches that also serve the other shapes
+  r.chain = r.h2 && tune_get(MACX_TUNE_CHAIN, 1) && chain_supported(d, N);
+  // the tallest tile that still leaves the chip one tile per CU (chain_tile_rows; short tiles exist for d = 512 only)
+  r.tile_rows = r.chain ? chain_tile_rows(d, M) : 0;
+  r.tile_shift = r.chain ? chain_tile_shift(d, M) : 0;
+  r.ntile = r.chain ? chain_tiles(d, M) : 0;
+  // a tile of N >= 32 touches at most three questions: chain_bwd then sums what is per question in three segments per tile
+  r.chain_sums = r.chain && N >= 32;
+  // dy from the chain kernel and S_b of all steps as one deferred launch; MACX_TUNE_SB_DEFER = 0: sb_h2 once per step (what N < 32 runs)
+  r.sb_deferred = r.chain_sums && tune_get(MACX_TUNE_SB_DEFER, 1);
+  // the PART form of small_linear sums at most LIN_PART_TILES tiles per question, for at most 128 questions
+  r.dy_in_linear = r.sb_deferred && B <= 128 && ((N - 2) >> r.tile_shift) + 2 <= LIN_PART_TILES;
+  // otherwise the next launch needs dy_i from a reduction of its own; the caller whose control unit is recurrent reduces per step too
+  // (CellBwd::dc_in_loop, see CellBwd::dc_per_step)
+  r.dc_reduce_per_step = r.sb_deferred && !r.dy_in_linear;
+  // the deferred S_b contraction on 128 x 256 tiles with summation by parts (sb_h2w_kernel); MACX_TUNE_SB_WIDE = 0: the 128 x 128 kernel.
+  // (Measured and removed: dW1a / dW1b as ONE dual-A contraction over X * y and X -- twice the matrix work, 392 against 345 us,
+  // profiles/r05_dual_contraction_ab.txt; a side queue for the per-step dKB / dW2 contractions -- +8 % / +130 us per step,
+  // profiles/r04_side_queue_ab.txt.)
+  r.sb_wide = r.sb_deferred && tune_get(MACX_TUNE_SB_WIDE, 1) && sb_h2_wide_ok(B, N, d);
+  // each S_b kernel's own rule: ~256 workgroups, what its LDS holds per group
+  r.sb_qpg = r.sb_wide ? sb_h2_wide_qpg(B, N, d) : sb_qpg(r.h2, B, N);
+  r.ngroup = (size_t)((B + r.sb_qpg - 1) / r.sb_qpg);
+  // one slab per group: of the one deferred launch, or of every step's
+  r.nslab_sb = (r.sb_deferred ? 1 : (size_t)p) * r.ngroup;
+  // splits x output tiles ~ one workgroup per CU (wgrad_big_splits)
+  r.ns_big = (size_t)wgrad_big_splits(r.h2, (int)((size_t)p * M), d, d);
+  // column-sum partials of dI1 / dX: one row per tile of the chain kernel, or per GEMM workgroup row block (nrb_of)
+  r.db_rows = r.chain ? r.ntile : (size_t)B * nrb_of(N, B, d);
+  // dw_k / db2 partials: one row per tile when the chain kernel sums them, else per question
+  r.dwk_rows = r.chain_sums ? r.ntile : (size_t)B;
+
+  const bool rdrop = dp && dp->keep_read < 1.0f, wdrop = dp && dp->keep_write < 1.0f;
+  const int pf = tune_get(MACX_TUNE_PRE_FILL, 1);
+  // chain_fwd's idle CUs (pre_fill_count; d = 512 only), where the hand-off counters (p <= 32) and the linear tiles (B <= 128) reach
+  r.nfill = (r.chain && p <= 32 && B <= 128) ? pre_fill_count(d, M, ncu) : 0;
+  // any filler computes y
+  r.fill_y = r.nfill > 0;
+  // stage 0 depends on the step's site keys only; it exists as a stage of its own where the run keeps its dropped knowledge base
+  r.fill_stage0 = r.nfill > 0 && keep && rdrop;
+  // the write unit's linear where it is ONE launch: the plain write unit of the published flag files (MACX_TUNE_PRE_FILL = 2: not it)
+  r.fill_write = r.nfill > 0 && !o->write_gate && !o->write_self_att && !o->control_feed_prev && !wdrop && pf >= 1 && pf != 2;
+  // chain_bwd's idle CUs (dkb_fill_plan: d = 512, 64-row tiles, N >= 64, p >= 2)
+  r.dkb = r.chain ? dkb_fill_plan(d, M, N, p, ncu) : DkbFillPlan{0, 0, 0};
+  return r;
 }
 
 // ---- layout of the backward workspace ---------------------------------------------------------
@@ -294,17 +378,9 @@ struct BwdLayout {
   size_t dmd;       // [B,d]
   size_t dt, du;    // [B,d]
   size_t dt_part;   // [p,B,d] per-step products of the unshared control inputs' backward linear
-  size_t slab_w2, slab_wx, slab_w1a, slab_w1b;
-  size_t ns_big, ngroup;
-  bool sb_wide;               // the deferred S_b contraction runs on sb_h2w_kernel (128 x 256 tiles, summation by parts)
-  int sb_qpg;                 // questions per workgroup group of the S_b kernel in use
-  size_t db_rows;   // rows per step of db1_part / dbx_part
-  size_t dwk_rows;  // rows per step of dwk_part / db2_part
-  size_t dc_part, dls_part;   // chain kernel: per-row-group partials of dc / db_k, [p][dwk_rows][3][d] and [p][dwk_rows][3]
-  size_t dyc_part;            // chain kernel: per-row-group partials of dy, [dwk_rows][3][d]
-  bool chain_sums;
-  bool dy_in_linear;          // ... and its per-tile partials are summed by the dy linear itself (small_linear PART form)
-  bool sb_deferred;           // dy comes from the chain kernel: dI1 is kept per step and S_b of all steps is ONE launch at the end
+  size_t slab_w2, slab_wx, slab_w1a, slab_w1b;     // [R.ns_big][d,d] twice, [R.nslab_sb][d,d] twice
+  size_t dc_part, dls_part;   // chain kernel: per-row-group partials of dc / db_k, [p][R.dwk_rows][3][d] and [p][R.dwk_rows][3]
+  size_t dyc_part;            // chain kernel: per-row-group partials of dy, [R.dwk_rows][3][d]
   size_t dI1_stride;          // floats between the steps' dI1 (0: one buffer)
   size_t db2_part, db1_part, dbx_part, dwk_part, dbk_part, dwc_part, dbc_part, ctrl_dl;
   size_t tmpBd[4];  // [B,d] scratch
@@ -322,7 +398,7 @@ struct BwdLayout {
   size_t total;
 };
 
-BwdLayout make_bwd(const macx_opts* o, const macx_shapes* s) {
+BwdLayout make_bwd(const macx_opts* o, const macx_shapes* s, const CellRoute& R) {
   BwdLayout L;
   memset(&L, 0, sizeof(L));
   const size_t B = s->B, N = s->N, d = s->d, p = s->p;
@@ -337,12 +413,9 @@ BwdLayout make_bwd(const macx_opts* o, const macx_shapes* s) {
   L.wccT = take(2 * d * d); L.wcc2T = take(d * d); L.wscT = take(d * d); L.wgT = take(d * d);
   L.packs_end = off;                  // == bwd_packs_floats(o, s).  These are offsets into SavedLayout::bwd_packs: the forward pass's pack
   off = 0;                            // launch writes the backward pass's packs into `saved`; the workspace proper starts here
-  L.act_floats = h2_mode() ? al4(h2_floats(B * N, d)) : B * N * d;
-  L.chain_sums = use_chain((int)d, (int)N) && N >= 32;
-  L.sb_deferred = L.chain_sums && sb_defer_mode();
-  L.dI1_stride = L.sb_deferred ? L.act_floats : 0;
-  L.dy_in_linear = L.sb_deferred && B <= 128 && ((N - 2) >> chain_tile_shift((int)d, B * N)) + 2 <= (size_t)LIN_PART_TILES;
-  L.dI2 = take(p * L.act_floats); L.dI1 = take((L.sb_deferred ? p : 1) * L.act_floats); L.dX = take(p * L.act_floats); L.da = take(B * N);   // dI2, dX (dI1) kept per step
+  L.act_floats = R.h2 ? al4(h2_floats(B * N, d)) : B * N * d;
+  L.dI1_stride = R.sb_deferred ? L.act_floats : 0;
+  L.dI2 = take(p * L.act_floats); L.dI1 = take((R.sb_deferred ? p : 1) * L.act_floats); L.dX = take(p * L.act_floats); L.da = take(B * N);   // dI2, dX (dI1) kept per step
   L.DM = take((p + 1) * B * d);
   L.DC = take((p + 1) * B * d);
   L.dcI = take(p * B * d);
@@ -355,24 +428,15 @@ BwdLayout make_bwd(const macx_opts* o, const macx_shapes* s) {
   L.dmd = take(B * d);
   L.dt = take(B * d); L.du = take(B * d);
   L.dt_part = o->control_input_unshared ? take(p * B * d) : 0;
-  L.ns_big = wgrad_big_splits((int)(p * B * N), (int)d, (int)d);
-  L.sb_wide = L.sb_deferred && h2_mode() && sb_wide_mode() && sb_h2_wide_ok((int)B, (int)N, (int)d);
-  L.sb_qpg = L.sb_wide ? sb_h2_wide_qpg((int)B, (int)N, (int)d) : sb_qpg((int)B, (int)N);
-  L.ngroup = (B + L.sb_qpg - 1) / L.sb_qpg;
-  L.slab_w2 = take(L.ns_big * d * d);
-  L.slab_wx = take(L.ns_big * d * d);
-  L.slab_w1a = take((L.sb_deferred ? 1 : p) * L.ngroup * d * d);
-  L.slab_w1b = take((L.sb_deferred ? 1 : p) * L.ngroup * d * d);
-  // column-sum partials of dI1 / dX: one row per GEMM workgroup row block, or per 64-row tile of the chain kernel
-  const size_t nrb = use_chain((int)d, (int)N) ? chain_tiles((int)d, B * N) : B * nrb_of((int)N, (int)B, (int)d);
-  L.db_rows = nrb;
-  // dw_k / db2 partials: one row per question, or per 64-row tile when the chain kernel sums them (N >= 32)
-  L.dwk_rows = L.chain_sums ? chain_tiles((int)d, B * N) : B;
-  L.db2_part = take(p * L.dwk_rows * d);
-  L.db1_part = take(p * nrb * d);
-  L.dbx_part = take(p * nrb * d);
-  L.dwk_part = take(p * L.dwk_rows * d);
-  if (L.chain_sums) { L.dc_part = take(p * L.dwk_rows * 3 * d); L.dls_part = take(p * L.dwk_rows * 3); L.dyc_part = take(L.dwk_rows * 3 * d); }
+  L.slab_w2 = take(R.ns_big * d * d);
+  L.slab_wx = take(R.ns_big * d * d);
+  L.slab_w1a = take(R.nslab_sb * d * d);
+  L.slab_w1b = take(R.nslab_sb * d * d);
+  L.db2_part = take(p * R.dwk_rows * d);
+  L.db1_part = take(p * R.db_rows * d);       // column-sum partials of dI1 / dX
+  L.dbx_part = take(p * R.db_rows * d);
+  L.dwk_part = take(p * R.dwk_rows * d);
+  if (R.chain_sums) { L.dc_part = take(p * R.dwk_rows * 3 * d); L.dls_part = take(p * R.dwk_rows * 3); L.dyc_part = take(R.dwk_rows * 3 * d); }
   L.dbk_part = take(p * B);
   L.dwc_part = take(B * d);
   L.dbc_part = take(p * B);
@@ -391,8 +455,8 @@ BwdLayout make_bwd(const macx_opts* o, const macx_shapes* s) {
   L.small_slab = take(8 * L.small_slab_stride);        // SmallWgradBatch: one slab set per batched contraction
   L.tmp_dd = take(d * d);
   L.ecom = take(4 * EMIN_NB * 8);
-  L.wg_ftab = take(h2_mode() ? (d / 128) * (d / 128) * wgrad_h2_mpad(p * B * N) / 2 + 4 : 4);
-  L.wg_ftab2 = take(h2_mode() ? (d / 128) * (d / 128) * wgrad_h2_mpad(p * B * N) / 2 + 4 : 4);
+  L.wg_ftab = take(R.h2 ? (d / 128) * (d / 128) * wgrad_h2_mpad(p * B * N) / 2 + 4 : 4);
+  L.wg_ftab2 = take(R.h2 ? (d / 128) * (d / 128) * wgrad_h2_mpad(p * B * N) / 2 + 4 : 4);
   L.total = off;
   return L;
 }
@@ -418,6 +482,10 @@ int check_impl(const macx_opts* o, const macx_shapes* s) {
   if (o->write_self_att && s->p + 1 > SA_MAXH) return MACX_EINVAL;
   return MACX_OK;
 }
+
+// a [K, Nout] weight in pack format 3 at `w` (macx_h2.hip.h: pack_h2_weight): the planes, and behind kn = K * Nout floats the exponent
+inline ChainW h2_weight(const float* w, size_t kn) { return ChainW{reinterpret_cast<const char*>(w), reinterpret_cast<const int*>(w) + kn}; }
+inline void set_h2_weight(GemmH2P& g, const float* w, size_t kn) { const ChainW c = h2_weight(w, kn); g.Wh = c.planes; g.w_exp = c.exp; }
 
 // the parameter block of the read unit's forward chain kernel for step `i`; `ob`: the step whose X / H1 / I2 / KBd / keep-bit
 // buffers receive the outputs (= i in a run; the timing hook rotates it)
@@ -452,12 +520,12 @@ enum {
   PRE_WRITE_PREV = 16,    // this launch's fillers run the previous step's write unit (ChainPreP::wlin)
 };
 ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, const macx_params* P,
-                         const macx_inputs* in, float* saved, const SavedLayout& L, int keep, int i, int ob, int pre = 0) {
+                         const macx_inputs* in, float* saved, const SavedLayout& L, const CellRoute& route, int keep, int i, int ob,
+                         int pre = 0) {
   const int B = s->B, N = s->N, d = s->d;
   const int R = B * N;
   const size_t Bd = (size_t)B * d, dd_ = (size_t)d * d;
   const bool rdrop = dp->keep_read < 1.0f;
-  auto wref = [&](size_t off) { return ChainW{reinterpret_cast<const char*>(saved + off), reinterpret_cast<const int*>(saved + off) + dd_}; };
   ChainFwdP c;
   memset(&c, 0, sizeof(c));
   c.M = R; c.N = N; c.d = d;
@@ -481,7 +549,8 @@ ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dr
   if (rdrop || i == 0) {
     c.KBd = h2_view(rdrop ? saved + L.KBd + (size_t)ob * L.act_stride : saved + L.KBd, R, d);
   }
-  c.Wx = wref(L.wx_p); c.W1a = wref(L.w1a_p); c.W1b = wref(L.w1b_p); c.W2 = wref(L.w2_p);
+  c.Wx = h2_weight(saved + L.wx_p, dd_); c.W1a = h2_weight(saved + L.w1a_p, dd_); c.W1b = h2_weight(saved + L.w1b_p, dd_);
+  c.W2 = h2_weight(saved + L.w2_p, dd_);
   c.bx = P->projX_b; c.b1 = P->memKbProj_b; c.b2 = P->memKbProj2_b;
   c.act1 = o->read_mem_act; c.act2 = o->read_ctrl_act;
   c.y = saved + L.y + (size_t)i * Bd;
@@ -494,7 +563,7 @@ ChainFwdP make_chain_fwd(const macx_opts* o, const macx_shapes* s, const macx_dr
   }
   c.logits = saved + L.logit_part;
   if (rdrop && c.mode == 0 && (pre & PRE_STAGE0_DONE)) c.mode = 2;
-  if (pre & (PRE_STAGE0_NEXT | PRE_YLIN)) c.pre.nfill = pre_fill_count(d, (size_t)R, device_cu_count());
+  if (pre & (PRE_STAGE0_NEXT | PRE_YLIN)) c.pre.nfill = route.nfill;
   if ((pre & PRE_YLIN) && c.pre.nfill) {
     // this step's y = md Wy + by on the filler workgroups (read_step then launches no linear for it)
     c.pre.ylin = lin_basic(saved + L.md + (size_t)i * Bd, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, saved + L.y + (size_t)i * Bd, d);
@@ -756,24 +825,37 @@ const char* macx_strerror(int code) {
 
 int macx_check(const macx_opts* o, const macx_shapes* s) { ModeScope ms(o); return check_impl(o, s); }
 
+int macx_cell_route(const macx_opts* o, const macx_shapes* s, const macx_dropout* dp, int keep, int ncu, macx_route* out) {
+  ModeScope ms(o);
+  CKI(check_impl(o, s));
+  if (!out) return MACX_EINVAL;
+  const CellRoute r = plan_route(o, s, dp, keep, ncu > 0 ? ncu : NCU_ASK);      // the plan the launches follow, copied field by field
+  const int kw = r.h2 ? wgrad_h2_kw(s->d) : 0;                                  // (the launcher's own rule, by width alone)
+  *out = macx_route{r.family, r.chain, r.tile_rows, (int32_t)r.ntile, r.chain_sums, r.sb_deferred, r.dy_in_linear, r.dc_reduce_per_step,
+                    r.sb_wide, r.sb_qpg, (int32_t)r.ngroup, (int32_t)r.nslab_sb, (int32_t)r.ns_big, kw, (int32_t)r.db_rows,
+                    (int32_t)r.dwk_rows, r.wfmt_plain, r.wfmt_ymix, r.nfill, r.fill_y, r.fill_stage0, r.fill_write, r.dkb.njobs,
+                    r.dkb.nfill, r.dkb.nskip};
+  return MACX_OK;
+}
+
 size_t macx_saved_floats(const macx_opts* o, const macx_shapes* s, int keep) {
   ModeScope ms(o);
   if (check_impl(o, s) != MACX_OK) return 0;
-  return make_saved(o, s, keep).total;
+  return make_saved(o, s, keep, plan_route(o, s, nullptr, keep, NCU_NONE)).total;
 }
 
 size_t macx_ws_floats(const macx_opts* o, const macx_shapes* s, int for_backward) {
   ModeScope ms(o);
   if (check_impl(o, s) != MACX_OK) return 0;
   if (!for_backward) return 4;   // forward keeps everything in `saved`
-  return make_bwd(o, s).total;
+  return make_bwd(o, s, plan_route(o, s, nullptr, 1, NCU_NONE)).total;
 }
 
 int macx_saved_segment(const macx_opts* o, const macx_shapes* s, int keep, int segment, size_t* offset, size_t* count) {
   ModeScope ms(o);
   CKI(check_impl(o, s));
   if (segment < 0 || segment >= MACX_SEG_COUNT || !offset || !count) return MACX_EINVAL;
-  SavedLayout L = make_saved(o, s, keep);
+  const SavedLayout L = make_saved(o, s, keep, plan_route(o, s, nullptr, keep, NCU_NONE));
   *offset = L.seg[segment];
   *count = L.seg_count[segment];
   return MACX_OK;
@@ -811,7 +893,7 @@ int status_layout(const macx_opts* o, const macx_shapes* s, int keep, const floa
   ModeScope ms(o);
   CKI(check_impl(o, s));
   if (!saved || misaligned(saved)) return MACX_EINVAL;
-  const SavedLayout L = make_saved(o, s, keep);
+  const SavedLayout L = make_saved(o, s, keep, plan_route(o, s, nullptr, keep, NCU_NONE));
   if (saved_floats < L.total) return MACX_ESMALL;
   *off = L.status;
   return MACX_OK;
@@ -864,24 +946,23 @@ int macx_handoff_selftest(void* stream, uint32_t* host_out) {
 
 // -------------------------------------------------------------------------------------------------
 namespace {
-// One call of the fused cell, forward or backward: its arguments, the layout of `saved`, the derived sizes and the kernel-family /
-// route decisions, taken once per call under the entry point's ModeScope
+// One call of the fused cell, forward or backward: its arguments, its route (planned once per call under the entry point's
+// ModeScope, for the current device), the layout of `saved` and the derived sizes
 struct CellRun {
   const macx_opts* o; const macx_shapes* s; const macx_dropout* dp; const macx_params* P; const macx_inputs* in;
   float* saved;
+  CellRoute R;
   SavedLayout L;
   hipStream_t st;
   int B, N, d, p, keep;
   size_t Bd, dd;
   bool rdrop;     // read dropout
-  bool h2;        // the H2 kernel family
-  bool chain;     // ... and the read unit's products in the chain kernels
   CellRun(const macx_opts* o_, const macx_shapes* s_, const macx_dropout* dp_, const macx_params* P_, const macx_inputs* in_,
           float* saved_, int keep_, void* stream)
-      : o(o_), s(s_), dp(dp_), P(P_), in(in_), saved(saved_), L(make_saved(o_, s_, keep_)), st((hipStream_t)stream), B(s_->B),
-        N(s_->N), d(s_->d), p(s_->p), keep(keep_), Bd((size_t)s_->B * s_->d), dd((size_t)s_->d * s_->d),
-        rdrop(dp_->keep_read < 1.0f), h2(h2_mode()), chain(use_chain(s_->d, s_->N)) {}
-  WMaxRef mx(int k) const { return wmax_ref(saved, L.wmax, k, chain); }
+      : o(o_), s(s_), dp(dp_), P(P_), in(in_), saved(saved_), R(plan_route(o_, s_, dp_, keep_, NCU_ASK)),
+        L(make_saved(o_, s_, keep_, R)), st((hipStream_t)stream), B(s_->B), N(s_->N), d(s_->d), p(s_->p), keep(keep_),
+        Bd((size_t)s_->B * s_->d), dd((size_t)s_->d * s_->d), rdrop(dp_->keep_read < 1.0f) {}
+  WMaxRef mx(int k) const { return wmax_ref(saved, L.wmax, k, R.chain); }
   float* controls() const { return saved + L.seg[MACX_SEG_CONTROLS]; }
   float* memories() const { return saved + L.seg[MACX_SEG_MEMORIES]; }
   // step i's information before the write dropout (mac_cell.py:461-463); self.infos keeps the dropped value (mac_cell.py:474)
@@ -925,7 +1006,7 @@ void add_pack(Packer& pk, bool T, const float* W, int K, int Nout, float* dst, i
 hipError_t CellRun::read_weight_maxima() const {
   static_assert(ABSMAX_BLOCKS == 64, "wmax_ref's partial layout");
   return absmax4(P->projX_W, dd, P->memKbProj2_W, dd, P->memKbProj_W, dd, P->memKbProj_W + dd, dd, saved + L.wmax,
-                 saved + L.wmax + 8, st, !chain);
+                 saved + L.wmax + 8, st, !R.chain);
 }
 
 void CellRun::add_read_packs(Packer& pk, const BwdLayout* W) const {
@@ -934,15 +1015,15 @@ void CellRun::add_read_packs(Packer& pk, const BwdLayout* W) const {
   const float* W1 = P->memKbProj_W;
   float* w1a = T ? wT + W->w1aT_p : saved + L.w1a_p;
   float* w1b = T ? wT + W->w1bT_p : saved + L.w1b_p;
-  add_pack(pk, T, P->projX_W, d, d, T ? wT + W->wxT_p : saved + L.wx_p, wfmt_plain(), mx(0));
-  if (chain) {      // the chain kernels apply y to the accumulators: W1a and W1b are plain H2 weights there
+  add_pack(pk, T, P->projX_W, d, d, T ? wT + W->wxT_p : saved + L.wx_p, R.wfmt_plain, mx(0));
+  if (R.chain) {      // the chain kernels apply y to the accumulators: W1a and W1b are plain H2 weights there
     add_pack(pk, T, W1, d, d, w1a, 3, mx(2));
     add_pack(pk, T, W1 + dd, d, d, w1b, 3, mx(3));
   } else {
-    add_pack(pk, T, W1, d, d, w1a, wfmt_ymix());
-    add_pack(pk, T, W1 + dd, d, d, w1b, wfmt_ymix());
+    add_pack(pk, T, W1, d, d, w1a, R.wfmt_ymix);
+    add_pack(pk, T, W1 + dd, d, d, w1b, R.wfmt_ymix);
   }
-  add_pack(pk, T, P->memKbProj2_W, d, d, T ? wT + W->w2T_p : saved + L.w2_p, wfmt_plain(), mx(1));
+  add_pack(pk, T, P->memKbProj2_W, d, d, T ? wT + W->w2T_p : saved + L.w2_p, R.wfmt_plain, mx(1));
   add_pack(pk, T, P->projY_W, d, d, T ? wT + W->wyT : saved + L.wy_p);
 }
 
@@ -988,11 +1069,11 @@ int macx_cell_begin(const macx_opts* o, const macx_shapes* s, const macx_dropout
 
   {
     Packer pk;
-    if (r.h2) CK(r.read_weight_maxima());
+    if (r.R.h2) CK(r.read_weight_maxima());
     r.add_read_packs(pk);
     r.add_write_packs(pk);
     if (keep && L.bwd_packs) {        // a run that keeps its activations will be differentiated
-      const BwdLayout W = make_bwd(o, s);
+      const BwdLayout W = make_bwd(o, s, r.R);
       r.add_read_packs(pk, &W);
       r.add_write_packs(pk, &W);
       CKI(r.add_control_packs(pk, &W));
@@ -1077,7 +1158,7 @@ int CellRun::control_step(int i) const {
 // the read unit's three knowledge-base products, X = dropout(KB) Wx + bx, H1 = act(X (diag(y) W1a + W1b) + b1), I2 = H1 W2 + b2,
 // and the attention logits: KB -> X -> H1 -> I2 -> logits in one launch (macx_chain_h2.hip.h)
 int CellRun::read_products_chain(int i, int pre) const {
-  const ChainFwdP c = make_chain_fwd(o, s, dp, P, in, saved, L, keep, i, i, pre);
+  const ChainFwdP c = make_chain_fwd(o, s, dp, P, in, saved, L, R, keep, i, i, pre);
   ChainProbe& cp = *chain_probe();
   if (cp.on && cp.n < 64) {      // the kernel's own start / stop timestamps into the probe's event pair
     CK(chain_fwd_launch(c, st, cp.ev[2 * cp.n], cp.ev[2 * cp.n + 1]));
@@ -1091,10 +1172,10 @@ int CellRun::read_products_chain(int i, int pre) const {
 // ... on H2 operands, one launch per product (macx_gemm_h2.hip.h): the knowledge base enters the format (through its dropout site)
 // once per step -- once per run without read dropout -- and X, H1, I2 never exist as fp32 tensors
 int CellRun::read_products_h2(int i) const {
-  const int R = B * N;
-  const H2View hX = h2_view(saved + L.X + (size_t)i * L.act_stride, R, d), hH1 = h2_view(saved + L.H1 + (size_t)i * L.act_stride, R, d),
-               hI2 = h2_view(saved + L.I2 + (size_t)i * L.act_stride, R, d);
-  const H2View hKB = h2_view(saved + L.KBd + (rdrop ? (size_t)i * L.act_stride : 0), R, d);
+  const int M = B * N;
+  const H2View hX = h2_view(saved + L.X + (size_t)i * L.act_stride, M, d), hH1 = h2_view(saved + L.H1 + (size_t)i * L.act_stride, M, d),
+               hI2 = h2_view(saved + L.I2 + (size_t)i * L.act_stride, M, d);
+  const H2View hKB = h2_view(saved + L.KBd + (rdrop ? (size_t)i * L.act_stride : 0), M, d);
   uint8_t* att_bytes = rdrop ? reinterpret_cast<uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
   if (rdrop || i == 0) {
     H2FromP f;
@@ -1116,7 +1197,7 @@ int CellRun::read_products_h2(int i) const {
   GemmH2P g = h2_gemm_params();
   // X = dropout(KB) Wx + bx  (ops.py:678,688)
   g.A = hKB;
-  g.Wh = reinterpret_cast<const char*>(saved + L.wx_p); g.w_exp = reinterpret_cast<const int*>(saved + L.wx_p) + dd;
+  set_h2_weight(g, saved + L.wx_p, dd);
   g.out = hX; g.bias = P->projX_b; g.act = MACX_ACT_NON;
   if (rdrop || L.act_stride != 0 || i == 0) CK((kb_gemm_h2_launch<B_PLAIN, E_BIAS_ACT, false>(g, st)));
   // H1 = act( X (diag(y) W1a + W1b) + b1 )   (ops.py:703,718; mac_cell.py:237)
@@ -1126,7 +1207,7 @@ int CellRun::read_products_h2(int i) const {
   CK((kb_gemm_h2_launch<B_YMIX_ROW, E_BIAS_ACT, false>(g, st)));
   // I2 = H1 W2 + b2 ; logits = dropout(act(I2 * c)) . w_k   (ops.py:326; mac_cell.py:248,262,266)
   g.A = hH1; g.Wt = nullptr; g.Wt2 = nullptr; g.y = nullptr;
-  g.Wh = reinterpret_cast<const char*>(saved + L.w2_p); g.w_exp = reinterpret_cast<const int*>(saved + L.w2_p) + dd;
+  set_h2_weight(g, saved + L.w2_p, dd);
   g.out = hI2; g.bias = P->memKbProj2_b; g.act = o->read_ctrl_act;
   g.cvec = controls() + (size_t)(i + 1) * Bd; g.wvec = P->kbLogits_w; g.logit_part = saved + L.logit_part;
   g.e_bytes = att_bytes;
@@ -1188,14 +1269,14 @@ int CellRun::read_step(int i, int pre, bool md_fused) const {
                        (uint32_t)s->b0, dm, dry, md, dlog_of(s));
     CK(hipGetLastError());
   }
-  if (!((pre & PRE_YLIN) && chain)) {
+  if (!((pre & PRE_YLIN) && R.chain)) {
     LinP l = lin_basic(md, d, d, B, saved + L.wy_p, P->projY_b, d, MACX_ACT_NON, saved + L.y + (size_t)i * Bd, d);
     CK(small_linear_launch(l, 1, st));
   }
-  CKI(chain ? read_products_chain(i, pre) : h2 ? read_products_h2(i) : read_products_f32(i));
+  CKI(R.chain ? read_products_chain(i, pre) : R.h2 ? read_products_h2(i) : read_products_f32(i));
   // attention over the knowledge base + summary (mac_cell.py:266-275)
   KbAttP a;
-  a.B = B; a.N = N; a.d = d; a.nparts = chain ? 1 : d / (16 * kb_gemm_nw());
+  a.B = B; a.N = N; a.d = d; a.nparts = R.chain ? 1 : d / (16 * kb_gemm_nw());
   a.logit_part = saved + L.logit_part; a.bias = P->kbLogits_b;
   a.kb = in->knowledgeBase; a.kb_len = in->kbLengths;
   a.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
@@ -1283,15 +1364,13 @@ int macx_cell_forward(const macx_opts* o, const macx_shapes* s, const macx_dropo
   ModeScope ms(o);
   const CellRun r(o, s, dp, P, in, saved, keep, stream);
   // a training run's steps are sequenced here: stage 0 of the read unit's chain for step i + 1 (state-independent) rides the
-  // launch of step i on its idle CUs (ChainPreP).  The step-wise entry point makes no assumption about what ran before it.
-  const bool fill = r.chain && s->p <= 32 && s->B <= 128 && pre_fill_count(s->d, (size_t)s->B * s->N, device_cu_count()) > 0;
-  const bool pre = fill && keep && dp && dp->keep_read < 1.0f;
-  // the write unit's linear too, where it is one launch: the plain write unit of the published flag files
-  const bool tail = fill && s->B <= 128 && !o->write_gate && !o->write_self_att && !o->control_feed_prev && dp && !(dp->keep_write < 1.0f) &&
-                    tune_get(MACX_TUNE_PRE_FILL, 1) >= 1 && tune_get(MACX_TUNE_PRE_FILL, 1) != 2;
+  // launch of step i on its idle CUs (ChainPreP), and what else the route lets the fillers take over.  The step-wise entry point
+  // makes no assumption about what ran before it.
+  const CellRoute& R = r.R;
   for (int i = 0; i < s->p; ++i) {
-    const int flags = (pre && i > 0 ? PRE_STAGE0_DONE : 0) | (pre && i + 1 < s->p ? PRE_STAGE0_NEXT : 0) | (fill ? PRE_YLIN : 0) |
-                      (tail && i + 1 < s->p ? PRE_WRITE_NEXT : 0) | (tail && i > 0 ? PRE_WRITE_PREV : 0);
+    const int flags = (R.fill_stage0 && i > 0 ? PRE_STAGE0_DONE : 0) | (R.fill_stage0 && i + 1 < s->p ? PRE_STAGE0_NEXT : 0) |
+                      (R.fill_y ? PRE_YLIN : 0) | (R.fill_write && i + 1 < s->p ? PRE_WRITE_NEXT : 0) |
+                      (R.fill_write && i > 0 ? PRE_WRITE_PREV : 0);
     CKI(r.cell_step(i, flags));
   }
   return MACX_OK;
@@ -1321,12 +1400,13 @@ struct CellBwd : CellRun {
   float* DC;                    // [p + 1][B,d] dL/dc_i
   float* dwlin_all;             // [p][B,d] dL/d(newMemory linear output); with writeMemAct = NON and no gate it IS dL/dm_{1..p}
   const macx_param_grads* GP; const macx_input_grads* GI;
-  int win, nrb;
+  int win;
   StepSlab dinfo;               // dL/d(info_i), the read unit's output (ahead of the write dropout)
   // the recurrent control unit differentiates through dL/dc_i inside iteration i; otherwise every step's dc / db_k partials are
   // reduced in one launch after the loop
   bool dc_in_loop = false;
-  DkbFillPlan dkb_plan{0, 0, 0};
+  // a dc_reduce launch follows every chain_bwd launch (read_bwd_chain); else ONE follows the loop (read_dc_reduce_all)
+  bool dc_per_step() const { return R.chain_sums && (dc_in_loop || R.dc_reduce_per_step); }
   ChainDkbP dkb_q;
   RowsumBatch rs;               // bias-gradient row sums of this call: one launch at the end of each phase
   SmallWgradBatch wb;           // weight gradients of the [B,d] linears: one launch at the end of phase 1
@@ -1335,9 +1415,9 @@ struct CellBwd : CellRun {
   macx_state_grads sg{};
   CellBwd(const macx_opts* o_, const macx_shapes* s_, const macx_dropout* dp_, const macx_params* P_, const macx_inputs* in_,
           const float* saved_, float* ws_, const macx_param_grads* GP_, const macx_input_grads* GI_, void* stream)
-      : CellRun(o_, s_, dp_, P_, in_, const_cast<float*>(saved_), 1, stream), ws(ws_), W(make_bwd(o_, s_)), wT(saved_ + L.bwd_packs),
+      : CellRun(o_, s_, dp_, P_, in_, const_cast<float*>(saved_), 1, stream), ws(ws_), W(make_bwd(o_, s_, R)), wT(saved_ + L.bwd_packs),
         DM(ws_ + W.DM), DC(ws_ + W.DC), dwlin_all((o_->write_mem_act == MACX_ACT_NON && !o_->write_gate) ? DM + Bd : ws_ + W.dwlin),
-        GP(GP_), GI(GI_), win(write_in_dim(o_, d)), nrb(nrb_of(N, B, d)), wb(ws_ + W.small_slab, W.small_slab_stride) {
+        GP(GP_), GI(GI_), win(write_in_dim(o_, d)), wb(ws_ + W.small_slab, W.small_slab_stride) {
     dinfo = dp->keep_write < 1.0f ? StepSlab{ws + W.dinfo, d, Bd} : StepSlab{ws + W.dwin + d, win, (size_t)B * win};
     memset(&dkb_q, 0, sizeof(dkb_q));
   }
@@ -1398,13 +1478,11 @@ int CellBwd::init_state_grads(const float* d_memory, const float* d_control) {
 // dKB of step i + 1 rides chain_bwd's launch of step i on the CUs that launch leaves idle (ChainDkbP, macx_chain_api.hip.h); what
 // the fillers leave out and step 0 run in chain_dkb_rest_launch after the last step.  Off (njobs = 0): the merged dKB launch.
 void CellBwd::plan_dkb_fill() {
-  if (!chain) return;
-  dkb_plan = dkb_fill_plan(d, (size_t)B * N, N, p, device_cu_count());
-  if (!dkb_plan.njobs) return;
+  if (!R.dkb.njobs) return;
   ChainDkbP& q = dkb_q;
-  q.njobs = dkb_plan.njobs; q.nfill = dkb_plan.nfill; q.nskip = dkb_plan.nskip; q.p = p;
+  q.njobs = R.dkb.njobs; q.nfill = R.dkb.nfill; q.nskip = R.dkb.nskip; q.p = p;
   q.dX = reinterpret_cast<const char*>(ws + W.dX); q.dx_step = W.act_floats * sizeof(float);
-  q.WxT = ChainW{reinterpret_cast<const char*>(wT + W.wxT_p), reinterpret_cast<const int*>(wT + W.wxT_p) + dd};
+  q.WxT = h2_weight(wT + W.wxT_p, dd);
   q.bits = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.kb_bits) : nullptr;
   q.bits_step = L.bits_stride * sizeof(uint32_t);
   q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
@@ -1472,37 +1550,36 @@ int CellBwd::write_unit_bwd(int i) {
 
 // the read unit's products backward, dl -> dI2 -> dI1 -> dX, in one launch (macx_chain_h2.hip.h)
 int CellBwd::read_bwd_chain(int i, const ReadH2& v) {
-  auto wref = [&](size_t off) { return ChainW{reinterpret_cast<const char*>(wT + off), reinterpret_cast<const int*>(wT + off) + dd}; };
   ChainBwdP c;
   memset(&c, 0, sizeof(c));
   c.M = B * N; c.N = N; c.d = d;
   c.dbg = (kb_gemm_dbg() >> 17) & 31;
   c.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N; c.da = ws + W.da;
   c.I2 = v.I2; c.c = controls() + (size_t)(i + 1) * Bd; c.wk = P->kbLogits_w; c.act2 = o->read_ctrl_act;
-  if (W.chain_sums) {
-    c.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
-    c.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
-    c.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; c.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
+  if (R.chain_sums) {
+    c.dwk_part = ws + W.dwk_part + (size_t)i * R.dwk_rows * d;
+    c.db2_part = ws + W.db2_part + (size_t)i * R.dwk_rows * d;
+    c.dc_part = ws + W.dc_part + (size_t)i * R.dwk_rows * 3 * d; c.dls_part = ws + W.dls_part + (size_t)i * R.dwk_rows * 3;
   }
   c.bytes2 = rdrop ? reinterpret_cast<const uint8_t*>(saved + L.att_bits + (size_t)i * L.bits_stride) : nullptr;
   c.inv2 = rdrop ? 1.0f / dp->keep_read : 1.0f;
   c.dI2 = v.dI2;
-  c.W2T = wref(W.w2T_p); c.H1 = v.H1; c.act1 = o->read_mem_act;
-  c.dI1 = v.dI1; c.db1_part = ws + W.db1_part + (size_t)i * W.db_rows * d;
-  c.W1aT = wref(W.w1aT_p); c.W1bT = wref(W.w1bT_p); c.y = saved + L.y + (size_t)i * Bd;
-  c.dX = v.dX; c.dbx_part = ws + W.dbx_part + (size_t)i * W.db_rows * d;
-  if (W.sb_deferred) { c.X = v.X; c.dy_part = ws + W.dyc_part; }
-  if (dkb_plan.njobs && i + 1 < p) { c.dkb = dkb_q; c.dkb.step = i + 1; }
+  c.W2T = h2_weight(wT + W.w2T_p, dd); c.H1 = v.H1; c.act1 = o->read_mem_act;
+  c.dI1 = v.dI1; c.db1_part = ws + W.db1_part + (size_t)i * R.db_rows * d;
+  c.W1aT = h2_weight(wT + W.w1aT_p, dd); c.W1bT = h2_weight(wT + W.w1bT_p, dd); c.y = saved + L.y + (size_t)i * Bd;
+  c.dX = v.dX; c.dbx_part = ws + W.dbx_part + (size_t)i * R.db_rows * d;
+  if (R.sb_deferred) { c.X = v.X; c.dy_part = ws + W.dyc_part; }
+  if (R.dkb.njobs && i + 1 < p) { c.dkb = dkb_q; c.dkb.step = i + 1; }
   CK(chain_bwd_launch(c, st));
-  if (W.chain_sums && (dc_in_loop || (W.sb_deferred && !W.dy_in_linear))) {
+  if (dc_per_step()) {
     // the per-tile partials of this step: dL/dc_i += read-unit part, db_k partials, dy_i (the next launch needs dy_i)
     DcReduceP q;
     memset(&q, 0, sizeof(q));
     q.B = B; q.N = N; q.d = d;
-    q.dc_part = ws + W.dc_part + (size_t)i * W.dwk_rows * 3 * d; q.dls_part = ws + W.dls_part + (size_t)i * W.dwk_rows * 3;
+    q.dc_part = ws + W.dc_part + (size_t)i * R.dwk_rows * 3 * d; q.dls_part = ws + W.dls_part + (size_t)i * R.dwk_rows * 3;
     q.dc = DC + (size_t)(i + 1) * Bd; q.dbk_part = ws + W.dbk_part + (size_t)i * B;
-    q.tile_shift = chain_tile_shift(d, (size_t)B * N);
-    if (W.sb_deferred && !W.dy_in_linear) { q.dy_part = ws + W.dyc_part; q.dy = ws + W.DY + (size_t)i * Bd; }
+    q.tile_shift = R.tile_shift;
+    if (R.dc_reduce_per_step) { q.dy_part = ws + W.dyc_part; q.dy = ws + W.DY + (size_t)i * Bd; }
     hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, 1), dim3(128), 0, st, q);
     CK(hipGetLastError());
   }
@@ -1511,11 +1588,11 @@ int CellBwd::read_bwd_chain(int i, const ReadH2& v) {
 
 // ... on H2 operands, one launch per product
 int CellBwd::read_bwd_h2(int i, const ReadH2& v) {
-  const size_t parts = (size_t)i * B * nrb * d;
+  const size_t parts = (size_t)i * R.db_rows * d;
   GemmH2P g = h2_gemm_params();
   // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
   g.A = v.dI2;
-  g.Wh = reinterpret_cast<const char*>(wT + W.w2T_p); g.w_exp = reinterpret_cast<const int*>(wT + W.w2T_p) + dd;
+  set_h2_weight(g, wT + W.w2T_p, dd);
   g.out = v.dI1; g.aux = v.H1; g.act = o->read_mem_act;
   g.colsum_part = ws + W.db1_part + parts;
   CK((kb_gemm_h2_launch<B_PLAIN, E_MUL_DACT, true>(g, st)));
@@ -1532,9 +1609,9 @@ int CellBwd::read_bwd_h2(int i, const ReadH2& v) {
 int CellBwd::dkb_merged_h2() {
   GemmH2P g = h2_gemm_params();
   g.A = h2_view(ws + W.dX, B * N, d);
-  g.Wh = reinterpret_cast<const char*>(wT + W.wxT_p); g.w_exp = reinterpret_cast<const int*>(wT + W.wxT_p) + dd;
+  set_h2_weight(g, wT + W.wxT_p, dd);
   g.nsteps = p; g.a_step_bytes = W.act_floats * sizeof(float);
-  g.a_row_exp = chain ? 1 : 0;          // chain_bwd_kernel gives a row of dX ONE exponent: the merged launch may fold once per step
+  g.a_row_exp = R.chain ? 1 : 0;          // chain_bwd_kernel gives a row of dX ONE exponent: the merged launch may fold once per step
   g.out_f32 = GI->knowledgeBase; g.ldo = d;
   g.dr = dinfo.base; g.ld_dr = dinfo.ld; g.dr_step = dinfo.step;
   g.att = saved + L.seg[MACX_SEG_ATT_KB]; g.att_step = (size_t)B * N;
@@ -1573,20 +1650,20 @@ int CellBwd::read_bwd_f32(int i) {
   // dI1 = (dI2 W2^T) * act'(H1) ; db1 partials
   g.A = dI2_i; g.lda = d; g.Wp = wT + W.w2T_p;
   g.out = ws + W.dI1; g.ldo = d; g.aux = saved + L.H1 + (size_t)i * L.act_stride; g.act = o->read_mem_act;
-  g.colsum_part = ws + W.db1_part + (size_t)i * B * nrb * d;
+  g.colsum_part = ws + W.db1_part + (size_t)i * R.db_rows * d;
   CK((kb_gemm<A_PLAIN, B_PLAIN, E_MUL_DACT, true>(g, st)));
   // dX = dI1 (diag(y) W1a + W1b)^T ; dbx partials
   g.A = ws + W.dI1; g.Wp = wT + W.w1aT_p; g.Wp2 = wT + W.w1bT_p; g.y = y; g.ldy = d;
   g.out = dX_i; g.aux = nullptr;
-  g.colsum_part = ws + W.dbx_part + (size_t)i * B * nrb * d;
+  g.colsum_part = ws + W.dbx_part + (size_t)i * R.db_rows * d;
   CK((kb_gemm<A_PLAIN, B_YMIX_COL, E_PLAIN, true>(g, st)));
   // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials
   {
     SbP q;
-    q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
+    q.B = B; q.N = N; q.d = d; q.qpg = R.sb_qpg;
     q.X = saved + L.X + (size_t)i * L.act_stride; q.dI1 = ws + W.dI1; q.y = y; q.W1a = P->memKbProj_W;
-    q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
-    q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
+    q.dW1a_part = ws + W.slab_w1a + (size_t)i * R.ngroup * dd;
+    q.dW1b_part = ws + W.slab_w1b + (size_t)i * R.ngroup * dd;
     q.dy_part = ws + W.dy_part;
     CK((gemm_split_mode() && !(kb_gemm_dbg() & 256)) ? sb6_wgrad_launch(q, st) : sb_wgrad_launch(q, st));   // dbg 256: f32 kernel
   }
@@ -1602,18 +1679,18 @@ int CellBwd::read_bwd_f32(int i) {
 
 // the read unit, from dL/d(info_i): dL/dc_i += its part, the dy partials, the products' gradients and dKB
 int CellBwd::read_unit_bwd(int i) {
-  const int R = B * N;
+  const int M = B * N;
   hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo.at(i), dinfo.ld, in->knowledgeBase, B, N, d,
                      ws + W.da, sg.d_att_kb ? sg.d_att_kb + (size_t)i * B * N : nullptr);
   CK(hipGetLastError());
-  if (!h2) return read_bwd_f32(i);
+  if (!R.h2) return read_bwd_f32(i);
   const size_t a = (size_t)i * L.act_stride;
-  const ReadH2 v{h2_view(saved + L.X + a, R, d), h2_view(saved + L.H1 + a, R, d), h2_view(saved + L.I2 + a, R, d),
-                 h2_view(ws + W.dI2 + (size_t)i * W.act_floats, R, d), h2_view(ws + W.dI1 + (size_t)i * W.dI1_stride, R, d),
-                 h2_view(ws + W.dX + (size_t)i * W.act_floats, R, d)};
-  if (!(chain && W.chain_sums)) {
+  const ReadH2 v{h2_view(saved + L.X + a, M, d), h2_view(saved + L.H1 + a, M, d), h2_view(saved + L.I2 + a, M, d),
+                 h2_view(ws + W.dI2 + (size_t)i * W.act_floats, M, d), h2_view(ws + W.dI1 + (size_t)i * W.dI1_stride, M, d),
+                 h2_view(ws + W.dX + (size_t)i * W.act_floats, M, d)};
+  if (!R.chain_sums) {
     ReadAttBwdH2P q;
-    q.dl = nullptr; q.no_out = chain ? 1 : 0;    // chain with tiny N: only dc / dw_k / db2 / db_k (dI2 comes from the chain kernel)
+    q.dl = nullptr; q.no_out = R.chain ? 1 : 0;    // chain with tiny N: only dc / dw_k / db2 / db_k (dI2 comes from the chain kernel)
     q.B = B; q.N = N; q.d = d;
     q.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N; q.da = ws + W.da; q.I2 = v.I2;
     q.c = controls() + (size_t)(i + 1) * Bd; q.wk = P->kbLogits_w;
@@ -1622,30 +1699,30 @@ int CellBwd::read_unit_bwd(int i) {
     q.inv_keep = rdrop ? 1.0f / dp->keep_read : 1.0f;
     q.dI2 = v.dI2;
     q.dc = DC + (size_t)(i + 1) * Bd;
-    q.dwk_part = ws + W.dwk_part + (size_t)i * W.dwk_rows * d;
-    q.db2_part = ws + W.db2_part + (size_t)i * W.dwk_rows * d;
+    q.dwk_part = ws + W.dwk_part + (size_t)i * R.dwk_rows * d;
+    q.db2_part = ws + W.db2_part + (size_t)i * R.dwk_rows * d;
     q.dbk_part = ws + W.dbk_part + (size_t)i * B;
     hipLaunchKernelGGL(read_att_bwd_h2_kernel, dim3(B, d / 128), dim3(RABH_THREADS), 0, st, q);
     CK(hipGetLastError());
   }
-  CKI(chain ? read_bwd_chain(i, v) : read_bwd_h2(i, v));
+  CKI(R.chain ? read_bwd_chain(i, v) : read_bwd_h2(i, v));
   // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials (deferred: one launch over all steps in phase 2, dy from the chain kernel)
-  if (!W.sb_deferred) {
+  if (!R.sb_deferred) {
     SbH2P q;
     memset(&q, 0, sizeof(q));
     q.nsteps = 1;
-    q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
+    q.B = B; q.N = N; q.d = d; q.qpg = R.sb_qpg;
     q.X = v.X; q.dI1 = v.dI1;
     q.y = saved + L.y + (size_t)i * Bd; q.W1a = P->memKbProj_W;
-    q.dW1a_part = ws + W.slab_w1a + (size_t)i * W.ngroup * dd;
-    q.dW1b_part = ws + W.slab_w1b + (size_t)i * W.ngroup * dd;
+    q.dW1a_part = ws + W.slab_w1a + (size_t)i * R.ngroup * dd;
+    q.dW1b_part = ws + W.slab_w1b + (size_t)i * R.ngroup * dd;
     q.dy_part = ws + W.dy_part;
     q.dbg = kb_gemm_dbg();
     CK(sb_h2_launch(q, st));
   }
   // dKB of every step after step 0: the merged launch, or where chain_bwd's launches carried steps p - 1 .. 1 on their idle CUs,
   // the closing launch of that route
-  if (i == 0 && dkb_plan.njobs) CK(chain_dkb_rest_launch(dkb_q, B * N, N, d, st));
+  if (i == 0 && R.dkb.njobs) CK(chain_dkb_rest_launch(dkb_q, B * N, N, d, st));
   else if (i == 0) CKI(dkb_merged_h2());
   return MACX_OK;
 }
@@ -1654,8 +1731,8 @@ int CellBwd::read_unit_bwd(int i) {
 int CellBwd::dy_linear_bwd(int i, bool with_write) {
   float* DYi = ws + W.DY + (size_t)i * Bd;
   float* dm_prev = DM + (size_t)i * Bd;
-  if (!(h2 && W.sb_deferred)) {
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dy_part), (h2 ? SBH_CW / 2 : 2) * d / 128, Bd, DYi);
+  if (!R.sb_deferred) {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dy_part), (R.h2 ? SBH_CW / 2 : 2) * d / 128, Bd, DYi);
     CK(hipGetLastError());
   }
   // with self attention DM[i] already holds the parts later steps sent to this memory, with a loss on the memories history the
@@ -1668,8 +1745,8 @@ int CellBwd::dy_linear_bwd(int i, bool with_write) {
   l.d2 = make_drop(dp->keep_read, dp, SITE_READ_MEM, i);
   l.drop_row0 = (uint32_t)s->b0;
   if (with_write) { l.addend = ws + W.dwin + (size_t)i * B * win; l.ld_add = win; }
-  if (h2 && W.dy_in_linear) {
-    l.part = ws + W.dyc_part; l.part_N = N; l.part_sum = DYi; l.part_shift = chain_tile_shift(d, (size_t)B * N);
+  if (R.dy_in_linear) {
+    l.part = ws + W.dyc_part; l.part_N = N; l.part_sum = DYi; l.part_shift = R.tile_shift;
     CK(small_linear_part_launch(l, st));
   } else {
     CK(small_linear_launch(l, 1, st));
@@ -1742,13 +1819,13 @@ int CellBwd::control_step_bwd(int i) {
 // ---- backward: after the step loop
 // the chain launches' per-tile partials of every step that did not reduce its own: dL/dc_i += read-unit part, db_k partials
 int CellBwd::read_dc_reduce_all() {
-  if (!(h2 && W.chain_sums) || dc_in_loop || (W.sb_deferred && !W.dy_in_linear)) return MACX_OK;
+  if (!R.chain_sums || dc_per_step()) return MACX_OK;
   DcReduceP q;
   memset(&q, 0, sizeof(q));
   q.B = B; q.N = N; q.d = d;
   q.dc_part = ws + W.dc_part; q.dls_part = ws + W.dls_part; q.dc = DC + Bd; q.dbk_part = ws + W.dbk_part;
-  q.part_step = W.dwk_rows * 3 * d; q.dls_step = W.dwk_rows * 3; q.dc_step = Bd; q.dbk_step = B;
-  q.tile_shift = chain_tile_shift(d, (size_t)B * N);
+  q.part_step = R.dwk_rows * 3 * d; q.dls_step = R.dwk_rows * 3; q.dc_step = Bd; q.dbk_step = B;
+  q.tile_shift = R.tile_shift;
   hipLaunchKernelGGL(dc_reduce_kernel, dim3(B, p), dim3(128), 0, st, q);
   CK(hipGetLastError());
   return MACX_OK;
@@ -1907,8 +1984,8 @@ int CellBwd::write_linear_wgrads() {
 // dWx = sum_i dropout_i(KB)^T dX_i: ONE contraction each over all p*B*N rows (the per-step operands are kept; 288 GB of HBM makes
 // that the cheap choice)
 int CellBwd::read_weight_contractions() {
-  int ns_w = (int)W.ns_big;          // reduction splits of the dW2 / dWx contractions (H2 family: decided below)
-  if (h2) {
+  int ns_w = (int)R.ns_big;          // reduction splits of the dW2 / dWx contractions (H2 family: decided below)
+  if (R.h2) {
     int* ecom = reinterpret_cast<int*>(ws + W.ecom);       // [H1 | dI2 | KBd | dX][EMIN_NB][8]
     constexpr int ES = EMIN_NB * 8;
     {
@@ -1926,7 +2003,7 @@ int CellBwd::read_weight_contractions() {
     // mode 3: the two contractions share ONE launch AND the chip -- half the reduction splits each, so that the 2 x 128 workgroups
     // are all resident at once (one per CU) instead of 2 x 256 in two rounds: a workgroup's prologue, its 256 KB slab and the slab
     // reduction's input are paid for once per CU instead of twice
-    ns_w = (wgrad_pipe_mode() >= 3 && wgrad_h2_kw(d) == 2 && wgrad_h2_jw(d) == 2 && W.ns_big >= 2) ? (int)W.ns_big / 2 : (int)W.ns_big;
+    ns_w = (wgrad_pipe_mode() >= 3 && wgrad_h2_kw(d) == 2 && wgrad_h2_jw(d) == 2 && R.ns_big >= 2) ? (int)R.ns_big / 2 : (int)R.ns_big;
     t.M = p * B * N; t.Kd = d; t.Jd = d; t.nsplit = ns_w; t.rows_per_split = rows_per_split(t.M, t.nsplit);
     t.R = B * N;
     t.A = reinterpret_cast<const char*>(saved + L.H1); t.a_stride = L.act_stride * sizeof(float); t.a_mod = 0;
@@ -1946,7 +2023,7 @@ int CellBwd::read_weight_contractions() {
   } else {
     TnP t;
     memset(&t, 0, sizeof(t));
-    t.M = p * B * N; t.Kd = d; t.Jd = d; t.nsplit = (int)W.ns_big; t.rows_per_split = rows_per_split(t.M, t.nsplit);
+    t.M = p * B * N; t.Kd = d; t.Jd = d; t.nsplit = (int)R.ns_big; t.rows_per_split = rows_per_split(t.M, t.nsplit);
     t.A = saved + L.H1; t.lda = d; t.a_mod = t.M; t.G = ws + W.dI2; t.ldg = d;
     t.part = ws + W.slab_w2;
     CK(wgrad_any(t, st));
@@ -1956,32 +2033,30 @@ int CellBwd::read_weight_contractions() {
     t.part = ws + W.slab_wx;
     CK(wgrad_any(t, st));
   }
-  if (h2 && W.sb_deferred) {
+  if (R.sb_deferred) {
     // dW1a = sum_i sum_b diag(y_ib) S_ib, dW1b = sum_i sum_b S_ib, S_ib = X_ib^T dI1_ib: every step in one launch, the two
     // accumulators of a workgroup run through all of them (macx_wgrad_h2.hip.h)
     SbH2P q;
     memset(&q, 0, sizeof(q));
-    q.B = B; q.N = N; q.d = d; q.qpg = sb_qpg(B, N);
+    q.B = B; q.N = N; q.d = d; q.qpg = R.sb_qpg;
     q.X = h2_view(saved + L.X, B * N, d); q.dI1 = h2_view(ws + W.dI1, B * N, d);
     q.y = saved + L.y; q.W1a = P->memKbProj_W;
     q.dW1a_part = ws + W.slab_w1a; q.dW1b_part = ws + W.slab_w1b; q.dy_part = nullptr;
     q.nsteps = p;
     q.x_step = L.act_stride * sizeof(float); q.g_step = W.dI1_stride * sizeof(float); q.y_step = Bd;
     q.dbg = kb_gemm_dbg();
-    q.qpg = W.sb_qpg;
-    CK(W.sb_wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
+    CK(R.sb_wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
   }
-  const int nslab1 = (int)((h2 && W.sb_deferred ? 1 : p) * W.ngroup);
   SlabList sl;
   sl.d[0] = SlabDesc{ws + W.slab_w2, ns_w, dd / 4, GP->memKbProj2_W, 0};
   sl.d[1] = SlabDesc{ws + W.slab_wx, ns_w, dd / 4, GP->projX_W, 0};
-  sl.d[2] = SlabDesc{ws + W.slab_w1a, nslab1, dd / 4, GP->memKbProj_W, 0};
-  sl.d[3] = SlabDesc{ws + W.slab_w1b, nslab1, dd / 4, GP->memKbProj_W + dd, 0};
+  sl.d[2] = SlabDesc{ws + W.slab_w1a, (int)R.nslab_sb, dd / 4, GP->memKbProj_W, 0};
+  sl.d[3] = SlabDesc{ws + W.slab_w1b, (int)R.nslab_sb, dd / 4, GP->memKbProj_W + dd, 0};
   CK(slab_reduce_list_launch(sl, 4, dd, st));
-  CK(rs.add(ws + W.db2_part, p * (int)W.dwk_rows, d, d, GP->memKbProj2_b, st));
-  CK(rs.add(ws + W.db1_part, p * (int)W.db_rows, d, d, GP->memKbProj_b, st));
-  CK(rs.add(ws + W.dbx_part, p * (int)W.db_rows, d, d, GP->projX_b, st));
-  CK(rs.add(ws + W.dwk_part, p * (int)W.dwk_rows, d, d, GP->kbLogits_w, st));
+  CK(rs.add(ws + W.db2_part, p * (int)R.dwk_rows, d, d, GP->memKbProj2_b, st));
+  CK(rs.add(ws + W.db1_part, p * (int)R.db_rows, d, d, GP->memKbProj_b, st));
+  CK(rs.add(ws + W.dbx_part, p * (int)R.db_rows, d, d, GP->projX_b, st));
+  CK(rs.add(ws + W.dwk_part, p * (int)R.dwk_rows, d, d, GP->kbLogits_w, st));
   CK(rs.add(ws + W.dbk_part, p * B, 1, 1, GP->kbLogits_b, st));
   CK(rs.run(st));
   return MACX_OK;
@@ -2090,10 +2165,10 @@ int macx_read_fwd_l(const macx_opts* o, const macx_shapes* s, const macx_dropout
   if (saved_floats < r.L.total) return MACX_ESMALL;
   {
     Packer pk;
-    if (r.h2) CK(r.read_weight_maxima());
+    if (r.R.h2) CK(r.read_weight_maxima());
     r.add_read_packs(pk);
     if (r.L.bwd_packs) {
-      const BwdLayout W = make_bwd(o, s);
+      const BwdLayout W = make_bwd(o, s, r.R);
       r.add_read_packs(pk, &W);
     }
     CK(pk.run(r.st));
@@ -2147,7 +2222,7 @@ int macx_write_fwd(const macx_opts* o, const macx_shapes* s, const macx_dropout*
     Packer pk;
     r.add_write_packs(pk);
     if (r.L.bwd_packs) {
-      const BwdLayout W = make_bwd(o, s);
+      const BwdLayout W = make_bwd(o, s, r.R);
       r.add_write_packs(pk, &W);
     }
     CK(pk.run(r.st));
@@ -3233,7 +3308,7 @@ int macx_h2_gemm_planes(const float* hA, int B, int N, int K, const float* Wh, i
   memset(&g, 0, sizeof(g));
   g.B = B; g.N = N; g.K = K; g.Nout = n_out;
   g.A = h2_view(hA, B * N, K);
-  g.Wh = reinterpret_cast<const char*>(Wh); g.w_exp = reinterpret_cast<const int*>(Wh) + (size_t)K * n_out;
+  set_h2_weight(g, Wh, (size_t)K * n_out);
   g.out = h2_view(hO, B * N, n_out); g.bias = bias; g.act = act; g.e_inv_keep = 1.0f;
   g.dbg = kb_gemm_dbg();
   static const int reps = getenv("MACX_H2_DEBUG_REPS") ? atoi(getenv("MACX_H2_DEBUG_REPS")) : 1;   // timing aid (tools/h2_gemm_time.py)
@@ -3265,16 +3340,17 @@ int macx_read_chain_time(const macx_opts* o, const macx_shapes* s, const macx_dr
   ModeScope ms(o);
   CKI(check_impl(o, s));
   if (!dp || !P || !in || !saved || !ms_out || reps < 1 || step < 0 || step >= s->p) return MACX_EINVAL;
-  if (!use_chain(s->d, s->N)) return MACX_EUNSUPPORTED;
-  const SavedLayout L = make_saved(o, s, 1);
+  const CellRoute R = plan_route(o, s, dp, 1, NCU_ASK);
+  if (!R.chain) return MACX_EUNSUPPORTED;
+  const SavedLayout L = make_saved(o, s, 1, R);
   if (saved_floats < L.total) return MACX_ESMALL;
   hipStream_t st = (hipStream_t)stream;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  CK(chain_fwd_launch(make_chain_fwd(o, s, dp, P, in, saved, L, 1, step, step), st));      // untimed: code object, LDS attribute
+  CK(chain_fwd_launch(make_chain_fwd(o, s, dp, P, in, saved, L, R, 1, step, step), st));      // untimed: code object, LDS attribute
   CK(hipEventRecord(e0, st));
-  for (int r = 0; r < reps; ++r) CK(chain_fwd_launch(make_chain_fwd(o, s, dp, P, in, saved, L, 1, step, (step + r) % s->p), st));
+  for (int r = 0; r < reps; ++r) CK(chain_fwd_launch(make_chain_fwd(o, s, dp, P, in, saved, L, R, 1, step, (step + r) % s->p), st));
   CK(hipEventRecord(e1, st));
   CK(hipEventSynchronize(e1));
   float t = 0.f;
@@ -3295,7 +3371,7 @@ int macx_cell_forward_chain_time(const macx_opts* o, const macx_shapes* s, const
   ModeScope ms(o);
   CKI(check_impl(o, s));
   if (!ms_out) return MACX_EINVAL;
-  if (!use_chain(s->d, s->N)) return MACX_EUNSUPPORTED;
+  if (!plan_route(o, s, dp, 1, NCU_NONE).chain) return MACX_EUNSUPPORTED;
   ChainProbe& cp = *chain_probe();
   if (cp.on) return MACX_EINVAL;
   const int ne = 2 * (s->p < 64 ? s->p : 64);
@@ -3423,13 +3499,14 @@ int macx_saved_activation(const macx_opts* o, const macx_shapes* s, int which, i
   ModeScope ms(o);
   CKI(check_impl(o, s));
   if (!saved || !out || which < 0 || which > 3 || step < 0 || step >= s->p || misaligned(out)) return MACX_EINVAL;
-  const SavedLayout L = make_saved(o, s, 1);
+  const CellRoute route = plan_route(o, s, nullptr, 1, NCU_NONE);
+  const SavedLayout L = make_saved(o, s, 1, route);
   if (saved_floats < L.total) return MACX_ESMALL;
   const size_t base = which == 0 ? L.KBd : (which == 1 ? L.X : (which == 2 ? L.H1 : L.I2));
   const float* src = saved + base + (size_t)step * L.act_stride;
   hipStream_t st = (hipStream_t)stream;
   const size_t R = (size_t)s->B * s->N;
-  if (h2_mode()) {
+  if (route.h2) {
     hipLaunchKernelGGL(h2_to_f32_kernel, dim3(1024), dim3(256), 0, st, h2_view(src, (int)R, s->d), out);
     CK(hipGetLastError());
   } else {

@@ -33,13 +33,14 @@ INF = float("inf")
 B = 4
 SCALES = (0, -10, -20, -30)              # per-question gradient scales 2^s_b
 SCALES_PERMUTED = (-20, -30, 0, -10)     # ... with the large question not in front
-# (config, S, N, d, p): the smallest shapes that still select each route of the backward pass
+# (config, S, N, d, p): the smallest shapes that still select each route of the backward pass (asserted on the library's own route
+# plan by tests/test_route_host.py)
 SHAPES = {
-    "launch": ("args", 7, 49, 128, 2),       # per-launch H2
+    "launch": ("args", 7, 49, 128, 2),       # the narrowest chain kernel (64-row tiles), S_b deferred on the 128 x 128 kernel
     "step_sb": ("args1", 7, 20, 256, 3),     # N < 32: the per-step S_b route
     "nochain": ("args", 7, 14, 128, 2),      # N < 16: no chain kernels
     "chain": ("args", 7, 196, 512, 2),       # chain kernels, 16-row tiles
-    "selfatt": ("args3", 6, 49, 128, 3),     # self-attention and gate
+    "selfatt": ("args3", 6, 49, 128, 3),     # self-attention (args3 has no gate)
 }
 ZERO_QUESTIONS = (1, 3)
 HOMOGENEITY_K = (-40, -16, 16, 40)

@@ -5,10 +5,11 @@ columns), 512 < d < 1024 (the per-product H2 route at 640 / 768 / 896), the ragg
 
 The checks are test_gpu_cell's own (final state, dKB / dwords / dvecQ and every parameter gradient to FWD_TOL / GRAD_TOL; attentions
 and histories where the forward test is named), re-used as test_gpu_limits.py does.  Each case prints the largest forward and
-gradient error it saw and the route the launcher's host predicates select for it (`pytest -s`).
+gradient error it saw and the route the library planned for it (macx_cell_route; `pytest -s`).
 
 Observed on an MI355X (256 CUs), default kernel family: flag file, B S N d p, largest forward error (bound 2e-5), largest gradient
-error (bound 2e-4), route as restated below ("fill a/b": filler workgroups of chain_fwd / of chain_bwd for dKB).  A kernel trace of the
+error (bound 2e-4), route ("fill a/b": filler workgroups of chain_fwd / of chain_bwd for dKB; tests/route_cases.py holds this column as
+data and tests/test_route_host.py asserts it on the library's plan for 256 compute units).  A kernel trace of the
 d = 384, M = 8232 and 640 / 768 / 896 cases shows chain_fwd/bwd_kernel<384, 0, .., 64> + sb_h2_kernel + wgrad_h2_kernel<1, 1>,
 chain_fwd/bwd_kernel<512, 4, .., 64> + chain_dkb_rest_kernel<512, 4> + sb_h2w_kernel + wgrad_h2_kernel<2, 2>, and kb_gemm_h2_kernel
 per product with no chain kernel.  Intermediate products (bound 1e-6): 1.6e-7 / 1.7e-7 / 1.3e-7 (X / H1 / I2) at d = 384,
@@ -42,6 +43,7 @@ import pytest
 import torch
 
 import helpers
+import route_cases as rc
 import test_gpu_cell as cellmod
 from helpers import make_case
 from test_gpu_cell import FWD_TOL, GRAD_TOL, build_cell
@@ -49,41 +51,11 @@ from test_gpu_cell import FWD_TOL, GRAD_TOL, build_cell
 pytestmark = pytest.mark.gpu
 
 
-# ---- the launcher's host predicates, RESTATED for the printed record only: not authoritative.  Nothing asserts on them, they know
-# nothing of macx_opts.tune or the kernel family (default table, H2 only), and they must be re-read against the headers named below
-# whenever those change; a kernel trace of the run is the authority on what was launched.
-def _chain_tile_rows(d, M):                         # macx_chain_api.hip.h: chain_tile_rows
-    if d != 512:
-        return 64
-    if (M + 31) // 32 > 256:
-        return 64
-    return 32 if (M + 15) // 16 > 256 else 16
-
-
-def _route(dev, B, N, d, p):
-    """macx_api.hip use_chain / make_ws (chain_sums, sb_wide), macx_chain_api.hip.h pre_fill_count / dkb_fill_plan,
-    macx_wgrad_h2.hip.h wgrad_h2_kw / _jw -- on the default kernel family and tuning table"""
-    dk = (d + 127) // 128 * 128
-    M = B * N
-    kw = 2 if dk % 256 == 0 else 1
-    if not (dk <= 512 and N >= 16):
-        return "per-product H2 launches, wgrad kw=jw=%d" % kw
-    rows = _chain_tile_rows(dk, M)
-    tiles = (M + rows - 1) // rows
-    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    idle = (ncu - tiles % ncu) % ncu
-    if dk != 512:
-        pre = 0
-    elif rows == 16:
-        pre = ncu // 4 if ncu >= 64 else 0
-    else:
-        pre = idle if idle * 6 >= tiles else 0
-    pre = pre if (p <= 32 and B <= 128) else 0
-    dkb = idle if (dk == 512 and N >= 64 and p >= 2 and rows == 64 and idle * 12 >= tiles) else 0
-    sums = N >= 32
-    sb = ("deferred S_b, %s" % ("128x256" if dk % 256 == 0 and (N + 31) // 32 * 32 <= 512 else "128x128")) if sums else "S_b per step"
-    return ("chain<%d>, %d-row tiles x %d%s, %s, wgrad kw=jw=%d, fwd fillers %d, dKB fillers %d"
-            % (dk, rows, tiles, " (ragged)" if M % rows else "", sb, kw, pre, dkb))
+def _route(macx, name, B, S, N, d, p):
+    """the library's own route plan for this case on the current device (macx_cell_route, ncu = 0: exactly what the launches follow;
+    the dropout moves no field that is printed).  What it says on 256 compute units is asserted in tests/test_route_host.py."""
+    dk, dlog = rc.padded(d)
+    return rc.route(macx, *rc.frozen(macx, name, (B, S, N, dk, p, dlog), None), ncu=0)
 
 
 @pytest.fixture
@@ -117,7 +89,7 @@ def _parity(macx, dev, observed, name, B, S, N, d, p, train):
         e = observed["errs"]
         if e:
             print("\nGEOMETRY %s B=%d S=%d N=%d d=%d p=%d train=%d: fwd %.2e (tol %.0e) grad %.2e (tol %.0e) | %s"
-                  % (name, B, S, N, d, p, train, e[0], FWD_TOL, max(e[1:] or [0.0]), GRAD_TOL, _route(dev, B, N, d, p)))
+                  % (name, B, S, N, d, p, train, e[0], FWD_TOL, max(e[1:] or [0.0]), GRAD_TOL, rc.describe(_route(macx, name, B, S, N, d, p))))
     cell = observed["cells"][-1]
     assert cell.status() == (0, -1)
     return cell
@@ -179,6 +151,18 @@ def test_questions_per_tile_match_the_oracle(macx, dev, observed, name, B, S, N,
     _parity(macx, dev, observed, name, B, S, N, d, p, train)
 
 
+@pytest.mark.parametrize("row", rc.GEOMETRY, ids=["%s-B%d-N%d-d%d-p%d" % (r[0], r[1], r[3], r[4], r[5]) for r in rc.GEOMETRY])
+def test_route_for_the_current_device_is_the_route_for_its_compute_units(macx, dev, row):
+    """ncu = 0 (what every launch plans with) asks the device: the same plan as naming its compute units.  Nothing is launched."""
+    name, B, S, N, d, p = row[:6]
+    dk, dlog = rc.padded(d)
+    opts, sh = rc.frozen(macx, name, (B, S, N, dk, p, dlog), None)
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    for dp in (None, rc.dropout(macx, 0.9, 0.85, 0.8)):
+        assert rc.route(macx, opts, sh, drop=dp, ncu=0) == rc.route(macx, opts, sh, drop=dp, ncu=ncu)
+    assert ncu > 0
+
+
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -222,7 +206,7 @@ def test_chain_kernel_intermediate_products(macx, dev, B, S, N, d):
     stages = [("X", X, A0 @ w("projX_W") + w("projX_b"), A0.abs() @ w("projX_W").abs() + w("projX_b").abs()),
               ("H1", H1, torch.nn.functional.elu(pre1), (X * yr).abs() @ W1a.abs() + X.abs() @ W1b.abs() + w("memKbProj_b").abs()),
               ("I2", I2, H1 @ w("memKbProj2_W") + w("memKbProj2_b"), H1.abs() @ w("memKbProj2_W").abs() + w("memKbProj2_b").abs())]
-    rows = _chain_tile_rows(d, B * N)
+    rows = _route(macx, "args", B, S, N, d, p)["tile_rows"]
     for name, got, ref, mag in stages:
         scale = mag.amax(dim=1, keepdim=True) + 1e-300
         e = ((got - ref).abs() / scale).amax(dim=1)
