@@ -409,7 +409,10 @@ int macx_output_backward_w(const macx_out_shapes*, int act, float keep, uint32_t
  *   KB = act(conv3x3_SAME(dropout(act(conv3x3_SAME(dropout(images), K0) + b0)), K1) + b1)
  * images [B, H*W, Cin] NHWC (config.imageDims = 14 x 14 x 1024), KB [B, H*W, Cout] (model.py:202).
  * Variables: stem/cnnLayercnn_{0,1}/kernels/kernel [3,3,in,out] (HWIO), .../biases/bias [out].
- * Cin, Cmid, Cout multiples of 128.  No gradient is returned for `images` (pre-extracted features). */
+ * Cin, Cmid, Cout multiples of 128.  No gradient is returned for `images` (pre-extracted features).
+ * Limits (anything else: the size calls return 0, the others MACX_EINVAL): W >= 2, H W <= 1024, (b0 + B) H W max(Cin, Cmid) < 2^32
+ * (the dropout's element index), and, with N = H W and e = ceil(2^32 / N) N - 2^32, (B N - 1) e < 2^32 unless e = 0 (the kernel
+ * gradients divide a flattened row by N with one 32-bit multiply: about 4,100 images at N = 1023, 6,100 at N = 1000). */
 typedef struct macx_stem_shapes { int32_t B, H, W, Cin, Cmid, Cout, b0; } macx_stem_shapes;
 typedef struct macx_stem_params { const float* kernel0; const float* bias0; const float* kernel1; const float* bias1; } macx_stem_params;
 typedef struct macx_stem_grads { float* kernel0; float* bias0; float* kernel1; float* bias1; } macx_stem_grads;

@@ -2746,6 +2746,15 @@ int stem_check(const macx_stem_shapes* s) {
   if (s->Cin % 128 || s->Cmid % 128 || s->Cout % 128 || s->Cin < 128 || s->Cmid < 128 || s->Cout < 128) return MACX_EINVAL;
   if (s->H * s->W > K_MAXN) return MACX_EINVAL;
   if ((size_t)(s->b0 + s->B) * s->H * s->W * (size_t)(s->Cin > s->Cmid ? s->Cin : s->Cmid) >= (1ull << 32)) return MACX_EINVAL;
+  // the CONV weight-gradient kernels take the image of flattened row m as __umulhi(m, magic), magic = ceil(2^32 / N) (conv_wgrad):
+  // m magic / 2^32 = m / N + m e / (N 2^32) with e = magic N - 2^32 < N, whose floor is m / N for every remainder while m e < 2^32.
+  // Refuse what the largest row, B N - 1, does not satisfy (N a power of two: e = 0, never refused; the pixel's row, n < 1024
+  // by W <= 1024, always satisfies it).  Conservative, and exact below the bound: tests/test_stem_geometry_host.py.
+  {
+    const uint64_t N = (uint64_t)s->H * s->W;
+    const uint64_t e = (((1ull << 32) + N - 1) / N) * N - (1ull << 32);
+    if (e && ((uint64_t)s->B * N - 1) * e >= (1ull << 32)) return MACX_EINVAL;
+  }
   return MACX_OK;
 }
 hipError_t launch_pad_drop(const float* src, const PadP& q, float keep, uint32_t seed, uint32_t site, uint32_t first, float* dst,
