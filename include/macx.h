@@ -549,6 +549,31 @@ int macx_kb_gather_bwd_l(const float* dkb /*[B,N,d]*/, const int32_t* image_inde
                          const int32_t* image_lengths /*[G], device, or NULL*/, int G, int B, int N, int d,
                          float* dkb_images /*[G,N,d]*/, void* stream);
 
+/* ---- image features resident in device memory ------------------------------------------------- */
+/* The whole feature set of a dataset as ONE device table [rows][HW][C] (NHWC rows, what macx_stem_forward reads), fp32 or fp16,
+ * filled once from the feature file's chunks; a batch then names its images by row id.
+ *   macx_features_pack    table[row0 + i] = convert(src[i]), i = 0 .. n-1, and nothing else is written
+ *   macx_features_gather  out[g] = (float) table[ids[g]]
+ * dtype: MACX_FEATURES_F32 | MACX_FEATURES_F16.  layout: 0 = src is [n][C][HW] (the h5 file's; the transpose of
+ * macx_images_to_nhwc per image, tiled through LDS), 1 = src is [n][HW][C].  rows < 2^31; row0 and rows are 64-bit and travel as
+ * size_t: a negative value of a signed caller arrives as 2^63 or more and is refused like any other row0 + n > rows.
+ * Pack: fp32 -> fp16 is round-to-nearest-even with subnormals kept and the sign of zero preserved; an fp32 table takes the source
+ * bits.  overflow (int32 in DEVICE memory, or NULL): a source value that is NaN or infinite, or that rounds to an infinity, is
+ * stored as such AND the constant 1 is written to overflow[0] (a plain store from every thread that sees one, no atomics).  The
+ * call never clears the word: zero it once, pack every chunk, read it once.
+ * Gather: ids [G] int32 in DEVICE memory, read when the kernel runs (a captured graph follows ids rewritten between replays).  An
+ * id outside [0, rows) is never dereferenced; that image's block is filled with quiet NaN (the call still returns MACX_OK: the id
+ * is device data), every other block is exact (fp16 -> fp32 loses nothing).  Nothing outside out[0 .. G*HW*C) is written.  For an
+ * fp32 table this is the copy kernel of macx_kb_gather, bit for bit.
+ * MACX_EINVAL (nothing is launched): a NULL table, src, out or ids; n, G, C, HW or rows < 1; C*HW % 4 != 0; rows >= 2^31;
+ * row0 + n > rows; a dtype or layout other than the listed values; a float or table pointer off a 16-byte boundary, an int32
+ * pointer off a 4-byte boundary.  Like every call here: no allocation, no memcpy / memset, stream-ordered only. */
+enum { MACX_FEATURES_F32 = 0, MACX_FEATURES_F16 = 1 };
+int macx_features_pack(const float* src, int layout, int n, int C, int HW, void* table, int dtype, size_t row0, size_t rows,
+                       int32_t* overflow /*[1], device, or NULL*/, void* stream);
+int macx_features_gather(const void* table, int dtype, size_t rows, const int32_t* ids /*[G], device*/, int G, int C, int HW,
+                         float* out /*[G,HW,C]*/, void* stream);
+
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)
  * on fp32 MFMA; `W_packed` from macx_pack_weight(W, k1 + k2, n_out, 0); k1, k2, n_out % 16 == 0. */

@@ -247,6 +247,13 @@ TABLE.update(
     # (the sizes per image, [G] int32 or NULL, behind the index; the forward call also writes kb_lengths_out [B] in front of the stream)
     macx_kb_gather_l=(_I, _GATHER[:2] + (_V,) + _GATHER[2:-1] + (_V, _GATHER[-1])),
     macx_kb_gather_bwd_l=(_I, _GATHER[:2] + (_V,) + _GATHER[2:]))
+# ---- image features resident in device memory
+TABLE.update(
+    # (src, layout, n, C, HW; table, dtype, row0, rows; overflow, stream)
+    macx_features_pack=(_I, (_V, _I, _I, _I, _I, _V, _I, _Z, _Z, _V, _V)),
+    # (table, dtype, rows; ids, G, C, HW; out, stream)
+    macx_features_gather=(_I, (_V, _I, _Z, _V, _I, _I, _I, _V, _V)))
+FEATURES_DTYPE = {torch.float32: 0, torch.float16: 1}                       # MACX_FEATURES_*
 # ---- unit-level entry points
 TABLE.update(
     macx_linear=(_I, (_V, _I, _V, _I, _I, _V, _V, _F, _I, _I, _V, _V)),

@@ -21,6 +21,7 @@
 #include "macx_ops.hip.h"
 #include "macx_conv.hip.h"
 #include "macx_kb_gather.hip.h"
+#include "macx_features.hip.h"
 #include "macx_att_loss.hip.h"
 
 using namespace macx;
@@ -3268,6 +3269,50 @@ int macx_kb_gather_bwd_l(const float* dkb, const int32_t* image_index, const int
   hipLaunchKernelGGL(kb_gather_bwd_l_kernel, kbg_grid(quads, 256, G), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const f32x4*>(dkb), image_index, image_lengths, G, B, N, (size_t)d / 4,
                      reinterpret_cast<f32x4*>(dkb_images));
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// ---- image features resident in device memory (macx_features.hip.h) ----
+namespace {
+// what both calls refuse before anything else: sizes, dtype, the quad rule, rows < 2^31 (row0 and rows travel as size_t: a negative
+// 64-bit value arrives as 2^63 or more and fails the range test)
+inline bool features_ok(int C, int HW, int dtype, size_t rows) {
+  return C >= 1 && HW >= 1 && (dtype == MACX_FEATURES_F32 || dtype == MACX_FEATURES_F16) && ((size_t)C * HW) % 4 == 0 && rows >= 1 &&
+         rows < ((size_t)1 << 31);
+}
+}  // namespace
+
+int macx_features_pack(const float* src, int layout, int n, int C, int HW, void* table, int dtype, size_t row0, size_t rows,
+                       int32_t* overflow, void* stream) {
+  if (!src || !table || n < 1 || (layout != 0 && layout != 1) || !features_ok(C, HW, dtype, rows)) return MACX_EINVAL;
+  if (row0 > rows || (size_t)n > rows - row0) return MACX_EINVAL;
+  if (misaligned(src) || misaligned(table) || ((uintptr_t)overflow & 3)) return MACX_EINVAL;
+  if (((size_t)C + FT_TILE - 1) / FT_TILE > 65535 || HW > 0x7FFFFFFF - FT_TILE) return MACX_EINVAL;   // (grid y; int tile edges)
+  const hipStream_t st = (hipStream_t)stream;
+  if (dtype == MACX_FEATURES_F16)
+    CK(feat_pack_launch(src, layout, n, C, HW, reinterpret_cast<_Float16*>(table), row0, overflow, st));
+  else
+    CK(feat_pack_launch(src, layout, n, C, HW, reinterpret_cast<float*>(table), row0, overflow, st));
+  return MACX_OK;
+}
+
+int macx_features_gather(const void* table, int dtype, size_t rows, const int32_t* ids, int G, int C, int HW, float* out, void* stream) {
+  if (!table || !ids || !out || G < 1 || !features_ok(C, HW, dtype, rows)) return MACX_EINVAL;
+  if (misaligned(table) || misaligned(out) || ((uintptr_t)ids & 3)) return MACX_EINVAL;
+  const size_t image = (size_t)C * HW;
+  const hipStream_t st = (hipStream_t)stream;
+  if (dtype == MACX_FEATURES_F32) {                      // the copy macx_kb_gather launches: table rows are its images
+    const size_t quads = image / 4;
+    hipLaunchKernelGGL(kb_gather_kernel, kbg_grid(quads, KBG_CHUNK, G), dim3(256), 0, st, reinterpret_cast<const f32x4*>(table), ids,
+                       (int)rows, G, quads, reinterpret_cast<f32x4*>(out));
+  } else if (image % 8 == 0) {
+    hipLaunchKernelGGL(feat_gather_h_kernel<2>, kbg_grid(image / 8, FT_CHUNK, G), dim3(256), 0, st,
+                       reinterpret_cast<const _Float16*>(table), ids, (int)rows, G, image / 8, reinterpret_cast<f32x4*>(out));
+  } else {
+    hipLaunchKernelGGL(feat_gather_h_kernel<1>, kbg_grid(image / 4, FT_CHUNK, G), dim3(256), 0, st,
+                       reinterpret_cast<const _Float16*>(table), ids, (int)rows, G, image / 4, reinterpret_cast<f32x4*>(out));
+  }
   CK(hipGetLastError());
   return MACX_OK;
 }

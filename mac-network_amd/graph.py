@@ -754,6 +754,7 @@ class _TowerInputs(_AttLoss):
     G, image_index = None, None            # questions that share images (images=G): see _alloc_inputs
     kb_lengths, image_lengths = None, None # knowledge bases of per-question / per-image size: see _alloc_inputs
     weights, totals, n = None, None, None  # per-question answer weights, running totals, questions of the last load: _alloc_weights
+    features, image_ids = None, None       # image features resident in device memory (features=store): see _alloc_inputs
     _WEIGHTS_HOW = "weights=True"          # the constructor argument that builds `weights`
 
     def _alloc_weights(self, dev, totals):
@@ -839,12 +840,20 @@ class _TowerInputs(_AttLoss):
             from .stem import check_image_index
             check_image_index(torch.zeros(1, dtype=torch.int32), 1, True, net.stem)
 
-    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev, images=None, kb_lengths=False, image_lengths=False):
-        """images: None (one image per question), or G: the static image tensor holds G images and a static [B] int32
+    def _alloc_inputs(self, net, B, S, H, W, imageInDim, dev, images=None, kb_lengths=False, image_lengths=False, features=None):
+        """features: None, or a macx.FeatureStore: no static image tensor; a static int32 `image_ids` ([B], or [G] with images=G)
+        names the table rows of the batch's images and the captured gather (macx_features_gather) reads it at replay time.  H, W and
+        imageInDim are then the store's.  Allocated here, before the capture, like every buffer the host writes.
+        images: None (one image per question), or G: the static image tensor holds G images and a static [B] int32
         `image_index`, read by the captured gather kernel at replay time, says which one each question looks at.
         kb_lengths: a static [B] int32 `kb_lengths` (all N), read by the cell's attention kernel at replay time.
         image_lengths (with images=G): a static [G] int32 `image_lengths` (all N), read by the captured gather (macx_kb_gather_l),
         which makes the cell's per-question lengths on the device.  Both are allocated here, before the capture."""
+        if features is not None:
+            from .features import FeatureStore
+            if not isinstance(features, FeatureStore):
+                raise TypeError("features is None or a macx.FeatureStore, not %r" % type(features).__name__)
+            H, W, imageInDim = features.hwc
         self.B, self.S, self.H, self.W, self.imageInDim = int(B), int(S), int(H), int(W), int(imageInDim)
         self.n = self.B
         self.N = net.stem.out_hw[0] * net.stem.out_hw[1]
@@ -860,14 +869,40 @@ class _TowerInputs(_AttLoss):
         if (net.stem.H, net.stem.W, net.stem.inDim) != (self.H, self.W, self.imageInDim):
             raise ValueError("the net's stem was built for %d x %d x %d image features, not %d x %d x %d"
                              % (net.stem.H, net.stem.W, net.stem.inDim, self.H, self.W, self.imageInDim))
-        self.images = torch.zeros(self.B if self.G is None else self.G, self.H * self.W, self.imageInDim, device=dev)   # NHWC, what the stem's kernels read
+        count = self.B if self.G is None else self.G
+        if features is not None:
+            if features.table.device != dev:
+                raise ValueError("the FeatureStore lives on %s, the net on %s" % (features.table.device, dev))
+            self.features, self.images = features, None
+            self.image_ids = torch.zeros(count, dtype=torch.int32, device=dev)
+        else:
+            self.images = torch.zeros(count, self.H * self.W, self.imageInDim, device=dev)   # NHWC, what the stem's kernels read
         self.questions = torch.zeros(self.B, self.S, dtype=torch.int32, device=dev)
         self.lengths = torch.full((self.B,), self.S, dtype=torch.int32, device=dev)
 
     def _net_arguments(self):
         """the keyword arguments of the net's call that the static tensors stand for ({}: the call of before)"""
-        named = (("image_index", self.image_index), ("kb_lengths", self.kb_lengths), ("image_lengths", self.image_lengths))
+        named = (("image_index", self.image_index), ("kb_lengths", self.kb_lengths), ("image_lengths", self.image_lengths),
+                 ("image_ids", self.image_ids))
         return {k: t for k, t in named if t is not None}
+
+    def _net_images(self):
+        """the net's `images` argument: the static image tensor, or the FeatureStore that `image_ids` names rows of"""
+        return self.images if self.features is None else self.features
+
+    def _random_images(self, gen, answers):
+        """(images, questions, lengths, answers) and {"image_ids": ...} for the self-checks: _random_tower_inputs' features, or for
+        a class built with features= no images and row ids with a repeat: the table's last row in the first and the last slot"""
+        dev = self.questions.device
+        shape = (0,) if self.features is not None else self.images.shape
+        images, q, lengths, ans = _random_tower_inputs(gen, self.B, self.S, self.net.enc.vocab, shape, answers, dev)
+        if self.features is None:
+            return (images, q, lengths, ans), {}
+        rows, count = self.features.rows, self.image_ids.shape[0]
+        ids = torch.randint(0, max(rows - 1, 1), (count,), generator=gen, dtype=torch.int32)
+        ids[0] = rows - 1
+        ids[-1] = ids[0]
+        return (None, q, lengths, ans), {"image_ids": ids.to(dev)}
 
     def _random_groups(self, gen):
         """(image_index, kb_lengths, image_lengths) for the self-checks, None where the class has none: an index with repeats and
@@ -881,26 +916,38 @@ class _TowerInputs(_AttLoss):
         return index, kbl, iml
 
     def _load_inputs(self, images, questions, lengths, check_ids, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
-                     weights=None):
+                     weights=None, image_ids=None):
         """A batch into the static tensors.  A class built with `weights` takes n <= B questions (n = questions.shape[0]; with
         images=G also g <= G images): every per-question argument -- lengths, answers, images (one image per question), image_index,
         kb_lengths; the training step's att_target and att_row_weights: _check_att_loss -- must have that leading size (ValueError
         naming it).
         Slots n .. B-1 of every per-question static tensor become copies of slot 0 (_pad_slots: finite and in range), their weights 0;
-        image slots g .. G-1 copies of image 0 and of image_lengths[0].  A class built without `weights` refuses n != B."""
+        image slots g .. G-1 copies of image 0 and of image_lengths[0].  A class built without `weights` refuses n != B.
+        A class built with features= takes image_ids (the table rows of the batch's images, an integer tensor with the leading size
+        `images` would have) and images=None; its dead slots take slot 0's id.  check_ids also tests 0 <= image_ids < rows."""
         who = type(self).__name__
+        if self.features is None and image_ids is not None:
+            raise ValueError("%s.load() takes no image_ids: the graph was captured without features= (a macx.FeatureStore)" % who)
+        if self.features is not None and (images is not None or image_ids is None):
+            raise ValueError("%s was captured with features= (a macx.FeatureStore): load() takes image_ids=, the table rows of the "
+                             "batch's images, and images=None" % who)
         _lengths_argument(who, "kb_lengths", kb_lengths is not None, self.kb_lengths is not None)
         _lengths_argument(who, "image_lengths", image_lengths is not None, self.image_lengths is not None)
         per_question = [("lengths", lengths), ("answers", answers), ("image_index", image_index), ("kb_lengths", kb_lengths)]
         # (images: with one image per question, and in a class built with `weights` only -- a class built without keeps taking any
         # tensor with the static tensor's element count, e.g. [B * N, C], as it always did)
+        if self.features is not None and self.G is None:
+            per_question.append(("image_ids", image_ids))
         n = self._batch(questions, weights, per_question + ([("images", images)] if self.G is None and self.weights is not None else []))
         g = n if self.G is None else self.G
         if self.G is not None and self.weights is not None:
-            g = int(images.shape[0]) if torch.is_tensor(images) and images.dim() else 0
+            per_image, name = (images, "images") if self.features is None else (image_ids, "image_ids")
+            g = int(per_image.shape[0]) if torch.is_tensor(per_image) and per_image.dim() else 0
             if not 1 <= g <= self.G:
-                raise ValueError("images: this graph was captured for %d shared images: load() takes 1 <= g <= %d of them, got %d"
-                                 % (self.G, self.G, g))
+                raise ValueError("%s: this graph was captured for %d shared images: load() takes 1 <= g <= %d of them, got %d"
+                                 % (name, self.G, self.G, g))
+        if self.features is not None:
+            self.features.check_ids(image_ids, g, host_check=check_ids)
         if kb_lengths is not None:
             _check_lengths(kb_lengths, n, self.N, check_ids, "kb_lengths")
         if image_lengths is not None:
@@ -926,10 +973,13 @@ class _TowerInputs(_AttLoss):
             if int(lengths.max()) > self.S or int(lengths.min()) < 0:
                 raise ValueError("question length outside [0, %d]" % self.S)
         with torch.no_grad():
-            if images.dim() == 4 and images.shape[1] == self.imageInDim and tuple(images.shape[2:]) == (self.H, self.W):
-                from .stem import k_nchw_to_nhwc          # the feed-dict layout [B, C, H, W]: transposed on the device
-                images = k_nchw_to_nhwc(images.to(self.images.device).contiguous(), self.imageInDim, self.H * self.W)
-            _pad_slots(self.images, images.reshape((g,) + tuple(self.images.shape[1:])), g)
+            if self.features is not None:
+                _pad_slots(self.image_ids, image_ids, g)
+            else:
+                if images.dim() == 4 and images.shape[1] == self.imageInDim and tuple(images.shape[2:]) == (self.H, self.W):
+                    from .stem import k_nchw_to_nhwc          # the feed-dict layout [B, C, H, W]: transposed on the device
+                    images = k_nchw_to_nhwc(images.to(self.images.device).contiguous(), self.imageInDim, self.H * self.W)
+                _pad_slots(self.images, images.reshape((g,) + tuple(self.images.shape[1:])), g)
             _pad_slots(self.questions, questions, n)
             _pad_slots(self.lengths, lengths, n)
             if self.G is not None:
@@ -969,6 +1019,13 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         fwd = macx.CapturedTowerForward(net, B=64, S=50, images=7, image_lengths=True)
         logits = fwd(images7, questions, lengths, image_index=index, image_lengths=sizes)
 
+    Image features resident in device memory: `features=store` (a macx.FeatureStore; H, W, imageInDim are the store's) captures
+    the gather of the batch's images from the table (macx_features_gather) in front of the stem; it reads the static int32
+    `fwd.image_ids` ([B], or [G] with images=G) when it runs, so a batch is a vector of row ids and no image crosses the bus:
+
+        fwd = macx.CapturedTowerForward(net, B=64, S=50, features=store)
+        logits = fwd(None, questions, lengths, image_ids=ids)
+
     Evaluation only (train=False: no dropout, nothing kept for a backward pass).  Parameters are read at replay time: an optimizer
     step or a checkpoint load between calls is seen; changing a parameter's storage needs a new capture.  `load()` validates ids
     and lengths on the host as QuestionEncoder.forward does (check_ids=False skips the synchronisation); the graph itself runs
@@ -980,7 +1037,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     answers, loss = None, None
 
     def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None, kb_lengths=False,
-                 image_lengths=False, score=False):
+                 image_lengths=False, score=False, features=None):
         """score=True: the graph scores its answers -- static int32 [B] `answers`, float32 [B] `weights` (ones) and an
         output.AnswerTotals `totals`, allocated with the other inputs; the argmax launch becomes macx_answer_loss_weighted without a
         gradient, which adds every replay's weighted loss, correct count and weight to `totals`.  load() / __call__ then take
@@ -999,7 +1056,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
-        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths,
+                           features=features)
         if score:
             self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self._alloc_weights(dev, True)
@@ -1015,7 +1073,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     @torch.no_grad()
     def _eager(self):
         from .output import _AnswerLoss
-        logits = self.net(self.images, self.questions, self.lengths, train=False, check_ids=False, **self._net_arguments())
+        logits = self.net(self._net_images(), self.questions, self.lengths, train=False, check_ids=False, **self._net_arguments())
         self.cell = self.net.last_cell                      # (status(): the latest run's buffers)
         if self.weights is not None:                        # score=True: the weighted call, dlogits = NULL (no_grad), one kernel
             loss, pred = self.net.loss_and_pred(logits, self.answers, **self._loss_arguments())
@@ -1033,8 +1091,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     def _replays_match_eager(self, replays=3):
         g = torch.Generator().manual_seed(20240521)
         answers = 2 if self.weights is None else self.net.out.answers
-        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, answers, self.images.device)
-        self._load_inputs(images, q, lengths, False, *self._random_groups(g), answers=None if self.weights is None else ans)
+        (images, q, lengths, ans), ids = self._random_images(g, answers)
+        self._load_inputs(images, q, lengths, False, *self._random_groups(g), answers=None if self.weights is None else ans, **ids)
         self._draw_weights()
         written = lambda: [("logits", self.logits), ("pred", self.pred)]
         clear = None
@@ -1046,14 +1104,18 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         return self._compare_replays(replays, written, want, before=clear)
 
     def load(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
-             weights=None):
-        """image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
+             weights=None, image_ids=None):
+        """image_ids: a graph captured with features=store, and such a graph only: load(None, questions, lengths, image_ids=ids) --
+        the table rows of the batch's images ([B], or [G] with images=G) in the place of `images`; passing the wrong one is a
+        ValueError.  Their range is validated with the ids (check_ids).
+        image_index: the [B] integer tensor of a graph captured with images=G (required there, refused otherwise); its range is
         validated with the ids (check_ids).  kb_lengths [B] / image_lengths [G]: the integer sizes of a graph captured with
         kb_lengths=True / image_lengths=True (required there, refused otherwise); 1 <= size <= N is validated with the ids.
         answers [n] / weights [n] (float32, default ones): a graph captured with score=True, and such a graph only; it takes
         n <= B questions (the constructor's docstring)"""
         _lengths_argument(type(self).__name__, "answers", answers is not None, self.answers is not None, "score=True")
-        return self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
+        return self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights,
+                                 image_ids)
 
     def replay(self):
         if self.captured:
@@ -1064,8 +1126,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         return self.logits if self.weights is None else self.logits[:self.n]
 
     def __call__(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
-                 weights=None):
-        self.load(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
+                 weights=None, image_ids=None):
+        self.load(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights, image_ids)
         return self.replay()
 
 
@@ -1095,6 +1157,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     images=G / kb_lengths=True / image_lengths=True: CapturedTowerForward's (load() takes image_index / kb_lengths / image_lengths
     accordingly).  With images=G the stem runs once per image and the gather and its backward (macx_kb_gather[_l] / _bwd[_l]) are
     part of the graph; a stem that drops (stemDropout < 1) is refused at construction with the eager path's ValueError.
+    features=store: CapturedTowerForward's (load(None, questions, lengths, answers, image_ids=ids); the gather from the table is
+    part of the graph and takes no gradient; with weights=True dead slots take slot 0's id).
 
     verify=True replays three times against the eager step on random inputs -- loss, logits, pred, norm, the flat gradient, every
     parameter, m, v, ema -- each time from the same restored state, and falls back to eager launches when anything differs
@@ -1133,7 +1197,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     aux = None
 
     def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0, images=None,
-                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None, weights=False, totals=None):
+                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None, weights=False, totals=None, features=None):
         self._check_options(net, "CapturedTowerTrainStep", images, kb_lengths, image_lengths, train=True)
         att_loss = _att_loss_spec("CapturedTowerTrainStep", att_loss)
         self._check_totals("CapturedTowerTrainStep", weights, totals)
@@ -1152,7 +1216,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
                              "bucket.flat as it is")
         self.net, self.opt, self.bucket, self.seed = net, opt, bucket, int(seed)
         self.check_every = int(check_every)
-        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths,
+                           features=features)
         self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
         if weights:
             self._alloc_weights(dev, totals)
@@ -1201,7 +1266,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         """the step's launches on the current stream (opt.advance() is the caller's: it is not part of the graph)"""
         self._clear_grads()
         net, B = self.net, self.B
-        logits = net(self.images, self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
+        logits = net(self._net_images(), self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
                      **self._net_arguments())
         self.cell = net.last_cell
         ce, pred = net.loss_and_pred(logits, self.answers, **self._loss_arguments())
@@ -1241,10 +1306,9 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
 
     def _replays_match_eager(self, state, replays=3):
         g = torch.Generator().manual_seed(20240522)
-        images, q, lengths, ans = _random_tower_inputs(g, self.B, self.S, self.net.enc.vocab, self.images.shape, self.net.out.answers,
-                                                       self.images.device)
+        (images, q, lengths, ans), ids = self._random_images(g, self.net.out.answers)
         index, kbl, iml = self._random_groups(g)
-        self._load_inputs(images, q, lengths, False, index, kbl, iml)
+        self._load_inputs(images, q, lengths, False, index, kbl, iml, **ids)
         self.answers.copy_(ans)
         if self.att_loss is not None:
             live = kbl if iml is None else iml[index.long()]     # the per-question sizes the gather makes on the device
@@ -1266,8 +1330,9 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         return self._compare_replays(replays, written, want, before=from_state)
 
     def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None,
-             att_target=None, att_row_weights=None, att_step_weights=None, weights=None):
-        """image_index / kb_lengths / image_lengths: CapturedTowerForward.load's; att_target / att_row_weights / att_step_weights:
+             att_target=None, att_row_weights=None, att_step_weights=None, weights=None, image_ids=None):
+        """image_index / kb_lengths / image_lengths / image_ids: CapturedTowerForward.load's (image_ids: a class built with
+        features=store takes load(None, questions, lengths, answers, image_ids=ids)); att_target / att_row_weights / att_step_weights:
         CapturedTrainStep.load's (a class built with att_loss=).
         weights: a class built with weights=True, and such a class only: [n] float32 (default ones).  Such a class takes n <= B
         questions -- every per-question argument (lengths, answers, images or image_index, kb_lengths, att_target, att_row_weights)
@@ -1276,7 +1341,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         short = self.weights is not None and torch.is_tensor(questions) and questions.dim() == 2
         n = int(questions.shape[0]) if short else None
         self._check_att_loss(att_target, att_row_weights, att_step_weights, n)
-        n = self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights)
+        n = self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights, image_ids)
         self._copy_att_loss(att_target, att_row_weights, att_step_weights, n if self.weights is not None else None)
         return n
 

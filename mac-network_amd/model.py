@@ -15,6 +15,7 @@ from .encoder import QuestionEncoder
 from .options import UnsupportedOptions, freeze, fresh_seed, get
 from .output import OutputClassifier, answer_loss_and_pred
 from .params import MACCellParams
+from .features import check_store_images
 from .stem import Stem, check_image_index, check_image_lengths, kb_gather
 
 
@@ -45,7 +46,7 @@ class MACNetCore(torch.nn.Module):
 
     def forward(self, images, vecQuestions, questionCntxWords, questionLengths, train=False, seed=None, b0=0,
                 questionWords=None, mask_word=None, image_index=None, check_index=False, kb_lengths=None,
-                check_kb_lengths=False, image_lengths=None):
+                check_kb_lengths=False, image_lengths=None, image_ids=None):
         """Auxiliary losses: after the call `self.last_cell` is the cell of this pass.  Its attentions["kb" | "question" | "self" |
         "gate"][i], controls and memories carry the autograd edge (train / grad enabled), so a loss such as
         CE + lam * (net.last_cell.attentions["kb"][i] * target).sum() trains the stem, the encoder and the cell; infos is a constant.
@@ -65,11 +66,19 @@ class MACNetCore(torch.nn.Module):
         then holds the G distinct images, question b looks at images[image_index[b]], the stem runs once per image and its output
         is gathered into the cell's [B, N, d] knowledge base (macx_kb_gather; gradients flow back through macx_kb_gather_bwd).
         With train=True the stem must not drop (stemDropout = 1.0): the reference draws that mask per question.  An index outside
-        [0, G) gives that question a NaN knowledge base; check_index=True tests the range on the host first (synchronises)."""
+        [0, G) gives that question a NaN knowledge base; check_index=True tests the range on the host first (synchronises).
+        image_ids: None, or -- when `images` is a macx.FeatureStore (features resident in device memory) -- the table rows of this
+        batch's images: a [B] integer device tensor, or [G] together with image_index [B].  The stem runs on
+        images.gather(image_ids) (macx_features_gather; no gradient) and everything downstream is the call on that tensor.  A row
+        outside [0, rows) gives that image NaN features; check_index=True tests the range on the host first.  image_ids with a
+        tensor `images` is a TypeError, a store whose (H, W, C) is not the stem's a ValueError."""
         cfg = self.config
-        image_index = check_image_index(image_index, vecQuestions.shape[0], train, self.stem, images, host_check=check_index)
+        store_ids = check_store_images(images, image_ids, self.stem, vecQuestions.shape[0] if image_index is None else None,
+                                       host_check=check_index)
+        per_image = images if store_ids is None else store_ids        # (what the image count is read from)
+        image_index = check_image_index(image_index, vecQuestions.shape[0], train, self.stem, per_image, host_check=check_index)
         if image_lengths is not None:
-            check_image_lengths(image_lengths, image_index, kb_lengths, images, self.stem.out_hw[0] * self.stem.out_hw[1],
+            check_image_lengths(image_lengths, image_index, kb_lengths, per_image, self.stem.out_hw[0] * self.stem.out_hw[1],
                                 host_check=check_kb_lengths)
         if mask_word is not None and not isinstance(self.cell, MACCellParams):
             raise UnsupportedOptions("a run's mask word over the whole tower needs the fused cell (MACCellParams); this option set "
@@ -83,6 +92,8 @@ class MACNetCore(torch.nn.Module):
             questionWords = questionCntxWords
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}               # (None: the modules' calls of before)
+        if store_ids is not None:
+            images = images.gather(store_ids)                                        # macx_features_gather: [G, H*W, C] fp32
         kb = self.stem(images, train=train, seed=seed, b0=b0, **word)               # model.py:791
         if image_lengths is not None:
             kb, kb_lengths = kb_gather(kb, image_index.to(kb.device), image_lengths.to(kb.device))
@@ -124,13 +135,18 @@ class MACNet(MACNetCore):
         return self.enc.tensors() + super().tensors()
 
     def forward(self, images, questions, questionLengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None,
-                image_index=None, check_index=False, kb_lengths=None, image_lengths=None):
-        """image_lengths: MACNetCore.forward's (live knowledge-base cells per IMAGE of a batch with image_index).
+                image_index=None, check_index=False, kb_lengths=None, image_lengths=None, image_ids=None):
+        """image_ids: MACNetCore.forward's (`images` is a macx.FeatureStore and the batch names table rows); check_ids=True or
+        check_index=True also tests 0 <= image_ids < rows on the host.
+        image_lengths: MACNetCore.forward's (live knowledge-base cells per IMAGE of a batch with image_index).
         image_index / check_index: MACNetCore.forward's (questions that share images: `images` is [G, ...], image_index [B]).
         kb_lengths: MACNetCore.forward's (live knowledge-base cells per question); check_ids=True also tests its range on the host."""
-        check_image_index(image_index, questions.shape[0], train, self.stem, images, host_check=check_index)
+        store_ids = check_store_images(images, image_ids, self.stem, questions.shape[0] if image_index is None else None,
+                                       host_check=check_ids or check_index)
+        per_image = images if store_ids is None else store_ids
+        check_image_index(image_index, questions.shape[0], train, self.stem, per_image, host_check=check_index)
         if image_lengths is not None:
-            check_image_lengths(image_lengths, image_index, kb_lengths, images, self.stem.out_hw[0] * self.stem.out_hw[1],
+            check_image_lengths(image_lengths, image_index, kb_lengths, per_image, self.stem.out_hw[0] * self.stem.out_hw[1],
                                 host_check=check_ids)
         seed = fresh_seed(seed, train)
         word = {} if mask_word is None else {"mask_word": mask_word}
@@ -144,4 +160,5 @@ class MACNet(MACNetCore):
                                  "the control state ctrlDim = %d (mac_cell.py:154)" % (raw.shape[-1], get(self.config, "ctrlDim")))
         return super().forward(images, vecQ, words, questionLengths, train=train, seed=seed, b0=b0, questionWords=raw,
                                image_index=image_index, kb_lengths=kb_lengths, check_kb_lengths=check_ids and image_lengths is None, **word,
-                               **({} if image_lengths is None else {"image_lengths": image_lengths}))
+                               **({} if image_lengths is None else {"image_lengths": image_lengths}),
+                               **({} if image_ids is None else {"image_ids": image_ids}))
