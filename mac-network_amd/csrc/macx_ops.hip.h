@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void answer_loss_kernel(const float* logits, c
   const int lane = threadIdx.x & 63;
   const float* p = logits + (size_t)b * A;
   float m = -INFINITY;
-  int am = 0x7FFFFFFF;
+  int am = lane;                                        // a row of -inf moves no lane: lane 0's column 0 wins, as tf.argmax
   for (int c = lane; c < A; c += 64) {
     const float v = p[c];
     if (v > m) { m = v; am = c; }                       // strict: keeps the first maximum of this lane's columns
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(AW_WAVES * 64) void answer_loss_weighted_kernel(con
     }
     const float* p = logits + (size_t)b * A;
     float m = -INFINITY;
-    int am = 0x7FFFFFFF;
+    int am = lane;                                      // a row of -inf moves no lane: lane 0's column 0 wins, as tf.argmax
     for (int c = lane; c < A; c += 64) {
       const float v = p[c];
       if (v > m) { m = v; am = c; }                       // strict: keeps the first maximum of this lane's columns
