@@ -2313,7 +2313,7 @@ int macx_kb_project(const macx_shapes* s, const macx_dropout* dp, int step, cons
 int macx_control_attend(const macx_shapes* s, const float* cc, const float* words, const int32_t* lengths, const float* w,
                         const float* b, float* att, float* control, void* stream) {
   if (!s || !cc || !words || !lengths || !w || !b || !att || !control) return MACX_EINVAL;
-  if (s->S > C_MAXS || s->d % 4 != 0) return MACX_EINVAL;
+  if (s->B < 1 || s->S < 1 || s->S > C_MAXS || s->d < 4 || s->d % 4 != 0) return MACX_EINVAL;
   CtrlP c;
   c.B = s->B; c.S = s->S; c.d = s->d;
   c.cc = cc; c.z_cc = 0; c.words = words; c.lengths = lengths; c.w = w; c.bias = b;
@@ -2332,7 +2332,7 @@ int macx_control_attend_bwd(const macx_shapes* s, const float* d_control, const 
                             const float* w, float* ws, size_t ws_floats, float* d_cc, float* d_words, float* d_w, float* d_b,
                             void* stream) {
   if (!s || !d_control || !cc || !att || !words || !w || !ws || !d_cc || !d_words || !d_w || !d_b) return MACX_EINVAL;
-  if (s->S > C_MAXS || s->d % 64 != 0) return MACX_EINVAL;
+  if (s->B < 1 || s->S < 1 || s->S > C_MAXS || s->d < 64 || s->d % 64 != 0) return MACX_EINVAL;
   if (ws_floats < macx_control_attend_bwd_ws_floats(s)) return MACX_ESMALL;
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, S = s->S, d = s->d;
