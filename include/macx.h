@@ -630,6 +630,35 @@ int macx_h2_gemm_planes(const float* hA, int B, int N, int K, const float* Wh, i
                         void* stream);
 int macx_h2_gemm(const float* A, int B, int N, int K, const float* W, int n_out, const float* bias, int act, float* out,
                  float* ws, size_t ws_floats, void* stream);
+/* The backward pass's contractions over the ROWS of H2 tensors (mac-network_amd/csrc/macx_wgrad_h2.hip.h), each on its own: thin
+ * wrappers over the launchers the fused cell calls, so that the kernels are testable against fp64 in isolation
+ * (tests/test_gpu_h2_contractions.py).  Operands are H2 tensors made with macx_h2_from_f32; a sequence of tensors lies `*_stride`
+ * FLOATS apart (a multiple of 4, >= macx_h2_floats of one tensor).  `o`: NULL = defaults; its tune table selects the kernel forms
+ * (MACX_TUNE_WGRAD_PIPE, MACX_TUNE_SB_CONT, MACX_TUNE_PHASE_MASK); the calls run in the H2 family whatever gemm_family says.
+ * Dimensions are multiples of 128 up to 1024, at most 2^24 rows per call.  A refused call (MACX_EINVAL; MACX_ESMALL: ws_floats
+ * below the sizing call's answer) launches nothing; the sizing calls return 0 for a shape the entry point refuses.
+ *   macx_h2_wgrad   out[Kd][Jd] = sum_m A[m][k] G[m][j] over M = nt * R rows: reduction row m is row m % R of tensor m / R of A
+ *                   (nt tensors [R][Kd]) and of G (nt tensors [R][Jd]); a_shared = 1: A is ONE tensor, row m % R of it for every
+ *                   tensor of G.  nsplit >= 1 reduction splits of the library's own rows per split (a multiple of 32; a split
+ *                   that starts at or behind M is empty and adds exact zeros).  hA2 / hG2 / out2: NULL all three, or a second
+ *                   contraction of the same shape; at Kd % 256 == Jd % 256 == 0 and MACX_TUNE_WGRAD_PIPE >= 2 the two run as one
+ *                   launch, as in the cell.  Launches: row-exponent minima, factor tables, contraction(s), slab reduction.
+ *   macx_h2_sb      per question b of each of nsteps steps S_b = X_b^T dI1_b (X, dI1: nsteps tensors [B*N][d]) and
+ *                     dW1b[k][j] = sum S_b[k][j],   dW1a[k][j] = sum y[step][b][k] S_b[k][j]       (sums over steps and questions)
+ *                   y [nsteps][B][d] fp32.  wide = 0: sb_h2_kernel (128 x 128 tiles); wide = 1: sb_h2w_kernel (128 x 256 tiles,
+ *                   summation by parts; d % 256 == 0, N <= 512).  qpg: questions per workgroup, 0 = the route plan's own choice;
+ *                   narrow: qpg <= 32 and qpg * roundup(N, 32) <= 4096, wide: qpg <= 4 and qpg * roundup(N, 32) <= 512.
+ *                   dy_part (NULL, or wide = 0 and nsteps = 1 only; needs W1a [d][d] row-major (k, j)): the kernel's partials of
+ *                   dy[b][k] = sum_j W1a[k][j] S_b[k][j] as it leaves them, [4 * d / 128][B][d]: partial 4 * tj + c holds the
+ *                   sum over columns j in [128 tj + 32 c, 128 tj + 32 c + 32); dy is the sum over the 4 * d / 128 partials. */
+size_t macx_h2_wgrad_ws_floats(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit, int pair);
+int macx_h2_wgrad(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit, const float* hA, size_t a_stride, int a_shared,
+                  const float* hG, size_t g_stride, float* out, const float* hA2, size_t a2_stride, int a2_shared, const float* hG2,
+                  size_t g2_stride, float* out2, float* ws, size_t ws_floats, void* stream);
+size_t macx_h2_sb_ws_floats(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int wide);
+int macx_h2_sb(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int wide, const float* hX, size_t x_stride,
+               const float* hdI1, size_t g_stride, const float* y, const float* W1a, float* dW1a, float* dW1b, float* dy_part,
+               float* ws, size_t ws_floats, void* stream);
 /* bench / profiling hook (mode MACX_GEMM_H2, d <= 512, N >= 16): the kernel that runs the read unit's three knowledge-base
  * products of one step -- dropout(KB) -> X -> H1 -> I2 -> attention logits (mac_cell.py:230-266, ops.py:668-725;
  * mac-network_amd/csrc/macx_chain_h2.hip.h) -- re-launched `reps` times on `stream` between two HIP events; *ms_out = average

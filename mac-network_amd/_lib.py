@@ -267,6 +267,12 @@ TABLE.update(
     macx_h2_pack_weight=(_I, (_V, _I, _I, _I, _V, _V)),
     macx_h2_gemm_planes=(_I, (_V, _I, _I, _I, _V, _I, _V, _I, _V, _V)),
     macx_h2_gemm=(_I, (_V, _I, _I, _I, _V, _I, _V, _I, _V, _V, _Z, _V)),
+    # (opts; nt, R, Kd, Jd, nsplit; [A, stride, shared, G, stride, out] x 2; ws, ws_floats, stream)
+    macx_h2_wgrad_ws_floats=(_Z, (_P(MacxOpts),) + (_I,) * 6),
+    macx_h2_wgrad=(_I, (_P(MacxOpts),) + (_I,) * 5 + (_V, _Z, _I, _V, _Z, _V) * 2 + (_V, _Z, _V)),
+    # (opts; B, N, d, nsteps, qpg, wide; X, stride, dI1, stride; y, W1a, dW1a, dW1b, dy_part; ws, ws_floats, stream)
+    macx_h2_sb_ws_floats=(_Z, (_P(MacxOpts),) + (_I,) * 6),
+    macx_h2_sb=(_I, (_P(MacxOpts),) + (_I,) * 6 + (_V, _Z, _V, _Z) + (_V,) * 5 + (_V, _Z, _V)),
     macx_read_chain_time=(_I, _RUN[:7] + (_I, _I, _P(_F), _V)),
     macx_cell_forward_chain_time=(_I, _RUN + (_P(_F), _V)),
     macx_saved_activation=(_I, _OS + (_I, _I, _V, _Z, _V, _V)),

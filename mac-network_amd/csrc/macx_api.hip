@@ -805,6 +805,62 @@ struct SmallWgradBatch {
   }
 };
 
+// ---- the H2 row contractions as entry points of their own (macx_h2_wgrad / macx_h2_sb): what the exports refuse and how their
+// workspaces are laid out.  Every limit here is one a kernel or a launcher of macx_wgrad_h2.hip.h rests on.
+constexpr int H2X_MAX_DIM = 1024;        // 8 column blocks: what h2_emin_list_kernel's partials and the factor kernel's sE[2][8] hold
+constexpr size_t H2X_MAX_ROWS = (size_t)1 << 24;   // rows of one call: row, slot and table indices stay inside 32 bits
+constexpr int H2X_MAX_SPLITS = 4096, H2X_MAX_STEPS = 1024;
+constexpr int H2X_ES = EMIN_NB * 8;      // ints of one family's partial minima
+// the H2 family and the caller's tuning table for the duration of one of these calls
+struct H2Scope {
+  ModeScope ms;
+  explicit H2Scope(const macx_opts* o) : ms(o) { gemm_call_override() = 2; }     // (~ModeScope restores what it found)
+};
+inline bool h2x_dim_ok(int d) { return d >= 128 && d % 128 == 0 && d <= H2X_MAX_DIM; }
+// tensors `stride` floats apart: 16-byte steps, and no tensor inside the next one
+inline bool h2x_stride_ok(size_t stride, int nt, size_t rows, int cols) {
+  return nt <= 1 || (stride % 4 == 0 && stride >= al4(h2_floats(rows, (size_t)cols)));
+}
+struct H2WgradWs { size_t ecom, ftab[2], slab[2], total; int rows_per_split; };
+// call under an H2Scope (rows_per_split asks the family).  false: a shape the contraction is not written for
+inline bool h2_wgrad_plan(int nt, int R, int Kd, int Jd, int nsplit, int pair, H2WgradWs* w) {
+  if (nt < 1 || R < 1 || nsplit < 1 || nsplit > H2X_MAX_SPLITS || !h2x_dim_ok(Kd) || !h2x_dim_ok(Jd)) return false;
+  if ((size_t)nt * R > H2X_MAX_ROWS) return false;
+  const size_t M = (size_t)nt * R;
+  w->rows_per_split = rows_per_split((int)M, nsplit);
+  if (w->rows_per_split % 32 || (size_t)nsplit * w->rows_per_split > (size_t)INT32_MAX) return false;
+  const size_t ft = al4(((size_t)(Kd >> 7) * (Jd >> 7) * wgrad_h2_mpad(M) * sizeof(uint16_t) + 3) / 4);
+  const size_t sl = (size_t)nsplit * Kd * Jd;
+  size_t off = 0;
+  w->ecom = off; off += 4 * (size_t)H2X_ES;                       // [A | G | A2 | G2][EMIN_NB][8]
+  for (int i = 0; i < 2; ++i) { w->ftab[i] = off; off += (i == 0 || pair) ? ft : 0; }
+  for (int i = 0; i < 2; ++i) { w->slab[i] = off; off += (i == 0 || pair) ? sl : 0; }
+  w->total = off;
+  return true;
+}
+struct H2SbWs { size_t slab_a, slab_b, total; int qpg, ngroup; };
+inline bool h2_sb_plan(int B, int N, int d, int nsteps, int qpg, int wide, int with_dy, H2SbWs* w) {
+  if (B < 1 || N < 1 || !h2x_dim_ok(d) || nsteps < 1 || nsteps > H2X_MAX_STEPS || qpg < 0 || (wide != 0 && wide != 1)) return false;
+  if ((size_t)B * N > H2X_MAX_ROWS || (size_t)B * N * nsteps > H2X_MAX_ROWS) return false;
+  if (with_dy && (wide || nsteps > 1)) return false;              // dy is per question and per step: the narrow kernel, one step
+  const int rows_q = ((N + 31) / 32) * 32;
+  if (wide) {
+    if (!sb_h2_wide_ok(B, N, d)) return false;
+    if (qpg == 0) qpg = sb_h2_wide_qpg(B, N, d);
+    if (qpg > SBW_MAXQ || (size_t)qpg * rows_q > SBW_MAXROWS / 2) return false;
+  } else {
+    if (rows_q > SBH_MAXROWS) return false;
+    if (qpg == 0) qpg = sb_qpg(true, B, N);
+    if (qpg > SBH_MAXQ || (size_t)qpg * rows_q > SBH_MAXROWS) return false;
+  }
+  if (qpg < 1) return false;
+  w->qpg = qpg;
+  w->ngroup = (B + qpg - 1) / qpg;
+  const size_t dd = (size_t)d * d;
+  w->slab_a = 0; w->slab_b = (size_t)w->ngroup * dd; w->total = 2 * (size_t)w->ngroup * dd;
+  return true;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -3382,6 +3438,110 @@ int macx_h2_gemm(const float* A, int B, int N, int K, const float* Wm, int n_out
   CKI(macx_h2_pack_weight(Wm, K, n_out, 0, wp, stream));
   CKI(macx_h2_gemm_planes(hA, B, N, K, wp, n_out, bias, act, hO, stream));
   return macx_h2_to_f32(hO, B * N, n_out, out, stream);
+}
+
+size_t macx_h2_wgrad_ws_floats(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit, int pair) {
+  if (o && o->abi_version != MACX_ABI_VERSION) return 0;
+  H2Scope sc(o);
+  H2WgradWs w;
+  return h2_wgrad_plan(nt, R, Kd, Jd, nsplit, pair != 0, &w) ? w.total : 0;
+}
+
+// CellBwd::read_weight_contractions' H2 branch on the caller's operands: minima, factor tables, contraction(s), slab reduction
+int macx_h2_wgrad(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit, const float* hA, size_t a_stride, int a_shared,
+                  const float* hG, size_t g_stride, float* out, const float* hA2, size_t a2_stride, int a2_shared, const float* hG2,
+                  size_t g2_stride, float* out2, float* ws, size_t ws_floats, void* stream) {
+  if (o && o->abi_version != MACX_ABI_VERSION) return MACX_EINVAL;
+  H2Scope sc(o);
+  const bool pair = hA2 || hG2 || out2;
+  H2WgradWs w;
+  if (!h2_wgrad_plan(nt, R, Kd, Jd, nsplit, pair, &w)) return MACX_EINVAL;
+  if (!hA || !hG || !out || !ws || (pair && (!hA2 || !hG2 || !out2 || out2 == out))) return MACX_EINVAL;
+  if (misaligned(hA) || misaligned(hG) || misaligned(out) || misaligned(ws) || misaligned(hA2) || misaligned(hG2) || misaligned(out2))
+    return MACX_EINVAL;
+  if ((a_shared != 0 && a_shared != 1) || (a2_shared != 0 && a2_shared != 1)) return MACX_EINVAL;
+  if (!h2x_stride_ok(a_stride, a_shared ? 1 : nt, R, Kd) || !h2x_stride_ok(g_stride, nt, R, Jd)) return MACX_EINVAL;
+  if (pair && (!h2x_stride_ok(a2_stride, a2_shared ? 1 : nt, R, Kd) || !h2x_stride_ok(g2_stride, nt, R, Jd))) return MACX_EINVAL;
+  if (ws_floats < w.total) return MACX_ESMALL;
+  const hipStream_t st = (hipStream_t)stream;
+  int* ecom = reinterpret_cast<int*>(ws + w.ecom);
+  const int np = pair ? 2 : 1;
+  {
+    // the A families have Kd columns and the G families Jd: one list each (family i of a list -> ecom + (2 i + which) ES)
+    EminList el;
+    memset(&el, 0, sizeof(el));
+    el.R = R; el.C = Kd; el.part = ecom;
+    el.base[0] = reinterpret_cast<const char*>(hA); el.stride[0] = a_stride * sizeof(float); el.nt[0] = a_shared ? 1 : nt;
+    el.base[1] = reinterpret_cast<const char*>(hA2); el.stride[1] = a2_stride * sizeof(float); el.nt[1] = a2_shared ? 1 : nt;
+    CK(emin_list(el, np, st));
+    el.C = Jd; el.part = ecom + 2 * H2X_ES;
+    el.base[0] = reinterpret_cast<const char*>(hG); el.stride[0] = g_stride * sizeof(float); el.nt[0] = nt;
+    el.base[1] = reinterpret_cast<const char*>(hG2); el.stride[1] = g2_stride * sizeof(float); el.nt[1] = nt;
+    CK(emin_list(el, np, st));
+  }
+  TnH2P t;
+  memset(&t, 0, sizeof(t));
+  t.M = nt * R; t.Kd = Kd; t.Jd = Jd; t.nsplit = nsplit; t.rows_per_split = w.rows_per_split;
+  t.R = R;
+  t.A = reinterpret_cast<const char*>(hA); t.a_stride = a_stride * sizeof(float); t.a_mod = a_shared ? R : 0;
+  t.G = reinterpret_cast<const char*>(hG); t.g_stride = g_stride * sizeof(float);
+  t.ecomA = ecom; t.ecomG = ecom + 2 * H2X_ES; t.ecom_nb = EMIN_NB;
+  t.ftab = reinterpret_cast<uint16_t*>(ws + w.ftab[0]);
+  t.dbg = kb_gemm_dbg();
+  t.part = ws + w.slab[0];
+  if (pair) {
+    TnH2P u = t;
+    u.A = reinterpret_cast<const char*>(hA2); u.a_stride = a2_stride * sizeof(float); u.a_mod = a2_shared ? R : 0;
+    u.G = reinterpret_cast<const char*>(hG2); u.g_stride = g2_stride * sizeof(float);
+    u.ecomA = ecom + H2X_ES; u.ecomG = ecom + 3 * H2X_ES;
+    u.ftab = reinterpret_cast<uint16_t*>(ws + w.ftab[1]);
+    u.part = ws + w.slab[1];
+    CK(wgrad_h2_launch_pair(t, u, st));
+  } else {
+    CK(wgrad_h2_launch(t, st));
+  }
+  CK(slab_reduce_launch(ws + w.slab[0], nsplit, (size_t)Kd * Jd, out, 0, st));
+  if (pair) CK(slab_reduce_launch(ws + w.slab[1], nsplit, (size_t)Kd * Jd, out2, 0, st));
+  return MACX_OK;
+}
+
+size_t macx_h2_sb_ws_floats(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int wide) {
+  if (o && o->abi_version != MACX_ABI_VERSION) return 0;
+  H2Scope sc(o);
+  H2SbWs w;
+  return h2_sb_plan(B, N, d, nsteps, qpg, wide, 0, &w) ? w.total : 0;
+}
+
+// the S_b launch of CellBwd (per step with dy, or deferred over all steps) on the caller's operands, and its slab reduction
+int macx_h2_sb(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int wide, const float* hX, size_t x_stride,
+               const float* hdI1, size_t g_stride, const float* y, const float* W1a, float* dW1a, float* dW1b, float* dy_part,
+               float* ws, size_t ws_floats, void* stream) {
+  if (o && o->abi_version != MACX_ABI_VERSION) return MACX_EINVAL;
+  H2Scope sc(o);
+  H2SbWs w;
+  if (!h2_sb_plan(B, N, d, nsteps, qpg, wide, dy_part != nullptr, &w)) return MACX_EINVAL;
+  if (!hX || !hdI1 || !y || !dW1a || !dW1b || !ws || dW1a == dW1b || (dy_part && !W1a)) return MACX_EINVAL;
+  if (misaligned(hX) || misaligned(hdI1) || misaligned(y) || misaligned(W1a) || misaligned(dW1a) || misaligned(dW1b) ||
+      misaligned(dy_part) || misaligned(ws))
+    return MACX_EINVAL;
+  const size_t rows = (size_t)B * N;
+  if (!h2x_stride_ok(x_stride, nsteps, rows, d) || !h2x_stride_ok(g_stride, nsteps, rows, d)) return MACX_EINVAL;
+  if (ws_floats < w.total) return MACX_ESMALL;
+  const hipStream_t st = (hipStream_t)stream;
+  SbH2P q;
+  memset(&q, 0, sizeof(q));
+  q.B = B; q.N = N; q.d = d; q.qpg = w.qpg;
+  q.X = h2_view(hX, B * N, d); q.dI1 = h2_view(hdI1, B * N, d);
+  q.y = y; q.W1a = W1a;
+  q.dW1a_part = ws + w.slab_a; q.dW1b_part = ws + w.slab_b; q.dy_part = dy_part;
+  q.nsteps = nsteps;
+  q.x_step = x_stride * sizeof(float); q.g_step = g_stride * sizeof(float); q.y_step = (size_t)B * d;
+  q.dbg = kb_gemm_dbg();
+  CK(wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
+  const size_t dd = (size_t)d * d;
+  CK(slab_reduce_launch(ws + w.slab_a, w.ngroup, dd, dW1a, 0, st));
+  CK(slab_reduce_launch(ws + w.slab_b, w.ngroup, dd, dW1b, 0, st));
+  return MACX_OK;
 }
 
 /* bench / profiling hook: the read unit's forward chain kernel of `step`, re-launched `reps` times on `stream` between two HIP

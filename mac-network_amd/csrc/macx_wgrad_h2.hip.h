@@ -1006,8 +1006,15 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
   //   dW1a += (y_k - y_next) * T_k * 2^-e_k ;  T_k (unit 2^-e_k) -> unit 2^-e_next
   // (y of the question before lives in LDS, two buffers taken in turn: a question is at least one stage -- one barrier -- long,
   // so the buffer a fold reads was written a barrier ago and is overwritten two questions later)
+  // A question whose unit 2^-(EX + EG) underflows fp32 -- every value of both operands tiny: in practice an all-zero question, whose
+  // rows carry H2_E_MAX -- adds nothing, exactly as sb_h2_kernel's fold (S_b times a unit of 0) makes it add nothing.  It must not
+  // become T's unit: moving T there is a factor of up to 2^126, which took every sum behind such a question to infinity.  Its
+  // products are skipped (q_dead) and T stays in the unit of the question before.
   int ex_prev = 0, eg_prev = 0, ybuf = 0;
-  bool pending = false;
+  bool pending = false, q_dead = false;
+  auto sbw_dead = [](int ex, int eg) __attribute__((always_inline)) {        // (workgroup-uniform: a scalar branch around the products)
+    return __builtin_amdgcn_readfirstlane((int)(h2_unscale(ex, eg) == 0.f)) != 0;
+  };
   auto keep_y = [&](const float* ynext) __attribute__((always_inline)) {
     if (tid < T_TILE) yold[(ybuf ^ 1) * T_TILE + tid] = ynext ? ynext[tid] : 0.f;
     ybuf ^= 1;
@@ -1081,8 +1088,10 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
       if (!(p.dbg & 2048)) issue_g(g + 2);                  // ring slot (g + 2) % 3 was last read in iteration g - 1
       if (qch == 0) {
         const float* yn = ytab_c + qi * T_TILE;
-        const int exn = min(qmn_c[qi], 126), egn = min(qmn_c[SBW_MAXQ + qi], 126);
+        int exn = min(qmn_c[qi], 126), egn = min(qmn_c[SBW_MAXQ + qi], 126);
+        q_dead = sbw_dead(exn, egn);
         if (pending) {
+          if (q_dead) { exn = ex_prev; egn = eg_prev; }     // T stays in the unit it is in
           if (!(p.dbg & 512)) fold(yn, exn, egn);
         } else {
           keep_y(yn);
@@ -1090,7 +1099,7 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
           pending = true;
         }
       }
-      if (!(p.dbg & 1024)) compute(g % SBW_RING, qi, qch);
+      if (!(p.dbg & 1024) && !q_dead) compute(g % SBW_RING, qi, qch);
       if (p.dbg & 2048) wait_vmcnt<0>(); else wait_vmcnt<6>();      // stage g + 1 has landed (and this iteration's table loads); g + 2 stays in flight
       if (more) {
         if (sg == 0) {
@@ -1145,8 +1154,10 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
         if (qch == 0) {
           // a question starts: the fold of the one before it (none in front of the very first), or just its y and unit
           const float* yn = ytab + qi * T_TILE;
-          const int exn = min(qmn[qi], 126), egn = min(qmn[SBW_MAXQ + qi], 126);
+          int exn = min(qmn[qi], 126), egn = min(qmn[SBW_MAXQ + qi], 126);
+          q_dead = sbw_dead(exn, egn);
           if (pending) {
+            if (q_dead) { exn = ex_prev; egn = eg_prev; }   // T stays in the unit it is in
             if (!(p.dbg & 512)) fold(yn, exn, egn);
           } else {
             keep_y(yn);
@@ -1154,7 +1165,7 @@ __global__ __launch_bounds__(512) void sb_h2w_kernel(SbH2P p) {
             pending = true;
           }
         }
-        if (!(p.dbg & 1024)) compute(s % SBW_RING, qi, qch);
+        if (!(p.dbg & 1024) && !q_dead) compute(s % SBW_RING, qi, qch);
         wait_vmcnt<6>();                                    // stage s + 1 has landed; stage s + 2 stays in flight
         if (++qch == nchunk) { qch = 0; ++qi; }
         __syncthreads();

@@ -48,8 +48,9 @@ def test_t0_zero_row_in_a_contraction(macx, dev, M, zero_in):
     What it can and cannot show: macx_wgrad takes fp32 operands, and in family 2 it runs the split-bf16 kernel (wgrad_any), which
     has no per-row exponents -- so this passes with either zero-block exponent (before the change to h2_exponent, on an MI355X:
     family 2 err / S 1.57e-07 / 1.71e-07 / 7.3e-08 / 5.8e-08 against family 0's 9.0e-08 / 1.07e-07 / 5.0e-08 / 5.7e-08).  The
-    contractions that do bring rows to a common exponent (wgrad_h2_kernel, sb_h2_kernel, sb_h2w_kernel) have no entry point of
-    their own; T3 and T5 below run them through the cell, and those are the tests that fail with exponent 0 for a zero block
+    contractions that do bring rows to a common exponent (wgrad_h2_kernel, sb_h2_kernel, sb_h2w_kernel) run on their own, zero
+    rows included, in test_gpu_h2_contractions.py (macx_h2_wgrad / macx_h2_sb, every element against fp64 within a derived
+    bound); T3 and T5 below run them through the cell, and those are the tests that fail with exponent 0 for a zero block
     (dWx wrong by 1.0 of its largest entry, dW2 by 0.15 .. 0.62, dW1 by 0.03 .. 0.22; the split and native families pass)."""
     L = macx._lib.lib()
     Kd, Jd = 128, 256
