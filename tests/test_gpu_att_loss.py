@@ -24,6 +24,7 @@ import torch.multiprocessing as mp
 
 import att_loss_ref as ar
 import state_grads_ref as sr
+from abi_kit import bits, bits_equal
 from helpers import make_case
 from kb_lengths_ref import masked_kb_attention
 from oracle import mac_oracle as mo
@@ -34,14 +35,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KIND = {"ce": 0, "entropy": 1}
 EPS, SCALE = 1e-8, 0.37
 POISON = 7.0
-
-
-def bits(t):
-    return t.detach().contiguous().view(torch.int32).cpu()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def call(macx, dev, att, target, lengths, sw, rw, kind, eps=EPS, scale=SCALE, want_d=True, target_steps=None, null_target=False):
@@ -107,18 +100,18 @@ def test_kernel_exactness(macx, dev, p, B, n, kind):
     # NULL weights == weights of ones
     rc, rows, d = call(macx, dev, att, t, lengths, None, None, kind)
     rc1, rows1, d1 = call(macx, dev, att, t, lengths, torch.ones(p), torch.ones(B), kind)
-    assert rc == rc1 == 0 and same_bits(rows, rows1) and same_bits(d, d1)
+    assert rc == rc1 == 0 and bits_equal(rows, rows1) and bits_equal(d, d1)
     # two calls give the same bits; d_att = NULL gives the same rows
     rc, rows, d = call(macx, dev, att, t, lengths, sw, rw, kind)
     rc1, rows1, d1 = call(macx, dev, att, t, lengths, sw, rw, kind)
     rc2, rows2, _ = call(macx, dev, att, t, lengths, sw, rw, kind, want_d=False)
-    assert rc == rc1 == rc2 == 0 and same_bits(rows, rows1) and same_bits(d, d1) and same_bits(rows, rows2)
+    assert rc == rc1 == rc2 == 0 and bits_equal(rows, rows1) and bits_equal(d, d1) and bits_equal(rows, rows2)
     if kind == "ce":                                          # one target for every step == the same target repeated per step
         where_live = ar.live_mask(lengths, B, n)
         rep = target[0].unsqueeze(0).expand(p, B, n).clone()
         assert bool(torch.isnan(rep[:, ~where_live]).all())
         rc3, rows3, d3 = call(macx, dev, att, rep, lengths, sw, rw, kind)
-        assert rc3 == 0 and same_bits(rows, rows3) and same_bits(d, d3)
+        assert rc3 == 0 and bits_equal(rows, rows3) and bits_equal(d, d3)
     # a row weight of 0: an exactly zero row and +0.0f gradient row, even where att holds 0 under a positive target (and NaN elsewhere)
     rw0 = rw.clone()
     rw0[1] = 0.0
@@ -133,7 +126,7 @@ def test_kernel_exactness(macx, dev, p, B, n, kind):
     assert rc4 == 0 and bool((bits(rows4)[:, 1] == 0).all()) and bool((bits(d4)[:, 1] == 0).all())
     assert bool(torch.isfinite(rows4).all()) and bool(torch.isfinite(d4).all())
     others = [b for b in range(B) if b != 1]
-    assert same_bits(rows4[:, others], rows[:, others]) and same_bits(d4[:, others], d[:, others])
+    assert bits_equal(rows4[:, others], rows[:, others]) and bits_equal(d4[:, others], d[:, others])
 
 
 # ================================================= 3 ===============================================================================
@@ -219,7 +212,7 @@ def test_state_tensor_gradient_is_the_per_step_gradient(macx, dev, name):
         cell.run()
         stacked = cell.state_tensor("att_kb")
         assert stacked.shape == (p, B, N) and stacked.requires_grad
-        assert all(same_bits(stacked[i], cell.attentions["kb"][i]) for i in range(p))
+        assert all(bits_equal(stacked[i], cell.attentions["kb"][i]) for i in range(p))
         assert cell.state_tensor("memories").shape == (p + 1, B, d) and cell.state_tensor("att_question").shape == (p, B, S)
         if route == "stacked":
             loss = (stacked * G).sum()
@@ -229,7 +222,7 @@ def test_state_tensor_gradient_is_the_per_step_gradient(macx, dev, name):
         torch.cuda.synchronize()
         assert not cell.state_tensor("att_kb").requires_grad                       # the pass is over: a plain view again
         results.append([t.grad for t in inputs] + [t.grad for t in params.tensors()])
-    assert all(same_bits(a, b) for a, b in zip(*results))
+    assert all(bits_equal(a, b) for a, b in zip(*results))
     assert float(results[0][2].abs().max()) > 0
     with pytest.raises(KeyError):
         cell.state_tensor("infos")
@@ -273,7 +266,7 @@ def _replays_equal_eager(step, extra=()):
         ref_mem, ref = step.eager_reference()
         want = [ref_mem] + ref + [t.grad.clone() for t in extra] + ([] if step.aux_rows is None else [step.aux_rows.clone()])
         torch.cuda.synchronize()
-        assert len(got) == len(want) and all(same_bits(a, b) for a, b in zip(got, want))
+        assert len(got) == len(want) and all(bits_equal(a, b) for a, b in zip(got, want))
     return got
 
 
@@ -303,7 +296,7 @@ def test_captured_train_step_with_att_loss(macx, dev, on, kind, kb_lengths):
         seen.append(got)
     # the gradients follow the target and the weights (a loss on the question map does not reach the knowledge base: REACHED)
     reached = 4 if on == "kb" else 3
-    assert not any(same_bits(a, b) for a, b in zip(seen[0][1:reached], seen[1][1:reached]))
+    assert not any(bits_equal(a, b) for a, b in zip(seen[0][1:reached], seen[1][1:reached]))
     step.check()
 
 
@@ -321,9 +314,9 @@ def test_captured_train_step_att_loss_changes_the_gradients(macx, dev):
         step.load(*x, **({} if weight is None else dict(att_target=target, att_row_weights=rw, att_step_weights=sw)))
         mem = step.replay().clone()
         grads[weight] = [mem] + [t.grad.clone() for t in step._leaves()]
-    assert all(same_bits(a, b) for a, b in zip(grads[None], grads[0.0]))
-    assert same_bits(grads[None][0], grads[0.5][0])                                   # the forward pass is the same
-    assert not any(same_bits(a, b) for a, b in zip(grads[None][1:4], grads[0.5][1:4]))
+    assert all(bits_equal(a, b) for a, b in zip(grads[None], grads[0.0]))
+    assert bits_equal(grads[None][0], grads[0.5][0])                                   # the forward pass is the same
+    assert not any(bits_equal(a, b) for a, b in zip(grads[None][1:4], grads[0.5][1:4]))
 
 
 @pytest.mark.parametrize("kind", ["ce", "entropy"])
@@ -347,7 +340,7 @@ def test_self_check_leaves_the_weights_at_ones(macx, dev, kind):
         torch.cuda.synchronize()
         out.append([mem, step.aux_rows.clone()] + [t.grad.clone() for t in step._leaves()])
         maps = torch.stack([a.detach().cpu() for a in step.cell.attentions["kb"]], dim=0)
-    assert all(same_bits(a, b) for a, b in zip(*out))
+    assert all(bits_equal(a, b) for a, b in zip(*out))
     want = ar.rows(maps, target=target.cpu() if kind == "ce" else None, kind=kind, eps=1e-8, scale=0.5 / (TP * TB))      # unit weights
     assert float(want.abs().min()) > 0
     assert float((out[0][1].cpu().double() - want).abs().max()) <= 1e-5 * float(want.abs().max())
@@ -372,7 +365,7 @@ def test_captured_train_step_with_aux_loss_callable(macx, dev):
     plain = macx.CapturedTrainStep(cfg, params, TB, TS, TN, seed=77)
     plain.load(*x)
     plain.replay()
-    assert not same_bits(plain.knowledgeBase.grad, got[3])                            # the head's loss reached the inputs
+    assert not bits_equal(plain.knowledgeBase.grad, got[3])                            # the head's loss reached the inputs
 
 
 # ---- two gloo ranks on the one GPU, as tests/test_gpu_dp.py
@@ -500,7 +493,7 @@ def test_captured_tower_train_step_with_att_loss(macx, dev):
         step._restore(state)
         step.replay(iteration=4)
         torch.cuda.synchronize()
-        assert tg.bits_equal((step.ce + step.aux).reshape(1), step.loss.reshape(1))
+        assert bits_equal((step.ce + step.aux).reshape(1), step.loss.reshape(1))
         assert float(step.aux) > 0 and abs(float(step.aux) - float(step.aux_rows.double().sum())) <= 1e-5 * float(step.aux)
         runs.append([t.clone() for t in [step.loss, step.ce, step.aux, step.aux_rows, step.logits, step.pred] + step._stepped()])
     step._restore(state)
@@ -510,7 +503,7 @@ def test_captured_tower_train_step_with_att_loss(macx, dev):
     for r, got in enumerate(runs):
         assert len(got) == len(eager)
         for i, (a, b) in enumerate(zip(got, eager)):
-            assert tg.bits_equal(a.reshape(-1), b.reshape(-1)), (r, i)
+            assert bits_equal(a.reshape(-1), b.reshape(-1)), (r, i)
     step._restore(state)
     step.check()
 
@@ -544,9 +537,9 @@ def test_captured_tower_weight_zero_is_the_step_without_att_loss(macx, dev):
         step.replay(iteration=0)
         torch.cuda.synchronize()
         if att is None:
-            assert step.aux is None and tg.bits_equal(step.loss.reshape(1), step.ce.reshape(1))
+            assert step.aux is None and bits_equal(step.loss.reshape(1), step.ce.reshape(1))
         else:
             assert float(step.aux) == 0.0 and bool((bits(step.aux_rows) == 0).all())
         out.append([t.clone() for t in (step.loss, step.ce, opt.flat, opt.m, opt.v, step.norm, step.logits)])
     for i, (a, b) in enumerate(zip(*out)):
-        assert tg.bits_equal(a.reshape(-1), b.reshape(-1)), i
+        assert bits_equal(a.reshape(-1), b.reshape(-1)), i

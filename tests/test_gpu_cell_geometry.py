@@ -42,6 +42,7 @@ import ctypes as C
 import pytest
 import torch
 
+from abi_kit import ptr
 import helpers
 import route_cases as rc
 import test_gpu_cell as cellmod
@@ -163,10 +164,6 @@ def test_route_for_the_current_device_is_the_route_for_its_compute_units(macx, d
     assert ncu > 0
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 @pytest.mark.parametrize("B,S,N,d", [(3, 7, 49, 384), (42, 5, 196, 512)])
 def test_chain_kernel_intermediate_products(macx, dev, B, S, N, d):
     """X, H1 and I2 of step 0 (macx_saved_activation), each against the fp64 product of the operand the kernel multiplied (the kept
@@ -190,7 +187,7 @@ def test_chain_kernel_intermediate_products(macx, dev, B, S, N, d):
     outs = []
     for which in (1, 2, 3):
         o = torch.empty(B * N, d, device=dev)
-        macx._lib.check(L.macx_saved_activation(C.byref(run.opts), C.byref(run.shapes), which, 0, _p(run.saved), run.saved_floats, _p(o),
+        macx._lib.check(L.macx_saved_activation(C.byref(run.opts), C.byref(run.shapes), which, 0, ptr(run.saved), run.saved_floats, ptr(o),
                                                 run.stream), "macx_saved_activation")
         outs.append(o)
     mem0 = run.segment("memories", (p + 1, B, d))[0].clone()

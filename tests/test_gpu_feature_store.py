@@ -6,12 +6,13 @@ Shapes (n, C, HW) of the pack: (1, 4, 1) one quad; (3, 36, 196) C off the 8-elem
 off the 16-byte load and the tile, two channel tiles; (5, 8, 9) the file fixture's; (2, 72, 68) both vector paths with a tile edge
 on both axes (the workload's route: C % 8 == 0, HW % 4 == 0).  Gather: images whose unit count lies before, on and behind the 1 024
 units of a workgroup's pass, for 16-byte loads (C*HW % 8 == 0), 8-byte loads and the fp32 copy."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import torch
+
+from abi_kit import bits_equal, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +20,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H5 = os.path.join(ROOT, "tests", "golden", "h5", "features_like_reference.h5")
 DTYPES = {"fp16": torch.float16, "fp32": torch.float32}
 CODE = {torch.float32: 0, torch.float16: 1}
-BITS = {torch.float32: torch.int32, torch.float16: torch.int16}
 PACK_SHAPES = [(1, 4, 1), (3, 36, 196), (2, 128, 49), (5, 8, 9), (2, 72, 68)]
 # +-0, fp16 subnormals (the smallest is 2^-24 = 5.96e-8: 3e-8 lies just above the tie to zero), exact ties to even in both
 # directions, the largest fp16 and the largest value that still rounds to it
@@ -27,15 +27,6 @@ SPECIAL = [0.0, -0.0, 1e-7, 6e-8, 3e-8, -1e-7, -6e-8, -3e-8, 2.0 ** -25, 1 + 2.0
            65519.99, -65504.0, -65519.99, 2.0 ** -14, 2.0 ** -14 - 2.0 ** -25]
 SENTINEL = 7.0
 UNITS = 1024                        # FT_CHUNK / KBG_CHUNK: units (quads) per workgroup and pass
-
-
-def p_(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def bits_equal(a, b):
-    """same bits (torch.equal would take -0.0 for +0.0 and refuse equal NaNs)"""
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(BITS[a.dtype]), b.contiguous().view(BITS[b.dtype]))
 
 
 def source(n, C_, HW, seed):
@@ -65,7 +56,7 @@ def test_pack_is_torchs_conversion_bit_for_bit(macx, dev, shape, dtype, layout):
     rows, row0 = n + 3, 2
     table = torch.full((rows, HW, C_), SENTINEL, dtype=dt, device=dev)
     word = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = macx._lib.lib().macx_features_pack(p_(given.to(dev)), layout, n, C_, HW, p_(table), CODE[dt], row0, rows, p_(word), None)
+    rc = macx._lib.lib().macx_features_pack(ptr(given.to(dev)), layout, n, C_, HW, ptr(table), CODE[dt], row0, rows, ptr(word), None)
     torch.cuda.synchronize()
     assert rc == 0
     got = table.cpu()
@@ -126,7 +117,7 @@ def test_gather_is_indexing_bit_for_bit(macx, dev, dtype, shape):
     buf = torch.full((G * image + 64,), SENTINEL, device=dev)               # a sentinel behind `out`
     L = macx._lib.lib()
     dtab, dids = table.to(dev), ids.to(dev)
-    rc = L.macx_features_gather(p_(dtab), CODE[dt], ROWS, p_(dids), G, C_, HW, p_(buf), None)
+    rc = L.macx_features_gather(ptr(dtab), CODE[dt], ROWS, ptr(dids), G, C_, HW, ptr(buf), None)
     torch.cuda.synchronize()
     assert rc == 0
     got = buf[:G * image].view(G, HW, C_).cpu()
@@ -136,7 +127,7 @@ def test_gather_is_indexing_bit_for_bit(macx, dev, dtype, shape):
     assert bool((buf[G * image:] == SENTINEL).all())
     if dt == torch.float32:                                                 # the same launch as macx_kb_gather: the copy, bit for bit
         other = torch.full_like(buf, SENTINEL)
-        assert L.macx_kb_gather(p_(dtab), p_(dids), ROWS, G, HW, C_, p_(other), None) == 0
+        assert L.macx_kb_gather(ptr(dtab), ptr(dids), ROWS, G, HW, C_, ptr(other), None) == 0
         torch.cuda.synchronize()
         assert torch.equal(buf.view(torch.int32), other.view(torch.int32))
     # the store's method: the same call, any integer dtype of ids
@@ -162,10 +153,10 @@ def test_offsets_are_64_bit(macx, dev):
         want = (src.permute(0, 2, 1) if layout == 0 else src).contiguous().to(torch.float16).float()
         dsrc = src.to(dev)
         for i, r in enumerate(pick):
-            assert L.macx_features_pack(p_(dsrc[i]), layout, 1, C_, H * W, p_(table), 1, r, rows, p_(word), None) == 0
+            assert L.macx_features_pack(ptr(dsrc[i]), layout, 1, C_, H * W, ptr(table), 1, r, rows, ptr(word), None) == 0
         ids = torch.tensor(pick[::-1] + [pick[1]], dtype=torch.int32, device=dev)
         out = torch.empty(4, H * W, C_, device=dev)
-        assert L.macx_features_gather(p_(table), 1, rows, p_(ids), 4, C_, H * W, p_(out), None) == 0
+        assert L.macx_features_gather(ptr(table), 1, rows, ptr(ids), 4, C_, H * W, ptr(out), None) == 0
         torch.cuda.synchronize()
         assert torch.equal(out.cpu(), want[[2, 1, 0, 1]]), (round_, layout)
         assert torch.equal(table[rows - 1].cpu().float(), want[2]) and torch.equal(table[66000].cpu().float(), want[1])

@@ -48,37 +48,10 @@ import ctypes as C
 import pytest
 import torch
 
+from abi_kit import GUARD, SENT, Guarded, bits, ptr
 from helpers import default_gemm_mode
 
 pytestmark = pytest.mark.gpu
-
-SENT = -7.03125e11            # what guard zones are filled with: exactly representable, far from any result of these tests
-GUARD = 1024                  # floats in front of / behind a guarded buffer (keeps 16-byte alignment)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-class _Guarded:
-    """n floats in the middle of a larger buffer filled with SENT"""
-
-    def __init__(self, n, dev, before=GUARD, after=GUARD):
-        self.n, self.before = int(n), before
-        self.buf = torch.full((before + self.n + after,), SENT, device=dev)
-        self.view = self.buf[before:before + self.n]
-        assert self.view.data_ptr() % 16 == 0
-
-    def outside_untouched(self):
-        return bool((self.buf[:self.before] == SENT).all()) and bool((self.buf[self.before + self.n:] == SENT).all())
-
-    def untouched(self):
-        return bool((self.buf == SENT).all())
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
 
 def _ulp32(ref64):
     r = ref64.float()
@@ -112,7 +85,7 @@ def _linear_inputs(rows, k1, k2, n_out):
 
 
 def _call_linear(macx, x1, k1, x2, k2, rows, wp, b, bc, n_out, act, out):
-    return macx._lib.lib().macx_linear(_p(x1), k1, _p(x2), k2, rows, _p(wp), _p(b), bc, n_out, macx._lib.ACT[act], _p(out), None)
+    return macx._lib.lib().macx_linear(ptr(x1), k1, ptr(x2), k2, rows, ptr(wp), ptr(b), bc, n_out, macx._lib.ACT[act], ptr(out), None)
 
 
 @pytest.mark.parametrize("rows,k1,k2,n_out,act,bc", LINEAR_CASES)
@@ -126,9 +99,9 @@ def test_linear_against_fp64(macx, dev, rows, k1, k2, n_out, act, bc):
     x1d, Wd, bd = x1.to(dev), W.to(dev), b.to(dev)
     x2d = x2.to(dev) if x2 is not None else None
     wp = torch.empty_like(Wd)
-    macx._lib.check(L.macx_pack_weight(_p(Wd), k1 + k2, n_out, 0, _p(wp), None), "pack")
+    macx._lib.check(L.macx_pack_weight(ptr(Wd), k1 + k2, n_out, 0, ptr(wp), None), "pack")
     # a ragged tile's clamped rows would land behind row rows - 1: up to 63 rows of n_out floats, all inside the guard zone
-    outs = [_Guarded(rows * n_out, dev, after=64 * n_out + GUARD) for _ in range(5)]
+    outs = [Guarded(rows * n_out, dev, after=64 * n_out + GUARD) for _ in range(5)]
     try:
         for o, mode in zip(outs, (None, None, 0, 1, 2)):
             if mode is not None:
@@ -146,10 +119,10 @@ def test_linear_against_fp64(macx, dev, rows, k1, k2, n_out, act, bc):
     assert torch.isfinite(got).all()
     assert float(ratio.max()) <= 1.0, "err/bound %.3f at row %d column %d" % (float(ratio.max()), worst // n_out, worst % n_out)
     for o in outs:
-        assert o.outside_untouched(), "macx_linear wrote outside rows [0, %d) of its output" % rows
-    assert torch.equal(_bits(outs[0].view), _bits(outs[1].view)), "second call differs"
+        assert o.intact(), "macx_linear wrote outside rows [0, %d) of its output" % rows
+    assert torch.equal(bits(outs[0].view), bits(outs[1].view)), "second call differs"
     for o, mode in zip(outs[2:], (0, 1, 2)):
-        assert torch.equal(_bits(outs[0].view), _bits(o.view)), "family %d differs" % mode
+        assert torch.equal(bits(outs[0].view), bits(o.view)), "family %d differs" % mode
 
 
 def test_linear_guards(macx, dev):
@@ -164,14 +137,14 @@ def test_linear_guards(macx, dev):
            "k2 > 0, x2 NULL": (x1, k1, None, k2, rows, n_out), "x2 set, k2 = 0": (x1, k1, x2, 0, rows, n_out),
            "x1 off a 16-byte boundary": (off, k1, None, 0, rows, n_out), "rows = 0": (x1, k1, None, 0, 0, n_out)}
     for what, (a1, kk1, a2, kk2, r, n) in bad.items():
-        o = _Guarded(rows * n_out, dev)
+        o = Guarded(rows * n_out, dev)
         assert _call_linear(macx, a1, kk1, a2, kk2, r, wp, b, 0.25, n, "NON", o.view) == macx._lib.MACX_EINVAL, what
         torch.cuda.synchronize()
         assert o.untouched(), what
-    o = _Guarded(rows * n_out, dev)                # the same operands, well-formed: the guards above did not reject a legal call
+    o = Guarded(rows * n_out, dev)                # the same operands, well-formed: the guards above did not reject a legal call
     macx._lib.check(_call_linear(macx, x1, k1, x2, k2, rows, wp, b, 0.25, n_out, "NON", o.view), "linear")
     torch.cuda.synchronize()
-    assert o.outside_untouched() and bool((o.view != SENT).all())
+    assert o.intact() and bool((o.view != SENT).all())
 
 
 # ================================================= 2. macx_wgrad ==================================================================
@@ -226,10 +199,10 @@ def test_wgrad_three_families(macx, dev, M, Kd, Jd, lda_kind, ldg_kind, data):
             L.macx_gemm_mode(mode)
             ns = L.macx_wgrad_splits(M, Kd, Jd)
             assert ns >= 1
-            outs = [_Guarded(Kd * Jd, dev), _Guarded(Kd * Jd, dev)]
-            ws = _Guarded(ns * Kd * Jd, dev)
+            outs = [Guarded(Kd * Jd, dev), Guarded(Kd * Jd, dev)]
+            ws = Guarded(ns * Kd * Jd, dev)
             for o in outs:
-                macx._lib.check(L.macx_wgrad(Ap, lda, Gp, ldg, M, Kd, Jd, _p(o.view), _p(ws.view), None), "wgrad")
+                macx._lib.check(L.macx_wgrad(Ap, lda, Gp, ldg, M, Kd, Jd, ptr(o.view), ptr(ws.view), None), "wgrad")
             keep.append((mode, ns, outs, ws))
     finally:
         L.macx_gemm_mode(default_gemm_mode())
@@ -239,8 +212,8 @@ def test_wgrad_three_families(macx, dev, M, Kd, Jd, lda_kind, ldg_kind, data):
         assert torch.isfinite(got).all()
         e = (got - ref).abs() / S
         stats[mode] = (float(e.max()), float(e.mean()), ns)
-        assert outs[0].outside_untouched() and outs[1].outside_untouched() and ws.outside_untouched(), "family %d wrote out of bounds" % mode
-        assert torch.equal(_bits(outs[0].view), _bits(outs[1].view)), "family %d: second call differs" % mode
+        assert outs[0].intact() and outs[1].intact() and ws.intact(), "family %d wrote out of bounds" % mode
+        assert torch.equal(bits(outs[0].view), bits(outs[1].view)), "family %d: second call differs" % mode
     (m0, a0, ns0), (m1, a1, ns1), (m2, a2, ns2) = stats[0], stats[1], stats[2]
     b0 = (M + ns0 + 4) * 2.0 ** -24
     print("\nGEMMX wgrad M=%d %dx%d lda=%d ldg=%d %s: err/S max (mean) family 0 %.3e (%.3e) = %.3f of its bound, nsplit %d | 1 %.3e (%.3e) "
@@ -270,12 +243,12 @@ def test_wgrad_guards(macx, dev):
     M, Kd, Jd = 8, 128, 128
     A = torch.randn(M, 2 * Kd, device=dev)
     G = torch.randn(M, 2 * Jd, device=dev)
-    ws = _Guarded(2 * Kd * Jd, dev)
+    ws = Guarded(2 * Kd * Jd, dev)
     bad = {"Kd = 64": (2 * Kd, M, 64, Jd, ws.view), "Jd = 192": (2 * Kd, M, Kd, 192, ws.view), "lda = Kd + 2": (Kd + 2, M, Kd, Jd, ws.view),
            "M = 0": (2 * Kd, 0, Kd, Jd, ws.view), "ws NULL": (2 * Kd, M, Kd, Jd, None)}
     for what, (lda, m, kd, jd, w) in bad.items():
-        o = _Guarded(Kd * 2 * Jd, dev)
-        assert L.macx_wgrad(_p(A), lda, _p(G), 2 * Jd, m, kd, jd, _p(o.view), _p(w), None) == macx._lib.MACX_EINVAL, what
+        o = Guarded(Kd * 2 * Jd, dev)
+        assert L.macx_wgrad(ptr(A), lda, ptr(G), 2 * Jd, m, kd, jd, ptr(o.view), ptr(w), None) == macx._lib.MACX_EINVAL, what
         torch.cuda.synchronize()
         assert o.untouched() and ws.untouched(), what
     assert L.macx_wgrad_splits(M, 64, Jd) == macx._lib.MACX_EINVAL and L.macx_wgrad_splits(0, Kd, Jd) == macx._lib.MACX_EINVAL
@@ -305,20 +278,20 @@ def _expected_pack(W, fmt):
     """include/macx.h's layouts as int32 words"""
     K, n_out = W.shape
     if fmt == 0:                                   # out[Q][g][j][e] = W[16Q + 4g + e][j]
-        return _bits(W.reshape(K // 16, 4, 4, n_out).permute(0, 1, 3, 2).reshape(-1))
+        return bits(W.reshape(K // 16, 4, 4, n_out).permute(0, 1, 3, 2).reshape(-1))
     if fmt == 2:                                   # out[kt][j][kk] = W[32 kt + kk][j]
-        return _bits(W.reshape(K // 32, 32, n_out).permute(0, 2, 1).reshape(-1))
+        return bits(W.reshape(K // 32, 32, n_out).permute(0, 2, 1).reshape(-1))
     planes = [h.reshape(K // 32, 32, n_out).permute(0, 2, 1) for h in _bf16_chain(W)]       # [K/32][3][n_out][32] bf16
     return torch.stack(planes, dim=1).contiguous().reshape(-1).view(torch.int32)
 
 
 def _pack(macx, dev, src, K, n_out, flags):
     n = K * n_out * 3 // 2 if (flags >> 1) == 1 else K * n_out
-    o = _Guarded(n, dev)
-    macx._lib.check(macx._lib.lib().macx_pack_weight(src, K, n_out, flags, _p(o.view), None), "pack")
+    o = Guarded(n, dev)
+    macx._lib.check(macx._lib.lib().macx_pack_weight(src, K, n_out, flags, ptr(o.view), None), "pack")
     torch.cuda.synchronize()
-    assert o.outside_untouched(), "macx_pack_weight(flags = %d) wrote behind its %d floats" % (flags, n)
-    return _bits(o.view)
+    assert o.intact(), "macx_pack_weight(flags = %d) wrote behind its %d floats" % (flags, n)
+    return bits(o.view)
 
 
 @pytest.mark.parametrize("K,n_out", [(16, 16), (32, 48), (96, 16), (512, 128)])
@@ -337,12 +310,12 @@ def test_pack_weight_byte_layout(macx, dev, K, n_out):
     off = C.c_void_p(shifted.data_ptr() + 4)                                # W^T from 4 bytes past a 16-byte boundary: the scalar path
     for fmt in (0, 1, 2):
         if fmt and K % 32:
-            assert macx._lib.lib().macx_pack_weight(_p(Wd), K, n_out, fmt << 1, _p(shifted), None) == macx._lib.MACX_EINVAL
+            assert macx._lib.lib().macx_pack_weight(ptr(Wd), K, n_out, fmt << 1, ptr(shifted), None) == macx._lib.MACX_EINVAL
             continue
         want = _expected_pack(W, fmt)
-        got = _pack(macx, dev, _p(Wd), K, n_out, fmt << 1)
+        got = _pack(macx, dev, ptr(Wd), K, n_out, fmt << 1)
         assert torch.equal(got, want), "format %d: %d of %d words differ from include/macx.h's layout" % (fmt, int((got != want).sum()), want.numel())
-        got_t = _pack(macx, dev, _p(Wt), K, n_out, (fmt << 1) | 1)
+        got_t = _pack(macx, dev, ptr(Wt), K, n_out, (fmt << 1) | 1)
         assert torch.equal(got_t, got), "format %d: the transposed source packs differently" % fmt
         if fmt == 0:
             got_s = _pack(macx, dev, off, K, n_out, 1)
@@ -367,18 +340,18 @@ def test_h2_pack_weight_transposed(macx, dev, K, n_out):
     Ad, Wd, bd = A.to(dev), W.to(dev), b.to(dev)
     Wt = W.t().contiguous().to(dev)
     n = K * n_out + 16                                     # the documented size
-    plain, trans = _Guarded(n, dev), _Guarded(n, dev)
-    macx._lib.check(L.macx_h2_pack_weight(_p(Wd), K, n_out, 0, _p(plain.view), None), "h2 pack")
-    macx._lib.check(L.macx_h2_pack_weight(_p(Wt), K, n_out, 1, _p(trans.view), None), "h2 pack^T")
+    plain, trans = Guarded(n, dev), Guarded(n, dev)
+    macx._lib.check(L.macx_h2_pack_weight(ptr(Wd), K, n_out, 0, ptr(plain.view), None), "h2 pack")
+    macx._lib.check(L.macx_h2_pack_weight(ptr(Wt), K, n_out, 1, ptr(trans.view), None), "h2 pack^T")
     hA = torch.empty(L.macx_h2_floats(B * N, K), device=dev)
     hO = torch.empty(L.macx_h2_floats(B * N, n_out), device=dev)
     out = torch.empty(B * N, n_out, device=dev)
-    macx._lib.check(L.macx_h2_from_f32(_p(Ad), B, N, K, _p(hA), None), "from")
-    macx._lib.check(L.macx_h2_gemm_planes(_p(hA), B, N, K, _p(trans.view), n_out, _p(bd), 0, _p(hO), None), "planes")
-    macx._lib.check(L.macx_h2_to_f32(_p(hO), B * N, n_out, _p(out), None), "to")
+    macx._lib.check(L.macx_h2_from_f32(ptr(Ad), B, N, K, ptr(hA), None), "from")
+    macx._lib.check(L.macx_h2_gemm_planes(ptr(hA), B, N, K, ptr(trans.view), n_out, ptr(bd), 0, ptr(hO), None), "planes")
+    macx._lib.check(L.macx_h2_to_f32(ptr(hO), B * N, n_out, ptr(out), None), "to")
     torch.cuda.synchronize()
-    assert plain.outside_untouched() and trans.outside_untouched()
-    pb, tb = _bits(plain.view), _bits(trans.view)
+    assert plain.intact() and trans.intact()
+    pb, tb = bits(plain.view), bits(trans.view)
     assert torch.equal(pb[:K * n_out + 1], tb[:K * n_out + 1]), "%d plane words differ, exponent %d vs %d" % (
         int((pb[:K * n_out] != tb[:K * n_out]).sum()), int(pb[K * n_out]), int(tb[K * n_out]))
     e = (out.cpu().double() - ref).abs() / scale

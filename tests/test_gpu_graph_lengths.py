@@ -11,20 +11,14 @@ import math
 import pytest
 import torch
 
+import abi_kit
+from abi_kit import bits_equal, ptr
+
 pytestmark = pytest.mark.gpu
 
 CELL_SHAPES = [(3, 5, 20, 128, 2), (2, 5, 49, 256, 2)]
 # two sets of sizes per shape: N, 1 and one in between; then others, so that a replay has to read them again
 SIZES = {20: ([7, 20, 1], [20, 3, 12]), 49: ([1, 30], [49, 17])}
-
-
-def bits_equal(a, b):
-    """same bits (torch.equal would take -0.0 for +0.0 and refuse equal NaNs)"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def P_(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def cell_setup(macx, dev, shape):
@@ -190,15 +184,15 @@ def test_read_unit_export_with_lengths(macx, dev):
     want_att, want_info = cell._att_kb[0].clone(), cell._infos_all[0].clone()
     head = (C.byref(run.opts), C.byref(run.shapes), C.byref(run.drop), C.byref(run.pstruct))
     saved_floats = L.macx_saved_floats(C.byref(run.opts), C.byref(run.shapes), 1)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = abi_kit.stream(dev)
 
     def read(sizes_or_none, plain=False):
         saved = torch.empty(saved_floats, dtype=torch.float32, device=dev)
         info, att = torch.full((B, d), float("nan"), device=dev), torch.full((B, N), float("nan"), device=dev)
         if plain:
-            rc = L.macx_read_fwd(*head, P_(kb), P_(memory), P_(control), P_(saved), saved_floats, P_(info), P_(att), st)
+            rc = L.macx_read_fwd(*head, ptr(kb), ptr(memory), ptr(control), ptr(saved), saved_floats, ptr(info), ptr(att), st)
         else:
-            rc = L.macx_read_fwd_l(*head, P_(kb), P_(sizes_or_none), P_(memory), P_(control), P_(saved), saved_floats, P_(info), P_(att), st)
+            rc = L.macx_read_fwd_l(*head, ptr(kb), ptr(sizes_or_none), ptr(memory), ptr(control), ptr(saved), saved_floats, ptr(info), ptr(att), st)
         lib.check(rc, "macx_read_fwd(_l)")
         return saved, info, att
 
@@ -222,8 +216,8 @@ def test_read_unit_export_with_lengths(macx, dev):
     ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
     dinfo = torch.randn(B, d, generator=torch.Generator().manual_seed(4)).to(dev)
     dkb, dmem, dctl = torch.full_like(kb, float("nan")), torch.empty(B, d, device=dev), torch.empty(B, d, device=dev)
-    lib.check(L.macx_read_bwd(*head, P_(kb), P_(saved), saved_floats, P_(ws), ws_floats, P_(dinfo), C.byref(gstruct), P_(dkb), P_(dmem),
-                              P_(dctl), st), "macx_read_bwd")
+    lib.check(L.macx_read_bwd(*head, ptr(kb), ptr(saved), saved_floats, ptr(ws), ws_floats, ptr(dinfo), C.byref(gstruct), ptr(dkb), ptr(dmem),
+                              ptr(dctl), st), "macx_read_bwd")
     torch.cuda.synchronize()
     assert bool(torch.isfinite(dkb).all()) and padded_are_zero(dkb, sizes)
     assert all(bool((dkb[b, :int(n)] != 0).any()) for b, n in enumerate(sizes))

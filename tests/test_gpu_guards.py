@@ -2,47 +2,14 @@
 while a module runs (`saved`, `ws`: sized by macx_*_saved_floats / macx_*_ws_floats) gets a sentinel-filled guard band on
 both sides; after forward + backward on random shapes the bands must be untouched.  (The encoder's slab workspace was found
 too small for h > pad128(E) by the shape fuzz -- this is the direct check.)"""
-import contextlib
 import random
 
 import pytest
 import torch
 
+from abi_kit import assert_guards_intact, guarded_allocations
+
 pytestmark = pytest.mark.gpu
-
-GUARD = 2048                 # floats per side (multiple of 4: the inner view stays 16-byte aligned)
-SENTINEL = -7.25e11
-
-
-@contextlib.contextmanager
-def guarded_allocations():
-    real_empty = torch.empty
-    seen = []
-
-    def empty(*size, **kw):
-        one_d = len(size) == 1 and isinstance(size[0], int)
-        if one_d and kw.get("dtype") is torch.float32 and str(kw.get("device", "cpu")).startswith("cuda") and size[0] >= 16:
-            n = (size[0] + 3) & ~3
-            full = real_empty(n + 2 * GUARD, **kw)
-            full.fill_(SENTINEL)
-            seen.append((full, n))
-            return full[GUARD: GUARD + size[0]]
-        return real_empty(*size, **kw)
-
-    torch.empty = empty
-    try:
-        yield seen
-    finally:
-        torch.empty = real_empty
-
-
-def assert_guards_intact(seen, what):
-    assert seen, what
-    for full, n in seen:
-        lo, hi = full[:GUARD], full[GUARD + n:]
-        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), \
-            (what, "buffer of %d floats: %d guard floats overwritten below, %d above"
-             % (n, int((lo != SENTINEL).sum()), int((hi != SENTINEL).sum())))
 
 
 @pytest.mark.parametrize("seed", range(3))

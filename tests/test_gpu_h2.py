@@ -6,13 +6,10 @@ import numpy as np
 import pytest
 import torch
 
+from abi_kit import ptr
 from helpers import default_gemm_mode, rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 @pytest.mark.parametrize("B,N,C_", [(3, 196, 512), (2, 49, 128), (1, 1, 128), (2, 209, 256), (1, 450, 128)])
@@ -31,8 +28,8 @@ def test_h2_round_trip(macx, dev, B, N, C_):
     assert n > 0
     h2 = torch.empty(n, device=dev)
     out = torch.empty(B * N, C_, device=dev)
-    macx._lib.check(L.macx_h2_from_f32(_p(xd), B, N, C_, _p(h2), None), "from")
-    macx._lib.check(L.macx_h2_to_f32(_p(h2), B * N, C_, _p(out), None), "to")
+    macx._lib.check(L.macx_h2_from_f32(ptr(xd), B, N, C_, ptr(h2), None), "from")
+    macx._lib.check(L.macx_h2_to_f32(ptr(h2), B * N, C_, ptr(out), None), "to")
     torch.cuda.synchronize()
     y = out.cpu().reshape(B, N, C_)
     xb = x.reshape(B, N, C_ // 128, 128).double()
@@ -67,7 +64,7 @@ def test_h2_gemm_error_is_fp32_class(macx, dev, B, N, K, n_out):
     ws = torch.empty(n, device=dev)
     out = torch.empty(B * N, n_out, device=dev)
     Ad, Wd, bd = A.to(dev), W.to(dev), b.to(dev)        # keep the device copies alive across the asynchronous call
-    macx._lib.check(L.macx_h2_gemm(_p(Ad), B, N, K, _p(Wd), n_out, _p(bd), 0, _p(out), _p(ws), n, None), "h2_gemm")
+    macx._lib.check(L.macx_h2_gemm(ptr(Ad), B, N, K, ptr(Wd), n_out, ptr(bd), 0, ptr(out), ptr(ws), n, None), "h2_gemm")
     torch.cuda.synchronize()
     e = (out.cpu().double() - ref).abs() / scale
     emax, emean = float(e.max()), float(e.mean())
@@ -79,8 +76,8 @@ def test_h2_gemm_error_is_fp32_class(macx, dev, B, N, K, n_out):
             dp = macx._lib.MacxDropout(keep_memory=1.0, keep_read=1.0, keep_write=1.0, seed=1)
             wp = torch.zeros(2 * K * K, device=dev)
             o2 = torch.empty(B, N, K, device=dev)
-            macx._lib.check(L.macx_pack_weight(_p(Wd), K, K, macx._lib.kb_pack_flags(), _p(wp), None), "pack")
-            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, _p(Ad), _p(wp), _p(bd), _p(o2), None, None), "proj")
+            macx._lib.check(L.macx_pack_weight(ptr(Wd), K, K, macx._lib.kb_pack_flags(), ptr(wp), None), "pack")
+            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, ptr(Ad), ptr(wp), ptr(bd), ptr(o2), None, None), "proj")
             torch.cuda.synchronize()
             e0 = (o2.cpu().double().reshape(-1, K) - ref).abs() / scale
             assert emax <= 1.5 * float(e0.max()) and emean <= 1.5 * float(e0.mean()), (emax, emean, float(e0.max()), float(e0.mean()))
@@ -101,7 +98,7 @@ def test_h2_gemm_activation_and_determinism(macx, dev):
     Ad, Wd, bd = A.to(dev), W.to(dev), b.to(dev)
     for _ in range(2):
         out = torch.empty(B * N, K, device=dev)
-        macx._lib.check(L.macx_h2_gemm(_p(Ad), B, N, K, _p(Wd), K, _p(bd), macx._lib.ACT["ELU"], _p(out), _p(ws), n, None), "h2_gemm")
+        macx._lib.check(L.macx_h2_gemm(ptr(Ad), B, N, K, ptr(Wd), K, ptr(bd), macx._lib.ACT["ELU"], ptr(out), ptr(ws), n, None), "h2_gemm")
         torch.cuda.synchronize()
         outs.append(out.cpu())
     ref = torch.nn.functional.elu(A.double().reshape(-1, K) @ W.double() + b.double())
@@ -142,7 +139,7 @@ def test_chain_kernel_products_on_wide_dynamic_range(macx, dev, B, N, d):
     outs = []
     for which in (1, 2, 3):
         o = torch.empty(B * N, d, device=dev)
-        macx._lib.check(L.macx_saved_activation(C.byref(run.opts), C.byref(run.shapes), which, 0, _p(run.saved), run.saved_floats, _p(o),
+        macx._lib.check(L.macx_saved_activation(C.byref(run.opts), C.byref(run.shapes), which, 0, ptr(run.saved), run.saved_floats, ptr(o),
                                                 run.stream), "macx_saved_activation")
         outs.append(o)
     torch.cuda.synchronize()
@@ -166,8 +163,8 @@ def test_chain_kernel_products_on_wide_dynamic_range(macx, dev, B, N, d):
             wp = torch.zeros(2 * d * d, device=dev)
             o2 = torch.empty(B, N, d, device=dev)
             Ad = A32.to(dev).contiguous()
-            macx._lib.check(L.macx_pack_weight(_p(Wt.detach()), d, d, macx._lib.kb_pack_flags(), _p(wp), None), "pack")
-            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, _p(Ad), _p(wp), _p(bt.detach()), _p(o2), None, None), "proj")
+            macx._lib.check(L.macx_pack_weight(ptr(Wt.detach()), d, d, macx._lib.kb_pack_flags(), ptr(wp), None), "pack")
+            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, ptr(Ad), ptr(wp), ptr(bt.detach()), ptr(o2), None, None), "proj")
             torch.cuda.synchronize()
             e0 = (o2.cpu().double().reshape(-1, d) - ref).abs() / scale
         finally:

@@ -24,41 +24,13 @@ import numpy as np
 import pytest
 import torch
 
+import abi_kit
 import h2_contraction_cases as hc
+from abi_kit import Guarded, bits_equal, ptr
 
 pytestmark = pytest.mark.gpu
 
-SENT = -7.03125e11
-GUARD = 1024
 EXTRA = 64                    # floats between one tensor's end and the next one's start
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-class _Guarded:
-    """n floats in the middle of a larger buffer filled with SENT"""
-
-    def __init__(self, n, dev):
-        self.n = int(n)
-        self.buf = torch.full((GUARD + self.n + GUARD,), SENT, device=dev)
-        self.view = self.buf[GUARD:GUARD + self.n]
-        assert self.view.data_ptr() % 16 == 0
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == SENT).all()) and bool((self.buf[GUARD + self.n:] == SENT).all())
-
-    def np(self, *shape):
-        return self.view.cpu().numpy().reshape(shape)
-
-
-def _opts(macx, **tune):
-    o = macx._lib.MacxOpts()
-    o.abi_version = macx._lib.ABI_VERSION
-    for k, v in tune.items():
-        macx._lib.set_tune(o, k, v)
-    return o
 
 
 def _h2(macx, dev, x, fill):
@@ -70,7 +42,7 @@ def _h2(macx, dev, x, fill):
     buf = torch.full((nt * stride * 4,), fill, dtype=torch.uint8, device=dev).view(torch.float32)
     src = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     for t in range(nt):
-        macx._lib.check(L.macx_h2_from_f32(_p(src[t]), B, N, Cc, _p(buf[t * stride:]), None), "h2_from_f32")
+        macx._lib.check(L.macx_h2_from_f32(ptr(src[t]), B, N, Cc, ptr(buf[t * stride:]), None), "h2_from_f32")
     return buf, stride
 
 
@@ -78,12 +50,8 @@ def _round_trip(macx, dev, buf, stride, nt, rows, Cc):
     L = macx._lib.lib()
     out = torch.empty(nt, rows, Cc, device=dev)
     for t in range(nt):
-        macx._lib.check(L.macx_h2_to_f32(_p(buf[t * stride:]), rows, Cc, _p(out[t]), None), "h2_to_f32")
+        macx._lib.check(L.macx_h2_to_f32(ptr(buf[t * stride:]), rows, Cc, ptr(out[t]), None), "h2_to_f32")
     return out.cpu().numpy()
-
-
-def _same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def _report(what, cid, name, got, ref, bound, where):
@@ -100,13 +68,13 @@ def _wgrad_call(macx, dev, c, bufs, strides, o=None, pair=None):
     op = C.byref(o) if o is not None else None
     need = L.macx_h2_wgrad_ws_floats(op, c.nt, c.R, c.Kd, c.Jd, c.nsplit, int(pair is not None))
     assert need > 0
-    ws = _Guarded(need, dev)
-    out = _Guarded(c.Kd * c.Jd, dev)
-    out2 = _Guarded(c.Kd * c.Jd, dev) if pair is not None else None
+    ws = Guarded(need, dev)
+    out = Guarded(c.Kd * c.Jd, dev)
+    out2 = Guarded(c.Kd * c.Jd, dev) if pair is not None else None
     (a, g), (sa, sg) = bufs, strides
     a2, g2, sa2, sg2 = (pair[0][0], pair[0][1], pair[1][0], pair[1][1]) if pair is not None else (None, None, 0, 0)
-    macx._lib.check(L.macx_h2_wgrad(op, c.nt, c.R, c.Kd, c.Jd, c.nsplit, _p(a), sa, c.a_shared, _p(g), sg, _p(out.view),
-                                    _p(a2), sa2, c.a_shared, _p(g2), sg2, _p(out2.view) if out2 else None, _p(ws.view), need, None),
+    macx._lib.check(L.macx_h2_wgrad(op, c.nt, c.R, c.Kd, c.Jd, c.nsplit, ptr(a), sa, c.a_shared, ptr(g), sg, ptr(out.view),
+                                    ptr(a2), sa2, c.a_shared, ptr(g2), sg2, ptr(out2.view) if out2 else None, ptr(ws.view), need, None),
                     "macx_h2_wgrad")
     torch.cuda.synchronize()
     assert out.intact() and ws.intact() and (out2 is None or out2.intact()), "wrote outside its buffers"
@@ -130,7 +98,7 @@ def test_wgrad_h2(macx, dev, c):
     nta = 1 if c.a_shared else c.nt
     A1 = _round_trip(macx, dev, bufs[0], strides[0], nta, c.R, c.Kd).reshape(-1, c.Kd)
     G1 = _round_trip(macx, dev, bufs[1], strides[1], c.nt, c.R, c.Jd).reshape(-1, c.Jd)
-    assert _same_bits(A1[np.arange(M) % c.R] if c.a_shared else A1, o.A1) and _same_bits(G1, o.G1), "the format restatement is off"
+    assert bits_equal(A1[np.arange(M) % c.R] if c.a_shared else A1, o.A1) and bits_equal(G1, o.G1), "the format restatement is off"
     got, _ = _wgrad_call(macx, dev, c, bufs, strides)
     again, _ = _wgrad_call(macx, dev, c, bufs, strides)
     zero, _ = _wgrad_call(macx, dev, c, *_wgrad_buffers(macx, dev, c, 0))
@@ -147,18 +115,18 @@ def test_wgrad_h2(macx, dev, c):
     assert np.isfinite(got).all(), "not finite"
     assert worst <= 1.0
     assert (got[bound == 0] == 0).all()
-    assert _same_bits(got, again), "a second call differs"
-    assert _same_bits(got, zero), "NaN-filled pad rows change the result"
+    assert bits_equal(got, again), "a second call differs"
+    assert bits_equal(got, zero), "NaN-filled pad rows change the result"
     if (c.Kd, c.Jd) == (256, 256):
-        assert _same_bits(got, _wgrad_call(macx, dev, c, bufs, strides, o=_opts(macx, wgrad_pipe=0))[0]), "WGRAD_PIPE = 0 differs"
+        assert bits_equal(got, _wgrad_call(macx, dev, c, bufs, strides, o=abi_kit.opts(macx, wgrad_pipe=0))[0]), "WGRAD_PIPE = 0 differs"
         c2 = c._replace(seed=c.seed + 100)
         bufs2, strides2 = _wgrad_buffers(macx, dev, c2, 0xFF)
         single2, _ = _wgrad_call(macx, dev, c2, bufs2, strides2)
         o2 = hc.wgrad_operands(c2, *hc.wgrad_data(c2))
         assert float(hc.ratio(np.abs(single2.astype(np.float64) - hc.wgrad_reference(o2)), hc.wgrad_bound(c2, o2)[0]).max()) <= 1.0
         for pipe in (3, 2, 1):
-            p1, p2 = _wgrad_call(macx, dev, c, bufs, strides, o=_opts(macx, wgrad_pipe=pipe), pair=(bufs2, strides2))
-            assert _same_bits(p1, got) and _same_bits(p2, single2), "the pair form at WGRAD_PIPE = %d differs from two single calls" % pipe
+            p1, p2 = _wgrad_call(macx, dev, c, bufs, strides, o=abi_kit.opts(macx, wgrad_pipe=pipe), pair=(bufs2, strides2))
+            assert bits_equal(p1, got) and bits_equal(p2, single2), "the pair form at WGRAD_PIPE = %d differs from two single calls" % pipe
 
 
 # ================================================= sb_h2_kernel / sb_h2w_kernel ===================================================
@@ -175,12 +143,12 @@ def _sb_call(macx, dev, c, bufs, strides, o=None):
     op = C.byref(o) if o is not None else None
     need = L.macx_h2_sb_ws_floats(op, c.B, c.N, c.d, c.nsteps, c.qpg, c.wide)
     assert need == 2 * ((c.B + c.qpg - 1) // c.qpg) * c.d * c.d
-    ws, dA, dB = _Guarded(need, dev), _Guarded(c.d * c.d, dev), _Guarded(c.d * c.d, dev)
+    ws, dA, dB = Guarded(need, dev), Guarded(c.d * c.d, dev), Guarded(c.d * c.d, dev)
     nparts = 4 * c.d // 128
-    dyp = _Guarded(nparts * c.B * c.d, dev) if c.dy else None
+    dyp = Guarded(nparts * c.B * c.d, dev) if c.dy else None
     (x, g, y, W), (sx, sg) = bufs, strides
-    macx._lib.check(L.macx_h2_sb(op, c.B, c.N, c.d, c.nsteps, c.qpg, c.wide, _p(x), sx, _p(g), sg, _p(y), _p(W), _p(dA.view), _p(dB.view),
-                                 _p(dyp.view) if dyp else None, _p(ws.view), need, None), "macx_h2_sb")
+    macx._lib.check(L.macx_h2_sb(op, c.B, c.N, c.d, c.nsteps, c.qpg, c.wide, ptr(x), sx, ptr(g), sg, ptr(y), ptr(W), ptr(dA.view), ptr(dB.view),
+                                 ptr(dyp.view) if dyp else None, ptr(ws.view), need, None), "macx_h2_sb")
     torch.cuda.synchronize()
     assert dA.intact() and dB.intact() and ws.intact() and (dyp is None or dyp.intact()), "wrote outside its buffers"
     parts = dyp.np(nparts, c.B, c.d) if dyp else None
@@ -195,8 +163,8 @@ def _sb_case(macx, dev, c):
     bufs, strides = _sb_buffers(macx, dev, c, 0xFF)
     X1 = _round_trip(macx, dev, bufs[0], strides[0], c.nsteps, c.B * c.N, c.d)
     G1 = _round_trip(macx, dev, bufs[1], strides[1], c.nsteps, c.B * c.N, c.d)
-    assert _same_bits(X1.reshape(o.X1.shape), o.X1) and _same_bits(G1.reshape(o.G1.shape), o.G1), "the format restatement is off"
-    opts = _opts(macx, sb_cont=c.cont) if c.wide else None
+    assert bits_equal(X1.reshape(o.X1.shape), o.X1) and bits_equal(G1.reshape(o.G1.shape), o.G1), "the format restatement is off"
+    opts = abi_kit.opts(macx, sb_cont=c.cont) if c.wide else None
     got = _sb_call(macx, dev, c, bufs, strides, opts)
     again = _sb_call(macx, dev, c, bufs, strides, opts)
     zero = _sb_call(macx, dev, c, *_sb_buffers(macx, dev, c, 0), opts)
@@ -222,7 +190,7 @@ def _sb_case(macx, dev, c):
         assert worst <= 1.0, name
         assert (g[b == 0] == 0).all(), "%s: an element whose reference is exactly zero is not" % name
     for a, b, what in ((got, again, "a second call differs"), (got, zero, "NaN-filled pad rows change the result")):
-        assert all(_same_bits(u, v) for u, v in zip(a, b) if u is not None), what
+        assert all(bits_equal(u, v) for u, v in zip(a, b) if u is not None), what
     return got, ref, bound, bufs, strides
 
 
@@ -235,8 +203,8 @@ def test_sb_h2(macx, dev, c):
 def test_sb_h2w(macx, dev, c):
     got, ref, bound, bufs, strides = _sb_case(macx, dev, c)
     if hc.sb_cont(c.nsteps, c.N, c.qpg, c.cont):
-        per_step = _sb_call(macx, dev, c, bufs, strides, _opts(macx, sb_cont=0))
-        assert _same_bits(got[0], per_step[0]) and _same_bits(got[1], per_step[1]), "SB_CONT = 0 differs from the continuous stream"
+        per_step = _sb_call(macx, dev, c, bufs, strides, abi_kit.opts(macx, sb_cont=0))
+        assert bits_equal(got[0], per_step[0]) and bits_equal(got[1], per_step[1]), "SB_CONT = 0 differs from the continuous stream"
     if c in hc.BOTH_CASES:
         n = c._replace(wide=0)
         X, G, y, W = hc.sb_data(c)

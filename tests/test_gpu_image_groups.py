@@ -5,53 +5,32 @@ in training with a stem that keeps everything, and `CapturedTowerForward(images=
 Shapes of the kernel tests: the smallest legal call (one quad); 5 x 132 = 660 floats per block (165 quads: no multiple of the
 256-quad or the 1024-quad chunk) with an unsorted, repeating index that leaves one image out; and the workload's block (196 x 512
 floats: 25 forward chunks, 98 backward chunks per block) for B = 64."""
-import ctypes as C
-
 import pytest
 import torch
 
+from abi_kit import SENT, Guarded, bits_equal, ptr
 from helpers import rel_err, max_abs
 from test_gpu_encoder import make_questions
 
 pytestmark = pytest.mark.gpu
 
 GRAD_TOL = 3e-5     # the project's gradient bound (tests/test_gpu_configs.py): relative to each tensor's largest entry
-SENTINEL = -12345.0
-PAD = 64            # guard floats in front of and behind an output (a multiple of 4: the output stays 16-byte aligned)
 CASES = {"one quad": (1, 1, 1, 4, [0]),
          "odd block, image 3 unused": (4, 7, 5, 132, [2, 0, 0, 1, 2, 2, 0]),
          "workload block": (2, 64, 196, 512, [b % 2 for b in range(64)])}
 
 
-def p_(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def bits_equal(a, b):
-    """same bits (torch.equal would take -0.0 for +0.0 and refuse equal NaNs)"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def guarded(n, dev, fill=SENTINEL):
-    """(whole buffer, the n-float output inside it) with PAD sentinel floats on either side"""
-    buf = torch.full((n + 2 * PAD,), SENTINEL, device=dev)
-    out = buf[PAD:PAD + n]
-    out.fill_(fill)
-    assert out.data_ptr() % 16 == 0
-    return buf, out
-
-
-def guards_intact(buf):
-    return bool((buf[:PAD] == SENTINEL).all()) and bool((buf[-PAD:] == SENTINEL).all())
-
-
-def gather(macx, src, index, G, B, N, d, dev, bwd=False, fill=SENTINEL):
-    """one call of macx_kb_gather (src [G,N,d] -> [B,N,d]) or macx_kb_gather_bwd (src [B,N,d] -> [G,N,d]) into a guarded output"""
+def gather(macx, src, index, G, B, N, d, dev, bwd=False, fill=None):
+    """one call of macx_kb_gather (src [G,N,d] -> [B,N,d]) or macx_kb_gather_bwd (src [B,N,d] -> [G,N,d]) into a guarded output
+    (pre-filled with `fill`) -> (return code, the Guarded, the output)"""
     L = macx._lib.lib()
     rows = G if bwd else B
-    buf, out = guarded(rows * N * d, dev, fill)
+    buf = Guarded(rows * N * d, dev)
+    out = buf.view
+    if fill is not None:
+        out.fill_(fill)
     f = L.macx_kb_gather_bwd if bwd else L.macx_kb_gather
-    rc = f(p_(src), p_(index), G, B, N, d, p_(out), None)
+    rc = f(ptr(src), ptr(index), G, B, N, d, ptr(out), None)
     torch.cuda.synchronize()
     return rc, buf, out.view(rows, N, d)
 
@@ -65,7 +44,7 @@ def test_gather_forward_equals_indexing(macx, dev, case):
     rc, buf, kb = gather(macx, src, idx, G, B, N, d, dev)
     assert rc == 0
     assert torch.equal(kb, src[idx.long()])
-    assert guards_intact(buf)                                   # nothing outside kb[0 .. B*N*d) is written
+    assert buf.intact()                                         # nothing outside kb[0 .. B*N*d) is written
     rc2, _, kb2 = gather(macx, src, idx, G, B, N, d, dev)
     assert rc2 == 0 and bits_equal(kb, kb2)                     # calling twice: identical bits
 
@@ -80,7 +59,7 @@ def test_gather_forward_poisons_an_index_out_of_range(macx, dev, case, at, bad):
     src = torch.randn(G, N, d, generator=torch.Generator().manual_seed(2)).to(dev)
     idx = torch.tensor(index, dtype=torch.int32, device=dev)
     rc, buf, kb = gather(macx, src, idx, G, B, N, d, dev)
-    assert rc == 0 and guards_intact(buf)
+    assert rc == 0 and buf.intact()
     assert bool(torch.isnan(kb[at]).all())
     assert bool((kb[at].view(torch.int32) == 0x7FC00000).all())
     others = [b for b in range(B) if b != at]
@@ -113,7 +92,7 @@ def test_gather_backward_equals_the_ascending_sum(macx, dev, backward_cases, cas
     dkb, want = backward_cases[case]
     idx = torch.tensor(index, dtype=torch.int32, device=dev)
     rc, buf, got = gather(macx, dkb.to(dev), idx, G, B, N, d, dev, bwd=True, fill=float("nan"))      # output pre-filled with NaN
-    assert rc == 0 and guards_intact(buf)
+    assert rc == 0 and buf.intact()
     assert torch.equal(got.cpu(), want)                         # ascending b, plain fp32 adds: bit for bit
     for g in set(range(G)) - set(index):                        # an image no question names: exactly zero, every element written
         assert bool((got[g].view(torch.int32) == 0).all())
@@ -153,18 +132,18 @@ def test_kb_gather_function_agrees_with_index_select(macx, dev, case):
 def test_gather_refusals(macx, dev):
     L = macx._lib.lib()
     EINVAL = macx._lib.MACX_EINVAL
-    src, out = torch.zeros(2, 3, 4, device=dev), torch.full((5, 3, 4), SENTINEL, device=dev)
+    src, out = torch.zeros(2, 3, 4, device=dev), torch.full((5, 3, 4), SENT, device=dev)
     idx = torch.zeros(5, dtype=torch.int32, device=dev)
     for f in (L.macx_kb_gather, L.macx_kb_gather_bwd):
-        assert f(p_(src), p_(idx), 2, 5, 3, 2, p_(out), None) == EINVAL         # N * d = 6: no whole number of 16-byte quads
-        assert f(p_(src), p_(idx), 0, 5, 3, 4, p_(out), None) == EINVAL         # G = 0
-        assert f(p_(src), p_(idx), 2, 0, 3, 4, p_(out), None) == EINVAL
-        assert f(None, p_(idx), 2, 5, 3, 4, p_(out), None) == EINVAL            # a null pointer, each of the three
-        assert f(p_(src), None, 2, 5, 3, 4, p_(out), None) == EINVAL
-        assert f(p_(src), p_(idx), 2, 5, 3, 4, None, None) == EINVAL
+        assert f(ptr(src), ptr(idx), 2, 5, 3, 2, ptr(out), None) == EINVAL         # N * d = 6: no whole number of 16-byte quads
+        assert f(ptr(src), ptr(idx), 0, 5, 3, 4, ptr(out), None) == EINVAL         # G = 0
+        assert f(ptr(src), ptr(idx), 2, 0, 3, 4, ptr(out), None) == EINVAL
+        assert f(None, ptr(idx), 2, 5, 3, 4, ptr(out), None) == EINVAL            # a null pointer, each of the three
+        assert f(ptr(src), None, 2, 5, 3, 4, ptr(out), None) == EINVAL
+        assert f(ptr(src), ptr(idx), 2, 5, 3, 4, None, None) == EINVAL
     torch.cuda.synchronize()
-    assert bool((out == SENTINEL).all())                                        # nothing was launched
-    assert L.macx_kb_gather(p_(src), p_(idx), 2, 5, 3, 4, p_(out), None) == 0   # (the legal call of the same buffers)
+    assert bool((out == SENT).all())                                        # nothing was launched
+    assert L.macx_kb_gather(ptr(src), ptr(idx), 2, 5, 3, 4, ptr(out), None) == 0   # (the legal call of the same buffers)
     torch.cuda.synchronize()
     assert torch.equal(out, src[idx.long()])
 

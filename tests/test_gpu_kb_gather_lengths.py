@@ -6,15 +6,13 @@ Shapes (G, B, N, d): (3, 5, 9, 8) -- a block of 18 quads, far below one 1,024-qu
 64 starts exactly at quad 1,024 and the sizes 1 / 64 / 65 / 70 put the live / padded boundary before, on and behind a chunk edge
 (and 64 rows = 1,024 quads = four of the backward kernel's 256-quad chunks).  Sizes 0 and N + 3 exercise the clamp.  The padded rows
 of every source hold NaN: a kernel that read them would show it."""
-import ctypes as C
-
 import pytest
 import torch
 
+from abi_kit import Guarded, bits_equal, ptr
+
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -12345.0
-PAD = 64
 SMALL, EDGE = (3, 5, 9, 8), (3, 5, 70, 64)
 # (shape, index, image_lengths)
 CASES = {"small, image 1 unnamed": (SMALL, [2, 0, 0, 2, 0], [4, 9, 1]),
@@ -27,27 +25,6 @@ CASES = {"small, image 1 unnamed": (SMALL, [2, 0, 0, 2, 0], [4, 9, 1]),
          "edge, index out of range": (EDGE, [3, 0, 1, -1, 0], [64, 65, 1])}
 
 
-def p_(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def bits_equal(a, b):
-    """same bits (torch.equal would take -0.0 for +0.0 and refuse equal NaNs)"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def guarded(n, dev, fill=SENTINEL, dtype=torch.float32):
-    buf = torch.full((n + 2 * PAD,), SENTINEL, device=dev).to(dtype)
-    out = buf[PAD:PAD + n]
-    out.fill_(fill)
-    assert out.data_ptr() % 16 == 0
-    return buf, out
-
-
-def guards_intact(buf):
-    return bool((buf[:PAD] == int(SENTINEL)).all()) and bool((buf[-PAD:] == int(SENTINEL)).all())
-
-
 def clamp(lengths, N):
     return [min(max(x, 1), N) for x in lengths]
 
@@ -55,17 +32,18 @@ def clamp(lengths, N):
 def forward(macx, src, index, lengths, shape, dev):
     """macx_kb_gather_l into guarded outputs: (rc, kb buffer, kb [B,N,d], lengths buffer, kb_lengths [B])"""
     G, B, N, d = shape
-    kbuf, kb = guarded(B * N * d, dev, float("nan"))
-    lbuf, kbl = guarded(B, dev, -7, dtype=torch.int32)
-    rc = macx._lib.lib().macx_kb_gather_l(p_(src), p_(index), p_(lengths), G, B, N, d, p_(kb), p_(kbl), None)
+    kbuf, lbuf = Guarded(B * N * d, dev), Guarded(B, dev, dtype=torch.int32, fill=-12345)      # (the default sentinel is no int32)
+    kb, kbl = kbuf.view.fill_(float("nan")), lbuf.view.fill_(-7)                                # the outputs' pre-fill
+    rc = macx._lib.lib().macx_kb_gather_l(ptr(src), ptr(index), ptr(lengths), G, B, N, d, ptr(kb), ptr(kbl), None)
     torch.cuda.synchronize()
     return rc, kbuf, kb.view(B, N, d), lbuf, kbl
 
 
 def backward(macx, dkb, index, lengths, shape, dev):
     G, B, N, d = shape
-    buf, out = guarded(G * N * d, dev, float("nan"))
-    rc = macx._lib.lib().macx_kb_gather_bwd_l(p_(dkb), p_(index), p_(lengths), G, B, N, d, p_(out), None)
+    buf = Guarded(G * N * d, dev)
+    out = buf.view.fill_(float("nan"))
+    rc = macx._lib.lib().macx_kb_gather_bwd_l(ptr(dkb), ptr(index), ptr(lengths), G, B, N, d, ptr(out), None)
     torch.cuda.synchronize()
     return rc, buf, out.view(G, N, d)
 
@@ -105,7 +83,7 @@ def test_forward_copies_the_live_rows_and_zeroes_the_rest(macx, dev, data, case)
     src, want, want_len, _, _ = data[case]
     idx, lens = torch.tensor(index, dtype=torch.int32, device=dev), torch.tensor(lengths, dtype=torch.int32, device=dev)
     rc, kbuf, kb, lbuf, kbl = forward(macx, src.to(dev), idx, lens, shape, dev)
-    assert rc == 0 and guards_intact(kbuf) and guards_intact(lbuf)
+    assert rc == 0 and kbuf.intact() and lbuf.intact()
     assert bits_equal(kb.cpu(), want)                     # +0.0 by bit pattern in the padded rows; NaN only for an index out of range
     assert torch.equal(kbl.cpu(), want_len)
     L = clamp(lengths, N)
@@ -124,7 +102,7 @@ def test_backward_sums_the_live_rows_and_zeroes_the_rest(macx, dev, data, case):
     _, _, _, dkb, want = data[case]
     idx, lens = torch.tensor(index, dtype=torch.int32, device=dev), torch.tensor(lengths, dtype=torch.int32, device=dev)
     rc, buf, got = backward(macx, dkb.to(dev), idx, lens, shape, dev)
-    assert rc == 0 and guards_intact(buf)
+    assert rc == 0 and buf.intact()
     assert torch.equal(got.cpu(), want)                   # ascending b, plain fp32 adds: bit for bit; no NaN came through
     L = clamp(lengths, N)
     for i in range(G):
@@ -144,13 +122,13 @@ def test_null_lengths_are_the_plain_gather(macx, dev, shape, index):
     idx = torch.tensor(index, dtype=torch.int32, device=dev)
     rc, kbuf, kb, lbuf, kbl = forward(macx, src, idx, None, shape, dev)
     plain = torch.full((B, N, d), float("nan"), device=dev)
-    assert rc == 0 and L.macx_kb_gather(p_(src), p_(idx), G, B, N, d, p_(plain), None) == 0
+    assert rc == 0 and L.macx_kb_gather(ptr(src), ptr(idx), G, B, N, d, ptr(plain), None) == 0
     rc, buf, got = backward(macx, dkb, idx, None, shape, dev)
     plain_bwd = torch.full((G, N, d), float("nan"), device=dev)
-    assert rc == 0 and L.macx_kb_gather_bwd(p_(dkb), p_(idx), G, B, N, d, p_(plain_bwd), None) == 0
+    assert rc == 0 and L.macx_kb_gather_bwd(ptr(dkb), ptr(idx), G, B, N, d, ptr(plain_bwd), None) == 0
     torch.cuda.synchronize()
     assert bits_equal(kb, plain) and bits_equal(got, plain_bwd)
-    assert guards_intact(kbuf) and guards_intact(buf) and guards_intact(lbuf)
+    assert kbuf.intact() and buf.intact() and lbuf.intact()
     assert bool((kbl == -7).all())                        # without lengths there are none to hand on
 
 
@@ -174,10 +152,10 @@ def test_refusals(macx, dev):
     x, out = torch.zeros(2 * 2 * 6, device=dev), torch.zeros(2 * 2 * 6, device=dev)
     idx, lens, kbl = [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(3)]
     # N * d = 12 is a multiple of 4, d = 6 is not: a row is no whole number of 16-byte quads
-    assert L.macx_kb_gather_l(p_(x), p_(idx), p_(lens), 2, 2, 2, 6, p_(out), p_(kbl), None) == macx._lib.MACX_EINVAL
-    assert L.macx_kb_gather_bwd_l(p_(x), p_(idx), p_(lens), 2, 2, 2, 6, p_(out), None) == macx._lib.MACX_EINVAL
-    assert L.macx_kb_gather_l(p_(x), p_(idx), p_(lens), 2, 2, 3, 4, p_(out), None, None) == macx._lib.MACX_EINVAL    # no kb_lengths_out
-    assert L.macx_kb_gather_l(p_(x), p_(idx), p_(lens), 0, 2, 3, 4, p_(out), p_(kbl), None) == macx._lib.MACX_EINVAL
+    assert L.macx_kb_gather_l(ptr(x), ptr(idx), ptr(lens), 2, 2, 2, 6, ptr(out), ptr(kbl), None) == macx._lib.MACX_EINVAL
+    assert L.macx_kb_gather_bwd_l(ptr(x), ptr(idx), ptr(lens), 2, 2, 2, 6, ptr(out), None) == macx._lib.MACX_EINVAL
+    assert L.macx_kb_gather_l(ptr(x), ptr(idx), ptr(lens), 2, 2, 3, 4, ptr(out), None, None) == macx._lib.MACX_EINVAL    # no kb_lengths_out
+    assert L.macx_kb_gather_l(ptr(x), ptr(idx), ptr(lens), 0, 2, 3, 4, ptr(out), ptr(kbl), None) == macx._lib.MACX_EINVAL
     torch.cuda.synchronize()
     assert bool((out == 0).all())                         # nothing was launched
 
@@ -218,8 +196,8 @@ def test_kb_gather_function_without_lengths_is_the_plain_export(macx, dev, N, d)
     assert type(kb) is torch.Tensor
     kb.backward(dout)
     want, want_grad = torch.full((B, N, d), float("nan"), device=dev), torch.full((G, N, d), float("nan"), device=dev)
-    assert L.macx_kb_gather(p_(x.detach()), p_(idx), G, B, N, d, p_(want), None) == 0
-    assert L.macx_kb_gather_bwd(p_(dout), p_(idx), G, B, N, d, p_(want_grad), None) == 0
+    assert L.macx_kb_gather(ptr(x.detach()), ptr(idx), G, B, N, d, ptr(want), None) == 0
+    assert L.macx_kb_gather_bwd(ptr(dout), ptr(idx), G, B, N, d, ptr(want_grad), None) == 0
     torch.cuda.synchronize()
     assert bits_equal(kb.detach(), want) and bits_equal(x.grad, want_grad)
     assert bool((x.grad[0].view(torch.int32) == 0).all())

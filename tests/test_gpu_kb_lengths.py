@@ -14,11 +14,10 @@ T4  the same on PaddedMACCell (d = 200) and on the generic path (the reference's
 T5  what the padded rows hold (zeros against 1e3 N(0,1)) does not reach the forward pass; gradients agree within GRAD_TOL
 T6  MACNet.forward(kb_lengths=) is encoder -> stem -> MACCell(kb_lengths=) -> output unit, bit for bit; range, shape, device errors
 """
-import ctypes as C
-
 import pytest
 import torch
 
+from abi_kit import bits, ptr
 from oracle import mac_oracle as mo
 from helpers import make_case, oracle_run, rel_err, max_abs, default_gemm_mode
 from kb_lengths_ref import masked_kb_attention
@@ -28,14 +27,6 @@ pytestmark = pytest.mark.gpu
 FWD_TOL = 2e-5     # tests/test_gpu_cell.py
 GRAD_TOL = 2e-4
 ATT_TOL = 2e-6
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
 
 
 # ================================================= T0 ==============================================================================
@@ -69,7 +60,7 @@ def test_t0_zero_row_in_a_contraction(macx, dev, M, zero_in):
             ns = L.macx_wgrad_splits(M, Kd, Jd)
             out = torch.empty(Kd, Jd, device=dev)
             ws = torch.empty(ns * Kd * Jd, device=dev)
-            macx._lib.check(L.macx_wgrad(_p(Ad), Kd, _p(Gd), Jd, M, Kd, Jd, _p(out), _p(ws), None), "wgrad")
+            macx._lib.check(L.macx_wgrad(ptr(Ad), Kd, ptr(Gd), Jd, M, Kd, Jd, ptr(out), ptr(ws), None), "wgrad")
             torch.cuda.synchronize()
             e = (out.cpu().double() - ref).abs() / S
             stats[mode] = (float(e.max()), float(e.mean()))
@@ -113,9 +104,9 @@ def test_t1_kb_attend_kernel_with_lengths(macx, dev, B, N, d, lengths):
         lo, kbt = lo.to(dev), kbt.to(dev)
         att, info = torch.full((B, N), 7.0, device=dev), torch.full((B, d), 7.0, device=dev)
         if ln is False:
-            macx._lib.check(L.macx_kb_attend_fwd(B, N, d, _p(lo), _p(bi), _p(kbt), _p(att), _p(info), None), "fwd")
+            macx._lib.check(L.macx_kb_attend_fwd(B, N, d, ptr(lo), ptr(bi), ptr(kbt), ptr(att), ptr(info), None), "fwd")
         else:
-            macx._lib.check(L.macx_kb_attend_fwd_l(B, N, d, _p(lo), _p(bi), _p(kbt), _p(ln), _p(att), _p(info), None), "fwd_l")
+            macx._lib.check(L.macx_kb_attend_fwd_l(B, N, d, ptr(lo), ptr(bi), ptr(kbt), ptr(ln), ptr(att), ptr(info), None), "fwd_l")
         torch.cuda.synchronize()
         return att, info
 
@@ -123,16 +114,16 @@ def test_t1_kb_attend_kernel_with_lengths(macx, dev, B, N, d, lengths):
     assert torch.isfinite(att).all() and torch.isfinite(info).all()
     assert rel(att, att_ref) < 1e-5 and rel(info, info_ref) < 1e-5
     for b, n in enumerate(live):
-        assert bool((_bits(att[b, n:]) == 0).all()), "padded attention of question %d is not +0.0" % b
+        assert bool((bits(att[b, n:]) == 0).all()), "padded attention of question %d is not +0.0" % b
     # the padding's content is not an input: the clean tensors give the same bits
     att2, info2 = run(logits, kb, lens)
-    assert torch.equal(_bits(att), _bits(att2)) and torch.equal(_bits(info), _bits(info2))
+    assert torch.equal(bits(att), bits(att2)) and torch.equal(bits(info), bits(info2))
     # every length N, and no lengths at all (NULL), are macx_kb_attend_fwd bit for bit
     plain = run(logits, kb, False)
     for ln in (torch.full((B,), N, dtype=torch.int32, device=dev), None):
         full = run(logits, kb, ln)
-        assert torch.equal(_bits(full[0]), _bits(plain[0])) and torch.equal(_bits(full[1]), _bits(plain[1]))
-    assert L.macx_kb_attend_fwd_l(B, 1025, d, _p(logits.to(dev)), _p(bi), _p(kb.to(dev)), _p(lens), _p(att), _p(info), None) == macx._lib.MACX_EINVAL
+        assert torch.equal(bits(full[0]), bits(plain[0])) and torch.equal(bits(full[1]), bits(plain[1]))
+    assert L.macx_kb_attend_fwd_l(B, 1025, d, ptr(logits.to(dev)), ptr(bi), ptr(kb.to(dev)), ptr(lens), ptr(att), ptr(info), None) == macx._lib.MACX_EINVAL
 
 
 # ================================================= cells ===========================================================================
@@ -236,14 +227,14 @@ def test_t2_full_lengths_are_the_cell_without_lengths(macx, dev, name, B, S, N, 
         cell, params, inputs = _build(macx, dev, cfg, vq, words, lengths, kb, True, kl)
         runs.append((cell, _run(cell, dmem, dctl, dev), params, inputs))
     (c0, s0, p0, i0), (c1, s1, p1, i1) = runs
-    assert torch.equal(_bits(s0.memory), _bits(s1.memory)) and torch.equal(_bits(s0.control), _bits(s1.control))
+    assert torch.equal(bits(s0.memory), bits(s1.memory)) and torch.equal(bits(s0.control), bits(s1.control))
     for k in ("kb", "question"):
         for a, b in zip(c0.attentions[k], c1.attentions[k]):
-            assert torch.equal(_bits(a), _bits(b)), k
+            assert torch.equal(bits(a), bits(b)), k
     for a, b in zip(i0, i1):
-        assert torch.equal(_bits(a.grad), _bits(b.grad))
+        assert torch.equal(bits(a.grad), bits(b.grad))
     for f in p0.fields:
-        assert torch.equal(_bits(getattr(p0, f).grad), _bits(getattr(p1, f).grad)), f
+        assert torch.equal(bits(getattr(p0, f).grad), bits(getattr(p1, f).grad)), f
 
 
 # ================================================= T3 ==============================================================================
@@ -323,10 +314,10 @@ def test_t5_padding_content_does_not_matter(macx, dev, name, B, S, N, d, p, kb_l
         cell, params, inputs = _build(macx, dev, cfg, vq, words, lengths, k, True, kb_lengths)
         runs.append((cell, _run(cell, dmem, dctl, dev), params, inputs))
     (c0, s0, p0, i0), (c1, s1, p1, i1) = runs
-    assert torch.equal(_bits(s0.memory), _bits(s1.memory)) and torch.equal(_bits(s0.control), _bits(s1.control))
+    assert torch.equal(bits(s0.memory), bits(s1.memory)) and torch.equal(bits(s0.control), bits(s1.control))
     for k in ("kb", "question"):
         for a, b in zip(c0.attentions[k], c1.attentions[k]):
-            assert torch.equal(_bits(a), _bits(b)), k
+            assert torch.equal(bits(a), bits(b)), k
     errs = {"input %d" % j: rel_err(b.grad, a.grad) for j, (a, b) in enumerate(zip(i0, i1))}
     for f in p0.fields:
         floor = 5e-2 if f in ("kbLogits_b", "ctrlLogits_b", "selfLogits_b") else 1e-6      # softmax logit biases: analytically zero
@@ -366,9 +357,9 @@ def test_t6_tower_passes_kb_lengths_to_the_cell(macx, dev):
                             train=True, config=cfg, params=net.cell, netLength=p, seed=21, b0=0, kb_lengths=kl)
         by_hand = net.out(cell.run().memory, vecQ, train=True, seed=21, b0=0)
     torch.cuda.synchronize()
-    assert torch.equal(_bits(logits), _bits(by_hand))
-    assert not torch.equal(_bits(logits), _bits(plain))                     # the lengths arrived
-    assert torch.equal(_bits(logits[0]), _bits(plain[0]))                   # ... and question 0, all of whose cells are live, is unchanged
+    assert torch.equal(bits(logits), bits(by_hand))
+    assert not torch.equal(bits(logits), bits(plain))                     # the lengths arrived
+    assert torch.equal(bits(logits[0]), bits(plain[0]))                   # ... and question 0, all of whose cells are live, is unchanged
     for a in masked_cell.attentions["kb"]:
         assert bool((a[1, 1:] == 0).all()) and bool((a[2, 7:] == 0).all())
 

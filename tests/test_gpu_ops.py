@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_kit import ptr, stream
 from oracle import dropout_hash as dh
 from helpers import make_case
 from test_gpu_cell import build_cell
@@ -25,14 +26,6 @@ ADD, MUL = 0, 1
 B_SAME, B_MID, B_CHANNEL, B_ROW = 0, 1, 2, 3
 R_MID, R_LAST, R_ROWS = 0, 1, 2
 SITE_ENC_INPUT = 11
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _ulps(got, ref64):
@@ -111,8 +104,8 @@ def test_op_act_forward_and_backward(macx, dev, aname, act, n):
         ad = alpha.to(dev) if alpha is not None else None
         out, dx = torch.full((n,), float("nan"), device=dev), torch.full((n,), float("nan"), device=dev)
         de = torch.full((n,), float("nan"), device=dev) if act == PRELU else None
-        macx._lib.check(L.macx_op_act(act, _p(xd), _p(ad), n, inner, _p(out), _st(dev)), "macx_op_act")
-        macx._lib.check(L.macx_op_act_bwd(act, _p(xd), _p(ad), _p(dyd), n, inner, _p(dx), _p(de), _st(dev)), "macx_op_act_bwd")
+        macx._lib.check(L.macx_op_act(act, ptr(xd), ptr(ad), n, inner, ptr(out), stream(dev)), "macx_op_act")
+        macx._lib.check(L.macx_op_act_bwd(act, ptr(xd), ptr(ad), ptr(dyd), n, inner, ptr(dx), ptr(de), stream(dev)), "macx_op_act_bwd")
         torch.cuda.synchronize()
         x64 = x.double().requires_grad_(True)
         a64 = alpha.double().requires_grad_(True) if alpha is not None else None
@@ -152,8 +145,8 @@ def test_prelu_dalpha_after_rows_reduction(macx, dev, rows, inner):
     dx, de = torch.empty(n, device=dev), torch.empty(n, device=dev)
     ws = torch.full((64 * inner,), float("nan"), device=dev)
     da = torch.full((inner,), float("nan"), device=dev)
-    macx._lib.check(L.macx_op_act_bwd(PRELU, _p(xd), _p(ad), _p(dyd), n, inner, _p(dx), _p(de), _st(dev)), "macx_op_act_bwd")
-    macx._lib.check(L.macx_op_reduce(R_ROWS, _p(de), rows, 1, inner, _p(da), _p(ws), _st(dev)), "macx_op_reduce")
+    macx._lib.check(L.macx_op_act_bwd(PRELU, ptr(xd), ptr(ad), ptr(dyd), n, inner, ptr(dx), ptr(de), stream(dev)), "macx_op_act_bwd")
+    macx._lib.check(L.macx_op_reduce(R_ROWS, ptr(de), rows, 1, inner, ptr(da), ptr(ws), stream(dev)), "macx_op_reduce")
     torch.cuda.synchronize()
     x64, a64 = x.double(), alpha.double().requires_grad_(True)
     _act_ref(PRELU, x64, a64, inner).backward(dy.double())
@@ -189,7 +182,7 @@ def test_op_binary(macx, dev, op, bmode, shape):
     scale = float(np.float32(0.37))
     ad, bd = a.to(dev), b.to(dev)
     out = torch.full((n,), float("nan"), device=dev)
-    macx._lib.check(L.macx_op_binary(op, bmode, _p(ad), _p(bd), n, mid, inner, scale, _p(out), _st(dev)), "macx_op_binary")
+    macx._lib.check(L.macx_op_binary(op, bmode, ptr(ad), ptr(bd), n, mid, inner, scale, ptr(out), stream(dev)), "macx_op_binary")
     torch.cuda.synchronize()
     ref = scale * (a3 * bb if op == MUL else a3 + bb)          # (fl(a + b) is within 2^-24 of the SUM: cancellation costs nothing)
     _assert_ulps(out.reshape(a3.shape), ref, "binary %s mode %d %s" % ("MUL" if op == MUL else "ADD", bmode, shape))
@@ -199,10 +192,10 @@ def test_op_binary_refuses_a_size_its_broadcast_does_not_divide(macx, dev):
     L = macx._lib.lib()
     a = torch.zeros(100, device=dev)
     out = torch.zeros(100, device=dev)
-    assert L.macx_op_binary(ADD, B_MID, _p(a), _p(a), 100, 5, 7, 1.0, _p(out), _st(dev)) == macx._lib.MACX_EINVAL
-    assert L.macx_op_binary(MUL, B_CHANNEL, _p(a), _p(a), 100, 1, 7, 1.0, _p(out), _st(dev)) == macx._lib.MACX_EINVAL
-    assert L.macx_op_binary(MUL, B_ROW, _p(a), _p(a), 100, 1, 7, 1.0, _p(out), _st(dev)) == macx._lib.MACX_EINVAL
-    assert L.macx_op_binary(MUL, B_MID, _p(a), _p(a), 100, 5, 10, 1.0, _p(out), _st(dev)) == macx._lib.MACX_OK
+    assert L.macx_op_binary(ADD, B_MID, ptr(a), ptr(a), 100, 5, 7, 1.0, ptr(out), stream(dev)) == macx._lib.MACX_EINVAL
+    assert L.macx_op_binary(MUL, B_CHANNEL, ptr(a), ptr(a), 100, 1, 7, 1.0, ptr(out), stream(dev)) == macx._lib.MACX_EINVAL
+    assert L.macx_op_binary(MUL, B_ROW, ptr(a), ptr(a), 100, 1, 7, 1.0, ptr(out), stream(dev)) == macx._lib.MACX_EINVAL
+    assert L.macx_op_binary(MUL, B_MID, ptr(a), ptr(a), 100, 5, 10, 1.0, ptr(out), stream(dev)) == macx._lib.MACX_OK
     torch.cuda.synchronize()
 
 
@@ -213,7 +206,7 @@ def _reduce(macx, dev, mode, x, outer, mid, inner, n_out):
     for _ in range(2):
         out = torch.full((n_out,), float("nan"), device=dev)
         ws = torch.full((64 * inner,), float("nan"), device=dev) if mode == R_ROWS else None      # (NaN: an unwritten split would show)
-        macx._lib.check(L.macx_op_reduce(mode, _p(xd), outer, mid, inner, _p(out), _p(ws), _st(dev)), "macx_op_reduce")
+        macx._lib.check(L.macx_op_reduce(mode, ptr(xd), outer, mid, inner, ptr(out), ptr(ws), stream(dev)), "macx_op_reduce")
         torch.cuda.synchronize()
         outs.append(out.cpu())
     assert torch.equal(outs[0], outs[1])                    # fixed summation order
@@ -296,7 +289,7 @@ def test_op_softmax_forward_and_backward(macx, dev, rows, n):
     for what, lens, rpl in variants:
         ld = torch.tensor(lens, dtype=torch.int32, device=dev) if lens is not None else None
         out = torch.full((rows, n), float("nan"), device=dev)
-        macx._lib.check(L.macx_op_softmax(_p(xd), _p(ld), rpl, rows, n, _p(out), _st(dev)), "macx_op_softmax")
+        macx._lib.check(L.macx_op_softmax(ptr(xd), ptr(ld), rpl, rows, n, ptr(out), stream(dev)), "macx_op_softmax")
         torch.cuda.synchronize()
         row_len = torch.tensor(lens).repeat_interleave(rpl)[:rows] if lens is not None else torch.full((rows,), n)
         x64 = x.double().requires_grad_(True)
@@ -313,7 +306,7 @@ def test_op_softmax_forward_and_backward(macx, dev, rows, n):
         a32 = a64.detach().to(torch.float32)
         dx = torch.full((rows, n), float("nan"), device=dev)
         a32d = a32.to(dev)
-        macx._lib.check(L.macx_op_softmax_bwd(_p(a32d), _p(dad), rows, n, _p(dx), _st(dev)), "macx_op_softmax_bwd")
+        macx._lib.check(L.macx_op_softmax_bwd(ptr(a32d), ptr(dad), rows, n, ptr(dx), stream(dev)), "macx_op_softmax_bwd")
         torch.cuda.synchronize()
         a64.backward(da.double())
         ad = a64.detach()
@@ -331,7 +324,7 @@ def test_op_softmax_row_of_length_zero_is_nan(macx, dev, n):
     lens = torch.tensor([n, 0, 1], dtype=torch.int32)
     xd, ld = x.to(dev), lens.to(dev)
     out = torch.full((3, n), 7.0, device=dev)
-    macx._lib.check(L.macx_op_softmax(_p(xd), _p(ld), 1, 3, n, _p(out), _st(dev)), "macx_op_softmax")
+    macx._lib.check(L.macx_op_softmax(ptr(xd), ptr(ld), 1, 3, n, ptr(out), stream(dev)), "macx_op_softmax")
     torch.cuda.synchronize()
     got = out.cpu()
     assert bool(torch.isnan(got[1]).all())
@@ -351,10 +344,10 @@ def test_op_dropout_matches_the_numpy_stream(macx, dev, first, n):
     for word in (None, 0xC0FFEE11):
         out = torch.full((n,), float("nan"), device=dev)
         if word is None:
-            rc = L.macx_op_dropout(_p(xd), n, seed, site, step, keep, first, _p(out), _st(dev))
+            rc = L.macx_op_dropout(ptr(xd), n, seed, site, step, keep, first, ptr(out), stream(dev))
         else:
             wt = torch.tensor([word - (1 << 32)], dtype=torch.int32, device=dev)
-            rc = L.macx_op_dropout_w(_p(xd), n, seed, site, step, keep, first, _p(wt), _p(out), _st(dev))
+            rc = L.macx_op_dropout_w(ptr(xd), n, seed, site, step, keep, first, ptr(wt), ptr(out), stream(dev))
         macx._lib.check(rc, "macx_op_dropout")
         torch.cuda.synchronize()
         mask = torch.from_numpy(dh.keep_mask(seed, site, step, keep, first, n, word=word or 0))
@@ -371,11 +364,11 @@ def test_op_dropout_keep_one_is_the_identity_and_bad_keeps_are_refused(macx, dev
     x[:3] = torch.tensor([0.0, -0.0, 1e-30])
     xd = x.to(dev)
     out = torch.full((n,), float("nan"), device=dev)
-    macx._lib.check(L.macx_op_dropout(_p(xd), n, 7, 5, 0, 1.0, 2 ** 32 - 5, _p(out), _st(dev)), "macx_op_dropout")
+    macx._lib.check(L.macx_op_dropout(ptr(xd), n, 7, 5, 0, 1.0, 2 ** 32 - 5, ptr(out), stream(dev)), "macx_op_dropout")
     torch.cuda.synchronize()
     assert torch.equal(out.cpu().view(torch.int32), x.view(torch.int32))
     for keep in (0.0, -0.1, 1.5, float("nan")):
-        assert L.macx_op_dropout(_p(xd), n, 7, 5, 0, keep, 0, _p(out), _st(dev)) == macx._lib.MACX_EINVAL
+        assert L.macx_op_dropout(ptr(xd), n, 7, 5, 0, keep, 0, ptr(out), stream(dev)) == macx._lib.MACX_EINVAL
 
 
 @pytest.mark.parametrize("keep", [1.0, 0.8])
@@ -396,7 +389,7 @@ def test_embed_lookup_bwd(macx, dev, E, keep):
     outs = []
     for _ in range(2):
         demb = torch.full((V, E), float("nan"), device=dev)
-        macx._lib.check(L.macx_embed_lookup_bwd(_p(idd), _p(dxd), rows, E, ld, V, keep, seed, first_row, _p(demb), _st(dev)),
+        macx._lib.check(L.macx_embed_lookup_bwd(ptr(idd), ptr(dxd), rows, E, ld, V, keep, seed, first_row, ptr(demb), stream(dev)),
                         "macx_embed_lookup_bwd")
         torch.cuda.synchronize()
         outs.append(demb.cpu())
@@ -425,9 +418,9 @@ def test_run_status_reset_zeroes_the_status_words(macx, dev):
     with torch.no_grad():
         cell.run()
     run = cell._run
-    args = (C.byref(run.opts), C.byref(run.shapes), run.keep, _p(run.saved), C.c_size_t(run.saved_floats))
+    args = (C.byref(run.opts), C.byref(run.shapes), run.keep, ptr(run.saved), C.c_size_t(run.saved_floats))
     bits, first = C.c_uint32(99), C.c_int32(99)
-    assert L.macx_run_status(*args, _st(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_OK
+    assert L.macx_run_status(*args, stream(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_OK
     assert (bits.value, first.value) == (0, -1)
     off, cnt = C.c_size_t(0), C.c_size_t(0)
     assert L.macx_saved_segment(C.byref(run.opts), C.byref(run.shapes), run.keep, macx._lib.SEG["status"], C.byref(off), C.byref(cnt)) == 0
@@ -435,12 +428,12 @@ def test_run_status_reset_zeroes_the_status_words(macx, dev):
     status = run.saved.view(torch.int32)[off.value: off.value + 16]
     before = run.saved.clone()
     status.copy_(torch.arange(1, 17, dtype=torch.int32, device=dev))
-    assert L.macx_run_status(*args, _st(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_EWAIT
+    assert L.macx_run_status(*args, stream(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_EWAIT
     assert (bits.value, first.value) == (1, 1)
-    assert L.macx_run_status_reset(*args, _st(dev)) == macx._lib.MACX_OK
+    assert L.macx_run_status_reset(*args, stream(dev)) == macx._lib.MACX_OK
     torch.cuda.synchronize()
     assert int(status.abs().sum()) == 0
     assert torch.equal(run.saved.view(torch.int32), before.view(torch.int32))        # nothing but the 16 words changed (they were 0 before)
-    assert L.macx_run_status(*args, _st(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_OK
-    assert L.macx_run_status_reset(*args[:3], None, C.c_size_t(run.saved_floats), _st(dev)) == macx._lib.MACX_EINVAL
-    assert L.macx_run_status_reset(*args[:4], C.c_size_t(run.saved_floats - 1), _st(dev)) == macx._lib.MACX_ESMALL
+    assert L.macx_run_status(*args, stream(dev), C.byref(bits), C.byref(first)) == macx._lib.MACX_OK
+    assert L.macx_run_status_reset(*args[:3], None, C.c_size_t(run.saved_floats), stream(dev)) == macx._lib.MACX_EINVAL
+    assert L.macx_run_status_reset(*args[:4], C.c_size_t(run.saved_floats - 1), stream(dev)) == macx._lib.MACX_ESMALL

@@ -21,20 +21,20 @@ import math
 import pytest
 import torch
 
+import abi_kit
 import answer_weights_ref as awr
 import output_geometry_cases as og
 from oracle import dropout_hash as dh
 from oracle import mac_oracle as mo
-import test_gpu_guards as tg
 
 pytestmark = pytest.mark.gpu
 
 
 @contextlib.contextmanager
 def guarded(dev):
-    """test_gpu_guards.guarded_allocations, with n-D fp32 device tensors (torch.empty(B, A, ..), torch.empty_like) carved out of its
+    """abi_kit.guarded_allocations, with n-D fp32 device tensors (torch.empty(B, A, ..), torch.empty_like) carved out of its
     guarded 1-D buffers as well: the unit's logits, the input gradients and the parameter gradients"""
-    with tg.guarded_allocations() as seen:
+    with abi_kit.guarded_allocations() as seen:
         one_d, real_like = torch.empty, torch.empty_like
 
         def empty(*size, **kw):
@@ -85,7 +85,7 @@ def check_packs(unit, c, seen):
     size calls give): the forward pack's columns A .. Ap and the transposed pack's k rows A .. Ap hold zeros, the rest fc1_W's bits"""
     n = og.saved_floats(c.B, c.d, c.H, c.A)
     assert n == og.ws_floats(c.B, c.d, c.H, c.A)
-    bufs = [full[tg.GUARD: tg.GUARD + k] for full, k in seen if k == n]
+    bufs = [full[abi_kit.ALLOC_GUARD: abi_kit.ALLOC_GUARD + k] for full, k in seen if k == n]
     assert len(bufs) == 2, len(bufs)
     off, Ap, w = og.al4(c.d * c.d) + og.al4(2 * c.d * c.H), og.pad16(c.A), unit.fc1_W.detach().cpu()
     assert torch.equal(bufs[0][off: off + c.H * Ap].cpu(), pack(w, c.H, Ap)), "forward pack of fc1_W"
@@ -101,7 +101,7 @@ def run_fused(unit, c, mem, vq, dl, train, dev):
         logits = unit(memd, vqd, train=train, seed=og.SEED, b0=c.b0, mask_word=word)
         (logits * dld).sum().backward()
         torch.cuda.synchronize()
-    tg.assert_guards_intact(seen, ("output unit", c.id, train))
+    abi_kit.assert_guards_intact(seen, ("output unit", c.id, train))
     check_packs(unit, c, seen)
     assert len(seen) >= 10                                            # saved, ws; inputs; logits; input and parameter gradients (16 floats and up)
     got = dict(logits=logits.detach().clone(), d_memory=memd.grad.clone(), d_vecQ=vqd.grad.clone())
@@ -186,10 +186,6 @@ def launch_weighted(macx, dev, logits, answers, weights, scale):
     return rows.cpu(), pred.cpu(), dl.cpu(), out.cpu()
 
 
-def bits_equal(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 @pytest.mark.parametrize("B, A", og.LOSS_SHAPES)
 def test_answer_loss_at_real_sizes(macx, dev, B, A):
     logits, answers, first_max = og.loss_case(B, A)
@@ -220,7 +216,7 @@ def test_answer_loss_at_real_sizes(macx, dev, B, A):
         want = awr.reference(lg2, an2, weights, grad_scale=0.5)
         wrows, wpred, wdl, wloss = launch_weighted(macx, dev, lg2, an2, weights, 0.5)
         live = ~dead
-        assert bits_equal(wrows[live], rows[live]) and torch.equal(wpred[live], pred[live]), pattern
+        assert abi_kit.bits_equal(wrows[live], rows[live]) and torch.equal(wpred[live], pred[live]), pattern
         assert wpred[dead].tolist() == [-1] * int(dead.sum()) and aw.is_plus_zero(wrows[dead]) and aw.is_plus_zero(wdl[dead])
         err_loss, err_dl = abs(float(wloss[0]) - float(want["loss"])), float((wdl.double() - want["dlogits"]).abs().max())
         og.log("answer_loss_weighted B%d A%d %s: loss %.2e (bound %.0e) dlogits %.2e (bound 1e-06), %d dead" % (B, A, pattern, err_loss, og.LOSS_TOL,
@@ -243,7 +239,7 @@ def test_a_row_of_minus_infinity(macx, dev, B, A):
         assert math.isnan(float(r[1])) and bool(torch.isnan(g[1]).all())
         rest = [0, 2, 3, 4]
         assert torch.equal(p.long()[rest], logits.argmax(dim=-1)[rest]) and bool(torch.isfinite(r[rest]).all()) and bool(torch.isfinite(g[rest]).all())
-    assert bits_equal(rows[[0, 2, 3, 4]], wrows[[0, 2, 3, 4]]) and torch.equal(pred, wpred) and math.isnan(float(wloss[0]))
+    assert abi_kit.bits_equal(rows[[0, 2, 3, 4]], wrows[[0, 2, 3, 4]]) and torch.equal(pred, wpred) and math.isnan(float(wloss[0]))
 
 
 # ---- the tower ----------------------------------------------------------------------------------------------------------------

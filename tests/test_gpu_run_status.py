@@ -7,6 +7,7 @@ import ctypes as C
 import pytest
 import torch
 
+import abi_kit
 from helpers import make_case
 from test_gpu_cell import build_cell
 
@@ -27,8 +28,8 @@ def _train_run(macx, dev, name, B, S, N, d, p):
 
 def _abi_status(macx, run):
     bits, first = C.c_uint32(99), C.c_int32(99)
-    stream = C.c_void_p(torch.cuda.current_stream(run.saved.device).cuda_stream)
-    rc = run.L.macx_run_status(C.byref(run.opts), C.byref(run.shapes), run.keep, C.c_void_p(run.saved.data_ptr()),
+    stream = abi_kit.stream(run.saved.device)
+    rc = run.L.macx_run_status(C.byref(run.opts), C.byref(run.shapes), run.keep, abi_kit.ptr(run.saved),
                                C.c_size_t(run.saved_floats), stream, C.byref(bits), C.byref(first))
     return rc, bits.value, first.value
 
@@ -131,7 +132,7 @@ def test_captured_forward_has_the_interface(macx, dev):
 def test_wait_routine_selftest(macx, dev):
     L = macx._lib.lib()
     out = (C.c_uint32 * 8)(*([99] * 8))
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = abi_kit.stream(dev)
     assert L.macx_handoff_selftest(stream, out) == macx._lib.MACX_OK
     arrived, gave_up = list(out)[:4], list(out)[4:]
     assert arrived == [1, 0, 0, 0]            # arrived, status 0, no step, nobody told to poison

@@ -11,19 +11,14 @@ CapturedTowerTrainStep run at B = 64 and no other test holds against a reference
 * macx_gather_flat over more chunks than workgroups, entries that start a whole number of grids in, a misaligned destination.
 
 `-s` prints every observed error / ratio."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+from abi_kit import bits_equal, ptr
 from helpers import check_margin, rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def bits_equal(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # =====================================================================================================================
@@ -220,15 +215,14 @@ def _gpu_step(macx, dev, c, lr_t, device_rate=False, ema_buffer=True):
     if c["decay"] < 0:
         t["ema"].fill_(-12345.0)                          # EMA off: the buffer (passed or not) must keep its sentinel
     ws, norm = torch.empty(1024, device=dev), torch.zeros(1, device=dev)
-    p_ = lambda x: C.c_void_p(x.data_ptr())
-    ema = p_(t["ema"]) if ema_buffer else None
+    ema = ptr(t["ema"]) if ema_buffer else None
     if device_rate:
         rate = torch.tensor([lr_t], dtype=torch.float32, device=dev)
-        macx._lib.check(L.macx_adam_ema_step_p(c["n"], p_(t["p"]), p_(t["g"]), p_(t["m"]), p_(t["v"]), ema, p_(rate), c["beta1"], c["beta2"],
-                                               c["eps"], c["clip"], c["decay"], p_(ws), p_(norm), None), "macx_adam_ema_step_p")
+        macx._lib.check(L.macx_adam_ema_step_p(c["n"], ptr(t["p"]), ptr(t["g"]), ptr(t["m"]), ptr(t["v"]), ema, ptr(rate), c["beta1"], c["beta2"],
+                                               c["eps"], c["clip"], c["decay"], ptr(ws), ptr(norm), None), "macx_adam_ema_step_p")
     else:
-        macx._lib.check(L.macx_adam_ema_step(c["n"], p_(t["p"]), p_(t["g"]), p_(t["m"]), p_(t["v"]), ema, c["lr"], c["beta1"], c["beta2"],
-                                             c["eps"], c["step"], c["clip"], c["decay"], p_(ws), p_(norm), None), "macx_adam_ema_step")
+        macx._lib.check(L.macx_adam_ema_step(c["n"], ptr(t["p"]), ptr(t["g"]), ptr(t["m"]), ptr(t["v"]), ema, c["lr"], c["beta1"], c["beta2"],
+                                             c["eps"], c["step"], c["clip"], c["decay"], ptr(ws), ptr(norm), None), "macx_adam_ema_step")
     torch.cuda.synchronize()
     assert bits_equal(t["g"].cpu(), torch.from_numpy(c["g"]))          # the gradient is read only
     out = {k: t[k].cpu().numpy() for k in ("p", "m", "v", "ema")}
@@ -321,7 +315,7 @@ def test_gather_flat_past_one_grid(macx, dev):
     for _ in range(2):
         flat = torch.full((total,), sentinel, device=dev)
         assert flat.data_ptr() % 16 == 0
-        macx._lib.check(L.macx_gather_flat(C.c_void_p(table.data_ptr()), len(GATHER_ENTRIES), C.c_void_p(flat.data_ptr()), None),
+        macx._lib.check(L.macx_gather_flat(ptr(table), len(GATHER_ENTRIES), ptr(flat), None),
                         "macx_gather_flat")
         torch.cuda.synchronize()
         outs.append(flat)

@@ -20,6 +20,7 @@ import torch
 
 from oracle import mac_oracle as mo
 from helpers import make_case, rel_err
+import abi_kit
 import state_grads_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -162,7 +163,7 @@ def test_null_struct_and_zero_gradients_are_the_plain_backward(macx, dev, name, 
     run = cell._run
     g = torch.Generator().manual_seed(9)
     dmem, dctl = (torch.randn(B, d, generator=g) / B).to(dev), (torch.randn(B, d, generator=g) / B).to(dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = abi_kit.stream(dev)
 
     def call(fn, *extra):
         args, grads, gi, flat, keep = run.backward_begin(dctl, dmem)
@@ -195,7 +196,7 @@ def test_phases_with_struct_are_the_single_call(macx, dev, name, B, S, N, d, p):
     g = torch.Generator().manual_seed(4)
     dmem = (torch.randn(B, d, generator=g) / B).to(dev)
     sg = {k: torch.randn(v.shape, generator=g).to(dev) / B for k, v in _zero_state_grads(run, dev).items()}
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = abi_kit.stream(dev)
     args, grads, gi, flat, keep = run.backward_begin(None, dmem, sg)
     assert args[-1] is not None
     macx._lib.check(L.macx_cell_backward_x(*args, stream), "macx_cell_backward_x")
@@ -344,7 +345,7 @@ def test_map_gradient_without_the_option_is_refused(macx, dev):
     cell.run()
     run = cell._run
     assert not run.opts.write_self_att and not run.opts.write_gate
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = abi_kit.stream(dev)
     junk = torch.zeros(p * B * d, device=dev)
     for field in ("d_att_self", "d_att_gate"):
         args, grads, gi, flat, keep = run.backward_begin(None, torch.ones(B, d, device=dev))

@@ -8,6 +8,7 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+import abi_kit
 import stem_variants_ref as sv
 from helpers import max_abs, rel_err
 from oracle import dropout_hash as dh
@@ -137,25 +138,13 @@ def test_generic_stem_matches_fused_stem_on_default(macx, dev):
 
 def conv_call(macx, which, sh, *bufs, ws=None, n_ws=0):
     L = macx._lib.lib()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    p = [C.c_void_p(b.data_ptr()) if b is not None else None for b in bufs]
+    st = abi_kit.stream(None)
+    p = [abi_kit.ptr(b) for b in bufs]
     if which == "fwd":
         return L.macx_conv2d_fwd(C.byref(sh), *p, st)
     if which == "bwd":
         return L.macx_conv2d_bwd_data(C.byref(sh), *p, st)
-    return L.macx_conv2d_wgrad(C.byref(sh), *p, C.c_void_p(ws.data_ptr()) if ws is not None else None, n_ws, st)
-
-
-GUARD, SENT = 1024, -7.25e11
-
-
-def guarded(n, dev):
-    full = torch.full((n + 2 * GUARD,), SENT, dtype=torch.float32, device=dev)
-    return full, full[GUARD:GUARD + n]
-
-
-def intact(full, n):
-    return bool((full[:GUARD] == SENT).all()) and bool((full[GUARD + n:] == SENT).all())
+    return L.macx_conv2d_wgrad(C.byref(sh), *p, abi_kit.ptr(ws), n_ws, st)
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,k,s", [(1, 1, 1, 4, 4, 1, 1), (3, 5, 3, 12, 20, 3, 1), (2, 9, 7, 4, 132, 2, 2),
@@ -173,11 +162,11 @@ def test_conv_exports_odd_shapes_guards_and_repeatability(macx, dev, B, H, W, Ci
     yr = sv.conv2d_same(xr, wr, s) + b
     yr.backward(dy)
     ny, nx, nw = B * Ho * Wo * Cout, B * H * W * Cin, k * k * Cin * Cout
-    fy, y = guarded(ny, dev)
-    fx, dx = guarded(nx, dev)
-    fw, dw = guarded(nw, dev)
+    gy, gx, gw = abi_kit.Guarded(ny, dev), abi_kit.Guarded(nx, dev), abi_kit.Guarded(nw, dev)
+    y, dx, dw = gy.view, gx.view, gw.view
     n_ws = macx._lib.lib().macx_conv2d_ws_floats(C.byref(sh))
-    fs, ws = guarded(max(n_ws, 4), dev)
+    gs = abi_kit.Guarded(max(n_ws, 4), dev)
+    ws = gs.view
     xd, wd, bd, dyd = [t.float().contiguous().to(dev) for t in (x, w, b, dy)]
     assert conv_call(macx, "fwd", sh, xd, wd, bd, y) == 0
     assert conv_call(macx, "bwd", sh, dyd, wd, dx) == 0
@@ -186,7 +175,7 @@ def test_conv_exports_odd_shapes_guards_and_repeatability(macx, dev, B, H, W, Ci
     ey, ex, ew = rel_err(y.reshape(yr.shape), yr), rel_err(dx.reshape(x.shape), xr.grad), rel_err(dw.reshape(w.shape), wr.grad)
     print("conv", (B, H, W, Cin, Cout, k, s), "slabs ws", n_ws, "errors %.1e %.1e %.1e" % (ey, ex, ew))
     assert ey < 2e-5 and ex < 2e-5 and ew < 2e-5
-    assert intact(fy, ny) and intact(fx, nx) and intact(fw, nw) and intact(fs, max(n_ws, 4))
+    assert gy.intact() and gx.intact() and gw.intact() and gs.intact()
     y1, dx1, dw1 = y.clone(), dx.clone(), dw.clone()
     assert conv_call(macx, "fwd", sh, xd, wd, bd, y) == 0
     assert conv_call(macx, "bwd", sh, dyd, wd, dx) == 0

@@ -6,13 +6,13 @@ kept fraction of one dropout site (a 4 sigma binomial bound).
 Shapes: the smallest that reach every tail -- B = 6 (half-empty question block of the LSTM step), S = 7 with lengths 7 (full) and 1,
 5 x 5 cells (N = 25: no multiple of 16 or 64, >= 16 as the H2 chain needs), d = 256 (h = 128, the fused encoder's minimum),
 wrdEmbDim = 20 (padded embedding columns), 28 answers (padded to 32), p = 3."""
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 import torch
 
+from abi_kit import bits_equal, ptr
 from oracle import dropout_hash as dh
 
 pytestmark = pytest.mark.gpu
@@ -45,11 +45,6 @@ def inputs(dev, seed, b=B, s=S, lengths=LENGTHS, hw=H * W, cin=CIN, vocab=VOCAB)
 def word_tensor(dev, word):
     word &= 0xFFFFFFFF
     return torch.tensor([word - (1 << 32) if word >= (1 << 31) else word], dtype=torch.int32, device=dev)
-
-
-def bits_equal(a, b):
-    """same bits (torch.equal would take -0.0 for +0.0 and refuse equal NaNs)"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---- one (outputs, gradients) run per module: `call(**kw)` runs the module with the same inputs, seed and output gradient --------
@@ -163,18 +158,17 @@ def test_adam_step_with_the_rate_in_device_memory(macx, dev):
     state = [[p0.clone().to(dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev), p0.clone().to(dev),
               torch.empty(1024, device=dev), torch.zeros(1, device=dev)] for _ in range(2)]
     lr_t = torch.zeros(1, device=dev)
-    p_ = lambda t: C.c_void_p(t.data_ptr())
     lr, norms = 1e-2, []
     for t, scale in enumerate([1.0, 0.1, 1.0, 0.1, 0.5], start=1):       # ||g|| ~ 31.7 * scale: clipped at 8 on steps 1, 3, 5
         if t == 3:
             lr = 0.5e-2
         grad = (torch.randn(n, generator=g) * scale).to(dev)
         a, b = state
-        macx._lib.check(L.macx_adam_ema_step(n, p_(a[0]), p_(grad), p_(a[1]), p_(a[2]), p_(a[3]), lr, b1, b2, eps, t, clip, decay, p_(a[4]),
-                                             p_(a[5]), None), "macx_adam_ema_step")
+        macx._lib.check(L.macx_adam_ema_step(n, ptr(a[0]), ptr(grad), ptr(a[1]), ptr(a[2]), ptr(a[3]), lr, b1, b2, eps, t, clip, decay, ptr(a[4]),
+                                             ptr(a[5]), None), "macx_adam_ema_step")
         lr_t.fill_(macx.optim.FlatAdamEMA.bias_corrected_lr(lr, b1, b2, t))
-        macx._lib.check(L.macx_adam_ema_step_p(n, p_(b[0]), p_(grad), p_(b[1]), p_(b[2]), p_(b[3]), p_(lr_t), b1, b2, eps, clip, decay,
-                                               p_(b[4]), p_(b[5]), None), "macx_adam_ema_step_p")
+        macx._lib.check(L.macx_adam_ema_step_p(n, ptr(b[0]), ptr(grad), ptr(b[1]), ptr(b[2]), ptr(b[3]), ptr(lr_t), b1, b2, eps, clip, decay,
+                                               ptr(b[4]), ptr(b[5]), None), "macx_adam_ema_step_p")
         torch.cuda.synchronize()
         for i, what in enumerate(("params", "m", "v", "ema")):
             assert bits_equal(a[i], b[i]), (t, what)
@@ -210,7 +204,7 @@ def test_gather_flat(macx, dev):
     rows = [x for s, o, k in zip(srcs, offsets, sizes) for x in (0 if s is None else s.data_ptr(), o, k)]
     table = torch.tensor(rows, dtype=torch.int64).to(dev)
     flat = torch.full((off + 8,), sentinel, device=dev)
-    macx._lib.check(L.macx_gather_flat(C.c_void_p(table.data_ptr()), len(sizes), C.c_void_p(flat.data_ptr()), None), "macx_gather_flat")
+    macx._lib.check(L.macx_gather_flat(ptr(table), len(sizes), ptr(flat), None), "macx_gather_flat")
     torch.cuda.synchronize()
     assert bits_equal(flat, want)                 # slices, the zero slice and every pad float (still the sentinel)
     pads = torch.ones(off + 8, dtype=torch.bool)

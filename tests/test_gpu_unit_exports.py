@@ -9,6 +9,7 @@ import torch
 
 from oracle import mac_oracle as mo
 from oracle import dropout_hash as dh
+import abi_kit
 from helpers import rel_err
 from test_gpu_generic import oracle_params, assert_grad
 
@@ -17,10 +18,6 @@ pytestmark = pytest.mark.gpu
 READ_FIELDS = ("projX_W", "projX_b", "projY_W", "projY_b", "memKbProj_W", "memKbProj_b", "memKbProj2_W", "memKbProj2_b",
                "kbLogits_w", "kbLogits_b")
 WRITE_FIELDS = ("newMemory_W", "newMemory_b", "gate_W", "gate_b")
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class Unit:
@@ -52,7 +49,7 @@ class Unit:
         wb = self.L.macx_workspace_bytes(o, s, 1)
         assert wb == 4 * self.L.macx_ws_floats(o, s, 1) and wb > 0
         self.ws = torch.empty(wb // 4, dtype=torch.float32, device=dev)
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self.stream = abi_kit.stream(dev)
         # the oracle cell (fp64) on the same variables
         self.op = {k: v.double().clone().requires_grad_(True) for k, v in self.ref_params.items()}
         self.vs = mo.VarStore(params=self.op, dtype=torch.float64)
@@ -102,10 +99,10 @@ def test_read_unit_exports(macx, dev, name, over, train, B, N, d):
 
     kbd, memd, ctld, wd = [t.to(dev).contiguous() for t in (u.kb, mem, ctl, w)]
     info, att = torch.empty(B, d, device=dev), torch.empty(B, N, device=dev)
-    u.lib.check(u.L.macx_read_fwd(*u.head(), P(kbd), P(memd), P(ctld), P(u.saved), u.saved_floats, P(info), P(att), u.stream), "read_fwd")
+    u.lib.check(u.L.macx_read_fwd(*u.head(), abi_kit.ptr(kbd), abi_kit.ptr(memd), abi_kit.ptr(ctld), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(info), abi_kit.ptr(att), u.stream), "read_fwd")
     dkb, dmem, dctl = torch.empty_like(kbd), torch.empty_like(memd), torch.empty_like(ctld)
-    u.lib.check(u.L.macx_read_bwd(*u.head(), P(kbd), P(u.saved), u.saved_floats, P(u.ws), u.ws.numel(), P(wd), C.byref(u.gstruct),
-                                  P(dkb), P(dmem), P(dctl), u.stream), "read_bwd")
+    u.lib.check(u.L.macx_read_bwd(*u.head(), abi_kit.ptr(kbd), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(u.ws), u.ws.numel(), abi_kit.ptr(wd), C.byref(u.gstruct),
+                                  abi_kit.ptr(dkb), abi_kit.ptr(dmem), abi_kit.ptr(dctl), u.stream), "read_bwd")
     torch.cuda.synchronize()
     assert rel_err(info, info_ref) < 1e-5
     assert float((att.cpu().double() - u.ocell.attentions["kb"][-1].detach()).abs().max()) < 2e-6
@@ -133,10 +130,10 @@ def test_write_unit_exports(macx, dev, name, over, train):
 
     memd, infod, ctld, wd = [t.to(dev).contiguous() for t in (mem, info, ctl, w)]
     out = torch.empty(B, d, device=dev)
-    u.lib.check(u.L.macx_write_fwd(*u.head(), P(memd), P(infod), P(ctld), P(u.saved), u.saved_floats, P(out), u.stream), "write_fwd")
+    u.lib.check(u.L.macx_write_fwd(*u.head(), abi_kit.ptr(memd), abi_kit.ptr(infod), abi_kit.ptr(ctld), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(out), u.stream), "write_fwd")
     dmem, dinfo, dctl = torch.empty_like(memd), torch.empty_like(memd), torch.empty_like(memd)
-    u.lib.check(u.L.macx_write_bwd(*u.head(), P(u.saved), u.saved_floats, P(u.ws), u.ws.numel(), P(wd), C.byref(u.gstruct),
-                                   P(dmem), P(dinfo), P(dctl), u.stream), "write_bwd")
+    u.lib.check(u.L.macx_write_bwd(*u.head(), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(u.ws), u.ws.numel(), abi_kit.ptr(wd), C.byref(u.gstruct),
+                                   abi_kit.ptr(dmem), abi_kit.ptr(dinfo), abi_kit.ptr(dctl), u.stream), "write_bwd")
     torch.cuda.synchronize()
     assert rel_err(out, ref) < 1e-5
     assert rel_err(dmem, a[0].grad) < 2e-4
@@ -153,14 +150,14 @@ def test_unit_exports_reject_what_they_cannot_do(macx, dev):
     cfg = mo.flag_file_config("args3", netLength=1, memDim=d, ctrlDim=d, attDim=d)          # writeSelfAtt
     u = Unit(macx, dev, cfg, 2, 10, d, False, seed=1)
     x = torch.zeros(2, d, device=dev)
-    rc = u.L.macx_write_fwd(*u.head(), P(x), P(x), P(x), P(u.saved), u.saved_floats, P(x), u.stream)
+    rc = u.L.macx_write_fwd(*u.head(), abi_kit.ptr(x), abi_kit.ptr(x), abi_kit.ptr(x), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(x), u.stream)
     assert rc == -2                                                                               # MACX_EUNSUPPORTED
     u.shapes.p = 2                                                                                # units are single steps
     att = torch.zeros(2, 10, device=dev)
     kb = u.kb.to(dev)
-    assert u.L.macx_read_fwd(*u.head(), P(kb), P(x), P(x), P(u.saved), u.saved_floats, P(x), P(att), u.stream) == -1
+    assert u.L.macx_read_fwd(*u.head(), abi_kit.ptr(kb), abi_kit.ptr(x), abi_kit.ptr(x), abi_kit.ptr(u.saved), u.saved_floats, abi_kit.ptr(x), abi_kit.ptr(att), u.stream) == -1
     u.shapes.p = 1
-    assert u.L.macx_read_fwd(*u.head(), P(kb), P(x), P(x), P(u.saved), 16, P(x), P(att), u.stream) == -4      # MACX_ESMALL
+    assert u.L.macx_read_fwd(*u.head(), abi_kit.ptr(kb), abi_kit.ptr(x), abi_kit.ptr(x), abi_kit.ptr(u.saved), 16, abi_kit.ptr(x), abi_kit.ptr(att), u.stream) == -4      # MACX_ESMALL
 
 
 @pytest.mark.parametrize("unshared,act,B,d,p", [(True, "TANH", 5, 128, 3), (False, "TANH", 3, 256, 2), (True, "NON", 64, 512, 12),
@@ -190,10 +187,10 @@ def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p):
     assert n > 0
     ws = torch.empty(n, device=dev)
     t_out, cI = torch.empty(B, d, device=dev), torch.empty(p, B, d, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    lib.check(L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), P(vqd), P(t_out), P(cI), P(ws), n, st), "ctrl_inputs_fwd")
+    st = abi_kit.stream(dev)
+    lib.check(L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(cI), abi_kit.ptr(ws), n, st), "ctrl_inputs_fwd")
     dvq = torch.empty(B, d, device=dev)
-    lib.check(L.macx_ctrl_inputs_bwd(C.byref(opts), C.byref(shapes), C.byref(ps), P(vqd), P(t_out), P(dcId), C.byref(gs), P(dvq), P(ws), n, st),
+    lib.check(L.macx_ctrl_inputs_bwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(dcId), C.byref(gs), abi_kit.ptr(dvq), abi_kit.ptr(ws), n, st),
               "ctrl_inputs_bwd")
     torch.cuda.synchronize()
     # fp64 closed form through autograd
@@ -210,6 +207,6 @@ def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p):
         assert torch.isfinite(got).all(), name
         assert rel_err(got, ref) < 2e-4, (name, rel_err(got, ref))
     # too small a workspace, a missing field
-    assert L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), P(vqd), P(t_out), P(cI), P(ws), n - 1, st) != 0
+    assert L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(cI), abi_kit.ptr(ws), n - 1, st) != 0
     ps.qInputU_W = None
-    assert L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), P(vqd), P(t_out), P(cI), P(ws), n, st) != 0
+    assert L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(cI), abi_kit.ptr(ws), n, st) != 0

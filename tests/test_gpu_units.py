@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_kit import ptr
 from oracle import dropout_hash as dh
 from oracle import mac_oracle as mo
 from helpers import default_gemm_mode, rel_err, max_abs
@@ -12,16 +13,12 @@ from helpers import default_gemm_mode, rel_err, max_abs
 pytestmark = pytest.mark.gpu
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def test_dropout_stream_matches_numpy(macx, dev):
     L = macx._lib.lib()
     n = 100003
     for (seed, site, step, keep, first) in [(1234, 3, 0, 0.85, 0), (7, 5, 11, 0.5, 4000000000), (0, 1, 0, 1.0, 17)]:
         out = torch.empty(n, device=dev)
-        macx._lib.check(L.macx_dropout_mask(seed, site, step, keep, first, n, _p(out), None), "mask")
+        macx._lib.check(L.macx_dropout_mask(seed, site, step, keep, first, n, ptr(out), None), "mask")
         torch.cuda.synchronize()
         ref = dh.keep_mask(seed, site, step, keep, first, n)
         assert np.array_equal(out.cpu().numpy(), ref)
@@ -30,7 +27,7 @@ def test_dropout_stream_matches_numpy(macx, dev):
         # under a run's mask word (macx_dropout.mask_word): read from device memory when the kernel runs
         for word in (0, 0x9E3779B9, 0xFFFFFFFF):
             wt = torch.tensor([word - (1 << 32) if word >= (1 << 31) else word], dtype=torch.int32, device=dev)
-            macx._lib.check(L.macx_dropout_mask_w(seed, site, step, keep, first, n, _p(wt), _p(out), None), "mask_w")
+            macx._lib.check(L.macx_dropout_mask_w(seed, site, step, keep, first, n, ptr(wt), ptr(out), None), "mask_w")
             torch.cuda.synchronize()
             refw = dh.keep_mask(seed, site, step, keep, first, n, word=word)
             assert np.array_equal(out.cpu().numpy(), refw)
@@ -54,9 +51,9 @@ def test_linear(macx, dev, rows, k1, k2, nout, act):
     x1d, Wd, bd = x1.to(dev), W.to(dev), b.to(dev)
     x2d = x2.to(dev) if x2 is not None else None
     wp = torch.empty_like(Wd)
-    macx._lib.check(L.macx_pack_weight(_p(Wd), k1 + k2, nout, 0, _p(wp), None), "pack")
-    macx._lib.check(L.macx_linear(_p(x1d), k1, _p(x2d) if x2d is not None else None, k2, rows, _p(wp), _p(bd), 0.25, nout,
-                                  macx._lib.ACT[act], _p(out), None), "linear")
+    macx._lib.check(L.macx_pack_weight(ptr(Wd), k1 + k2, nout, 0, ptr(wp), None), "pack")
+    macx._lib.check(L.macx_linear(ptr(x1d), k1, ptr(x2d) if x2d is not None else None, k2, rows, ptr(wp), ptr(bd), 0.25, nout,
+                                  macx._lib.ACT[act], ptr(out), None), "linear")
     torch.cuda.synchronize()
     assert max_abs(out, ref) < 2e-5
 
@@ -85,9 +82,9 @@ def _kb_project_case(macx, dev, B, N, d, keep):
     out = torch.empty(B, N, d, device=dev)
     wp = torch.empty(2 * d * d, device=dev)
     kbd, Wd, bd = kb.to(dev), W.to(dev), b.to(dev)
-    macx._lib.check(L.macx_pack_weight(_p(Wd), d, d, macx._lib.kb_pack_flags(), _p(wp), None), "pack")
+    macx._lib.check(L.macx_pack_weight(ptr(Wd), d, d, macx._lib.kb_pack_flags(), ptr(wp), None), "pack")
     bits = torch.empty(B * N * d + B * N * d // 32 + 4, device=dev)
-    macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 5, _p(kbd), _p(wp), _p(bd), _p(out), _p(bits), None), "kb_project")
+    macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 5, ptr(kbd), ptr(wp), ptr(bd), ptr(out), ptr(bits), None), "kb_project")
     torch.cuda.synchronize()
     mask = torch.from_numpy(dh.mask_for(99, dh.SITE_READ_KB, 5, keep, (B, N, d), b0=3)).double()
     ref = ((kb.double() / keep) * mask) @ W.double() + b.double()
@@ -116,8 +113,8 @@ def test_split_gemm_error_is_fp32_class(macx, dev):
             L.macx_gemm_mode(mode)
             wp = torch.zeros(2 * d * d, device=dev)
             out = torch.empty(B, N, d, device=dev)
-            macx._lib.check(L.macx_pack_weight(_p(Wd), d, d, macx._lib.kb_pack_flags(), _p(wp), None), "pack")
-            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, _p(kbd), _p(wp), _p(bd), _p(out), None, None), "proj")
+            macx._lib.check(L.macx_pack_weight(ptr(Wd), d, d, macx._lib.kb_pack_flags(), ptr(wp), None), "pack")
+            macx._lib.check(L.macx_kb_project(C.byref(sh), C.byref(dp), 0, ptr(kbd), ptr(wp), ptr(bd), ptr(out), None, None), "proj")
             torch.cuda.synchronize()
             e = (out.cpu().double().reshape(-1, d) - ref).abs() / scale
             err[mode] = (float(e.max()), float(e.mean()))
@@ -140,7 +137,7 @@ def test_control_attend(macx, dev):
     att = torch.empty(B, S, device=dev)
     ctl = torch.empty(B, d, device=dev)
     args = [t.to(dev) for t in (cc, words, lengths, w, b)]
-    macx._lib.check(L.macx_control_attend(C.byref(sh), *[_p(t) for t in args], _p(att), _p(ctl), None), "control_attend")
+    macx._lib.check(L.macx_control_attend(C.byref(sh), *[ptr(t) for t in args], ptr(att), ptr(ctl), None), "control_attend")
     torch.cuda.synchronize()
     inter = cc.double().unsqueeze(1) * words.double()
     logits = (inter * w.double()).sum(-1) + 0.3
@@ -163,13 +160,13 @@ def test_control_attend(macx, dev):
     ws = torch.empty(n_ws, device=dev)
     dcc, dwords, dw, db = torch.empty(B, d, device=dev), torch.empty(B, S, d, device=dev), torch.empty(d, device=dev), torch.empty(1, device=dev)
     dctl_d = dctl.to(dev)
-    macx._lib.check(L.macx_control_attend_bwd(C.byref(sh), _p(dctl_d), _p(args[0]), _p(att), _p(args[1]), _p(args[3]), _p(ws), n_ws,
-                                              _p(dcc), _p(dwords), _p(dw), _p(db), None), "control_attend_bwd")
+    macx._lib.check(L.macx_control_attend_bwd(C.byref(sh), ptr(dctl_d), ptr(args[0]), ptr(att), ptr(args[1]), ptr(args[3]), ptr(ws), n_ws,
+                                              ptr(dcc), ptr(dwords), ptr(dw), ptr(db), None), "control_attend_bwd")
     torch.cuda.synchronize()
     assert rel_err(dcc, ccd.grad) < 2e-5 and rel_err(dwords, wdd.grad) < 2e-5 and rel_err(dw, wwd.grad) < 2e-5
     assert abs(float(db) - float(bd.grad)) < 1e-5          # analytically zero (a bias in front of a softmax)
-    assert L.macx_control_attend_bwd(C.byref(sh), _p(dctl_d), _p(args[0]), _p(att), _p(args[1]), _p(args[3]), _p(ws), 8,
-                                     _p(dcc), _p(dwords), _p(dw), _p(db), None) == -4
+    assert L.macx_control_attend_bwd(C.byref(sh), ptr(dctl_d), ptr(args[0]), ptr(att), ptr(args[1]), ptr(args[3]), ptr(ws), 8,
+                                     ptr(dcc), ptr(dwords), ptr(dw), ptr(db), None) == -4
 
 
 @pytest.mark.parametrize("mode", [1, 0])
@@ -196,13 +193,13 @@ def _wgrad_case(macx, dev, M, Kd, Jd):
     out = torch.empty(Kd, Jd, device=dev)
     ws = torch.empty(ns * Kd * Jd, device=dev)
     Ad, Gd = A.to(dev), G.to(dev)
-    macx._lib.check(L.macx_wgrad(_p(Ad), Kd, _p(Gd), Jd, M, Kd, Jd, _p(out), _p(ws), None), "wgrad")
+    macx._lib.check(L.macx_wgrad(ptr(Ad), Kd, ptr(Gd), Jd, M, Kd, Jd, ptr(out), ptr(ws), None), "wgrad")
     torch.cuda.synchronize()
     ref = A.double().t() @ G.double()
     assert rel_err(out, ref) < 3e-6
     # deterministic: a second call is bit-identical
     out2 = torch.empty_like(out)
-    macx._lib.check(L.macx_wgrad(_p(Ad), Kd, _p(Gd), Jd, M, Kd, Jd, _p(out2), _p(ws), None), "wgrad")
+    macx._lib.check(L.macx_wgrad(ptr(Ad), Kd, ptr(Gd), Jd, M, Kd, Jd, ptr(out2), ptr(ws), None), "wgrad")
     torch.cuda.synchronize()
     assert torch.equal(out, out2)
 
@@ -223,15 +220,15 @@ def test_kb_attend_unit_forward_and_backward(macx, dev, B, N, d):
     (info_ref * dinfo.double()).sum().backward()
     lo, bi, kbt, di = logits.to(dev), bias.to(dev), kb.to(dev), dinfo.to(dev)
     att, info = torch.empty(B, N, device=dev), torch.empty(B, d, device=dev)
-    macx._lib.check(L.macx_kb_attend_fwd(B, N, d, _p(lo), _p(bi), _p(kbt), _p(att), _p(info), None), "fwd")
+    macx._lib.check(L.macx_kb_attend_fwd(B, N, d, ptr(lo), ptr(bi), ptr(kbt), ptr(att), ptr(info), None), "fwd")
     nws = L.macx_kb_attend_bwd_ws_floats(B, N, d)
     ws = torch.empty(nws, device=dev)
     dl = torch.empty(B, N, device=dev)
     dkb = torch.full((B, N, d), 2.0, device=dev)
-    macx._lib.check(L.macx_kb_attend_bwd(B, N, d, _p(att), _p(kbt), _p(di), _p(dl), _p(dkb), 1, _p(ws), nws, None), "bwd")
+    macx._lib.check(L.macx_kb_attend_bwd(B, N, d, ptr(att), ptr(kbt), ptr(di), ptr(dl), ptr(dkb), 1, ptr(ws), nws, None), "bwd")
     torch.cuda.synchronize()
     rel = lambda a, b: float((a.cpu().double() - b).abs().max() / max(float(b.abs().max()), 1e-6))
     assert rel(att, att_ref.detach()) < 1e-5 and rel(info, info_ref.detach()) < 1e-5
     assert rel(dl, lg.grad) < 1e-5
     assert rel(dkb - 2.0, kbd_.grad) < 1e-5
-    assert L.macx_kb_attend_bwd(B, N, d, _p(att), _p(kbt), _p(di), _p(dl), None, 0, _p(ws), 1, None) == macx._lib.MACX_ESMALL
+    assert L.macx_kb_attend_bwd(B, N, d, ptr(att), ptr(kbt), ptr(di), ptr(dl), None, 0, ptr(ws), 1, None) == macx._lib.MACX_ESMALL

@@ -23,23 +23,15 @@ import ctypes as C
 import pytest
 import torch
 
+from abi_kit import Guarded, bits_equal, ptr
 from helpers import rel_err
 import state_grads_ref as sr
 import test_gpu_state_grads as sg
-from test_gpu_stem_variants import guarded, intact
 import word_attention_cases as wa
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ESMALL = -1, -4
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def bits_equal(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---- 2a: the exports ------------------------------------------------------------------------------------------------------
@@ -55,23 +47,22 @@ def run_exports(macx, dev, r, data):
     sizes = dict(att=B * S, control=B * d)
     if r.bwd:
         sizes.update(d_cc=B * d, d_words=B * S * d, d_w=d, d_b=1, ws=n_ws)
-    buf = {k: guarded(n, dev) for k, n in sizes.items()}
-    assert all(v.data_ptr() % 16 == 0 for _, v in buf.values())
-    macx._lib.check(L.macx_control_attend(C.byref(sh), _p(cc), _p(words), _p(lengths), _p(w), _p(bias), _p(buf["att"][1]),
-                                          _p(buf["control"][1]), None), "macx_control_attend")
+    buf = {k: Guarded(n, dev) for k, n in sizes.items()}
+    macx._lib.check(L.macx_control_attend(C.byref(sh), ptr(cc), ptr(words), ptr(lengths), ptr(w), ptr(bias), ptr(buf["att"].view),
+                                          ptr(buf["control"].view), None), "macx_control_attend")
     if r.bwd:
-        macx._lib.check(L.macx_control_attend_bwd(C.byref(sh), _p(dc), _p(cc), _p(buf["att"][1]), _p(words), _p(w), _p(buf["ws"][1]), n_ws,
-                                                  _p(buf["d_cc"][1]), _p(buf["d_words"][1]), _p(buf["d_w"][1]), _p(buf["d_b"][1]), None),
+        macx._lib.check(L.macx_control_attend_bwd(C.byref(sh), ptr(dc), ptr(cc), ptr(buf["att"].view), ptr(words), ptr(w), ptr(buf["ws"].view), n_ws,
+                                                  ptr(buf["d_cc"].view), ptr(buf["d_words"].view), ptr(buf["d_w"].view), ptr(buf["d_b"].view), None),
                         "macx_control_attend_bwd")
     else:
         one = torch.zeros(max(n_ws, B * S * d), device=dev)
-        assert L.macx_control_attend_bwd(C.byref(sh), _p(dc), _p(cc), _p(buf["att"][1]), _p(words), _p(w), _p(one), n_ws, _p(one), _p(one),
-                                         _p(one), _p(one), None) == EINVAL                     # d % 64
+        assert L.macx_control_attend_bwd(C.byref(sh), ptr(dc), ptr(cc), ptr(buf["att"].view), ptr(words), ptr(w), ptr(one), n_ws, ptr(one), ptr(one),
+                                         ptr(one), ptr(one), None) == EINVAL                     # d % 64
     torch.cuda.synchronize()
-    broken = [k for k, (full, _) in buf.items() if not intact(full, sizes[k])]
+    broken = [k for k, g in buf.items() if not g.intact()]
     assert not broken, "sentinel bands overwritten around %s (%s)" % (broken, r.id)
     shapes = dict(att=(B, S), control=(B, d), d_cc=(B, d), d_words=(B, S, d), d_w=(d,), d_b=(), ws=(n_ws,))
-    return {k: v.clone().cpu().view(shapes[k]) for k, (_, v) in buf.items()}
+    return {k: g.view.clone().cpu().view(shapes[k]) for k, g in buf.items()}
 
 
 def check_against_bounds(r, data, got, what="hip"):
@@ -143,13 +134,13 @@ def test_refusals_come_before_any_launch(macx, dev):
 
     def fwd(B, S, d):
         sh = macx._lib.MacxShapes(B=B, S=S, N=1, d=d, p=1, b0=0)
-        return L.macx_control_attend(C.byref(sh), _p(cc), _p(words), _p(lengths), _p(w), _p(bias), _p(att), _p(ctl), None)
+        return L.macx_control_attend(C.byref(sh), ptr(cc), ptr(words), ptr(lengths), ptr(w), ptr(bias), ptr(att), ptr(ctl), None)
 
     def bwd(B, S, d, short=0):
         sh = macx._lib.MacxShapes(B=B, S=S, N=1, d=d, p=1, b0=0)
         n = L.macx_control_attend_bwd_ws_floats(C.byref(sh))
-        return L.macx_control_attend_bwd(C.byref(sh), _p(dc), _p(cc), _p(att), _p(words), _p(w), _p(ws), n - short, _p(dcc), _p(dwords),
-                                         _p(dw), _p(db), None)
+        return L.macx_control_attend_bwd(C.byref(sh), ptr(dc), ptr(cc), ptr(att), ptr(words), ptr(w), ptr(ws), n - short, ptr(dcc), ptr(dwords),
+                                         ptr(dw), ptr(db), None)
 
     assert fwd(2, 257, 64) == EINVAL and bwd(2, 257, 64) == EINVAL                  # S above C_MAXS
     assert fwd(2, 5, 66) == EINVAL                                                  # d % 4

@@ -18,6 +18,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_kit
 import h2_contraction_cases as hc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -295,14 +296,6 @@ def L(macx):
 PTR = C.c_void_p(1 << 20)            # never dereferenced: every call below is refused on the host
 
 
-def _opts(macx, **tune):
-    o = macx._lib.MacxOpts()
-    o.abi_version = macx._lib.ABI_VERSION
-    for k, v in tune.items():
-        macx._lib.set_tune(o, k, v)
-    return o
-
-
 def test_wgrad_size_call(macx, L):
     for c in hc.WGRAD_CASES:
         for pair in (0, 1):
@@ -311,7 +304,7 @@ def test_wgrad_size_call(macx, L):
             want = 4 * 64 * 8 + (1 + pair) * (ft + c.nsplit * c.Kd * c.Jd)
             assert L.macx_h2_wgrad_ws_floats(None, c.nt, c.R, c.Kd, c.Jd, c.nsplit, pair) == want, c.id
     # the family is forced: the answer does not depend on the process default or on opts.gemm_family
-    o = _opts(macx)
+    o = abi_kit.opts(macx)
     o.gemm_family = 1
     assert L.macx_h2_wgrad_ws_floats(C.byref(o), 1, 161, 128, 128, 3, 0) == L.macx_h2_wgrad_ws_floats(None, 1, 161, 128, 128, 3, 0)
     for bad in ((0, 32, 128, 128, 1), (1, 0, 128, 128, 1), (1, 32, 64, 128, 1), (1, 32, 128, 192, 1), (1, 32, 0, 128, 1),
@@ -354,7 +347,7 @@ def test_wgrad_refusals(macx, L):
     assert _wgrad_call(L, ws_floats=need - 1) == ESMALL
     need2 = L.macx_h2_wgrad_ws_floats(None, 3, 49, 256, 128, 2, 1)
     assert need2 > need and _wgrad_call(L, a2=P2, g2=P2, out2=P2, a2_stride=sa, g2_stride=sg, ws_floats=need2 - 1) == ESMALL
-    o = _opts(macx)
+    o = abi_kit.opts(macx)
     o.abi_version = macx._lib.ABI_VERSION + 1
     assert _wgrad_call(L, o=C.byref(o)) == EINVAL and L.macx_h2_wgrad_ws_floats(C.byref(o), 3, 49, 256, 128, 2, 0) == 0
     # a shared A needs no stride; one tensor needs none at all
@@ -407,7 +400,7 @@ def test_sb_refusals(macx, L):
     for wide, dy in ((0, None), (0, DY), (1, None)):
         need = L.macx_h2_sb_ws_floats(None, 5, 33, 256, 1, 2, wide)
         assert need == 2 * 3 * 256 * 256 and _sb_call(L, wide=wide, dy=dy, ws_floats=need - 1) == ESMALL
-    o = _opts(macx, sb_cont=0)
+    o = abi_kit.opts(macx, sb_cont=0)
     assert _sb_call(L, o=C.byref(o), ws_floats=1) == ESMALL
     o.abi_version = 4
     assert _sb_call(L, o=C.byref(o)) == EINVAL and L.macx_h2_sb_ws_floats(C.byref(o), 5, 33, 256, 1, 2, 0) == 0

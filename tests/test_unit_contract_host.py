@@ -8,6 +8,7 @@ import types
 import pytest
 import torch
 
+import abi_kit
 from test_tower_graph_host import small_net
 
 GENERIC = dict(enc=dict(encBi=False), stem=dict(stemKernelSize=1), out=dict(outClassifierDims=[128, 128]))
@@ -33,9 +34,10 @@ def unit_of(macx, which, generic, seed=None):
     return macx.OutputClassifier(net.config, answerWordsNum=28, generator=gen)
 
 
-def same_bits(a, b):
+def same_tensors(a, b):
+    """two units hold the same tensors bit for bit"""
     ta, tb = a.tensors(), b.tensors()
-    return len(ta) == len(tb) and all(x.dtype == y.dtype and torch.equal(x, y) for x, y in zip(ta, tb))
+    return len(ta) == len(tb) and all(abi_kit.bits_equal(x, y) for x, y in zip(ta, tb))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -63,14 +65,14 @@ def test_reference_dict_contract(macx, which, generic):
     assert list(c.to_reference_dict()) == names
     assert [float(v.flatten()[0]) for v in c.to_reference_dict().values()] == [float(i) for i in range(len(names))]
     # load_reference_dict: b takes a's bits
-    assert not same_bits(a, b)
+    assert not same_tensors(a, b)
     b.load_reference_dict(a.to_reference_dict())
-    assert same_bits(a, b)
+    assert same_tensors(a, b)
     # ... and so does checkpoint.load_reference on a single component
     d = unit_of(macx, which, generic, seed=3)
     state = macx.checkpoint.reference_state_dict(a)
     assert list(state) == ["macModel/" + n + ":0" for n in names]
-    assert macx.checkpoint.load_reference(d, state) == [] and same_bits(a, d)
+    assert macx.checkpoint.load_reference(d, state) == [] and same_tensors(a, d)
     # a wrong shape is a ValueError, a missing name a KeyError under strict (and reported, nothing else touched, without)
     first = next(iter(state))
     with pytest.raises(ValueError, match="shape mismatch"):
@@ -89,9 +91,9 @@ def test_checkpoint_restores_a_whole_net(macx, over):
     a = small_net(macx, **over)
     b = macx.MACNet(a.config, vocab=11, H=5, W=5, imageInDim=128, answerWordsNum=28, generator=torch.Generator().manual_seed(1))
     assert [type(getattr(a, m)) for m in ("enc", "stem", "out")] == [type(getattr(b, m)) for m in ("enc", "stem", "out")]
-    assert not same_bits(a, b)
+    assert not same_tensors(a, b)
     assert macx.checkpoint.load_reference(b, macx.checkpoint.reference_state_dict(a)) == []
-    assert same_bits(a, b)
+    assert same_tensors(a, b)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
