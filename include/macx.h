@@ -630,9 +630,10 @@ int macx_h2_gemm_planes(const float* hA, int B, int N, int K, const float* Wh, i
                         void* stream);
 int macx_h2_gemm(const float* A, int B, int N, int K, const float* W, int n_out, const float* bias, int act, float* out,
                  float* ws, size_t ws_floats, void* stream);
-/* The backward pass's contractions over the ROWS of H2 tensors (mac-network_amd/csrc/macx_wgrad_h2.hip.h), each on its own: thin
- * wrappers over the launchers the fused cell calls, so that the kernels are testable against fp64 in isolation
- * (tests/test_gpu_h2_contractions.py).  Operands are H2 tensors made with macx_h2_from_f32; a sequence of tensors lies `*_stride`
+/* The backward pass's contractions over the ROWS of H2 tensors (mac-network_amd/csrc/macx_wgrad_h2.hip.h), each on its own: the
+ * functions that fill the kernels' parameter blocks and launch them for the fused cell's backward pass, called on the caller's
+ * operands, plus a slab reduction per output (the cell reduces its four slab sets in one launch of its own) -- so that the kernels
+ * and their launch code are testable against fp64 in isolation (tests/test_gpu_h2_contractions.py).  Operands are H2 tensors made with macx_h2_from_f32; a sequence of tensors lies `*_stride`
  * FLOATS apart (a multiple of 4, >= macx_h2_floats of one tensor).  `o`: NULL = defaults; its tune table selects the kernel forms
  * (MACX_TUNE_WGRAD_PIPE, MACX_TUNE_SB_CONT, MACX_TUNE_PHASE_MASK); the calls run in the H2 family whatever gemm_family says.
  * Dimensions are multiples of 128 up to 1024, at most 2^24 rows per call.  A refused call (MACX_EINVAL; MACX_ESMALL: ws_floats
@@ -642,7 +643,8 @@ int macx_h2_gemm(const float* A, int B, int N, int K, const float* W, int n_out,
  *                   tensor of G.  nsplit >= 1 reduction splits of the library's own rows per split (a multiple of 32; a split
  *                   that starts at or behind M is empty and adds exact zeros).  hA2 / hG2 / out2: NULL all three, or a second
  *                   contraction of the same shape; at Kd % 256 == Jd % 256 == 0 and MACX_TUNE_WGRAD_PIPE >= 2 the two run as one
- *                   launch, as in the cell.  Launches: row-exponent minima, factor tables, contraction(s), slab reduction.
+ *                   launch, as in the cell.  Launches: row-exponent minima (one launch at Kd == Jd, as in the cell; else one per
+ *                   column count), factor tables, contraction(s), slab reduction.
  *   macx_h2_sb      per question b of each of nsteps steps S_b = X_b^T dI1_b (X, dI1: nsteps tensors [B*N][d]) and
  *                     dW1b[k][j] = sum S_b[k][j],   dW1a[k][j] = sum y[step][b][k] S_b[k][j]       (sums over steps and questions)
  *                   y [nsteps][B][d] fp32.  wide = 0: sb_h2_kernel (128 x 128 tiles); wide = 1: sb_h2w_kernel (128 x 256 tiles,
@@ -682,10 +684,16 @@ int macx_saved_activation(const macx_opts*, const macx_shapes*, int which, int s
                           float* out, void* stream);
 /* The control unit's question projections on their own (mac_cell.py:442-448; SURVEY 8b's `ctrl_inputs` unit):
  *   fwd:  ctrl_t[B,d] = controlInputAct(vecQuestions Wq + bq);  ctrl_inputs[p,B,d]: step i = ctrl_t WqU_i + bqU_i (one matrix per
- *         step with controlInputUnshared, else the shared one) -- the two launches macx_cell_begin issues for them;
- *   bwd:  d_ctrl_inputs[p,B,d] -> d_vecQuestions[B,d] and the non-NULL ones of GP->qInput_W / qInput_b / qInputU_W / qInputU_b.
- * Only the qInput / qInputU fields of macx_params / macx_param_grads are touched.  ws >= macx_ctrl_inputs_ws_floats() floats
- * (packed weights and [B,d] temporaries; nothing survives from fwd to bwd in it -- pass ctrl_t back in). */
+ *         step with controlInputUnshared, else the shared one) -- the function macx_cell_begin calls for its two launches;
+ *   bwd:  d_ctrl_inputs[p,B,d] -> d_vecQuestions[B,d] and the non-NULL ones of GP->qInput_W / qInput_b / qInputU_W / qInputU_b
+ *         (a NULL one is neither computed nor written) -- the function the cell's backward pass calls for this unit, launch for
+ *         launch: with controlInputUnshared the p products of dt as one batched launch and a fixed-order sum that also applies
+ *         act', and in the split family the p gradients of qInputU_W as one batched contraction.  The row sums and qInput_W's
+ *         contraction, which the cell collects into its end-of-pass batches, run in batches of this call's own before it returns.
+ * Only the qInput / qInputU fields of macx_params / macx_param_grads are touched.  ws >= macx_ctrl_inputs_ws_floats() floats:
+ * the packed weights (bwd: their transposes) [1 + nU][d,d] with nU = p or 1 matrices of qInputU, three [B,d] temporaries (dt, du,
+ * the summed d_ctrl_inputs), with controlInputUnshared the per-step products dt_part [p,B,d], and the eight slab sets of a batch of
+ * small weight gradients.  Nothing survives from fwd to bwd in it -- pass ctrl_t back in. */
 size_t macx_ctrl_inputs_ws_floats(const macx_opts*, const macx_shapes*);
 int macx_ctrl_inputs_fwd(const macx_opts*, const macx_shapes*, const macx_params*, const float* vecQuestions, float* ctrl_t,
                          float* ctrl_inputs, float* ws, size_t ws_floats, void* stream);
@@ -698,11 +706,12 @@ int macx_ctrl_inputs_bwd(const macx_opts*, const macx_shapes*, const macx_params
 int macx_kb_project(const macx_shapes*, const macx_dropout*, int step, const float* kb,
                     const float* W_packed, const float* b, float* out, float* drop_ws, void* stream);
 /* softmax(expMask(logits)) + att2Smry over the question words for one step
- * (mac_cell.py:155-181; ops.py:114-150, 243-247).  cc: continuous control [B,d]. */
+ * (mac_cell.py:155-181; ops.py:114-150, 243-247).  cc: continuous control [B,d].  The launcher the cell calls, for one step. */
 int macx_control_attend(const macx_shapes*, const float* cc, const float* words, const int32_t* lengths,
                         const float* w, const float* b, float* att, float* control, void* stream);
 /* its backward: d_control[B,d] -> d_cc[B,d], d_words[B,S,d] (written), d_w[d], d_b[1]; `att` is what the forward call
- * returned; ws >= macx_control_attend_bwd_ws_floats(shapes) floats.  d % 64 == 0. */
+ * returned; ws >= macx_control_attend_bwd_ws_floats(shapes) floats.  d % 64 == 0.  The cell's launcher of the two backward
+ * kernels for one step, then the two row sums of the parameter partials. */
 size_t macx_control_attend_bwd_ws_floats(const macx_shapes*);
 int macx_control_attend_bwd(const macx_shapes*, const float* d_control, const float* cc, const float* att, const float* words,
                             const float* w, float* ws, size_t ws_floats, float* d_cc, float* d_words, float* d_w, float* d_b,

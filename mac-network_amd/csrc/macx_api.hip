@@ -832,7 +832,7 @@ inline bool h2_wgrad_plan(int nt, int R, int Kd, int Jd, int nsplit, int pair, H
   const size_t ft = al4(((size_t)(Kd >> 7) * (Jd >> 7) * wgrad_h2_mpad(M) * sizeof(uint16_t) + 3) / 4);
   const size_t sl = (size_t)nsplit * Kd * Jd;
   size_t off = 0;
-  w->ecom = off; off += 4 * (size_t)H2X_ES;                       // [A | G | A2 | G2][EMIN_NB][8]
+  w->ecom = off; off += 4 * (size_t)H2X_ES;                       // h2_wgrad's [A families | G families][EMIN_NB][8]
   for (int i = 0; i < 2; ++i) { w->ftab[i] = off; off += (i == 0 || pair) ? ft : 0; }
   for (int i = 0; i < 2; ++i) { w->slab[i] = off; off += (i == 0 || pair) ? sl : 0; }
   w->total = off;
@@ -859,6 +859,191 @@ inline bool h2_sb_plan(int B, int N, int d, int nsteps, int qpg, int wide, int w
   const size_t dd = (size_t)d * d;
   w->slab_a = 0; w->slab_b = (size_t)w->ngroup * dd; w->total = 2 * (size_t)w->ngroup * dd;
   return true;
+}
+
+// ---- launch sequences on plain operands.  The fused cell's member functions and the unit-level exports both call these: each
+// parameter block is filled, and each of these kernels launched, in one place.
+
+// the control unit's question projections (mac_cell.py:442-448): t = act(vecQ Wq + bq), then the p control inputs cI_i = t WqU_i +
+// bqU_i in one launch (qInput is step-invariant; one WqU and bias per step where `unshared`).  wq_p, wqU_p: packed weights
+int ctrl_inputs_fwd(const float* vecQ, const float* wq_p, const float* bq, const float* wqU_p, const float* bqU, bool unshared, int act,
+                    int B, int d, int p, float* ctrl_t, float* cI, hipStream_t st) {
+  LinP l = lin_basic(vecQ, d, d, B, wq_p, bq, d, act, ctrl_t, d);
+  CK(small_linear_launch(l, 1, st));
+  LinP u = lin_basic(ctrl_t, d, d, B, wqU_p, bqU, d, MACX_ACT_NON, cI, d);
+  if (unshared) { u.zW = (size_t)d * d; u.zb = d; }
+  u.zout = (size_t)B * d;
+  CK(small_linear_launch(u, p, st));
+  return MACX_OK;
+}
+
+// ... backward: dt = sum_i dcI_i WqU_i^T ; du = dt * act'(t) ; dvecQ = du Wq^T (+ q_add, or NULL), and the gradients of qInput /
+// qInputU -- those whose field of GP is not NULL.  wqT, wqUT: packed transposes.  The row sums and qInput_W's contraction join the
+// caller's batches, which the caller runs; x.dt_part is read only where `unshared`
+struct CtrlInputsScratch { float* dt_part; float* dt; float* du; float* dcI_sum; float* slab; };    // [p,B,d], 3 x [B,d], wgrad_impl's
+int ctrl_inputs_bwd(bool unshared, int act, int B, int d, int p, const float* vecQ, const float* ctrl_t, const float* dcI,
+                    const float* wqT, const float* wqUT, const float* q_add, const CtrlInputsScratch& x, float* dvecQ,
+                    const macx_param_grads* GP, RowsumBatch& rs, SmallWgradBatch& wb, hipStream_t st) {
+  const size_t Bd = (size_t)B * d, dd = (size_t)d * d;
+  if (unshared) {
+    // dt: one batched launch of the p products (1536 workgroups at p = 12, one batch of operand loads each) and a fixed-order sum
+    // over the steps.  (Rounds 2-5 ran it as ONE linear over K = p d: 128 workgroups whose waves walked 96 k-groups in twelve
+    // dependent load batches -- 27.6 us of latency for 0.4 GFLOP.)
+    LinP li = lin_basic(dcI, d, d, B, wqUT, nullptr, d, MACX_ACT_NON, x.dt_part, d);
+    li.seg[0].zstride = Bd; li.zW = dd; li.zout = Bd;
+    CK(small_linear_launch(li, p, st));
+    // ... which also leaves du = dt * act'(t)
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)x.dt_part, p, Bd, x.dt, ctrl_t, act, x.du);
+    CK(hipGetLastError());
+    // the p weight gradients ctrl_t^T dcI_i share A: one batched launch (B rows -> a single split, no slabs)
+    if (GP->qInputU_W && gemm_split_mode() && !(kb_gemm_dbg() & 128) && wgrad_splits(B, d, d) == 1) {
+      TnP t;
+      memset(&t, 0, sizeof(t));
+      t.M = B; t.Kd = d; t.Jd = d; t.nsplit = 1; t.rows_per_split = rows_per_split(B, 1);
+      t.A = ctrl_t; t.lda = d; t.a_mod = B; t.G = dcI; t.ldg = d;
+      t.part = GP->qInputU_W; t.nz = p; t.zG = Bd; t.zpart = dd;
+      CK(wgrad6_launch(t, st));
+    } else if (GP->qInputU_W) {
+      for (int i = 0; i < p; ++i) CKI(wgrad_impl(ctrl_t, d, dcI + (size_t)i * Bd, d, B, d, d, GP->qInputU_W + (size_t)i * dd, x.slab, st));
+    }
+    CK(rs.add(dcI, B, d, d, GP->qInputU_b, st, p, Bd, d));
+  } else {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, dcI, p, Bd, x.dcI_sum);
+    CK(hipGetLastError());
+    LinP ls = lin_basic(x.dcI_sum, d, d, B, wqUT, nullptr, d, MACX_ACT_NON, x.dt, d);
+    CK(small_linear_launch(ls, 1, st));
+    if (GP->qInputU_W) CKI(wgrad_impl(ctrl_t, d, x.dcI_sum, d, B, d, d, GP->qInputU_W, x.slab, st));
+    CK(rs.add(x.dcI_sum, B, d, d, GP->qInputU_b, st));
+    hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, (const float*)x.dt, ctrl_t, act, Bd, x.du);
+    CK(hipGetLastError());
+  }
+  LinP l = lin_basic(x.du, d, d, B, wqT, nullptr, d, MACX_ACT_NON, dvecQ, d);
+  if (q_add) { l.addend = q_add; l.ld_add = d; }
+  CK(small_linear_launch(l, 1, st));
+  if (GP->qInput_W) CKI(wb.add(vecQ, d, x.du, d, B, d, d, GP->qInput_W, st));
+  CK(rs.add(x.du, B, d, d, GP->qInput_b, st));
+  return MACX_OK;
+}
+
+// the word attention (mac_cell.py:141-151) of nz steps in one launch: cc, att and control are [nz][B][.]
+int control_attend(int B, int S, int d, int nz, const float* cc, const float* words, const int32_t* lengths, const float* w,
+                   const float* bias, float* att, float* control, hipStream_t st) {
+  CtrlP c;
+  c.B = B; c.S = S; c.d = d;
+  c.cc = cc; c.z_cc = (size_t)B * d;
+  c.words = words; c.lengths = lengths;
+  c.w = w; c.bias = bias;
+  c.att = att; c.z_att = (size_t)B * S;
+  c.control = control; c.z_ctl = (size_t)B * d;
+  hipLaunchKernelGGL(control_attend_kernel, dim3(B, nz), dim3(256), 0, st, c);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// ... backward, its two kernels: dcontrol, cc, att, g_att (dL/d(att) of a loss on the map itself, or NULL), dl (scratch) and dcc
+// are [nz][B][.]; dwords and dw_part are written, or with acc_words added to (a recurrent control differentiates a step per call)
+int control_attend_bwd(int B, int S, int d, int nz, const float* dcontrol, const float* cc, const float* att, const float* words,
+                       const float* w, const float* g_att, float* dl, float* dcc, float* dwords, int acc_words, float* dw_part,
+                       float* db_part, hipStream_t st) {
+  CtrlBwdP c;
+  c.B = B; c.S = S; c.d = d; c.nz = nz;
+  c.dcontrol = dcontrol; c.z_dc = (size_t)B * d;
+  c.cc = cc; c.z_cc = (size_t)B * d;
+  c.att = att; c.z_att = (size_t)B * S;
+  c.words = words; c.w = w;
+  c.dl = dl;
+  c.dcc = dcc; c.z_dcc = (size_t)B * d;
+  c.dwords = dwords; c.acc_words = acc_words;
+  c.dw_part = dw_part; c.db_part = db_part;
+  c.g_att = g_att; c.z_g = (size_t)B * S;
+  hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, nz), dim3(256), 0, st, c);
+  CK(hipGetLastError());
+  hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// attention over the knowledge base + summary (mac_cell.py:266-275) from nparts partial logits; kb_len: NULL, or the live cells
+int kb_attend(int B, int N, int d, int nparts, const float* logit_part, const float* bias, const float* kb, const int32_t* kb_len,
+              float* att, float* info, hipStream_t st) {
+  KbAttP a;
+  a.B = B; a.N = N; a.d = d; a.nparts = nparts;
+  a.logit_part = logit_part; a.bias = bias;
+  a.kb = kb; a.kb_len = kb_len;
+  a.att = att; a.info = info;
+  hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, st, a);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// da = dinfo . KB (+ g_att, dL/d(att) of a loss on the map itself, or NULL)
+int kb_att_da(int B, int N, int d, const float* dinfo, int ld_dinfo, const float* kb, const float* g_att, float* da, hipStream_t st) {
+  hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo, ld_dinfo, kb, B, N, d, da, g_att);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// S_b = X_b^T dI1_b -> dW1a / dW1b slabs (and with dy_part the dy partials: the narrow kernel, one step) over nsteps steps in one
+// launch: the operands of step i lie x_stride / g_stride / y_stride floats behind step 0's (macx_wgrad_h2.hip.h)
+int sb_h2(int B, int N, int d, int nsteps, int qpg, bool wide, const float* hX, size_t x_stride, const float* hdI1, size_t g_stride,
+          const float* y, size_t y_stride, const float* W1a, float* slab_a, float* slab_b, float* dy_part, hipStream_t st) {
+  SbH2P q;
+  memset(&q, 0, sizeof(q));
+  q.B = B; q.N = N; q.d = d; q.qpg = qpg;
+  q.X = h2_view(hX, B * N, d); q.dI1 = h2_view(hdI1, B * N, d);
+  q.y = y; q.W1a = W1a;
+  q.dW1a_part = slab_a; q.dW1b_part = slab_b; q.dy_part = dy_part;
+  q.nsteps = nsteps;
+  q.x_step = x_stride * sizeof(float); q.g_step = g_stride * sizeof(float); q.y_step = y_stride;
+  q.dbg = kb_gemm_dbg();
+  CK(wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
+  return MACX_OK;
+}
+
+// One or two contractions sum_t A_t^T G_t over nt H2 tensors of R rows each (a_shared: tensor 0 of A at every t) into slabs
+// [nsplit][Kd][Jd]: the row-exponent minima, then the (pair) launch; the caller reduces the slabs.
+// ecom: [the np A families | the np G families][EMIN_NB][8]
+struct H2WgradOp { const float* A; size_t a_stride; bool a_shared; const float* G; size_t g_stride; float* ftab; float* slab; };
+int h2_wgrad(const H2WgradOp* op, int np, int nt, int R, int Kd, int Jd, int nsplit, int rows_per_split, int* ecom, hipStream_t st) {
+  {
+    EminList el;
+    memset(&el, 0, sizeof(el));
+    for (int i = 0; i < np; ++i) {
+      el.base[i] = reinterpret_cast<const char*>(op[i].A); el.stride[i] = op[i].a_stride * sizeof(float); el.nt[i] = op[i].a_shared ? 1 : nt;
+      el.base[np + i] = reinterpret_cast<const char*>(op[i].G); el.stride[np + i] = op[i].g_stride * sizeof(float); el.nt[np + i] = nt;
+    }
+    el.R = R; el.C = Kd; el.part = ecom;
+    if (Kd == Jd) {
+      CK(emin_list(el, 2 * np, st));
+    } else {        // a list has one column count: the G families as a list of their own
+      CK(emin_list(el, np, st));
+      for (int i = 0; i < np; ++i) { el.base[i] = el.base[np + i]; el.stride[i] = el.stride[np + i]; el.nt[i] = nt; }
+      el.C = Jd; el.part = ecom + np * H2X_ES;
+      CK(emin_list(el, np, st));
+    }
+  }
+  TnH2P t;
+  memset(&t, 0, sizeof(t));
+  t.M = nt * R; t.Kd = Kd; t.Jd = Jd; t.nsplit = nsplit; t.rows_per_split = rows_per_split;
+  t.R = R;
+  t.A = reinterpret_cast<const char*>(op[0].A); t.a_stride = op[0].a_stride * sizeof(float); t.a_mod = op[0].a_shared ? R : 0;
+  t.G = reinterpret_cast<const char*>(op[0].G); t.g_stride = op[0].g_stride * sizeof(float);
+  t.ecomA = ecom; t.ecomG = ecom + np * H2X_ES; t.ecom_nb = EMIN_NB;
+  t.ftab = reinterpret_cast<uint16_t*>(op[0].ftab);
+  t.dbg = kb_gemm_dbg();
+  t.part = op[0].slab;
+  if (np == 1) {
+    CK(wgrad_h2_launch(t, st));
+    return MACX_OK;
+  }
+  TnH2P u = t;
+  u.A = reinterpret_cast<const char*>(op[1].A); u.a_stride = op[1].a_stride * sizeof(float); u.a_mod = op[1].a_shared ? R : 0;
+  u.G = reinterpret_cast<const char*>(op[1].G); u.g_stride = op[1].g_stride * sizeof(float);
+  u.ecomA = ecom + H2X_ES; u.ecomG = ecom + 3 * H2X_ES;
+  u.ftab = reinterpret_cast<uint16_t*>(op[1].ftab);     // (a table of its own: the pair form builds both before either is read)
+  u.part = op[1].slab;
+  CK(wgrad_h2_launch_pair(t, u, st));
+  return MACX_OK;
 }
 
 }  // namespace
@@ -1155,26 +1340,12 @@ int macx_cell_begin(const macx_opts* o, const macx_shapes* s, const macx_dropout
   }
 
   // control inputs (mac_cell.py:442-448).  qInput is step-invariant; qInput{i} is batched over steps.
-  {
-    LinP l = lin_basic(in->vecQuestions, d, d, B, saved + L.wq_p, P->qInput_b, d, o->control_input_act, saved + L.ctrl_t, d);
-    CK(small_linear_launch(l, 1, st));
-    LinP u = lin_basic(saved + L.ctrl_t, d, d, B, saved + L.wqU_p, P->qInputU_b, d, MACX_ACT_NON, saved + L.cI, d);
-    if (o->control_input_unshared) { u.zW = (size_t)d * d; u.zb = d; }
-    u.zout = (size_t)B * d;
-    CK(small_linear_launch(u, p, st));
-  }
-  if (!o->control_feed_prev) {
-    // control is not recurrent (mac_cell.py:141-151): all p word attentions in one launch
-    CtrlP c;
-    c.B = B; c.S = s->S; c.d = d;
-    c.cc = saved + L.cc; c.z_cc = (size_t)B * d;
-    c.words = in->words; c.lengths = in->questionLengths;
-    c.w = P->ctrlLogits_w; c.bias = P->ctrlLogits_b;
-    c.att = saved + L.seg[MACX_SEG_ATT_QUESTION]; c.z_att = (size_t)B * s->S;
-    c.control = controls + (size_t)B * d; c.z_ctl = (size_t)B * d;
-    hipLaunchKernelGGL(control_attend_kernel, dim3(B, p), dim3(256), 0, st, c);
-    CK(hipGetLastError());
-  }
+  CKI(ctrl_inputs_fwd(in->vecQuestions, saved + L.wq_p, P->qInput_b, saved + L.wqU_p, P->qInputU_b, o->control_input_unshared,
+                      o->control_input_act, B, d, p, saved + L.ctrl_t, saved + L.cI, st));
+  // control is not recurrent (mac_cell.py:141-151): all p word attentions in one launch
+  if (!o->control_feed_prev)
+    CKI(control_attend(B, s->S, d, p, saved + L.cc, in->words, in->questionLengths, P->ctrlLogits_w, P->ctrlLogits_b,
+                       saved + L.seg[MACX_SEG_ATT_QUESTION], controls + (size_t)B * d, st));
   return MACX_OK;
 }
 
@@ -1200,16 +1371,8 @@ int CellRun::control_step(int i) const {
     LinP l2 = lin_basic(lin1, d, d, B, saved + L.wc2_p, P->contControl2_b, d, MACX_ACT_NON, cc_i, d);
     CK(small_linear_launch(l2, 1, st));
   }
-  CtrlP c;
-  c.B = B; c.S = S; c.d = d;
-  c.cc = cc_i; c.z_cc = 0;
-  c.words = in->words; c.lengths = in->questionLengths;
-  c.w = P->ctrlLogits_w; c.bias = P->ctrlLogits_b;
-  c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S; c.z_att = 0;
-  c.control = controls() + (size_t)(i + 1) * Bd; c.z_ctl = 0;
-  hipLaunchKernelGGL(control_attend_kernel, dim3(B, 1), dim3(256), 0, st, c);
-  CK(hipGetLastError());
-  return MACX_OK;
+  return control_attend(B, S, d, 1, cc_i, in->words, in->questionLengths, P->ctrlLogits_w, P->ctrlLogits_b,
+                        saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S, controls() + (size_t)(i + 1) * Bd, st);
 }
 
 // the read unit's three knowledge-base products, X = dropout(KB) Wx + bx, H1 = act(X (diag(y) W1a + W1b) + b1), I2 = H1 W2 + b2,
@@ -1332,15 +1495,8 @@ int CellRun::read_step(int i, int pre, bool md_fused) const {
   }
   CKI(R.chain ? read_products_chain(i, pre) : R.h2 ? read_products_h2(i) : read_products_f32(i));
   // attention over the knowledge base + summary (mac_cell.py:266-275)
-  KbAttP a;
-  a.B = B; a.N = N; a.d = d; a.nparts = R.chain ? 1 : d / (16 * kb_gemm_nw());
-  a.logit_part = saved + L.logit_part; a.bias = P->kbLogits_b;
-  a.kb = in->knowledgeBase; a.kb_len = in->kbLengths;
-  a.att = saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N;
-  a.info = info_raw(i);
-  hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, st, a);
-  CK(hipGetLastError());
-  return MACX_OK;
+  return kb_attend(B, N, d, R.chain ? 1 : d / (16 * kb_gemm_nw()), saved + L.logit_part, P->kbLogits_b, in->knowledgeBase,
+                   in->kbLengths, saved + L.seg[MACX_SEG_ATT_KB] + (size_t)i * B * N, info_raw(i), st);
 }
 
 // the write unit (mac_cell.py:305-375), writeInputs = BOTH: act(concat([memory, info (, selfSmry)]) W + b).  md_fused: its linear
@@ -1737,13 +1893,12 @@ int CellBwd::read_bwd_f32(int i) {
 // the read unit, from dL/d(info_i): dL/dc_i += its part, the dy partials, the products' gradients and dKB
 int CellBwd::read_unit_bwd(int i) {
   const int M = B * N;
-  hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo.at(i), dinfo.ld, in->knowledgeBase, B, N, d,
-                     ws + W.da, sg.d_att_kb ? sg.d_att_kb + (size_t)i * B * N : nullptr);
-  CK(hipGetLastError());
+  CKI(kb_att_da(B, N, d, dinfo.at(i), dinfo.ld, in->knowledgeBase, sg.d_att_kb ? sg.d_att_kb + (size_t)i * B * N : nullptr, ws + W.da, st));
   if (!R.h2) return read_bwd_f32(i);
   const size_t a = (size_t)i * L.act_stride;
+  float* dI1_i = ws + W.dI1 + (size_t)i * W.dI1_stride;
   const ReadH2 v{h2_view(saved + L.X + a, M, d), h2_view(saved + L.H1 + a, M, d), h2_view(saved + L.I2 + a, M, d),
-                 h2_view(ws + W.dI2 + (size_t)i * W.act_floats, M, d), h2_view(ws + W.dI1 + (size_t)i * W.dI1_stride, M, d),
+                 h2_view(ws + W.dI2 + (size_t)i * W.act_floats, M, d), h2_view(dI1_i, M, d),
                  h2_view(ws + W.dX + (size_t)i * W.act_floats, M, d)};
   if (!R.chain_sums) {
     ReadAttBwdH2P q;
@@ -1764,19 +1919,9 @@ int CellBwd::read_unit_bwd(int i) {
   }
   CKI(R.chain ? read_bwd_chain(i, v) : read_bwd_h2(i, v));
   // S_b = X_b^T dI1_b -> dW1a / dW1b slabs and dy partials (deferred: one launch over all steps in phase 2, dy from the chain kernel)
-  if (!R.sb_deferred) {
-    SbH2P q;
-    memset(&q, 0, sizeof(q));
-    q.nsteps = 1;
-    q.B = B; q.N = N; q.d = d; q.qpg = R.sb_qpg;
-    q.X = v.X; q.dI1 = v.dI1;
-    q.y = saved + L.y + (size_t)i * Bd; q.W1a = P->memKbProj_W;
-    q.dW1a_part = ws + W.slab_w1a + (size_t)i * R.ngroup * dd;
-    q.dW1b_part = ws + W.slab_w1b + (size_t)i * R.ngroup * dd;
-    q.dy_part = ws + W.dy_part;
-    q.dbg = kb_gemm_dbg();
-    CK(sb_h2_launch(q, st));
-  }
+  if (!R.sb_deferred)
+    CKI(sb_h2(B, N, d, 1, R.sb_qpg, false, saved + L.X + a, 0, dI1_i, 0, saved + L.y + (size_t)i * Bd, 0, P->memKbProj_W,
+              ws + W.slab_w1a + (size_t)i * R.ngroup * dd, ws + W.slab_w1b + (size_t)i * R.ngroup * dd, ws + W.dy_part, st));
   // dKB of every step after step 0: the merged launch, or where chain_bwd's launches carried steps p - 1 .. 1 on their idle CUs,
   // the closing launch of that route
   if (i == 0 && R.dkb.njobs) CK(chain_dkb_rest_launch(dkb_q, B * N, N, d, st));
@@ -1824,21 +1969,11 @@ int CellBwd::control_step_bwd(int i) {
     l.addend = DC + (size_t)(i + 1) * Bd; l.ld_add = d;
     CK(small_linear_launch(l, 1, st));
   }
-  CtrlBwdP c;
-  c.B = B; c.S = S; c.d = d; c.nz = 1;
-  c.dcontrol = DC + (size_t)(i + 1) * Bd; c.z_dc = 0;
-  c.cc = saved + L.cc + (size_t)i * Bd; c.z_cc = 0;
-  c.att = saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S; c.z_att = 0;
-  c.words = in->words; c.w = P->ctrlLogits_w;
-  c.dl = ws + W.ctrl_dl;
-  c.dcc = ws + W.dcc + (size_t)i * Bd; c.z_dcc = 0;
-  c.dwords = GI->words; c.acc_words = 1;
-  c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part + (size_t)i * B;
-  if (sg.d_att_question) c.g_att = sg.d_att_question + (size_t)i * B * S;
-  hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, 1), dim3(256), 0, st, c);
-  hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
-  CK(hipGetLastError());
   float* dcc_i = ws + W.dcc + (size_t)i * Bd;
+  CKI(control_attend_bwd(B, S, d, 1, DC + (size_t)(i + 1) * Bd, saved + L.cc + (size_t)i * Bd,
+                         saved + L.seg[MACX_SEG_ATT_QUESTION] + (size_t)i * B * S, in->words, P->ctrlLogits_w,
+                         sg.d_att_question ? sg.d_att_question + (size_t)i * B * S : nullptr, ws + W.ctrl_dl, dcc_i, GI->words, 1,
+                         ws + W.dwc_part, ws + W.dbc_part + (size_t)i * B, st));
   // parts of dL/dcc_i that did not come through the word attention
   if (!o->control_feed_prev_att) CK(axpy(ws + W.dccx + (size_t)(i + 1) * Bd, Bd, dcc_i, st));
   if (o->write_self_att && o->write_self_att_cont) {
@@ -1921,20 +2056,8 @@ int CellBwd::control_bwd_tail() {
       CK(rs.add(ws + W.dcc, p * B, d, d, GP->contControl2_b, st));
     }
   } else {
-    CtrlBwdP c;
-    c.B = B; c.S = S; c.d = d; c.nz = p;
-    c.dcontrol = DC + Bd; c.z_dc = Bd;
-    c.cc = saved + L.cc; c.z_cc = Bd;
-    c.att = saved + L.seg[MACX_SEG_ATT_QUESTION]; c.z_att = (size_t)B * S;
-    c.words = in->words; c.w = P->ctrlLogits_w;
-    c.dl = ws + W.ctrl_dl;
-    c.dcc = ws + W.dcc; c.z_dcc = Bd;
-    c.dwords = GI->words; c.acc_words = 0;
-    c.dw_part = ws + W.dwc_part; c.db_part = ws + W.dbc_part;
-    c.g_att = sg.d_att_question; c.z_g = (size_t)B * S;
-    hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, p), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
-    CK(hipGetLastError());
+    CKI(control_attend_bwd(B, S, d, p, DC + Bd, saved + L.cc, saved + L.seg[MACX_SEG_ATT_QUESTION], in->words, P->ctrlLogits_w,
+                           sg.d_att_question, ws + W.ctrl_dl, ws + W.dcc, GI->words, 0, ws + W.dwc_part, ws + W.dbc_part, st));
     CK(rs.add(ws + W.dwc_part, B, d, d, GP->ctrlLogits_w, st));
     CK(rs.add(ws + W.dbc_part, p * B, 1, 1, GP->ctrlLogits_b, st));
   }
@@ -1963,52 +2086,12 @@ int CellBwd::gate_wgrads() {
 
 // the control inputs (mac_cell.py:442-448): dt = sum_i dcI_i WqU_i^T ; du = dt * act'(t) ; dvecQ = du Wq^T
 int CellBwd::control_inputs_bwd() {
-  const float* ctrl_t = saved + L.ctrl_t;
-  if (o->control_input_unshared) {
-    // dt: one batched launch of the p products (1536 workgroups at p = 12, one batch of operand loads each) and a fixed-order sum
-    // over the steps.  (Rounds 2-5 ran it as ONE linear over K = p d: 128 workgroups whose waves walked 96 k-groups in twelve
-    // dependent load batches -- 27.6 us of latency for 0.4 GFLOP.)
-    LinP li = lin_basic(ws + W.dcI, d, d, B, wT + W.wqUT, nullptr, d, MACX_ACT_NON, ws + W.dt_part, d);
-    li.seg[0].zstride = Bd; li.zW = dd; li.zout = Bd;
-    CK(small_linear_launch(li, p, st));
-    // ... which also leaves du = dt * act'(t)
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dt_part), p, Bd, ws + W.dt, ctrl_t,
-                       (int)o->control_input_act, ws + W.du);
-    CK(hipGetLastError());
-    // the p weight gradients ctrl_t^T dcI_i share A: one batched launch (B rows -> a single split, no slabs)
-    if (gemm_split_mode() && !(kb_gemm_dbg() & 128) && wgrad_splits(B, d, d) == 1) {
-      TnP t;
-      memset(&t, 0, sizeof(t));
-      t.M = B; t.Kd = d; t.Jd = d; t.nsplit = 1; t.rows_per_split = rows_per_split(B, 1);
-      t.A = ctrl_t; t.lda = d; t.a_mod = B; t.G = ws + W.dcI; t.ldg = d;
-      t.part = GP->qInputU_W; t.nz = p; t.zG = Bd; t.zpart = dd;
-      CK(wgrad6_launch(t, st));
-    } else {
-      for (int i = 0; i < p; ++i)
-        CKI(wgrad_impl(ctrl_t, d, ws + W.dcI + (size_t)i * Bd, d, B, d, d, GP->qInputU_W + (size_t)i * dd, ws + W.small_slab, st));
-    }
-    CK(rs.add(ws + W.dcI, B, d, d, GP->qInputU_b, st, p, Bd, d));
-  } else {
-    float* dcI_sum = ws + W.tmpBd[1];
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, (const float*)(ws + W.dcI), p, Bd, dcI_sum);
-    CK(hipGetLastError());
-    LinP ls = lin_basic(dcI_sum, d, d, B, wT + W.wqUT, nullptr, d, MACX_ACT_NON, ws + W.dt, d);
-    CK(small_linear_launch(ls, 1, st));
-    CKI(wgrad_impl(ctrl_t, d, dcI_sum, d, B, d, d, GP->qInputU_W, ws + W.small_slab, st));
-    CK(rs.add(dcI_sum, B, d, d, GP->qInputU_b, st));
-    hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, (const float*)(ws + W.dt), ctrl_t, o->control_input_act, Bd,
-                       ws + W.du);
-    CK(hipGetLastError());
-  }
-  // dvecQ = du Wq^T (+ dL/d(initial state) where a state is initialised from the question vector, mac_cell.py:496-505: the first of
-  // them rides this launch's epilogue instead of an axpy of its own)
+  // (dL/d(initial state) where a state is initialised from the question vector, mac_cell.py:496-505: the first of them rides the
+  // dvecQ launch's epilogue instead of an axpy of its own)
   const float* q_add = o->init_ctrl == MACX_INIT_Q ? DC : (o->init_mem == MACX_INIT_Q ? DM : nullptr);
-  LinP l = lin_basic(ws + W.du, d, d, B, wT + W.wqT, nullptr, d, MACX_ACT_NON, GI->vecQuestions, d);
-  if (q_add) { l.addend = q_add; l.ld_add = d; }
-  CK(small_linear_launch(l, 1, st));
-  CKI(wb.add(in->vecQuestions, d, ws + W.du, d, B, d, d, GP->qInput_W, st));
-  CK(rs.add(ws + W.du, B, d, d, GP->qInput_b, st));
-  return MACX_OK;
+  const CtrlInputsScratch x{ws + W.dt_part, ws + W.dt, ws + W.du, ws + W.tmpBd[1], ws + W.small_slab};
+  return ctrl_inputs_bwd(o->control_input_unshared, o->control_input_act, B, d, p, in->vecQuestions, saved + L.ctrl_t, ws + W.dcI,
+                         wT + W.wqT, wT + W.wqUT, q_add, x, GI->vecQuestions, GP, rs, wb, st);
 }
 
 // the initial state (mac_cell.py:496-505)
@@ -2043,40 +2126,15 @@ int CellBwd::write_linear_wgrads() {
 int CellBwd::read_weight_contractions() {
   int ns_w = (int)R.ns_big;          // reduction splits of the dW2 / dWx contractions (H2 family: decided below)
   if (R.h2) {
-    int* ecom = reinterpret_cast<int*>(ws + W.ecom);       // [H1 | dI2 | KBd | dX][EMIN_NB][8]
-    constexpr int ES = EMIN_NB * 8;
-    {
-      EminList el;
-      memset(&el, 0, sizeof(el));
-      el.R = B * N; el.C = d; el.part = ecom;
-      el.base[0] = reinterpret_cast<const char*>(saved + L.H1); el.stride[0] = L.act_stride * sizeof(float); el.nt[0] = p;
-      el.base[1] = reinterpret_cast<const char*>(ws + W.dI2); el.stride[1] = W.act_floats * sizeof(float); el.nt[1] = p;
-      el.base[2] = reinterpret_cast<const char*>(saved + L.KBd); el.stride[2] = L.act_stride * sizeof(float); el.nt[2] = rdrop ? p : 1;
-      el.base[3] = reinterpret_cast<const char*>(ws + W.dX); el.stride[3] = W.act_floats * sizeof(float); el.nt[3] = p;
-      CK(emin_list(el, 4, st));
-    }
-    TnH2P t;
-    memset(&t, 0, sizeof(t));
     // mode 3: the two contractions share ONE launch AND the chip -- half the reduction splits each, so that the 2 x 128 workgroups
     // are all resident at once (one per CU) instead of 2 x 256 in two rounds: a workgroup's prologue, its 256 KB slab and the slab
     // reduction's input are paid for once per CU instead of twice
     ns_w = (wgrad_pipe_mode() >= 3 && wgrad_h2_kw(d) == 2 && wgrad_h2_jw(d) == 2 && R.ns_big >= 2) ? (int)R.ns_big / 2 : (int)R.ns_big;
-    t.M = p * B * N; t.Kd = d; t.Jd = d; t.nsplit = ns_w; t.rows_per_split = rows_per_split(t.M, t.nsplit);
-    t.R = B * N;
-    t.A = reinterpret_cast<const char*>(saved + L.H1); t.a_stride = L.act_stride * sizeof(float); t.a_mod = 0;
-    t.G = reinterpret_cast<const char*>(ws + W.dI2); t.g_stride = W.act_floats * sizeof(float);
-    t.ecomA = ecom; t.ecomG = ecom + ES; t.ecom_nb = EMIN_NB;
-    t.ftab = reinterpret_cast<uint16_t*>(ws + W.wg_ftab);
-    t.dbg = kb_gemm_dbg();
-    t.part = ws + W.slab_w2;
-    const TnH2P t_w2 = t;
-    t.A = reinterpret_cast<const char*>(saved + L.KBd);
-    t.a_mod = rdrop ? 0 : B * N;                            // no dropout: the same (converted) KB every step
-    t.G = reinterpret_cast<const char*>(ws + W.dX);
-    t.ecomA = ecom + 2 * ES; t.ecomG = ecom + 3 * ES;
-    t.part = ws + W.slab_wx;
-    t.ftab = reinterpret_cast<uint16_t*>(ws + W.wg_ftab2);    // (a table of its own: the pair form builds both before either is read)
-    CK(wgrad_h2_launch_pair(t_w2, t, st));
+    const H2WgradOp op[2] = {
+        {saved + L.H1, L.act_stride, false, ws + W.dI2, W.act_floats, ws + W.wg_ftab, ws + W.slab_w2},
+        // (no dropout: the same (converted) KB every step)
+        {saved + L.KBd, L.act_stride, !rdrop, ws + W.dX, W.act_floats, ws + W.wg_ftab2, ws + W.slab_wx}};
+    CKI(h2_wgrad(op, 2, p, B * N, d, d, ns_w, rows_per_split(p * B * N, ns_w), reinterpret_cast<int*>(ws + W.ecom), st));
   } else {
     TnP t;
     memset(&t, 0, sizeof(t));
@@ -2093,16 +2151,8 @@ int CellBwd::read_weight_contractions() {
   if (R.sb_deferred) {
     // dW1a = sum_i sum_b diag(y_ib) S_ib, dW1b = sum_i sum_b S_ib, S_ib = X_ib^T dI1_ib: every step in one launch, the two
     // accumulators of a workgroup run through all of them (macx_wgrad_h2.hip.h)
-    SbH2P q;
-    memset(&q, 0, sizeof(q));
-    q.B = B; q.N = N; q.d = d; q.qpg = R.sb_qpg;
-    q.X = h2_view(saved + L.X, B * N, d); q.dI1 = h2_view(ws + W.dI1, B * N, d);
-    q.y = saved + L.y; q.W1a = P->memKbProj_W;
-    q.dW1a_part = ws + W.slab_w1a; q.dW1b_part = ws + W.slab_w1b; q.dy_part = nullptr;
-    q.nsteps = p;
-    q.x_step = L.act_stride * sizeof(float); q.g_step = W.dI1_stride * sizeof(float); q.y_step = Bd;
-    q.dbg = kb_gemm_dbg();
-    CK(R.sb_wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
+    CKI(sb_h2(B, N, d, p, R.sb_qpg, R.sb_wide, saved + L.X, L.act_stride, ws + W.dI1, W.dI1_stride, saved + L.y, Bd, P->memKbProj_W,
+              ws + W.slab_w1a, ws + W.slab_w1b, nullptr, st));
   }
   SlabList sl;
   sl.d[0] = SlabDesc{ws + W.slab_w2, ns_w, dd / 4, GP->memKbProj2_W, 0};
@@ -2370,13 +2420,7 @@ int macx_control_attend(const macx_shapes* s, const float* cc, const float* word
                         const float* b, float* att, float* control, void* stream) {
   if (!s || !cc || !words || !lengths || !w || !b || !att || !control) return MACX_EINVAL;
   if (s->B < 1 || s->S < 1 || s->S > C_MAXS || s->d < 4 || s->d % 4 != 0) return MACX_EINVAL;
-  CtrlP c;
-  c.B = s->B; c.S = s->S; c.d = s->d;
-  c.cc = cc; c.z_cc = 0; c.words = words; c.lengths = lengths; c.w = w; c.bias = b;
-  c.att = att; c.z_att = 0; c.control = control; c.z_ctl = 0;
-  hipLaunchKernelGGL(control_attend_kernel, dim3(s->B, 1), dim3(256), 0, (hipStream_t)stream, c);
-  CK(hipGetLastError());
-  return MACX_OK;
+  return control_attend(s->B, s->S, s->d, 1, cc, words, lengths, w, b, att, control, (hipStream_t)stream);
 }
 
 size_t macx_control_attend_bwd_ws_floats(const macx_shapes* s) {
@@ -2392,19 +2436,11 @@ int macx_control_attend_bwd(const macx_shapes* s, const float* d_control, const 
   if (ws_floats < macx_control_attend_bwd_ws_floats(s)) return MACX_ESMALL;
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, S = s->S, d = s->d;
-  CtrlBwdP c;
-  c.B = B; c.S = S; c.d = d; c.nz = 1;
-  c.dcontrol = d_control; c.z_dc = 0; c.cc = cc; c.z_cc = 0; c.att = att; c.z_att = 0;
-  c.words = words; c.w = w;
-  c.dl = ws;
-  c.dw_part = ws + al4((size_t)B * S);
-  c.db_part = c.dw_part + al4((size_t)B * d);
-  c.dcc = d_cc; c.z_dcc = 0; c.dwords = d_words; c.acc_words = 0;
-  hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, 1), dim3(256), 0, st, c);
-  hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / 64), dim3(256), 0, st, c);
-  CK(hipGetLastError());
-  CK(rowsum(c.dw_part, B, d, d, d_w, st));
-  CK(rowsum(c.db_part, B, 1, 1, d_b, st));
+  float* dw_part = ws + al4((size_t)B * S);
+  float* db_part = dw_part + al4((size_t)B * d);
+  CKI(control_attend_bwd(B, S, d, 1, d_control, cc, att, words, w, nullptr, ws, d_cc, d_words, 0, dw_part, db_part, st));
+  CK(rowsum(dw_part, B, d, d, d_w, st));
+  CK(rowsum(db_part, B, 1, 1, d_b, st));
   return MACX_OK;
 }
 
@@ -2489,12 +2525,7 @@ int macx_kb_attend_fwd(int B, int N, int d, const float* logits, const float* bi
 int macx_kb_attend_fwd_l(int B, int N, int d, const float* logits, const float* bias, const float* kb, const int32_t* kb_lengths,
                          float* att, float* info, void* stream) {
   if (!logits || !bias || !kb || !att || !info || B < 1 || N < 1 || N > K_MAXN || d < 128 || d % 128) return MACX_EINVAL;
-  KbAttP a;
-  a.B = B; a.N = N; a.d = d; a.nparts = 1;
-  a.logit_part = logits; a.bias = bias; a.kb = kb; a.att = att; a.info = info; a.kb_len = kb_lengths;
-  hipLaunchKernelGGL(kb_attend_kernel, dim3(B, d / 128), dim3(KA_THREADS), 0, (hipStream_t)stream, a);
-  CK(hipGetLastError());
-  return MACX_OK;
+  return kb_attend(B, N, d, 1, logits, bias, kb, kb_lengths, att, info, (hipStream_t)stream);
 }
 size_t macx_kb_attend_bwd_ws_floats(int B, int N, int d) { return (size_t)B * N + 8; (void)d; }
 // backward: da = dinfo . KB ; dlogits = att (da - sum_n att da) ; dKB (=, or += with accumulate) att (x) dinfo
@@ -2504,13 +2535,14 @@ int macx_kb_attend_bwd(int B, int N, int d, const float* att, const float* kb, c
   if (ws_floats < macx_kb_attend_bwd_ws_floats(B, N, d)) return MACX_ESMALL;
   hipStream_t st = (hipStream_t)stream;
   float* da = ws;
-  hipLaunchKernelGGL(kb_att_da_kernel, dim3((B * N + 3) / 4), dim3(256), 0, st, dinfo, d, kb, B, N, d, da);
+  CKI(kb_att_da(B, N, d, dinfo, d, kb, nullptr, da, st));
   hipLaunchKernelGGL(op_softmax_bwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, att, (const float*)da, (size_t)B, N, dlogits);
+  CK(hipGetLastError());
   if (dkb) {
     const size_t n = (size_t)B * N * d;
     hipLaunchKernelGGL(kb_attend_dkb_kernel, dim3(op_grid(n)), dim3(256), 0, st, att, dinfo, n, N, d, accumulate, dkb);
+    CK(hipGetLastError());
   }
-  CK(hipGetLastError());
   return MACX_OK;
 }
 
@@ -3447,7 +3479,8 @@ size_t macx_h2_wgrad_ws_floats(const macx_opts* o, int nt, int R, int Kd, int Jd
   return h2_wgrad_plan(nt, R, Kd, Jd, nsplit, pair != 0, &w) ? w.total : 0;
 }
 
-// CellBwd::read_weight_contractions' H2 branch on the caller's operands: minima, factor tables, contraction(s), slab reduction
+// h2_wgrad, which is CellBwd::read_weight_contractions' H2 branch, on the caller's operands (minima, factor tables,
+// contraction(s)), then a slab reduction per contraction
 int macx_h2_wgrad(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit, const float* hA, size_t a_stride, int a_shared,
                   const float* hG, size_t g_stride, float* out, const float* hA2, size_t a2_stride, int a2_shared, const float* hG2,
                   size_t g2_stride, float* out2, float* ws, size_t ws_floats, void* stream) {
@@ -3464,42 +3497,9 @@ int macx_h2_wgrad(const macx_opts* o, int nt, int R, int Kd, int Jd, int nsplit,
   if (pair && (!h2x_stride_ok(a2_stride, a2_shared ? 1 : nt, R, Kd) || !h2x_stride_ok(g2_stride, nt, R, Jd))) return MACX_EINVAL;
   if (ws_floats < w.total) return MACX_ESMALL;
   const hipStream_t st = (hipStream_t)stream;
-  int* ecom = reinterpret_cast<int*>(ws + w.ecom);
-  const int np = pair ? 2 : 1;
-  {
-    // the A families have Kd columns and the G families Jd: one list each (family i of a list -> ecom + (2 i + which) ES)
-    EminList el;
-    memset(&el, 0, sizeof(el));
-    el.R = R; el.C = Kd; el.part = ecom;
-    el.base[0] = reinterpret_cast<const char*>(hA); el.stride[0] = a_stride * sizeof(float); el.nt[0] = a_shared ? 1 : nt;
-    el.base[1] = reinterpret_cast<const char*>(hA2); el.stride[1] = a2_stride * sizeof(float); el.nt[1] = a2_shared ? 1 : nt;
-    CK(emin_list(el, np, st));
-    el.C = Jd; el.part = ecom + 2 * H2X_ES;
-    el.base[0] = reinterpret_cast<const char*>(hG); el.stride[0] = g_stride * sizeof(float); el.nt[0] = nt;
-    el.base[1] = reinterpret_cast<const char*>(hG2); el.stride[1] = g2_stride * sizeof(float); el.nt[1] = nt;
-    CK(emin_list(el, np, st));
-  }
-  TnH2P t;
-  memset(&t, 0, sizeof(t));
-  t.M = nt * R; t.Kd = Kd; t.Jd = Jd; t.nsplit = nsplit; t.rows_per_split = w.rows_per_split;
-  t.R = R;
-  t.A = reinterpret_cast<const char*>(hA); t.a_stride = a_stride * sizeof(float); t.a_mod = a_shared ? R : 0;
-  t.G = reinterpret_cast<const char*>(hG); t.g_stride = g_stride * sizeof(float);
-  t.ecomA = ecom; t.ecomG = ecom + 2 * H2X_ES; t.ecom_nb = EMIN_NB;
-  t.ftab = reinterpret_cast<uint16_t*>(ws + w.ftab[0]);
-  t.dbg = kb_gemm_dbg();
-  t.part = ws + w.slab[0];
-  if (pair) {
-    TnH2P u = t;
-    u.A = reinterpret_cast<const char*>(hA2); u.a_stride = a2_stride * sizeof(float); u.a_mod = a2_shared ? R : 0;
-    u.G = reinterpret_cast<const char*>(hG2); u.g_stride = g2_stride * sizeof(float);
-    u.ecomA = ecom + H2X_ES; u.ecomG = ecom + 3 * H2X_ES;
-    u.ftab = reinterpret_cast<uint16_t*>(ws + w.ftab[1]);
-    u.part = ws + w.slab[1];
-    CK(wgrad_h2_launch_pair(t, u, st));
-  } else {
-    CK(wgrad_h2_launch(t, st));
-  }
+  const H2WgradOp op[2] = {{hA, a_stride, a_shared != 0, hG, g_stride, ws + w.ftab[0], ws + w.slab[0]},
+                           {hA2, a2_stride, a2_shared != 0, hG2, g2_stride, ws + w.ftab[1], ws + w.slab[1]}};
+  CKI(h2_wgrad(op, pair ? 2 : 1, nt, R, Kd, Jd, nsplit, w.rows_per_split, reinterpret_cast<int*>(ws + w.ecom), st));
   CK(slab_reduce_launch(ws + w.slab[0], nsplit, (size_t)Kd * Jd, out, 0, st));
   if (pair) CK(slab_reduce_launch(ws + w.slab[1], nsplit, (size_t)Kd * Jd, out2, 0, st));
   return MACX_OK;
@@ -3512,7 +3512,7 @@ size_t macx_h2_sb_ws_floats(const macx_opts* o, int B, int N, int d, int nsteps,
   return h2_sb_plan(B, N, d, nsteps, qpg, wide, 0, &w) ? w.total : 0;
 }
 
-// the S_b launch of CellBwd (per step with dy, or deferred over all steps) on the caller's operands, and its slab reduction
+// sb_h2, the S_b launch of CellBwd (per step with dy, or deferred over all steps), on the caller's operands, and its slab reductions
 int macx_h2_sb(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int wide, const float* hX, size_t x_stride,
                const float* hdI1, size_t g_stride, const float* y, const float* W1a, float* dW1a, float* dW1b, float* dy_part,
                float* ws, size_t ws_floats, void* stream) {
@@ -3528,16 +3528,7 @@ int macx_h2_sb(const macx_opts* o, int B, int N, int d, int nsteps, int qpg, int
   if (!h2x_stride_ok(x_stride, nsteps, rows, d) || !h2x_stride_ok(g_stride, nsteps, rows, d)) return MACX_EINVAL;
   if (ws_floats < w.total) return MACX_ESMALL;
   const hipStream_t st = (hipStream_t)stream;
-  SbH2P q;
-  memset(&q, 0, sizeof(q));
-  q.B = B; q.N = N; q.d = d; q.qpg = w.qpg;
-  q.X = h2_view(hX, B * N, d); q.dI1 = h2_view(hdI1, B * N, d);
-  q.y = y; q.W1a = W1a;
-  q.dW1a_part = ws + w.slab_a; q.dW1b_part = ws + w.slab_b; q.dy_part = dy_part;
-  q.nsteps = nsteps;
-  q.x_step = x_stride * sizeof(float); q.g_step = g_stride * sizeof(float); q.y_step = (size_t)B * d;
-  q.dbg = kb_gemm_dbg();
-  CK(wide ? sb_h2w_launch(q, st) : sb_h2_launch(q, st));
+  CKI(sb_h2(B, N, d, nsteps, w.qpg, wide != 0, hX, x_stride, hdI1, g_stride, y, (size_t)B * d, W1a, ws + w.slab_a, ws + w.slab_b, dy_part, st));
   const size_t dd = (size_t)d * d;
   CK(slab_reduce_launch(ws + w.slab_a, w.ngroup, dd, dW1a, 0, st));
   CK(slab_reduce_launch(ws + w.slab_b, w.ngroup, dd, dW1b, 0, st));
@@ -3614,11 +3605,29 @@ int macx_cell_forward_chain_time(const macx_opts* o, const macx_shapes* s, const
 
 // ---- the control unit's question projections (mac_cell.py:442-448) behind a contract of their own -----------------
 //   t = act(vecQ Wq + bq)  [B,d]  (controlInputAct);   cI_i = t WqU_i + bqU_i  [p,B,d]  (one matrix per step with
-//   controlInputUnshared, else the same one p times) -- the two launches macx_cell_begin issues for them.
+//   controlInputUnshared, else the same one p times): ctrl_inputs_fwd, which macx_cell_begin calls, on weights packed here.
+// The workspace: the packed weights (the backward call: their transposes) [1 + nU][d,d], then the backward pass's dt, du and summed
+// d_ctrl_inputs [3][B,d], with unshared inputs dt_part [p,B,d], and a SmallWgradBatch's eight slab sets.
+namespace {
+inline size_t ctrl_inputs_slab_stride(const macx_shapes* s) { return al4((size_t)wgrad_splits(s->B, s->d, s->d) * s->d * s->d); }
+// packs qInput_W and the nU matrices of qInputU_W (T: their transposes) into ws
+int ctrl_inputs_pack(const macx_params* P, bool T, int d, int nU, float* ws, hipStream_t st) {
+  const size_t dd = (size_t)d * d;
+  Packer pk;
+  add_pack(pk, T, P->qInput_W, d, d, ws);
+  for (int i = 0; i < nU; ++i) {
+    if (pk.n == PACK_MAX) CK(pk.run(st));
+    add_pack(pk, T, P->qInputU_W + (size_t)i * dd, d, d, ws + (1 + i) * dd);
+  }
+  CK(pk.run(st));
+  return MACX_OK;
+}
+}  // namespace
+
 size_t macx_ctrl_inputs_ws_floats(const macx_opts* o, const macx_shapes* s) {
   if (!o || !s || s->d < 1 || s->B < 1 || s->p < 1) return 0;
   const size_t dd = (size_t)s->d * s->d, Bd = (size_t)s->B * s->d, nU = o->control_input_unshared ? s->p : 1;
-  return (1 + nU) * dd + 3 * Bd + (size_t)wgrad_splits(s->B, s->d, s->d) * dd + 64;
+  return (1 + nU) * dd + (3 + (o->control_input_unshared ? s->p : 0)) * Bd + 8 * ctrl_inputs_slab_stride(s) + 64;
 }
 
 int macx_ctrl_inputs_fwd(const macx_opts* o, const macx_shapes* s, const macx_params* P, const float* vecQuestions, float* ctrl_t,
@@ -3629,30 +3638,15 @@ int macx_ctrl_inputs_fwd(const macx_opts* o, const macx_shapes* s, const macx_pa
   if (misaligned(vecQuestions) || misaligned(ctrl_t) || misaligned(ctrl_inputs) || misaligned(ws)) return MACX_EINVAL;
   if (ws_floats < macx_ctrl_inputs_ws_floats(o, s)) return MACX_ESMALL;
   hipStream_t st = (hipStream_t)stream;
-  const int B = s->B, d = s->d, p = s->p;
-  const size_t dd = (size_t)d * d;
-  const int nU = o->control_input_unshared ? p : 1;
-  float* wq_p = ws;
-  float* wqU_p = ws + dd;
-  Packer pk;
-  pk.add(P->qInput_W, d, 1, d, d, wq_p);
-  for (int i = 0; i < nU; ++i) {
-    if (pk.n == PACK_MAX) CK(pk.run(st));
-    pk.add(P->qInputU_W + (size_t)i * dd, d, 1, d, d, wqU_p + (size_t)i * dd);
-  }
-  CK(pk.run(st));
-  LinP l = lin_basic(vecQuestions, d, d, B, wq_p, P->qInput_b, d, o->control_input_act, ctrl_t, d);
-  CK(small_linear_launch(l, 1, st));
-  LinP u = lin_basic(ctrl_t, d, d, B, wqU_p, P->qInputU_b, d, MACX_ACT_NON, ctrl_inputs, d);
-  if (o->control_input_unshared) { u.zW = dd; u.zb = d; }
-  u.zout = (size_t)B * d;
-  CK(small_linear_launch(u, p, st));
-  return MACX_OK;
+  const int d = s->d;
+  CKI(ctrl_inputs_pack(P, false, d, o->control_input_unshared ? s->p : 1, ws, st));
+  return ctrl_inputs_fwd(vecQuestions, ws, P->qInput_b, ws + (size_t)d * d, P->qInputU_b, o->control_input_unshared,
+                         o->control_input_act, s->B, d, s->p, ctrl_t, ctrl_inputs, st);
 }
 
 // backward of the above: d_ctrl_inputs [p,B,d] -> d_vecQuestions [B,d] and the gradients of qInput / qInputU (the non-NULL fields of
-// `GP`: qInput_W [d,d], qInput_b [d], qInputU_W [nU,d,d], qInputU_b [nU,d]) -- the arithmetic of the cell's backward pass for this
-// unit (SURVEY appendix A rows "qInput", "qInput{i}"): dt = sum_i dcI_i WqU_i^T, du = dt * act'(t), dvecQ = du Wq^T.
+// `GP`: qInput_W [d,d], qInput_b [d], qInputU_W [nU,d,d], qInputU_b [nU,d]) -- ctrl_inputs_bwd, which CellBwd::control_inputs_bwd
+// calls (SURVEY appendix A rows "qInput", "qInput{i}"), with batches of this call's own that run before it returns.
 int macx_ctrl_inputs_bwd(const macx_opts* o, const macx_shapes* s, const macx_params* P, const float* vecQuestions, const float* ctrl_t,
                          const float* d_ctrl_inputs, const macx_param_grads* GP, float* d_vecQuestions, float* ws, size_t ws_floats,
                          void* stream) {
@@ -3664,43 +3658,18 @@ int macx_ctrl_inputs_bwd(const macx_opts* o, const macx_shapes* s, const macx_pa
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, d = s->d, p = s->p;
   const size_t dd = (size_t)d * d, Bd = (size_t)B * d;
-  const int nU = o->control_input_unshared ? p : 1;
-  float* wqT = ws;
-  float* wqUT = wqT + dd;
-  float* dt = wqUT + (size_t)nU * dd;
-  float* du = dt + Bd;
-  float* dsum = du + Bd;
-  float* slab = dsum + Bd;
-  Packer pk;
-  pk.add(P->qInput_W, 1, d, d, d, wqT);
-  for (int i = 0; i < nU; ++i) {
-    if (pk.n == PACK_MAX) CK(pk.run(st));
-    pk.add(P->qInputU_W + (size_t)i * dd, 1, d, d, d, wqUT + (size_t)i * dd);
-  }
-  CK(pk.run(st));
-  if (o->control_input_unshared) {
-    LinP li = lin_basic(d_ctrl_inputs, d, d, B, wqUT, nullptr, d, MACX_ACT_NON, dt, d);
-    li.Ktot = p * d;
-    li.rep_stride = Bd;
-    CK(small_linear_launch(li, 1, st));
-    if (GP->qInputU_W)
-      for (int i = 0; i < p; ++i)
-        CKI(wgrad_impl(ctrl_t, d, d_ctrl_inputs + (size_t)i * Bd, d, B, d, d, GP->qInputU_W + (size_t)i * dd, slab, st));
-    CK(rowsum(d_ctrl_inputs, B, d, d, GP->qInputU_b, st, p, Bd, d));
-  } else {
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(256), dim3(256), 0, st, d_ctrl_inputs, p, Bd, dsum);
-    CK(hipGetLastError());
-    LinP ls = lin_basic(dsum, d, d, B, wqUT, nullptr, d, MACX_ACT_NON, dt, d);
-    CK(small_linear_launch(ls, 1, st));
-    if (GP->qInputU_W) CKI(wgrad_impl(ctrl_t, d, dsum, d, B, d, d, GP->qInputU_W, slab, st));
-    CK(rowsum(dsum, B, d, d, GP->qInputU_b, st));
-  }
-  hipLaunchKernelGGL(mul_actgrad_kernel, dim3(64), dim3(256), 0, st, (const float*)dt, ctrl_t, o->control_input_act, Bd, du);
-  CK(hipGetLastError());
-  LinP l = lin_basic(du, d, d, B, wqT, nullptr, d, MACX_ACT_NON, d_vecQuestions, d);
-  CK(small_linear_launch(l, 1, st));
-  if (GP->qInput_W) CKI(wgrad_impl(vecQuestions, d, du, d, B, d, d, GP->qInput_W, slab, st));
-  CK(rowsum(du, B, d, d, GP->qInput_b, st));
+  const bool unshared = o->control_input_unshared != 0;
+  const int nU = unshared ? p : 1;
+  CKI(ctrl_inputs_pack(P, true, d, nU, ws, st));
+  float* dt = ws + (1 + nU) * dd;
+  float* slab = dt + (3 + (unshared ? p : 0)) * Bd;
+  const CtrlInputsScratch x{dt + 3 * Bd, dt, dt + Bd, dt + 2 * Bd, slab};
+  RowsumBatch rs;
+  SmallWgradBatch wb(slab, ctrl_inputs_slab_stride(s));
+  CKI(ctrl_inputs_bwd(unshared, o->control_input_act, B, d, p, vecQuestions, ctrl_t, d_ctrl_inputs, ws, ws + dd, nullptr, x,
+                      d_vecQuestions, GP, rs, wb, st));
+  CKI(wb.run(st));
+  CK(rs.run(st));
   return MACX_OK;
 }
 

@@ -7,8 +7,6 @@
 namespace macx {
 
 struct LinSeg { const float* x; int ld; int K; size_t zstride; };
-// rep_stride != 0: the input is seg[0] repeated along k -- block r (k in [r K0, (r+1) K0)) lives at seg[0].x + r * rep_stride
-// (per-step [B,d] tensors stored [p][B][d] read as one [B, p d] operand)
 struct LinP {
   LinSeg seg[3];
   int Ktot, rows, n_out;
@@ -22,7 +20,6 @@ struct LinP {
   int drop_ld;                      // row stride of the dropout index: the logical width of a zero-padded cell; 0 = n_out
   float* out_drop; int ld_od;       // use_drop == 2: `out` keeps val, out_drop receives val*f1*f2 (the next consumer's dropped copy)
   const float* addend; int ld_add; size_t zadd;                      // val += addend
-  size_t rep_stride;
   // PART form (small_linear_part_launch): the input row of question b is the sum of the chain kernel's per-tile partials
   // part[tile][3][Ktot] over the 64-row tiles the question's `part_N` rows touch (macx_chain_h2.hip.h, dy_part) -- the reduction
   // that would otherwise be a launch of its own in front of this one.  Column block 0 also writes the summed rows to part_sum.
@@ -123,15 +120,9 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
     for (int u = 0; u < PF; ++u) {
       const int Q = min(Q0 + NWV * u, nQ - 1);
       int s = 0, koff = Q * 16;
-      size_t rep_off = 0;
-      if (p.rep_stride) {
-        const int r = koff / p.seg[0].K;
-        koff -= r * p.seg[0].K;
-        rep_off = (size_t)r * p.rep_stride;
-      } else {
-        while (koff >= p.seg[s].K) { koff -= p.seg[s].K; ++s; }
-      }
-      const float* xs = p.seg[s].x + (size_t)z * p.seg[s].zstride + rep_off + koff + lg * 4;
+      // (the walk over the three segments written out: as a loop over p.seg[s] it put the parameter block into scratch)
+      if (koff >= p.seg[0].K) { koff -= p.seg[0].K; s = 1; if (koff >= p.seg[1].K) { koff -= p.seg[1].K; s = 2; } }
+      const float* xs = p.seg[s].x + (size_t)z * p.seg[s].zstride + koff + lg * 4;
       const int ld = p.seg[s].ld;
 #pragma unroll
       for (int c = 0; c < CTL; ++c) bf[u][c] = *reinterpret_cast<const f32x4*>(Wz + (size_t)Q * 4 * p.n_out * 4 + c * 64);

@@ -160,15 +160,27 @@ def test_unit_exports_reject_what_they_cannot_do(macx, dev):
     assert u.L.macx_read_fwd(*u.head(), abi_kit.ptr(kb), abi_kit.ptr(x), abi_kit.ptr(x), abi_kit.ptr(u.saved), 16, abi_kit.ptr(x), abi_kit.ptr(att), u.stream) == -4      # MACX_ESMALL
 
 
-@pytest.mark.parametrize("unshared,act,B,d,p", [(True, "TANH", 5, 128, 3), (False, "TANH", 3, 256, 2), (True, "NON", 64, 512, 12),
-                                                (True, "RELU", 4, 128, 2)])
-def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p):
+def _ctrl_case(unshared, act, B, d, p, gemm=None):
+    """the ids of the four first cases are what they were before the family became a parameter"""
+    base = "%s-%s-%d-%d-%d" % (unshared, act, B, d, p)
+    return pytest.param(unshared, act, B, d, p, gemm, id=base + ("-" + gemm if gemm else ""))
+
+
+# the smallest unshared case and the shared one again in each kernel family: the export's branches are the cell's, and with
+# unshared inputs the split family takes the batched contraction of the p qInputU_W gradients, the other two the per-step loop
+@pytest.mark.parametrize("unshared,act,B,d,p,gemm",
+                         [_ctrl_case(True, "TANH", 5, 128, 3), _ctrl_case(False, "TANH", 3, 256, 2), _ctrl_case(True, "NON", 64, 512, 12),
+                          _ctrl_case(True, "RELU", 4, 128, 2)]
+                         + [_ctrl_case(*c, gemm=f) for f in ("native", "split", "h2")
+                            for c in ((True, "TANH", 5, 128, 3), (False, "TANH", 3, 256, 2))])
+def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p, gemm):
     """SURVEY 8b's `ctrl_inputs` unit (mac_cell.py:442-448) through macx_ctrl_inputs_fwd / _bwd against the closed form in fp64:
-    t = act(vecQ Wq + bq), cI_i = t WqU_i + bqU_i; d_vecQ and the four parameter gradients from a random d_cI."""
+    t = act(vecQ Wq + bq), cI_i = t WqU_i + bqU_i; d_vecQ and the four parameter gradients from a random d_cI.  Then the backward
+    call again without qInputU_W and without qInput_W: the other gradients as before, nothing written in the missing one's place."""
     lib = macx._lib
     L = lib.lib()
     cfg = mo.flag_file_config("args", netLength=p, memDim=d, ctrlDim=d, attDim=d, controlInputUnshared=unshared, controlInputAct=act)
-    opts = macx.options.freeze(cfg)
+    opts = macx.options.freeze(cfg, gemm=gemm)
     shapes = lib.MacxShapes(B=B, S=4, N=16, d=d, p=p, b0=0)
     nU = p if unshared else 1
     g = torch.Generator().manual_seed(3)
@@ -178,21 +190,15 @@ def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p):
     dcI = torch.randn(p, B, d, generator=g)
     dv = [t.to(dev).contiguous() for t in (vq, Wq, bq, WqU, bqU, dcI)]
     vqd, Wqd, bqd, WqUd, bqUd, dcId = dv
-    ps, gs = lib.MacxParams(), lib.MacxParamGrads()
+    ps = lib.MacxParams()
     ps.qInput_W, ps.qInput_b, ps.qInputU_W, ps.qInputU_b = Wqd.data_ptr(), bqd.data_ptr(), WqUd.data_ptr(), bqUd.data_ptr()
-    grads = {k: torch.full_like(t, float("nan")) for k, t in (("qInput_W", Wqd), ("qInput_b", bqd), ("qInputU_W", WqUd), ("qInputU_b", bqUd))}
-    for k, t in grads.items():
-        setattr(gs, k, t.data_ptr())
+    like = {"qInput_W": Wqd, "qInput_b": bqd, "qInputU_W": WqUd, "qInputU_b": bqUd}
     n = L.macx_ctrl_inputs_ws_floats(C.byref(opts), C.byref(shapes))
     assert n > 0
     ws = torch.empty(n, device=dev)
     t_out, cI = torch.empty(B, d, device=dev), torch.empty(p, B, d, device=dev)
     st = abi_kit.stream(dev)
     lib.check(L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(cI), abi_kit.ptr(ws), n, st), "ctrl_inputs_fwd")
-    dvq = torch.empty(B, d, device=dev)
-    lib.check(L.macx_ctrl_inputs_bwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(dcId), C.byref(gs), abi_kit.ptr(dvq), abi_kit.ptr(ws), n, st),
-              "ctrl_inputs_bwd")
-    torch.cuda.synchronize()
     # fp64 closed form through autograd
     vq64, Wq64, bq64, WqU64, bqU64 = [t.double().requires_grad_(True) for t in (vq, Wq, bq, WqU, bqU)]
     assert cfg.relu == "ELU"                  # configs/args.txt: "RELU" resolves to ELU (ops.py:161-179)
@@ -200,12 +206,28 @@ def test_ctrl_inputs_exports(macx, dev, unshared, act, B, d, p):
     t64 = {"TANH": torch.tanh, "NON": lambda x: x, "RELU": torch.nn.functional.elu}[act](pre)
     c64 = torch.stack([t64 @ WqU64[i if unshared else 0] + bqU64[i if unshared else 0] for i in range(p)])
     (c64 * dcI.double()).sum().backward()
+    ref = {"qInput_W": Wq64.grad, "qInput_b": bq64.grad, "qInputU_W": WqU64.grad, "qInputU_b": bqU64.grad}
     assert rel_err(t_out, t64.detach()) < 1e-5
     assert rel_err(cI, c64.detach()) < 1e-5
-    for name, got, ref in (("d_vecQ", dvq, vq64.grad), ("qInput_W", grads["qInput_W"], Wq64.grad), ("qInput_b", grads["qInput_b"], bq64.grad),
-                           ("qInputU_W", grads["qInputU_W"], WqU64.grad), ("qInputU_b", grads["qInputU_b"], bqU64.grad)):
-        assert torch.isfinite(got).all(), name
-        assert rel_err(got, ref) < 2e-4, (name, rel_err(got, ref))
+    for missing in (None, "qInputU_W", "qInput_W"):
+        # every gradient buffer NaN-filled between NaN guard bands; the missing one is not handed to the call
+        grads = {k: abi_kit.Guarded(t.numel(), dev, fill=float("nan")) for k, t in like.items()}
+        gs = lib.MacxParamGrads()
+        for k, t in grads.items():
+            setattr(gs, k, t.view.data_ptr() if k != missing else None)
+        dvq = torch.empty(B, d, device=dev)
+        lib.check(L.macx_ctrl_inputs_bwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(dcId), C.byref(gs), abi_kit.ptr(dvq), abi_kit.ptr(ws), n, st),
+                  "ctrl_inputs_bwd without %s" % missing)
+        torch.cuda.synchronize()
+        assert rel_err(dvq, vq64.grad) < 2e-4, ("d_vecQ", missing, rel_err(dvq, vq64.grad))
+        for name, t in grads.items():
+            if name == missing:
+                assert t.untouched(), (name, "written although its field of GP is NULL")
+                continue
+            got = t.view.view_as(like[name])
+            assert t.intact(), (name, missing)
+            assert torch.isfinite(got).all(), (name, missing)
+            assert rel_err(got, ref[name]) < 2e-4, (name, missing, rel_err(got, ref[name]))
     # too small a workspace, a missing field
     assert L.macx_ctrl_inputs_fwd(C.byref(opts), C.byref(shapes), C.byref(ps), abi_kit.ptr(vqd), abi_kit.ptr(t_out), abi_kit.ptr(cI), abi_kit.ptr(ws), n - 1, st) != 0
     ps.qInputU_W = None

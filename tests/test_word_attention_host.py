@@ -241,13 +241,21 @@ def test_the_rules_read_as_restated():
     assert "float Racc[CB_MAXZ / 4];" in small and small.count("const int z = grp + 4 * i;") == 2
     assert "for (int s = grp; s < sn; s += 4) {" in small
     assert "*dst = p.acc_words ? *dst + v : v;" in small and "*dst = p.acc_words ? *dst + t : t;" in small
-    assert api.count("hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / %d), dim3(256), 0, st, c);" % wa.SLAB) == 3
-    assert "hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, p), dim3(256), 0, st, c);" in api
-    assert "hipLaunchKernelGGL(control_attend_kernel, dim3(B, p), dim3(256), 0, st, c);" in api
+    # one launcher per direction: every launch of the three kernels in the library is one of these three lines
+    assert api.count("hipLaunchKernelGGL(control_bwd_apply_kernel, dim3(B, d / %d), dim3(256), 0, st, c);" % wa.SLAB) == 1
+    assert api.count("hipLaunchKernelGGL(control_bwd_dl_kernel, dim3(B, nz), dim3(256), 0, st, c);") == 1
+    assert api.count("hipLaunchKernelGGL(control_attend_kernel, dim3(B, nz), dim3(256), 0, st, c);") == 1
+    assert [api.count(k) for k in ("control_bwd_apply_kernel,", "control_bwd_dl_kernel,", "control_attend_kernel,")] == [1, 1, 1]
+    assert "c.B = B; c.S = S; c.d = d; c.nz = nz;" in api
+    # ... which the cell calls with nz = p where the control is not recurrent, and step by step where it is
+    assert "CKI(control_attend(B, s->S, d, p, saved + L.cc," in api and "return control_attend(B, S, d, 1, cc_i," in api
+    assert "CKI(control_attend_bwd(B, S, d, p, DC + Bd," in api and "CKI(control_attend_bwd(B, S, d, 1, DC + (size_t)(i + 1) * Bd," in api
+    assert "return control_attend(s->B, s->S, s->d, 1, cc," in api and "CKI(control_attend_bwd(B, S, d, 1, d_control," in api
     assert "s->S > C_MAXS || s->N > K_MAXN || s->p > CB_MAXZ" in api
     assert "if (s->B < 1 || s->S < 1 || s->S > C_MAXS || s->d < 4 || s->d % 4 != 0) return MACX_EINVAL;" in api
     assert "if (s->B < 1 || s->S < 1 || s->S > C_MAXS || s->d < 64 || s->d % 64 != 0) return MACX_EINVAL;" in api
-    assert "c.dwords = GI->words; c.acc_words = 1;" in api and "c.dwords = GI->words; c.acc_words = 0;" in api
+    assert "c.dwords = dwords; c.acc_words = acc_words;" in api
+    assert "ws + W.ctrl_dl, dcc_i, GI->words, 1," in api and "ws + W.ctrl_dl, ws + W.dcc, GI->words, 0," in api
 
 
 # ---- the workspace size ---------------------------------------------------------------------------------------------------
