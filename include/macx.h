@@ -574,6 +574,55 @@ int macx_features_pack(const float* src, int layout, int n, int C, int HW, void*
 int macx_features_gather(const void* table, int dtype, size_t rows, const int32_t* ids /*[G], device*/, int G, int C, int HW,
                          float* out /*[G,HW,C]*/, void* stream);
 
+/* ---- questions resident in device memory ------------------------------------------------------- */
+/* A question set as per-question DEVICE tables (a CLEVR split: 700 k x 50 int32 = 140 MB), validated once on the host; a batch then
+ * names its questions by id, and ONE launch fills every per-question static input of the tower's captured graphs:
+ *   macx_questions_gather  slot b of every output <- question ids[b]
+ *   macx_preds_scatter     table[ids[b]] = pred[b]
+ * ids: [B] int32 in DEVICE memory, read when the kernel runs (a captured graph follows ids rewritten between replays).
+ * Tables: q_words [Q,S_tab] and q_lengths [Q] are required; q_answers, q_images (rows of a feature table), q_kb_len and q_weights may
+ * be NULL.  An output column (answers, image_ids, kb_lengths) whose table is NULL is refused; `weights` without q_weights is taken:
+ * live slots then get 1.0f.  An output that is NULL is not written.  Per slot b, id = ids[b]:
+ *   live   0 <= id < Q     questions[b] = q_words[id] in columns 0 .. S_tab-1 and 0 (the pad id) in columns S_tab .. S-1; every scalar
+ *                          column from its table; weights[b] = q_weights[id], or 1.0f without a table.
+ *   dead   id == -1        every integer column is that of slot 0's question -- finite, in range, the same launches downstream --
+ *                          and weights[b] = +0.0f.  If slot 0 is not live itself: the pad question (words 0, length 0, answer 0,
+ *                          image row 0, kb length 1).
+ *   other  any other id    is never dereferenced (it is compared before it is used as an offset).  Poison, never silently wrong:
+ *                          words 0, length 0, answer -1 (a NaN loss and NaN totals in the weighted answer loss), image row -1 (a NaN
+ *                          block in the feature gather), kb length 1, weight 1.0f -- not NaN, which the loss kernel counts as dead --
+ *                          and the constant 1 is written to bad[0] (int32 in DEVICE memory, or NULL): a plain store from every thread
+ *                          that sees such an id, no atomics.  The call never clears the word.  The call still returns MACX_OK.
+ * Grouping (image_index != NULL; needs q_images and image_ids, G >= 1, B <= 1024): image_ids is [G] and the batch's images are
+ * grouped on the device.  The distinct image rows of the LIVE slots are numbered in order of first appearance by slot;
+ * image_ids[g] = the g-th distinct row; image_index[b] = the group of slot b's row.  Dead slots take slot 0's group, which is 0 (a
+ * live slot 0 opens group 0; without one, group 0 still names a valid image).  Image slots beyond the D distinct rows are copies of
+ * image_ids[0] (no live slot at all: row 0).  D > G: the slots whose row did not fit get image_index = -1 (a NaN block in the
+ * knowledge-base gather) and bad[0] = 1.  A slot of the `other` kind joins no group: image_index = -1.
+ * One workgroup holds the whole batch in LDS and finds first occurrences by linear search -- quadratic in B, fine for the intended
+ * range of a few hundred questions (B = 1024: about 4 k LDS reads per thread), which is why B is capped.
+ * Rows move as 16-byte accesses where S_tab % 4 == 0, S % 4 == 0 and q_words and questions sit on 16-byte boundaries, as 8-byte
+ * accesses where both are even and the pointers sit on 8-byte boundaries, dword by dword otherwise: a pointer a vector path would
+ * need aligned is not refused but sent to the next narrower path.  Offsets are 64-bit; any B is covered by a capped grid-stride
+ * grid.  Identical calls give identical bits; nothing outside the outputs' [B] / [B,S] / [G] extents is written.
+ * macx_preds_scatter: for every slot with 0 <= ids[b] < Q, table[ids[b]] = pred[b]; dead and other slots write nothing; the rest of
+ * the table is not touched.  An id that appears twice in a batch takes the HIGHEST slot's value: a slot stores only if no later slot
+ * names its id (a linear search: quadratic in B, meant for batches up to a few thousand), so the result does not depend on the
+ * order in which stores retire.
+ * MACX_EINVAL (nothing is launched or written): a NULL q_words, q_lengths, ids, questions or lengths (scatter: pred, ids or table);
+ * Q, S_tab or B < 1; S < S_tab; Q >= 2^31; an output column without its table; grouping without q_images or image_ids, with G < 1 or
+ * B > 1024; an int32 or float pointer off a 4-byte boundary.  Like every call here: no allocation, no memcpy / memset,
+ * stream-ordered only. */
+int macx_questions_gather(const int32_t* q_words /*[Q,S_tab]*/, const int32_t* q_lengths /*[Q]*/, const int32_t* q_answers /*[Q] or NULL*/,
+                          const int32_t* q_images /*[Q] or NULL*/, const int32_t* q_kb_len /*[Q] or NULL*/,
+                          const float* q_weights /*[Q] or NULL*/, int Q, int S_tab, const int32_t* ids /*[B], device*/, int B,
+                          int S /* >= S_tab */, int32_t* questions /*[B,S]*/, int32_t* lengths /*[B]*/, int32_t* answers /*[B] or NULL*/,
+                          int32_t* image_ids /*[B], [G] when grouping, or NULL*/, int32_t* kb_lengths /*[B] or NULL*/,
+                          float* weights /*[B] or NULL*/, int32_t* image_index /*[B] or NULL: grouping*/, int G,
+                          int32_t* bad /*[1], device, or NULL*/, void* stream);
+int macx_preds_scatter(const int32_t* pred /*[B]*/, const int32_t* ids /*[B], device*/, int B, int Q, int32_t* table /*[Q]*/,
+                       void* stream);
+
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)
  * on fp32 MFMA; `W_packed` from macx_pack_weight(W, k1 + k2, n_out, 0); k1, k2, n_out % 16 == 0. */

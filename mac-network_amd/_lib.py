@@ -254,6 +254,12 @@ TABLE.update(
     # (table, dtype, rows; ids, G, C, HW; out, stream)
     macx_features_gather=(_I, (_V, _I, _Z, _V, _I, _I, _I, _V, _V)))
 FEATURES_DTYPE = {torch.float32: 0, torch.float16: 1}                       # MACX_FEATURES_*
+# ---- questions resident in device memory
+TABLE.update(
+    # (the six tables, Q, S_tab; ids, B, S; the six outputs; image_index, G; bad, stream)
+    macx_questions_gather=(_I, (_V,) * 6 + (_I, _I, _V, _I, _I) + (_V,) * 6 + (_V, _I, _V, _V)),
+    # (pred, ids, B, Q; table, stream)
+    macx_preds_scatter=(_I, (_V, _V, _I, _I, _V, _V)))
 # ---- unit-level entry points
 TABLE.update(
     macx_linear=(_I, (_V, _I, _V, _I, _I, _V, _V, _F, _I, _I, _V, _V)),

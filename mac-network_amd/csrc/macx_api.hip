@@ -22,6 +22,7 @@
 #include "macx_conv.hip.h"
 #include "macx_kb_gather.hip.h"
 #include "macx_features.hip.h"
+#include "macx_questions.hip.h"
 #include "macx_att_loss.hip.h"
 
 using namespace macx;
@@ -3401,6 +3402,39 @@ int macx_features_gather(const void* table, int dtype, size_t rows, const int32_
     hipLaunchKernelGGL(feat_gather_h_kernel<1>, kbg_grid(image / 4, FT_CHUNK, G), dim3(256), 0, st,
                        reinterpret_cast<const _Float16*>(table), ids, (int)rows, G, image / 4, reinterpret_cast<f32x4*>(out));
   }
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// ---- questions resident in device memory (macx_questions.hip.h) ----
+int macx_questions_gather(const int32_t* q_words, const int32_t* q_lengths, const int32_t* q_answers, const int32_t* q_images,
+                          const int32_t* q_kb_len, const float* q_weights, int Q, int S_tab, const int32_t* ids, int B, int S,
+                          int32_t* questions, int32_t* lengths, int32_t* answers, int32_t* image_ids, int32_t* kb_lengths, float* weights,
+                          int32_t* image_index, int G, int32_t* bad, void* stream) {
+  if (!q_words || !q_lengths || !ids || !questions || !lengths) return MACX_EINVAL;
+  if (Q < 1 || S_tab < 1 || B < 1 || S < S_tab || (size_t)Q >= ((size_t)1 << 31)) return MACX_EINVAL;
+  // an output column needs its table (weights alone has a default: ones)
+  if ((answers && !q_answers) || (image_ids && !q_images) || (kb_lengths && !q_kb_len)) return MACX_EINVAL;
+  if (image_index && (!q_images || !image_ids || G < 1 || B > QG_MAX_GROUP_B)) return MACX_EINVAL;
+  const uintptr_t all = (uintptr_t)q_words | (uintptr_t)q_lengths | (uintptr_t)q_answers | (uintptr_t)q_images | (uintptr_t)q_kb_len |
+                        (uintptr_t)q_weights | (uintptr_t)ids | (uintptr_t)questions | (uintptr_t)lengths | (uintptr_t)answers |
+                        (uintptr_t)image_ids | (uintptr_t)kb_lengths | (uintptr_t)weights | (uintptr_t)image_index | (uintptr_t)bad;
+  if (all & 3) return MACX_EINVAL;
+  QuestionsP a{q_words, q_lengths, q_answers, q_images, q_kb_len, q_weights, Q, S_tab, ids, B, S, questions, lengths, answers, image_ids,
+               kb_lengths, weights, image_index, G, bad};
+  // the widest access both row pitches and both base pointers allow; a narrower path serves what a wider one cannot
+  const uintptr_t rows = (uintptr_t)q_words | (uintptr_t)questions;
+  const hipStream_t st = (hipStream_t)stream;
+  if (S_tab % 4 == 0 && S % 4 == 0 && !(rows & 15)) CK(questions_gather_launch<4>(a, st));
+  else if (S_tab % 2 == 0 && S % 2 == 0 && !(rows & 7)) CK(questions_gather_launch<2>(a, st));
+  else CK(questions_gather_launch<1>(a, st));
+  return MACX_OK;
+}
+
+int macx_preds_scatter(const int32_t* pred, const int32_t* ids, int B, int Q, int32_t* table, void* stream) {
+  if (!pred || !ids || !table || B < 1 || Q < 1) return MACX_EINVAL;
+  if (((uintptr_t)pred | (uintptr_t)ids | (uintptr_t)table) & 3) return MACX_EINVAL;
+  hipLaunchKernelGGL(preds_scatter_kernel, dim3(qg_blocks((size_t)B)), dim3(256), 0, (hipStream_t)stream, pred, ids, B, Q, table);
   CK(hipGetLastError());
   return MACX_OK;
 }

@@ -756,6 +756,7 @@ class _TowerInputs(_AttLoss):
     weights, totals, n = None, None, None  # per-question answer weights, running totals, questions of the last load: _alloc_weights
     features, image_ids = None, None       # image features resident in device memory (features=store): see _alloc_inputs
     _WEIGHTS_HOW = "weights=True"          # the constructor argument that builds `weights`
+    question_store, question_ids, predictions = None, None, None   # questions resident in device memory (questions=store)
 
     def _alloc_weights(self, dev, totals):
         """A static [B] float32 `weights` (all ones), which the answer-loss kernel (macx_answer_loss_weighted) reads when it runs: one
@@ -798,12 +799,148 @@ class _TowerInputs(_AttLoss):
         if self.totals is not None:
             self.totals.reset()
 
+    def _refuse_other_count(self, n):
+        if self.weights is None and n != self.B:
+            raise ValueError("%s was captured for batches of %d questions and got %d: a class built with weights=True "
+                             "(CapturedTowerForward: score=True) takes any n <= %d" % (type(self).__name__, self.B, n, self.B))
+
     def _refuse_other_size(self, questions):
         """a class built without `weights` takes batches of B questions only (this used to be a reshape error, and n = 1 was broadcast
         into every slot); load() raises it before any other complaint about the batch's shapes"""
-        if self.weights is None and torch.is_tensor(questions) and questions.dim() == 2 and questions.shape[0] != self.B:
-            raise ValueError("%s was captured for batches of %d questions and got %d: a class built with weights=True "
-                             "(CapturedTowerForward: score=True) takes any n <= %d" % (type(self).__name__, self.B, questions.shape[0], self.B))
+        if torch.is_tensor(questions) and questions.dim() == 2:
+            self._refuse_other_count(questions.shape[0])
+
+    # ---- questions resident in device memory (questions=store): the batch is a vector of question ids
+    @staticmethod
+    def _check_questions(net, who, store, B, S, images, kb_lengths, image_lengths, features, att_loss, needs_answers, predictions=None):
+        """what a constructor refuses about questions= / predictions= before it asks for the device"""
+        from .questions import MAX_GROUP_BATCH, QuestionStore
+        if store is None:
+            if predictions is not None:
+                raise ValueError("%s: predictions= is a table over a question store: build the class with questions=" % who)
+            return
+        if not isinstance(store, QuestionStore):
+            raise TypeError("%s: questions is None or a macx.QuestionStore, not %s" % (who, type(store).__name__))
+        if store.S > int(S):
+            raise ValueError("%s: the QuestionStore holds questions of %d words, the graph is captured for S = %d" % (who, store.S, int(S)))
+        vocab = getattr(getattr(net, "enc", None), "vocab", None)
+        if vocab is not None and store.max_word > vocab:
+            raise ValueError("%s: the QuestionStore holds word id %d, the encoder's vocabulary ends at %d" % (who, store.max_word, vocab))
+        answers = getattr(getattr(net, "out", None), "answers", None)
+        if needs_answers and store.answers is None:
+            raise ValueError("%s: the class reads answers and the QuestionStore holds none" % who)
+        if store.max_answer is not None and answers is not None and store.max_answer >= answers:
+            raise ValueError("%s: the QuestionStore holds answer %d, the classifier has %d answers" % (who, store.max_answer, answers))
+        if (features is not None) != (store.image_rows is not None):
+            raise ValueError("%s: features= and the QuestionStore's image_rows go together (the rows of the questions' images in the "
+                             "FeatureStore): %s" % (who, "the store holds no image_rows" if features is not None
+                                                    else "the store holds image_rows and no features= was given"))
+        if kb_lengths and store.kb_lengths is None:
+            raise ValueError("%s(kb_lengths=True): the QuestionStore holds no kb_lengths" % who)
+        if images is not None and features is None:
+            raise ValueError("%s(questions=, images=G) groups the batch by FeatureStore row: it needs features=" % who)
+        if image_lengths:
+            raise ValueError("%s(questions=): image_lengths=True is out of scope -- per-image sizes do not come from a question store" % who)
+        if att_loss is not None:
+            raise ValueError("%s(questions=): att_loss= is out of scope -- the store holds no per-question attention targets" % who)
+        if images is not None and int(B) > MAX_GROUP_BATCH:
+            raise ValueError("%s(questions=, images=G): the grouping launch takes at most %d questions, B = %d" % (who, MAX_GROUP_BATCH, int(B)))
+        if hasattr(net, "tensors") and store.questions.device != net.tensors()[0].device:
+            raise ValueError("%s: the QuestionStore lives on %s, the net on %s" % (who, store.questions.device, net.tensors()[0].device))
+        if predictions is not None:
+            if (not torch.is_tensor(predictions) or predictions.dtype != torch.int32 or tuple(predictions.shape) != (store.count,)
+                    or not predictions.is_contiguous() or predictions.device != store.questions.device):
+                raise ValueError("%s: predictions is a contiguous [%d] int32 tensor on the store's device (store.predictions())"
+                                 % (who, store.count))
+
+    def _alloc_questions(self, store, dev, predictions=None):
+        """A static int32 `question_ids` [B], all -1 (dead slots), which the gather at the head of the graph (macx_questions_gather)
+        reads when it runs.  Allocated here, before the capture, like every buffer the host writes."""
+        self.question_store, self.predictions = store, predictions
+        if store is not None:
+            self.question_ids = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+
+    def _gather_questions(self):
+        """the head of the captured body: every per-question static tensor <- the questions `question_ids` names (one launch; with
+        images=G also the batch's distinct image rows and image_index)"""
+        if self.question_store is not None:
+            self.question_store.gather_into(self.question_ids, self.questions, self.lengths, self.answers, self.image_ids, self.kb_lengths,
+                                            self.weights, self.image_index)
+
+    def _scatter_predictions(self, pred):
+        if self.predictions is not None:
+            self.question_store.scatter_predictions(self.predictions, pred, self.question_ids)
+
+    def _draw_question_ids(self, gen):
+        """the self-checks' batch: random ids with the store's last row in slot 0, a repeat of it in the middle and, where the class has
+        weights, a dead slot at the end; with images=G no more than G distinct image rows (more would poison the run on purpose)"""
+        store, B = self.question_store, self.B
+        ids = torch.randint(0, store.count, (B,), generator=gen, dtype=torch.int32)
+        ids[0] = store.count - 1
+        ids[B // 2] = ids[0]
+        if self.G is not None:
+            rows = store.image_rows[ids.to(store.device).long()].cpu()
+            seen = []
+            for b in range(B):
+                if int(rows[b]) not in seen:
+                    if len(seen) == self.G:
+                        ids[b] = ids[0]
+                        continue
+                    seen.append(int(rows[b]))
+        if self.weights is not None and B > 1:
+            ids[-1] = -1
+        self.question_ids.copy_(ids)
+
+    def _reset_questions(self):
+        """as construction leaves them: every slot dead, the store's `bad` word cleared, a full batch"""
+        if self.question_store is not None:
+            self.question_ids.fill_(-1)
+            self.question_store.reset_bad()
+            self.n = self.B
+
+    def _refuse_load(self):
+        if self.question_store is not None:
+            raise ValueError("%s was captured with questions= (a macx.QuestionStore): a batch is a vector of question ids -- load_ids(ids) "
+                             "or next_batch(order), not load()" % type(self).__name__)
+
+    def _require_questions(self, what):
+        if self.question_store is None:
+            raise TypeError("%s.%s() belongs to a class built with questions= (a macx.QuestionStore)" % (type(self).__name__, what))
+        return self.question_store
+
+    def _write_ids(self, ids, n):
+        with torch.no_grad():
+            self.question_ids[:n].copy_(ids)
+            if n < self.B:
+                self.question_ids[n:].fill_(-1)
+        self.n = n
+        return n
+
+    def load_ids(self, ids, check_ids=True):
+        """A batch by question id: 1 <= n <= B ids of the store's questions (an integer tensor) into the static `question_ids`, -1 (dead
+        slots) behind them; n < B only in a class built with weights=True / score=True.  check_ids tests 0 <= ids < count on the host
+        (synchronises for a device tensor; unchecked ids outside the store poison their question and set store.bad).  Returns n."""
+        store = self._require_questions("load_ids")
+        store.check_ids(ids)
+        n = int(ids.shape[0])
+        self._refuse_other_count(n)
+        if not 1 <= n <= self.B:
+            raise ValueError("%s was captured for batches of %d questions: load_ids() takes 1 <= n <= %d of them, got %d"
+                             % (type(self).__name__, self.B, self.B, n))
+        store.check_ids(ids, n, host_check=check_ids)
+        return self._write_ids(ids, n)
+
+    def next_batch(self, order):
+        """The next B ids of a macx.EpochOrder into `question_ids` (a device-to-device copy; -1 behind the epoch's end, which needs a
+        class built with weights=True / score=True) and the order advanced.  Returns n; IndexError when the epoch is exhausted."""
+        store = self._require_questions("next_batch")
+        if getattr(order, "store", None) is not store or order.B != self.B:
+            raise ValueError("%s.next_batch(): the order must be a macx.EpochOrder over this class's QuestionStore with B = %d"
+                             % (type(self).__name__, self.B))
+        if order.remaining > 0:
+            self._refuse_other_count(min(self.B, order.remaining))
+        ids = order.take()
+        return self._write_ids(ids, int(ids.shape[0]))
 
     def _batch(self, questions, weights, per_question):
         """n, the questions of a load -- B, or with `weights` 1 <= n <= B -- and the refusals about it, raised before anything is
@@ -1026,6 +1163,25 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         fwd = macx.CapturedTowerForward(net, B=64, S=50, features=store)
         logits = fwd(None, questions, lengths, image_ids=ids)
 
+    Questions resident in device memory: `questions=qstore` (a macx.QuestionStore, validated once on the host) puts ONE launch
+    (macx_questions_gather) in front of the encoder.  It reads the static int32 `fwd.question_ids` [B] (all -1 after construction)
+    when it runs and writes every per-question static tensor -- questions, lengths, answers and weights (score=True), image_ids
+    (features=), kb_lengths -- so a batch is a vector of question ids: load_ids(ids), next_batch(order) with a macx.EpochOrder, or a
+    write into `question_ids`; load() is refused.  An id of -1 is a dead slot (slot 0's question under weight 0); any other id
+    outside the store poisons its question (NaN logits, NaN loss) and sets `qstore.bad` (qstore.check()).  With images=G the launch
+    also groups the batch by image row on the device: the [G] image_ids and image_index need no host work.  predictions=table
+    (qstore.predictions()): the graph ends with macx_preds_scatter, table[question_ids[b]] = pred[b].  An epoch is a loop of replays:
+
+        fwd = macx.CapturedTowerForward(net, B=64, S=50, features=store, questions=qstore, score=True, predictions=qstore.predictions())
+        order = macx.EpochOrder(qstore, 64)
+        for _ in range(order.steps):
+            fwd.next_batch(order); fwd.replay()
+        qstore.check(); result = fwd.totals.read()
+
+    Out of scope with questions=: image_lengths=True and (training) att_loss=, whose per-image sizes / per-question targets the store
+    does not hold.  The self-check draws ids (the store's last row, a repeat, a dead slot where the class has weights) and leaves
+    `question_ids` all -1 and the store's `bad` word cleared.
+
     Evaluation only (train=False: no dropout, nothing kept for a backward pass).  Parameters are read at replay time: an optimizer
     step or a checkpoint load between calls is seen; changing a parameter's storage needs a new capture.  `load()` validates ids
     and lengths on the host as QuestionEncoder.forward does (check_ids=False skips the synchronisation); the graph itself runs
@@ -1037,7 +1193,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     answers, loss = None, None
 
     def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None, kb_lengths=False,
-                 image_lengths=False, score=False, features=None):
+                 image_lengths=False, score=False, features=None, questions=None, predictions=None):
         """score=True: the graph scores its answers -- static int32 [B] `answers`, float32 [B] `weights` (ones) and an
         output.AnswerTotals `totals`, allocated with the other inputs; the argmax launch becomes macx_answer_loss_weighted without a
         gradient, which adds every replay's weighted loss, correct count and weight to `totals`.  load() / __call__ then take
@@ -1053,6 +1209,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         capture's, and towers with generic modules (capture stays refused; the eager net.loss_and_pred(logits, answers, weights=,
         totals=) works for them, because it only sees logits).  Without score the class is what it was."""
         self._check_options(net, "CapturedTowerForward", images, kb_lengths, image_lengths, train=False)
+        self._check_questions(net, "CapturedTowerForward", questions, B, S, images, kb_lengths, image_lengths, features, None, bool(score),
+                              predictions)
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
@@ -1063,22 +1221,29 @@ class CapturedTowerForward(_Captured, _TowerInputs):
             self._alloc_weights(dev, True)
         else:
             self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._alloc_questions(questions, dev, predictions)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
         try:
             self._self_check(verify)
         finally:
             self._reset_weights()                           # warm-up and verification scored their inputs: the totals start cleared
+            self._reset_questions()                         # ... and gathered theirs: every slot dead, the store's bad word cleared
+            if self.predictions is not None:
+                self.predictions.fill_(-1)
 
     @torch.no_grad()
     def _eager(self):
         from .output import _AnswerLoss
+        self._gather_questions()                            # (questions=store: the static inputs from question_ids, one launch)
         logits = self.net(self._net_images(), self.questions, self.lengths, train=False, check_ids=False, **self._net_arguments())
         self.cell = self.net.last_cell                      # (status(): the latest run's buffers)
         if self.weights is not None:                        # score=True: the weighted call, dlogits = NULL (no_grad), one kernel
             loss, pred = self.net.loss_and_pred(logits, self.answers, **self._loss_arguments())
+            self._scatter_predictions(pred)
             return logits, pred, loss
         _, pred = _AnswerLoss.apply(logits, self._no_answers)          # addPredOp's argmax (first maximum), one kernel
+        self._scatter_predictions(pred)
         return logits, pred
 
     def _issue(self):
@@ -1091,9 +1256,12 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     def _replays_match_eager(self, replays=3):
         g = torch.Generator().manual_seed(20240521)
         answers = 2 if self.weights is None else self.net.out.answers
-        (images, q, lengths, ans), ids = self._random_images(g, answers)
-        self._load_inputs(images, q, lengths, False, *self._random_groups(g), answers=None if self.weights is None else ans, **ids)
-        self._draw_weights()
+        if self.question_store is not None:                 # ids instead of questions; the gather writes the weights too
+            self._draw_question_ids(g)
+        else:
+            (images, q, lengths, ans), ids = self._random_images(g, answers)
+            self._load_inputs(images, q, lengths, False, *self._random_groups(g), answers=None if self.weights is None else ans, **ids)
+            self._draw_weights()
         written = lambda: [("logits", self.logits), ("pred", self.pred)]
         clear = None
         if self.weights is not None:                        # every run adds to the totals: each starts from cleared ones
@@ -1113,6 +1281,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         kb_lengths=True / image_lengths=True (required there, refused otherwise); 1 <= size <= N is validated with the ids.
         answers [n] / weights [n] (float32, default ones): a graph captured with score=True, and such a graph only; it takes
         n <= B questions (the constructor's docstring)"""
+        self._refuse_load()
         _lengths_argument(type(self).__name__, "answers", answers is not None, self.answers is not None, "score=True")
         return self._load_inputs(images, questions, lengths, check_ids, image_index, kb_lengths, image_lengths, answers, weights,
                                  image_ids)
@@ -1159,6 +1328,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     part of the graph; a stem that drops (stemDropout < 1) is refused at construction with the eager path's ValueError.
     features=store: CapturedTowerForward's (load(None, questions, lengths, answers, image_ids=ids); the gather from the table is
     part of the graph and takes no gradient; with weights=True dead slots take slot 0's id).
+    questions=qstore: CapturedTowerForward's (the store must hold answers; load_ids(ids) / next_batch(order) in the place of load(),
+    a short batch only with weights=True; the gather from the question tables is the first launch of the graph).
 
     verify=True replays three times against the eager step on random inputs -- loss, logits, pred, norm, the flat gradient, every
     parameter, m, v, ema -- each time from the same restored state, and falls back to eager launches when anything differs
@@ -1197,9 +1368,10 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     aux = None
 
     def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, seed=0, warmup=2, verify=True, check_every=0, images=None,
-                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None, weights=False, totals=None, features=None):
+                 kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None, weights=False, totals=None, features=None, questions=None):
         self._check_options(net, "CapturedTowerTrainStep", images, kb_lengths, image_lengths, train=True)
         att_loss = _att_loss_spec("CapturedTowerTrainStep", att_loss)
+        self._check_questions(net, "CapturedTowerTrainStep", questions, B, S, images, kb_lengths, image_lengths, features, att_loss, True)
         self._check_totals("CapturedTowerTrainStep", weights, totals)
         if weights and getattr(bucket, "_active", lambda: False)():
             raise ValueError("CapturedTowerTrainStep(weights=True): the bucket spans more than one process; the weighted mean over a "
@@ -1224,6 +1396,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         self._alloc_att_loss(att_loss, net.netLength, self.B, self.S, self.N, dev)
         self.aux_loss = aux_loss
         self._alloc_mask_word(dev)
+        self._alloc_questions(questions, dev)
         self.norm = opt.norm
         state = self._state()
         self.graph = torch.cuda.CUDAGraph()
@@ -1236,6 +1409,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
             self._self_check(verify, state)
         finally:
             self._reset_weights()                           # ... and scored them: weights back to ones, the totals cleared
+            self._reset_questions()
         self._restore(state)                                # warm-up (and verification) trained on zeros: undo
 
     def _after_capture(self):
@@ -1266,6 +1440,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         """the step's launches on the current stream (opt.advance() is the caller's: it is not part of the graph)"""
         self._clear_grads()
         net, B = self.net, self.B
+        self._gather_questions()                            # (questions=store: the static inputs from question_ids, one launch)
         logits = net(self._net_images(), self.questions, self.lengths, train=True, seed=self.seed, check_ids=False, mask_word=self.mask_word,
                      **self._net_arguments())
         self.cell = net.last_cell
@@ -1306,15 +1481,18 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
 
     def _replays_match_eager(self, state, replays=3):
         g = torch.Generator().manual_seed(20240522)
-        (images, q, lengths, ans), ids = self._random_images(g, self.net.out.answers)
-        index, kbl, iml = self._random_groups(g)
-        self._load_inputs(images, q, lengths, False, index, kbl, iml, **ids)
-        self.answers.copy_(ans)
-        if self.att_loss is not None:
-            live = kbl if iml is None else iml[index.long()]     # the per-question sizes the gather makes on the device
-            self._randomise_att_loss(g, live if self.att_loss["on"] == "kb" else lengths.cpu())
+        if self.question_store is not None:                 # ids instead of questions; the gather writes answers and weights too
+            self._draw_question_ids(g)
+        else:
+            (images, q, lengths, ans), ids = self._random_images(g, self.net.out.answers)
+            index, kbl, iml = self._random_groups(g)
+            self._load_inputs(images, q, lengths, False, index, kbl, iml, **ids)
+            self.answers.copy_(ans)
+            if self.att_loss is not None:
+                live = kbl if iml is None else iml[index.long()]     # the per-question sizes the gather makes on the device
+                self._randomise_att_loss(g, live if self.att_loss["on"] == "kb" else lengths.cpu())
+            self._draw_weights()
         self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
-        self._draw_weights()
 
         def from_state():                                   # the eager step and every replay start from the same state
             self._restore(state)
@@ -1337,6 +1515,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         weights: a class built with weights=True, and such a class only: [n] float32 (default ones).  Such a class takes n <= B
         questions -- every per-question argument (lengths, answers, images or image_index, kb_lengths, att_target, att_row_weights)
         with that leading size -- by the padding rule of the class docstring; a class built without refuses n != B.  Returns n."""
+        self._refuse_load()
         self._refuse_other_size(questions)                  # (ahead of the att_* shapes: a short batch is the first thing to say)
         short = self.weights is not None and torch.is_tensor(questions) and questions.dim() == 2
         n = int(questions.shape[0]) if short else None
