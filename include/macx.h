@@ -502,6 +502,26 @@ int macx_adam_ema_step(size_t n, float* params, const float* grads, float* m, fl
 int macx_adam_ema_step_p(size_t n, float* params, const float* grads, float* m, float* v, float* ema,
                          const float* lr_t_dev, float beta1, float beta2, float eps, float clip_norm, float ema_decay,
                          float* ws, float* norm_out, void* stream);
+/* The two steps above under a guard: the arguments of the namesake with `skip_above` and `guard` in front of `ws`.  The same two
+ * launches; the update kernel decides from the norm it has just folded, every workgroup from the same partials in the same
+ * order, so all of them decide alike.
+ *   The step is SKIPPED iff  !(norm <= FLT_MAX) || (skip_above > 0 && norm > skip_above)
+ * The first clause covers a NaN or an infinity anywhere in `grads` and a sum of squares that overflows fp32 (one finite element
+ * of 3e19 is enough: its square is no float); skip_above == 0 means no threshold, and the comparison is strictly greater.
+ * A skipped step leaves all state untouched: no byte of params, m, v, ema is written; norm_out[0] still receives the norm (the
+ * non-finite value, or the one above the threshold).  An applied step writes exactly the bits of the unguarded call.
+ * guard: four uint32 words in DEVICE memory, 4-byte aligned, zeroed by the caller before the first step:
+ *   [0] steps applied   [1] steps skipped   [2] attempt index of the first skipped step (1-based, 0: none)   [3] of the last
+ * The attempt index of a step is guard[0] + guard[1] + 1 as read before its update.  The words are written by one thread with plain
+ * loads and stores (no atomics): steps that share them must be ordered on one stream, as steps that share params are anyway.
+ * `step` and lr_t_dev stay the caller's and count attempts; guard[0] is the number of updates m and v have seen.
+ * MACX_EINVAL (nothing is launched): what the namesake refuses, guard NULL or off a 4-byte boundary, skip_above < 0 or NaN. */
+int macx_adam_ema_step_g(size_t n, float* params, const float* grads, float* m, float* v, float* ema,
+                         float lr, float beta1, float beta2, float eps, int step, float clip_norm, float ema_decay,
+                         float skip_above, uint32_t* guard, float* ws, float* norm_out, void* stream);
+int macx_adam_ema_step_pg(size_t n, float* params, const float* grads, float* m, float* v, float* ema,
+                          const float* lr_t_dev, float beta1, float beta2, float eps, float clip_norm, float ema_decay,
+                          float skip_above, uint32_t* guard, float* ws, float* norm_out, void* stream);
 
 /* ---- flat gather -------------------------------------------------------------------------------- */
 /* ONE launch copies `entries` tensors into their slices of a flat buffer: flat[dst_offset .. dst_offset + count) = src[0 .. count)

@@ -237,7 +237,10 @@ TABLE.update(macx_encoder_forward_w=_masked(TABLE["macx_encoder_forward"]),
 TABLE.update(
     macx_adam_ema_step=(_I, (_Z, _V, _V, _V, _V, _V, _F, _F, _F, _F, _I, _F, _F, _V, _V, _V)),
     # (the rate in device memory instead of lr and step)
-    macx_adam_ema_step_p=(_I, (_Z, _V, _V, _V, _V, _V, _V, _F, _F, _F, _F, _F, _V, _V, _V)))
+    macx_adam_ema_step_p=(_I, (_Z, _V, _V, _V, _V, _V, _V, _F, _F, _F, _F, _F, _V, _V, _V)),
+    # (guarded: skip_above and the four guard words in front of ws)
+    macx_adam_ema_step_g=(_I, (_Z, _V, _V, _V, _V, _V, _F, _F, _F, _F, _I, _F, _F, _F, _V, _V, _V, _V)),
+    macx_adam_ema_step_pg=(_I, (_Z, _V, _V, _V, _V, _V, _V, _F, _F, _F, _F, _F, _F, _V, _V, _V, _V)))
 # ---- flat gather
 TABLE.update(macx_gather_flat=(_I, (_V, _I, _V, _V)))             # (the table of MacxGatherEntry rows lives in device memory)
 # ---- questions that share images

@@ -3270,8 +3270,10 @@ int macx_encoder_backward_w(const macx_enc_shapes* s, float keep_input, float ke
 // =================================================================================================
 namespace {
 // lr_t_dev null: the by-value rate `lr_t`; else the kernel reads the rate from device memory when it runs
+// guard null: the plain update kernel; else the guarded one (skip_above, guard: see opt_apply_guarded_kernel)
 int adam_ema_launch(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr_t, const float* lr_t_dev,
-                    float beta1, float beta2, float eps, float clip_norm, float ema_decay, float* ws, float* norm_out, void* stream) {
+                    float beta1, float beta2, float eps, float clip_norm, float ema_decay, float* ws, float* norm_out, void* stream,
+                    float skip_above = 0.f, uint32_t* guard = nullptr) {
   hipStream_t st = (hipStream_t)stream;
   int blocks = (int)((n + 255) / 256);
   if (blocks > OPT_BLOCKS) blocks = OPT_BLOCKS;
@@ -3281,10 +3283,13 @@ int adam_ema_launch(size_t n, float* params, const float* grads, float* m, float
   q.lr_t = lr_t; q.lr_t_dev = lr_t_dev;
   q.beta1 = beta1; q.beta2 = beta2; q.eps = eps; q.clip = clip_norm; q.ema_decay = ema_decay;
   q.part = ws; q.nparts = blocks; q.norm_out = norm_out;
-  hipLaunchKernelGGL(opt_apply_kernel, dim3(blocks), dim3(256), 0, st, q);
+  if (guard) hipLaunchKernelGGL(opt_apply_guarded_kernel, dim3(blocks), dim3(256), 0, st, q, skip_above, guard);
+  else hipLaunchKernelGGL(opt_apply_kernel, dim3(blocks), dim3(256), 0, st, q);
   CK(hipGetLastError());
   return MACX_OK;
 }
+// what the guarded exports check on top of their namesakes (skip_above: 0 = no threshold; !(x >= 0) also catches NaN)
+bool guard_args_bad(float skip_above, const uint32_t* guard) { return !guard || ((uintptr_t)guard & 3) || !(skip_above >= 0.f); }
 }  // namespace
 
 int macx_adam_ema_step(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr, float beta1,
@@ -3303,6 +3308,27 @@ int macx_adam_ema_step_p(size_t n, float* params, const float* grads, float* m, 
   if (!params || !grads || !m || !v || !ws || !lr_t_dev || n == 0) return MACX_EINVAL;
   if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
   return adam_ema_launch(n, params, grads, m, v, ema, 0.f, lr_t_dev, beta1, beta2, eps, clip_norm, ema_decay, ws, norm_out, stream);
+}
+
+int macx_adam_ema_step_g(size_t n, float* params, const float* grads, float* m, float* v, float* ema, float lr, float beta1,
+                         float beta2, float eps, int step, float clip_norm, float ema_decay, float skip_above, uint32_t* guard,
+                         float* ws, float* norm_out, void* stream) {
+  if (!params || !grads || !m || !v || !ws || n == 0 || step < 1) return MACX_EINVAL;
+  if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
+  if (guard_args_bad(skip_above, guard)) return MACX_EINVAL;
+  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step)));
+  return adam_ema_launch(n, params, grads, m, v, ema, lr_t, nullptr, beta1, beta2, eps, clip_norm, ema_decay, ws, norm_out, stream,
+                         skip_above, guard);
+}
+
+int macx_adam_ema_step_pg(size_t n, float* params, const float* grads, float* m, float* v, float* ema, const float* lr_t_dev,
+                          float beta1, float beta2, float eps, float clip_norm, float ema_decay, float skip_above, uint32_t* guard,
+                          float* ws, float* norm_out, void* stream) {
+  if (!params || !grads || !m || !v || !ws || !lr_t_dev || n == 0) return MACX_EINVAL;
+  if (ema_decay >= 0.f && !ema) return MACX_EINVAL;
+  if (guard_args_bad(skip_above, guard)) return MACX_EINVAL;
+  return adam_ema_launch(n, params, grads, m, v, ema, 0.f, lr_t_dev, beta1, beta2, eps, clip_norm, ema_decay, ws, norm_out, stream,
+                         skip_above, guard);
 }
 
 int macx_gather_flat(const macx_gather_entry* table_dev, int entries, float* flat, void* stream) {

@@ -1318,26 +1318,70 @@ struct OptP {
   const float* part; int nparts;
   float* norm_out;                                   // [1] global gradient norm (before clipping)
 };
+// One element's update, shared by the plain and the guarded kernel.  Which products fuse into an fma is PINNED here (explicit fmaf,
+// no other contraction allowed): left to the compiler the choice differs from one kernel to the next -- m came out as
+// fma(b1, m, (1-b1)*g) in one and fma(1-b1, g, b1*m) in the other -- and an applied guarded step must write the plain step's bits.
+// The forms below are the ones the plain kernel has always been compiled to.
+__device__ __forceinline__ void opt_element(const OptP& q, size_t i, float scale, float lr_t) {
+#pragma clang fp contract(off)
+  const float g = q.g[i] * scale;
+  const float m = fmaf(q.beta1, q.m[i], (1.0f - q.beta1) * g);
+  const float v = fmaf(q.beta2, q.v[i], (1.0f - q.beta2) * g * g);
+  const float p = q.p[i] - lr_t * m / (sqrtf(v) + q.eps);
+  q.m[i] = m; q.v[i] = v; q.p[i] = p;
+  if (q.ema_decay >= 0.f) {                          // tf.train.ExponentialMovingAverage: ema - (1 - decay) * (ema - p)
+    const float e = q.ema[i];
+    q.ema[i] = fmaf(-(1.0f - q.ema_decay), e - p, e);
+  }
+}
+// thread 0's fold of the partials, in every workgroup the same adds in the same order; workgroup 0 also publishes the norm
+__device__ __forceinline__ void opt_fold_norm(const OptP& q, float& s_norm) {
+  float t = 0.f;
+  for (int i = 0; i < q.nparts; ++i) t += q.part[i];
+  s_norm = sqrtf(t);
+  if (blockIdx.x == 0 && q.norm_out) q.norm_out[0] = s_norm;
+}
+// this workgroup's slice of the update under the folded norm
+__device__ __forceinline__ void opt_update(const OptP& q, float norm) {
+  // tf.clip_by_global_norm: g * clip / max(norm, clip)
+  const float scale = q.clip > 0.f ? q.clip / fmaxf(norm, q.clip) : 1.0f;
+  const float lr_t = q.lr_t_dev ? *q.lr_t_dev : q.lr_t;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (size_t)gridDim.x * 256) opt_element(q, i, scale, lr_t);
+}
 __global__ __launch_bounds__(256) void opt_apply_kernel(OptP q) {
   __shared__ float s_norm;
+  if (threadIdx.x == 0) opt_fold_norm(q, s_norm);
+  __syncthreads();
+  opt_update(q, s_norm);
+}
+// The guarded step (macx_adam_ema_step_g / _pg) is skipped iff !(norm <= FLT_MAX) || (skip_above > 0 && norm > skip_above).
+// Every workgroup folds the same partials in the same order, so all of them decide alike without a word exchanged.  The first
+// clause is read off the bits (norm is a square root: NaN, +inf or >= +0, so "not <= FLT_MAX" is "exponent all ones"), which no
+// finite-math assumption of a compiler can fold away.  A skipped step writes nothing but norm_out and the guard words.
+// guard: [0] applied, [1] skipped, [2] first skipped attempt (1-based, 0: none), [3] last skipped attempt; plain loads and stores
+// by thread 0 of workgroup 0, like norm_out (the steps that share the words are ordered on one stream: no atomics).
+__device__ __forceinline__ bool opt_skip(float norm, float skip_above) {
+  const bool nonfinite = (__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u;
+  return nonfinite || (skip_above > 0.f && norm > skip_above);
+}
+__global__ __launch_bounds__(256) void opt_apply_guarded_kernel(OptP q, float skip_above, uint32_t* guard) {
+  __shared__ float s_norm;
   if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < q.nparts; ++i) t += q.part[i];
-    s_norm = sqrtf(t);
-    if (blockIdx.x == 0 && q.norm_out) q.norm_out[0] = s_norm;
+    opt_fold_norm(q, s_norm);
+    if (blockIdx.x == 0) {
+      const uint32_t applied = guard[0], skipped = guard[1], attempt = applied + skipped + 1u;
+      if (opt_skip(s_norm, skip_above)) {
+        guard[1] = skipped + 1u;
+        if (guard[2] == 0u) guard[2] = attempt;
+        guard[3] = attempt;
+      } else {
+        guard[0] = applied + 1u;
+      }
+    }
   }
   __syncthreads();
-  // tf.clip_by_global_norm: g * clip / max(norm, clip)
-  const float scale = q.clip > 0.f ? q.clip / fmaxf(s_norm, q.clip) : 1.0f;
-  const float lr_t = q.lr_t_dev ? *q.lr_t_dev : q.lr_t;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (size_t)gridDim.x * 256) {
-    const float g = q.g[i] * scale;
-    const float m = q.beta1 * q.m[i] + (1.0f - q.beta1) * g;
-    const float v = q.beta2 * q.v[i] + (1.0f - q.beta2) * g * g;
-    const float p = q.p[i] - lr_t * m / (sqrtf(v) + q.eps);
-    q.m[i] = m; q.v[i] = v; q.p[i] = p;
-    if (q.ema_decay >= 0.f) q.ema[i] = q.ema[i] - (1.0f - q.ema_decay) * (q.ema[i] - p);   // tf.train.ExponentialMovingAverage
-  }
+  if (opt_skip(s_norm, skip_above)) return;
+  opt_update(q, s_norm);
 }
 
 // ---------------------------------------------------------------------------------------------

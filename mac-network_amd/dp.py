@@ -227,6 +227,8 @@ class TowerBuckets(_TwoBuckets):
     gradients -- still run; the rest follows after backward().  The cell's gradient buffer IS its range of the flat buffer
     (MACCellParams.adopt_grad_buffer), the other modules' gradients are gathered into theirs.  Clipping comes
     after the exchange, as in model.py:645-650: hand `flat` to optim.FlatAdamEMA(bucket.tensors()).step(flat_grad=bucket.flat).
+    So does a guarded optimizer's decision (FlatAdamEMA(guard=True)): it is taken on `flat` AFTER the all-reduce, every rank holds
+    the same reduced buffer -- a NaN on one rank is a NaN on all -- so every rank skips or applies alike, with no code of its own.
 
         bucket = TowerBuckets(net); opt = FlatAdamEMA(bucket.tensors(), ...)
         bucket.begin_step(shard, global_batch); loss.backward(); bucket.allreduce_(shard, global_batch); opt.step(bucket.flat)

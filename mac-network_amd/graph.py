@@ -1336,6 +1336,16 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     (`captured` False, a RuntimeWarning; `verify_report` lists what differed).  Parameters, m, v, ema and t are restored
     afterwards: a constructed step has not trained.
 
+    A guarded optimizer (FlatAdamEMA(..., guard=True)): the graph's last launch is the guarded update, which skips the step ON THE
+    DEVICE when the gradient norm is not finite (a poisoned question id or feature row, a hand-off that gave up) or above
+    skip_above: parameters, m, v and ema keep every bit, the skip is counted, and the next replay trains on sound weights.  The
+    guard words are optimizer state here -- saved and restored around warm-up and verification with m and v, compared between replay
+    and eager step by the self-check -- so a constructed step reads opt.guard_counts() == (0, 0, 0, 0).  Read the counts once per
+    epoch, next to the other once-per-epoch reads: qs.check(); opt.guard_counts().  opt.t and the rate count attempts, skipped ones
+    included (FlatAdamEMA).  A NaN loss is still added to `totals`: that is the documented signal, the guard only protects the
+    weights.  Several processes need nothing more: the decision is taken on bucket.flat AFTER the all-reduce, every rank holds
+    the same reduced buffer, so every rank skips or applies alike.  An unguarded optimizer: the launches and bits of before.
+
     att_loss= / aux_loss=: CapturedTrainStep's, on net.last_cell.  The loss the step trains on becomes CE + aux with
     aux = lam * sum(aux_rows) / (p * B) (+ aux_loss(cell, state)): `step.loss` is the total, `step.ce` the mean cross-entropy,
     `step.aux` the auxiliary part (None for a class built without either; then loss is ce).  on="kb" masks by the lengths the cell ran
@@ -1418,8 +1428,9 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
 
     # ---- the optimizer's state, saved and restored around warm-up and verification
     def _buffers(self):
+        """(the guard words of a guarded optimizer are state like m and v: warm-up and verification must not count as attempts)"""
         o = self.opt
-        return [b for b in (o.flat, o.m, o.v, o.ema) if b is not None]
+        return [b for b in (o.flat, o.m, o.v, o.ema, getattr(o, "guard", None)) if b is not None]
 
     def _state(self):
         return [b.clone() for b in self._buffers()], self.opt.t, self.opt.lr_t.clone()
@@ -1502,6 +1513,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
         from_state()
         want = self._eager_reference()
         names = ["loss", "logits", "pred", "norm", "flat_grad", "params", "m", "v"] + (["ema"] if self.opt.ema is not None else [])
+        names += ["guard"] if getattr(self.opt, "guard", None) is not None else []
         names += ([] if self.aux is None else ["aux"]) + ([] if self.aux_rows is None else ["aux_rows"])
         names += [] if self.totals is None else ["totals"]
         written = lambda: zip(names, [self.loss, self.logits, self.pred] + self._stepped() + self._aux_written(self.aux))
