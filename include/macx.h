@@ -649,6 +649,14 @@ int macx_preds_scatter(const int32_t* pred /*[B]*/, const int32_t* ids /*[B], de
 int macx_linear(const float* x1, int k1, const float* x2, int k2, int rows,
                 const float* W_packed, const float* b, float bias_const, int n_out, int act,
                 float* out, void* stream);
+/* The same linear with its input row r given as per-tile partial sums, as the backward recurrence's dy linear runs it:
+ * x[r] = ((p0 + p1) + p2) + ... over the tiles of 2^part_shift rows (4 .. 6) that rows [r * part_N, (r + 1) * part_N) of a
+ * [rows * part_N]-row matrix touch, in ascending order; part[tile][3][k], a tile's slot for row r being r minus the first r
+ * whose range reaches into the tile.  part_sum[rows][k] receives x.  rows <= 128, ((part_N - 2) >> part_shift) + 2 <= 6,
+ * 2^part_shift <= 2 part_N (three slots per tile), k, n_out % 16 == 0. */
+int macx_linear_part(const float* part, int part_N, int part_shift, int k, int rows,
+                     const float* W_packed, const float* b, float bias_const, int n_out, int act,
+                     float* part_sum, float* out, void* stream);
 /* Re-lays a [K, n_out] weight (flags bit 0 = 0) or the transpose of a [n_out, K] weight (bit 0 = 1) into the operand
  * order a kernel reads; flags bits 1-2 select the format:
  *   MACX_PACK_F32MFMA (0)  out[Q][g][j][e] = W[16Q + 4g + e][j]            fp32, K*n_out floats   (macx_linear, native GEMM)

@@ -266,6 +266,8 @@ TABLE.update(
 # ---- unit-level entry points
 TABLE.update(
     macx_linear=(_I, (_V, _I, _V, _I, _I, _V, _V, _F, _I, _I, _V, _V)),
+    # (part, part_N, part_shift, k, rows; W_packed, b, bias_const, n_out, act; part_sum, out, stream)
+    macx_linear_part=(_I, (_V, _I, _I, _I, _I, _V, _V, _F, _I, _I, _V, _V, _V)),
     macx_pack_weight=(_I, (_V, _I, _I, _I, _V, _V)),
     macx_gemm_mode=(_I, (_I,)))
 # ---- the H2 tensor format

@@ -2379,6 +2379,19 @@ int macx_linear(const float* x1, int k1, const float* x2, int k2, int rows, cons
   return MACX_OK;
 }
 
+int macx_linear_part(const float* part, int part_N, int part_shift, int k, int rows, const float* Wp, const float* b, float bias_const,
+                     int n_out, int act, float* part_sum, float* out, void* stream) {
+  if (!part || !Wp || !part_sum || !out || rows < 1 || rows > 128 || n_out < 16 || n_out % 16 || k < 16 || k % 16) return MACX_EINVAL;
+  if (part_N < 1 || part_shift < 4 || part_shift > 6 || ((part_N - 2) >> part_shift) + 2 > LIN_PART_TILES) return MACX_EINVAL;
+  if ((1 << part_shift) > 2 * part_N) return MACX_EINVAL;      // a tile has three slots: it may reach into at most three questions
+  if (misaligned(part) || misaligned(Wp) || misaligned(part_sum) || misaligned(out)) return MACX_EINVAL;
+  LinP l = lin_basic(part_sum, k, k, rows, Wp, b, n_out, act, out, n_out);
+  l.bias_const = bias_const;
+  l.part = part; l.part_N = part_N; l.part_sum = part_sum; l.part_shift = part_shift;
+  CK(small_linear_part_launch(l, (hipStream_t)stream));
+  return MACX_OK;
+}
+
 int macx_pack_weight(const float* Wt, int K, int n_out, int flags, float* out, void* stream) {
   const int transpose = flags;
   if (!Wt || !out || K < 16 || K % 16 || n_out < 16 || n_out % 16) return MACX_EINVAL;

@@ -39,17 +39,28 @@ constexpr int LIN_PART_TILES = 6;     // tiles a question may touch in the PART 
 // over the workgroup): the wait for them gave up -- a quiet NaN stands in for every input value.
 // CTL: 16-column tiles side by side (1 for the launches; 2 -- `red` then holds [2 x 4] slabs -- where fewer, wider tiles save a
 // round on a handful of workgroups): every output keeps its products and its summation order.
-template <int RTL, bool PART = false, bool COH = false, bool COHIN = false, int CTL = 1>
+// NPT (PART): the tiles summed per question -- the most a question of the launch can touch (small_linear_part_launch), so that
+// no load is requested for a tile that none of them reaches; a question that touches fewer re-reads its last tile (clamped, unused).
+// The PART form takes LIN_PART_ROWS = 8 questions per workgroup: rows 8 .. 15 of its MFMA tile belong to nobody, so lanes 8 .. 15
+// of a row group request the same 8 questions' partials of the NEXT k-group of the wave instead of rows of their own, and a
+// rotation by 8 within the row group hands their sums to lanes 0 .. 7 for that k-group's product.  One request per pair of
+// k-groups, on twice the workgroups: what the launch costs is the requests a compute unit issues (profiles/backward_tail_ab.txt).
+// A row's products depend on nothing else in the tile, so every question keeps its sums, products and order.
+constexpr int LIN_PART_ROWS = 8;
+template <int RTL, bool PART = false, bool COH = false, bool COHIN = false, int CTL = 1, int NPT = LIN_PART_TILES>
 __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by, int z, float (*red)[16 * RTL][20], int tid, bool live = true,
                                                   bool poison = false) {
   constexpr int L_ROWS = 16 * RTL;
   constexpr int NWV = 4;               // waves that share the tile's reduction dimension
   static_assert(CTL == 1 || (CTL == 2 && !PART), "one or two column tiles");
+  static_assert(!PART || (RTL == 1 && NPT >= 1 && NPT <= LIN_PART_TILES), "PART: 8 questions per workgroup, 1 .. LIN_PART_TILES tiles each");
+  constexpr int RL = PART ? LIN_PART_ROWS : L_ROWS;      // rows of the tile that are rows of the output
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c0 = bx * 16 * CTL;
-  const int r0 = by * L_ROWS;
+  const int r0 = by * RL;
   const int li = lane & 15, lg = lane >> 4;
+  const int lr = PART ? li & (RL - 1) : li, lh = PART ? li >> 3 : 0;      // PART: the lane's question, and which k-group of a pair it requests
 
   f32x4 acc[RTL][CTL];
 #pragma unroll
@@ -58,7 +69,7 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
     for (int c = 0; c < CTL; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
   int rowc[RTL];
 #pragma unroll
-  for (int t = 0; t < RTL; ++t) rowc[t] = min(r0 + 16 * t + li, p.rows - 1);
+  for (int t = 0; t < RTL; ++t) rowc[t] = min(r0 + 16 * t + lr, p.rows - 1);
 
   const float* Wz = p.W + (size_t)z * p.zW + ((size_t)lg * p.n_out + c0 + li) * 4;
   const int nQ = p.Ktot >> 4;
@@ -72,24 +83,27 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
     if ((reinterpret_cast<uintptr_t>(q) & 15) == 0) return *reinterpret_cast<const f32x4*>(q);
     return f32x4{q[0], q[1], q[2], q[3]};
   };
-  if (er < L_ROWS) {
+  if (er < RL) {
     if (p.bias) e_bias = ld4(p.bias + (size_t)z * p.zb + ecol);
     if (p.addend) e_add = ld4(p.addend + (size_t)z * p.zadd + (size_t)erow * p.ld_add + ecol);
     if (p.actgrad_src) e_ag = ld4(p.actgrad_src + (size_t)z * p.zag + (size_t)erow * p.ld_ag + ecol);
   }
   // Operands are L2-resident and the chain is latency-bound: fetch the fragments of 8 k-groups
   // (40 x 16 B per lane in flight) before touching the matrix pipe.
-  constexpr int PF = PART ? 4 : 8;
+  constexpr int PF = 8;
   // PART: the partial rows of this lane's question (fixed order: ascending tiles, as dc_reduce_kernel sums them)
-  const float* pbase[LIN_PART_TILES];
-  bool pvalid[LIN_PART_TILES];
+  const float* pbase[NPT];
+  bool pvalid[NPT];
   if (PART) {
     const uint32_t first = (uint32_t)rowc[0] * (uint32_t)p.part_N;
     const int t0 = (int)(first >> p.part_shift), t1 = (int)((first + p.part_N - 1) >> p.part_shift);
+    // the question's slot in a tile is its distance from the tile's first question: every tile behind t0 starts inside the
+    // question (slot 0), so only t0's slot takes a division
+    const int seg0 = rowc[0] - (int)(((uint32_t)t0 << p.part_shift) / (uint32_t)p.part_N);
 #pragma unroll
-    for (int j = 0; j < LIN_PART_TILES; ++j) {
+    for (int j = 0; j < NPT; ++j) {
       const int tt = min(t0 + j, t1);
-      const int seg = rowc[0] - (int)(((uint32_t)tt << p.part_shift) / (uint32_t)p.part_N);
+      const int seg = tt == t0 ? seg0 : 0;
       pbase[j] = p.part + ((size_t)tt * 3 + seg) * p.Ktot + lg * 4;
       pvalid[j] = t0 + j <= t1;
     }
@@ -97,23 +111,32 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
   for (int Q0 = wave; Q0 < nQ; Q0 += NWV * PF) {
     f32x4 bf[PF][CTL], af[PF][RTL];
     if (PART) {
-      f32x4 pv[PF][LIN_PART_TILES];
+      f32x4 pv[PF / 2][NPT];
 #pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int Q = min(Q0 + NWV * u, nQ - 1);
-        bf[u][0] = *reinterpret_cast<const f32x4*>(Wz + (size_t)Q * 4 * p.n_out * 4);
+      for (int v = 0; v < PF / 2; ++v) {       // k-groups 2v and 2v + 1 of this pass: one request, lanes 0 .. 7 | 8 .. 15 of a row group
 #pragma unroll
-        for (int j = 0; j < LIN_PART_TILES; ++j) pv[u][j] = *reinterpret_cast<const f32x4*>(pbase[j] + Q * 16);
+        for (int h = 0; h < 2; ++h)
+          bf[2 * v + h][0] = *reinterpret_cast<const f32x4*>(Wz + (size_t)min(Q0 + NWV * (2 * v + h), nQ - 1) * 4 * p.n_out * 4);
+        const int Q = min(Q0 + NWV * (2 * v + lh), nQ - 1);
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) pv[v][j] = *reinterpret_cast<const f32x4*>(pbase[j] + Q * 16);
       }
 #pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        f32x4 sum = pv[u][0];
+      for (int v = 0; v < PF / 2; ++v) {
+        f32x4 sum = pv[v][0];
 #pragma unroll
-        for (int j = 1; j < LIN_PART_TILES; ++j) sum += pvalid[j] ? pv[u][j] : f32x4{0.f, 0.f, 0.f, 0.f};
-        af[u][0] = sum;
-        const int Q = Q0 + NWV * u;
-        if (live && bx == 0 && Q < nQ && r0 + li < p.rows)
-          *reinterpret_cast<f32x4*>(p.part_sum + (size_t)(r0 + li) * p.Ktot + Q * 16 + lg * 4) = sum;
+        for (int j = 1; j < NPT; ++j) sum += pvalid[j] ? pv[v][j] : f32x4{0.f, 0.f, 0.f, 0.f};
+        // (a question that touches fewer than LIN_PART_TILES tiles has always had + 0 behind its last partial: -0 stays +0)
+        if (NPT < LIN_PART_TILES) sum += f32x4{0.f, 0.f, 0.f, 0.f};
+        const int Q = Q0 + NWV * (2 * v + lh);
+        if (live && bx == 0 && Q < nQ && r0 + lr < p.rows)
+          *reinterpret_cast<f32x4*>(p.part_sum + (size_t)(r0 + lr) * p.Ktot + Q * 16 + lg * 4) = sum;
+        af[2 * v][0] = sum;                     // rows 0 .. 7: k-group 2v (rows 8 .. 15 hold the other one's: nobody's rows)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {           // row_ror:8 -- lanes 0 .. 7 of a row group receive lanes 8 .. 15: k-group 2v + 1
+          const float se = sum[e];              // (by value: a bit cast of the vector element itself reads element 0)
+          af[2 * v + 1][0][e] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, se), 0x128, 0xF, 0xF, false));
+        }
       }
     } else {
 #pragma unroll
@@ -163,7 +186,7 @@ __device__ __forceinline__ void small_linear_tile(const LinP& p, int bx, int by,
   __syncthreads();
   const int r = tid / (4 * CTL), cqt = (tid % (4 * CTL)) * 4, cs = (cqt >> 4) * NWV, cq = cqt & 15;
   const int row = r0 + r;
-  if (live && r < L_ROWS && row < p.rows) {
+  if (live && r < RL && row < p.rows) {
   f32x4 val, vald = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {

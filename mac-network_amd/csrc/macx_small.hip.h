@@ -170,19 +170,38 @@ __global__ void transpose_kernel(const float* __restrict__ src, int R, int C, fl
 // LDS combine and a float4 epilogue.  Grid = n_out/16 x ceil(rows/64) x batch.
 // ---------------------------------------------------------------------------------------------
 // (LinSeg, LinP and the tile function small_linear_tile: macx_lin_tile.hip.h)
-template <int RTL, bool PART = false>
+template <int RTL, bool PART = false, int NPT = LIN_PART_TILES>
 __global__ __launch_bounds__(256) void small_linear_kernel(LinP p) {
   __shared__ float red[4][16 * RTL][20];
-  small_linear_tile<RTL, PART>(p, blockIdx.x, blockIdx.y, blockIdx.z, red, (int)threadIdx.x);
+  small_linear_tile<RTL, PART, false, false, 1, NPT>(p, blockIdx.x, blockIdx.y, blockIdx.z, red, (int)threadIdx.x);
 }
 
 // the PART form (LinP::part): the dy-linear of the backward recurrence.  (Measured and removed in rounds 5-6: two dependent linears
 // in one launch with a device-scope barrier between them -- 2-13 % slower per step, profiles/r05_pair_launch_ab.txt,
 // r05_grid_barrier_probe.txt -- and 8-wave workgroups for the long reductions -- no gain, profiles/r05_wide_linear_ab.txt.)
+// What the launch costs beyond a plain linear is the 16-byte requests a compute unit issues for the partial rows, about 0.11 us
+// per request and wave at the flagship shape, so it asks for the tiles a question of part_N rows can touch and not for
+// LIN_PART_TILES, and runs LIN_PART_ROWS questions per workgroup with one request per pair of k-groups (macx_lin_tile.hip.h).
+// (Measured and not kept, profiles/backward_tail_ab.txt: 2 or 4 column tiles per workgroup -- slower; 8 or 4 questions per
+// workgroup with the spare lanes repeating rows, 8 k-groups per request round -- no change.)
+template <int NPT>
+inline void small_linear_part_launch_as(const LinP& p, hipStream_t st) {
+  hipLaunchKernelGGL((small_linear_kernel<1, true, NPT>), dim3(p.n_out / 16, (p.rows + LIN_PART_ROWS - 1) / LIN_PART_ROWS, 1), dim3(256), 0, st, p);
+}
 inline hipError_t small_linear_part_launch(const LinP& p, hipStream_t st) {
-  if (!p.part || !p.part_sum || p.rows > 128 || p.part_shift < 4 || p.part_shift > 6 ||
+  if (!p.part || !p.part_sum || p.rows > 128 || p.part_N < 1 || p.part_shift < 4 || p.part_shift > 6 ||
       ((p.part_N - 2) >> p.part_shift) + 2 > LIN_PART_TILES) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((small_linear_kernel<1, true>), dim3(p.n_out / 16, (p.rows + 15) / 16, 1), dim3(256), 0, st, p);
+  // the tiles a question can touch: it starts a multiple of g = gcd(part_N, T) rows into a tile of T, at most T - g
+  // (part_N = 196, T = 64: always 4 tiles, where the bound without g says 5)
+  const int T = 1 << p.part_shift, g = std::min(T, p.part_N & -p.part_N);
+  const int npt = ((T - g + p.part_N - 1) >> p.part_shift) + 1;
+  switch (npt) {
+    case 1: case 2: small_linear_part_launch_as<2>(p, st); break;
+    case 3: small_linear_part_launch_as<3>(p, st); break;
+    case 4: small_linear_part_launch_as<4>(p, st); break;
+    case 5: small_linear_part_launch_as<5>(p, st); break;
+    default: small_linear_part_launch_as<LIN_PART_TILES>(p, st); break;
+  }
   return hipGetLastError();
 }
 inline hipError_t small_linear_launch(const LinP& p, int nz, hipStream_t st) {
