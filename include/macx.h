@@ -643,6 +643,41 @@ int macx_questions_gather(const int32_t* q_words /*[Q,S_tab]*/, const int32_t* q
 int macx_preds_scatter(const int32_t* pred /*[B]*/, const int32_t* ids /*[B], device*/, int B, int Q, int32_t* table /*[Q]*/,
                        void* stream);
 
+/* ---- evaluation records resident in device memory ---------------------------------------------- */
+/* A run's attention maps and logits filed by question id, as macx_preds_scatter files its predictions: per-question DEVICE tables
+ * [Q][steps][n] (fp32 or fp16), and ONE launch that files a batch into up to MACX_RECORDS_MAX of them.  The descriptors are a HOST
+ * array, taken by value when the call is made (they travel in the kernel argument; the array may be reused at once):
+ *   src     [steps][B][n] fp32, contiguous: a viewable segment of a run's `saved` (MACX_SEG_ATT_KB, MACX_SEG_ATT_QUESTION,
+ *           MACX_SEG_ATT_SELF through macx_saved_segment), or the logits as [1][B][answers]
+ *   table   [Q][steps][n] of dtype, contiguous;  dtype: MACX_FEATURES_F32 | MACX_FEATURES_F16
+ * ids: [B] int32 in DEVICE memory, read when the kernel runs (a captured graph follows ids rewritten between replays); B and Q are
+ * shared by the tables of a call.
+ * Live slots: for every slot b with 0 <= ids[b] < Q, table[ids[b]][i][j] = convert(src[i][b][j]) for all i < steps, j < n -- a
+ * transpose from step-major to question-major.
+ * Other slots: a dead slot (-1) and any other id write nothing and are never used as an offset (the id is compared first).  Table
+ * rows that no slot names are not touched.
+ * Repeated ids: an id named by several slots takes the HIGHEST slot's rows.  A slot stores only if no later slot names its id; that
+ * is decided by comparison (one strided scan of ids[b+1 .. B) by the wave that owns the row, and a wave vote), never by the order
+ * in which stores retire.  No atomics.  Identical calls give identical bits.
+ * Conversion: fp32 -> fp32 copies the bits.  fp32 -> fp16 is the hardware's round-to-nearest-even with subnormals kept and the
+ * sign of zero preserved; NaN stays NaN (a poisoned question's map stays loud); a value that rounds past 65504 becomes an
+ * infinity -- torch's CPU .to(torch.float16) bit for bit, as macx_features_pack promises.
+ * Access: offsets are 64-bit; the grid is capped and grid-stride.  Rows move as 16-byte source accesses (four elements) where
+ * n % 4 == 0, src sits on a 16-byte boundary and table on a boundary of four of its elements, as 8-byte source accesses (two
+ * elements) where n % 2 == 0 and the pointers allow that, element by element otherwise: a pointer off the vector boundary takes
+ * the narrower path, it is not refused.  Nothing outside the tables' [Q][steps][n] extents is written.
+ * MACX_EINVAL (nothing is launched or written): count outside [1, MACX_RECORDS_MAX]; a NULL descs, ids, src or table; steps, n, B
+ * or Q < 1; Q >= 2^31; a dtype other than the listed values; a src or ids off a 4-byte boundary, a table off its element size.
+ * Like every call here: no allocation, no memcpy / memset, stream-ordered only. */
+enum { MACX_RECORDS_MAX = 4 };
+typedef struct macx_record_desc {
+  const float* src;
+  void* table;
+  int32_t steps, n, dtype;
+} macx_record_desc;
+int macx_records_scatter(const macx_record_desc* descs /*[count], host*/, int count, const int32_t* ids /*[B], device*/, int B, int Q,
+                         void* stream);
+
 /* ---- unit-level entry points (the ops.py primitives; used by the parity tests) -------------- */
 /* out[r, :] = act(concat(x1[r], x2[r]) @ W + b + bias_const)     ops.linear (ops.py:298-333)
  * on fp32 MFMA; `W_packed` from macx_pack_weight(W, k1 + k2, n_out, 0); k1, k2, n_out % 16 == 0. */

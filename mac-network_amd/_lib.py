@@ -141,6 +141,14 @@ class MacxInputGrads(C.Structure):
     _fields_ = [("vecQuestions", C.c_void_p), ("words", C.c_void_p), ("knowledgeBase", C.c_void_p)]
 
 
+class MacxRecordDesc(C.Structure):
+    """macx_record_desc: one table of a macx_records_scatter call -- src [steps][B][n] fp32, table [Q][steps][n] of dtype
+    (FEATURES_DTYPE's codes)"""
+    _fields_ = [("src", C.c_void_p), ("table", C.c_void_p), ("steps", C.c_int32), ("n", C.c_int32), ("dtype", C.c_int32)]
+
+
+RECORDS_MAX = 4                                                               # MACX_RECORDS_MAX
+
 STATE_GRAD_FIELDS = ("d_controls", "d_memories", "d_att_question", "d_att_kb", "d_att_self", "d_att_gate")
 
 
@@ -263,6 +271,9 @@ TABLE.update(
     macx_questions_gather=(_I, (_V,) * 6 + (_I, _I, _V, _I, _I) + (_V,) * 6 + (_V, _I, _V, _V)),
     # (pred, ids, B, Q; table, stream)
     macx_preds_scatter=(_I, (_V, _V, _I, _I, _V, _V)))
+# ---- evaluation records resident in device memory
+# (descs: a host array of MacxRecordDesc, count; ids, B, Q; stream)
+TABLE.update(macx_records_scatter=(_I, (_P(MacxRecordDesc), _I, _V, _I, _I, _V)))
 # ---- unit-level entry points
 TABLE.update(
     macx_linear=(_I, (_V, _I, _V, _I, _I, _V, _V, _F, _I, _I, _V, _V)),

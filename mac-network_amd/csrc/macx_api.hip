@@ -23,6 +23,7 @@
 #include "macx_kb_gather.hip.h"
 #include "macx_features.hip.h"
 #include "macx_questions.hip.h"
+#include "macx_records.hip.h"
 #include "macx_att_loss.hip.h"
 
 using namespace macx;
@@ -3474,6 +3475,30 @@ int macx_preds_scatter(const int32_t* pred, const int32_t* ids, int B, int Q, in
   if (!pred || !ids || !table || B < 1 || Q < 1) return MACX_EINVAL;
   if (((uintptr_t)pred | (uintptr_t)ids | (uintptr_t)table) & 3) return MACX_EINVAL;
   hipLaunchKernelGGL(preds_scatter_kernel, dim3(qg_blocks((size_t)B)), dim3(256), 0, (hipStream_t)stream, pred, ids, B, Q, table);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// ---- evaluation records resident in device memory (macx_records.hip.h) ----
+int macx_records_scatter(const macx_record_desc* descs, int count, const int32_t* ids, int B, int Q, void* stream) {
+  if (!descs || !ids || count < 1 || count > MACX_RECORDS_MAX || B < 1 || Q < 1 || (size_t)Q >= ((size_t)1 << 31)) return MACX_EINVAL;
+  if ((uintptr_t)ids & 3) return MACX_EINVAL;
+  RecordList L{};
+  size_t units = 0;
+  for (int k = 0; k < count; ++k) {                      // every descriptor is checked before anything is launched
+    const macx_record_desc& d = descs[k];
+    if (!d.src || !d.table || d.steps < 1 || d.n < 1 || (d.dtype != MACX_FEATURES_F32 && d.dtype != MACX_FEATURES_F16)) return MACX_EINVAL;
+    const uintptr_t esize = d.dtype == MACX_FEATURES_F16 ? 2 : 4, s = (uintptr_t)d.src, t = (uintptr_t)d.table;
+    if ((s & 3) || (t & (esize - 1))) return MACX_EINVAL;
+    // the widest access n and both base pointers allow; a narrower path serves what a wider one cannot
+    const int vec = (d.n % 4 == 0 && !(s & 15) && !(t & (4 * esize - 1))) ? 4 : (d.n % 2 == 0 && !(s & 7) && !(t & (2 * esize - 1))) ? 2 : 1;
+    L.d[k] = RecordDesc{d.src, d.table, d.steps, d.n, d.dtype, vec};
+    const size_t u = (size_t)d.steps * (size_t)B;
+    units = u > units ? u : units;
+  }
+  const size_t blocks = (units + 3) / 4;                 // one wave per row unit, four waves a workgroup
+  const dim3 grid((unsigned)(blocks < (size_t)REC_MAX_BLOCKS ? blocks : (size_t)REC_MAX_BLOCKS), (unsigned)count);
+  hipLaunchKernelGGL(records_scatter_kernel, grid, dim3(256), 0, (hipStream_t)stream, L, ids, B, Q);
   CK(hipGetLastError());
   return MACX_OK;
 }

@@ -757,6 +757,7 @@ class _TowerInputs(_AttLoss):
     features, image_ids = None, None       # image features resident in device memory (features=store): see _alloc_inputs
     _WEIGHTS_HOW = "weights=True"          # the constructor argument that builds `weights`
     question_store, question_ids, predictions = None, None, None   # questions resident in device memory (questions=store)
+    records = None                         # evaluation records resident in device memory (records=rec): see _check_questions
 
     def _alloc_weights(self, dev, totals):
         """A static [B] float32 `weights` (all ones), which the answer-loss kernel (macx_answer_loss_weighted) reads when it runs: one
@@ -812,12 +813,15 @@ class _TowerInputs(_AttLoss):
 
     # ---- questions resident in device memory (questions=store): the batch is a vector of question ids
     @staticmethod
-    def _check_questions(net, who, store, B, S, images, kb_lengths, image_lengths, features, att_loss, needs_answers, predictions=None):
-        """what a constructor refuses about questions= / predictions= before it asks for the device"""
+    def _check_questions(net, who, store, B, S, images, kb_lengths, image_lengths, features, att_loss, needs_answers, predictions=None,
+                         records=None):
+        """what a constructor refuses about questions= / predictions= / records= before it asks for the device"""
         from .questions import MAX_GROUP_BATCH, QuestionStore
         if store is None:
             if predictions is not None:
                 raise ValueError("%s: predictions= is a table over a question store: build the class with questions=" % who)
+            if records is not None:
+                raise ValueError("%s: records= files by the ids of a question store: build the class with questions=" % who)
             return
         if not isinstance(store, QuestionStore):
             raise TypeError("%s: questions is None or a macx.QuestionStore, not %s" % (who, type(store).__name__))
@@ -852,11 +856,29 @@ class _TowerInputs(_AttLoss):
                     or not predictions.is_contiguous() or predictions.device != store.questions.device):
                 raise ValueError("%s: predictions is a contiguous [%d] int32 tensor on the store's device (store.predictions())"
                                  % (who, store.count))
+        if records is not None:
+            from .records import EvalRecords
+            if not isinstance(records, EvalRecords):
+                raise TypeError("%s: records is None or a macx.EvalRecords, not %s" % (who, type(records).__name__))
+            if records.store is not store:
+                raise ValueError("%s: the EvalRecords were built over another QuestionStore than questions=" % who)
+            if records.device != store.questions.device:
+                raise ValueError("%s: the EvalRecords live on %s, the QuestionStore on %s" % (who, records.device, store.questions.device))
+            stem = getattr(net, "stem", None)
+            have = {"p": getattr(net, "netLength", None), "N": None if stem is None else stem.out_hw[0] * stem.out_hw[1], "S": int(S),
+                    "answers": getattr(getattr(net, "out", None), "answers", None)}
+            for name, want in have.items():
+                got = getattr(records, name)
+                if want is not None and got is not None and int(got) != int(want):
+                    raise ValueError("%s: the EvalRecords were built for %s = %d, the captured run has %s = %d" % (who, name, got, name, want))
+            if "self" in records.tables and not get(net.config, "writeSelfAtt"):
+                raise ValueError("%s: the EvalRecords hold a \"self\" table and the cell runs without writeSelfAtt" % who)
 
-    def _alloc_questions(self, store, dev, predictions=None):
+    def _alloc_questions(self, store, dev, predictions=None, records=None):
         """A static int32 `question_ids` [B], all -1 (dead slots), which the gather at the head of the graph (macx_questions_gather)
-        reads when it runs.  Allocated here, before the capture, like every buffer the host writes."""
-        self.question_store, self.predictions = store, predictions
+        reads when it runs.  Allocated here, before the capture, like every buffer the host writes; the predictions table
+        and the records' tables are the caller's, allocated before the capture for the same reason (the host reads them)."""
+        self.question_store, self.predictions, self.records = store, predictions, records
         if store is not None:
             self.question_ids = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
 
@@ -870,6 +892,11 @@ class _TowerInputs(_AttLoss):
     def _scatter_predictions(self, pred):
         if self.predictions is not None:
             self.question_store.scatter_predictions(self.predictions, pred, self.question_ids)
+
+    def _file_records(self, logits):
+        """the tail of the captured body: the run's attention maps and logits into the records' tables by question id (one launch)"""
+        if self.records is not None:
+            self.records.file_run(self.question_ids, self.cell, logits if "logits" in self.records.tables else None)
 
     def _draw_question_ids(self, gen):
         """the self-checks' batch: random ids with the store's last row in slot 0, a repeat of it in the middle and, where the class has
@@ -1170,7 +1197,12 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     write into `question_ids`; load() is refused.  An id of -1 is a dead slot (slot 0's question under weight 0); any other id
     outside the store poisons its question (NaN logits, NaN loss) and sets `qstore.bad` (qstore.check()).  With images=G the launch
     also groups the batch by image row on the device: the [G] image_ids and image_index need no host work.  predictions=table
-    (qstore.predictions()): the graph ends with macx_preds_scatter, table[question_ids[b]] = pred[b].  An epoch is a loop of replays:
+    (qstore.predictions()): the graph ends with macx_preds_scatter, table[question_ids[b]] = pred[b].  records=rec (a macx.EvalRecords
+    over the same store, built by the caller before the capture for this run's p, N, S and answer count): behind it ONE more launch
+    (macx_records_scatter) files the run's attention maps and logits in rec's tables by question id -- the reference's --getPreds /
+    --getAtt output without a copy per batch; rec.read() / rec.instances() at the epoch's end.  The self-check compares the drawn ids'
+    table rows between replay and eager launches bit for bit and leaves the tables cleared (NaN).  Out of scope for records=: the
+    training step, the cell-level classes, towers with generic modules, several processes.  An epoch is a loop of replays:
 
         fwd = macx.CapturedTowerForward(net, B=64, S=50, features=store, questions=qstore, score=True, predictions=qstore.predictions())
         order = macx.EpochOrder(qstore, 64)
@@ -1193,7 +1225,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
     answers, loss = None, None
 
     def __init__(self, net, B, S, H=14, W=14, imageInDim=1024, warmup=2, verify=True, check_every=0, images=None, kb_lengths=False,
-                 image_lengths=False, score=False, features=None, questions=None, predictions=None):
+                 image_lengths=False, score=False, features=None, questions=None, predictions=None, records=None):
         """score=True: the graph scores its answers -- static int32 [B] `answers`, float32 [B] `weights` (ones) and an
         output.AnswerTotals `totals`, allocated with the other inputs; the argmax launch becomes macx_answer_loss_weighted without a
         gradient, which adds every replay's weighted loss, correct count and weight to `totals`.  load() / __call__ then take
@@ -1210,7 +1242,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         totals=) works for them, because it only sees logits).  Without score the class is what it was."""
         self._check_options(net, "CapturedTowerForward", images, kb_lengths, image_lengths, train=False)
         self._check_questions(net, "CapturedTowerForward", questions, B, S, images, kb_lengths, image_lengths, features, None, bool(score),
-                              predictions)
+                              predictions, records)
         dev = _require_fused_tower(net, "CapturedTowerForward")
         self.net = net
         self.check_every = int(check_every)
@@ -1221,7 +1253,7 @@ class CapturedTowerForward(_Captured, _TowerInputs):
             self._alloc_weights(dev, True)
         else:
             self._no_answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self._alloc_questions(questions, dev, predictions)
+        self._alloc_questions(questions, dev, predictions, records)
         self.graph = torch.cuda.CUDAGraph()
         self._capture(dev, warmup, self._eager, [(self.graph, self._issue)])
         try:
@@ -1231,6 +1263,8 @@ class CapturedTowerForward(_Captured, _TowerInputs):
             self._reset_questions()                         # ... and gathered theirs: every slot dead, the store's bad word cleared
             if self.predictions is not None:
                 self.predictions.fill_(-1)
+            if self.records is not None:
+                self.records.clear()
 
     @torch.no_grad()
     def _eager(self):
@@ -1241,9 +1275,11 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         if self.weights is not None:                        # score=True: the weighted call, dlogits = NULL (no_grad), one kernel
             loss, pred = self.net.loss_and_pred(logits, self.answers, **self._loss_arguments())
             self._scatter_predictions(pred)
+            self._file_records(logits)
             return logits, pred, loss
         _, pred = _AnswerLoss.apply(logits, self._no_answers)          # addPredOp's argmax (first maximum), one kernel
         self._scatter_predictions(pred)
+        self._file_records(logits)
         return logits, pred
 
     def _issue(self):
@@ -1268,7 +1304,21 @@ class CapturedTowerForward(_Captured, _TowerInputs):
             written = lambda: [("logits", self.logits), ("pred", self.pred), ("loss", self.loss), ("totals", self.totals.tensor)]
             clear = self.totals.reset
             clear()
-        want = self._eager_on_captured([], lambda: [t.clone() for t in list(self._eager()) + ([] if clear is None else [self.totals.tensor])])
+        filed = lambda: []
+        if self.records is not None:                        # the drawn ids' rows of every table: cleared in front of every run
+            live = self.question_ids[self.question_ids >= 0].long()
+            # ("self": row i is its first i + 1 entries; behind them each run's own buffer holds what it held)
+            filed = lambda: [("records." + name, torch.tril(t[live]) if name == "self" else t[live]) for name, t in self.records.tables.items()]
+            scored, reset_totals = written, clear
+            written = lambda: scored() + filed()
+
+            def clear():
+                if reset_totals is not None:
+                    reset_totals()
+                self.records.clear()
+            clear()
+        want = self._eager_on_captured([], lambda: [t.clone() for t in list(self._eager()) + ([] if self.weights is None else [self.totals.tensor])]
+                                       + [t for _, t in filed()])
         return self._compare_replays(replays, written, want, before=clear)
 
     def load(self, images, questions, lengths, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None, answers=None,
