@@ -486,6 +486,41 @@ int macx_encoder_backward_w(const macx_enc_shapes*, float keep_input, float keep
                             float* ws, size_t ws_floats, const float* d_words, const float* d_vecQuestions,
                             const macx_enc_grads*, const uint32_t* mask_word, void* stream);
 
+/* ---- question encoder, every cell ops.createCell builds with an activation (ops.py:749-772) ------ */
+/* The encoder above for encType RNN | GRU | LSTM in one direction (ops.fwRNNLayer: tf.nn.dynamic_rnn, h = encDim) or two
+ * (ops.biRNNLayer, h = encDim/2); (MACX_RNN_LSTM, 2) runs macx_encoder_*'s launches and returns their bits.
+ *   MACX_RNN_BASIC  BasicRNNCell   h' = tanh([x, h] kernel + bias)                       kernel [E+h, h]
+ *   MACX_RNN_GRU    GRUCell        r, u = split(sigmoid([x, h] kernel + bias))           kernel [E+h, 2h]  (gru_cell/gates)
+ *                                  c = tanh([x, r h] candidate_kernel + candidate_bias)  candidate_kernel [E+h, h]
+ *                                  h' = u h + (1 - u) c
+ *   MACX_RNN_LSTM   BasicLSTMCell  as macx_encoder_*                                     kernel [E+h, 4h]
+ * words [B,S,dirs h] (+0 past a question's end), vecQuestions [B,dirs h] = dropout(concat of the final h).  One launch per
+ * time step and pass for all directions; the GRU two (gates, then candidate: r h of all units; backward: d(r h), then the gates).
+ * Pointers the cell or the direction count does not use (bw_* with dirs == 1, *candidate* outside the GRU) are ignored and may
+ * be NULL; a NULL one among those it needs is MACX_EINVAL, as are cell / dirs out of range and h % 128 != 0.  h > 512 is
+ * MACX_EUNSUPPORTED in every call and both sizing calls return 0 (one bound for all cells: the LSTM's backward LDS tile).
+ * The argument lists are macx_encoder_forward_w's / _backward_w's. */
+enum { MACX_RNN_BASIC = 0, MACX_RNN_GRU = 1, MACX_RNN_LSTM = 2 };
+typedef struct macx_rnn_shapes { int32_t B, S, V, E, h, b0, cell, dirs; } macx_rnn_shapes;   /* V rows in emb (ids 1..V) */
+typedef struct macx_rnn_params {
+  const float* emb; const float* fw_kernel; const float* fw_bias; const float* bw_kernel; const float* bw_bias;
+  const float* fw_candidate_kernel; const float* fw_candidate_bias; const float* bw_candidate_kernel; const float* bw_candidate_bias;
+} macx_rnn_params;
+typedef struct macx_rnn_grads {
+  float* emb; float* fw_kernel; float* fw_bias; float* bw_kernel; float* bw_bias;
+  float* fw_candidate_kernel; float* fw_candidate_bias; float* bw_candidate_kernel; float* bw_candidate_bias;
+} macx_rnn_grads;
+size_t macx_rnn_encoder_saved_floats(const macx_rnn_shapes*);
+size_t macx_rnn_encoder_ws_floats(const macx_rnn_shapes*);
+int macx_rnn_encoder_forward_w(const macx_rnn_shapes*, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params*,
+                               const int32_t* questions /*[B,S]*/, const int32_t* lengths /*[B]*/, float* words /*[B,S,dirs h]*/,
+                               float* vecQuestions /*[B,dirs h]*/, float* saved, size_t saved_floats, const uint32_t* mask_word,
+                               void* stream);
+int macx_rnn_encoder_backward_w(const macx_rnn_shapes*, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params*,
+                                const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats,
+                                float* ws, size_t ws_floats, const float* d_words, const float* d_vecQuestions,
+                                const macx_rnn_grads*, const uint32_t* mask_word, void* stream);
+
 /* ---- optimizer step ---------------------------------------------------------- */
 /* addTrainingOp (model.py:639-669) over ONE flat fp32 buffer of n elements:
  *   norm = ||g||_2 ; g *= clip / max(norm, clip)      tf.clip_by_global_norm, clip_norm <= 0 disables

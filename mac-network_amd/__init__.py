@@ -10,7 +10,7 @@ from .params import MACCellParams                   # noqa: F401
 from .generic import GenericMACCell, GenericParams  # noqa: F401
 from .output import GenericOutputClassifier, OutputClassifier   # noqa: F401
 from .stem import GenericStem, Stem                 # noqa: F401
-from .encoder import GenericQuestionEncoder, QuestionEncoder   # noqa: F401
+from .encoder import GenericQuestionEncoder, QuestionEncoder, RecurrentQuestionEncoder   # noqa: F401
 from .features import FeatureStore                  # noqa: F401
 from .questions import EpochOrder, QuestionStore    # noqa: F401
 from .records import EvalRecords                    # noqa: F401

@@ -127,6 +127,24 @@ class MacxEncGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ENC_FIELDS]
 
 
+RNN_CELL = {"RNN": 0, "GRU": 1, "LSTM": 2}                                    # MACX_RNN_BASIC | _GRU | _LSTM
+
+
+class MacxRnnShapes(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "S", "V", "E", "h", "b0", "cell", "dirs")]
+
+
+RNN_FIELDS = ENC_FIELDS + ("fw_candidate_kernel", "fw_candidate_bias", "bw_candidate_kernel", "bw_candidate_bias")
+
+
+class MacxRnnParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RNN_FIELDS]
+
+
+class MacxRnnGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RNN_FIELDS]
+
+
 class MacxGatherEntry(C.Structure):
     """macx_gather_entry: one row of macx_gather_flat's device table (24 bytes = three int64 of a torch tensor)"""
     _fields_ = [("src", C.c_void_p), ("dst_offset", C.c_uint64), ("count", C.c_uint64)]
@@ -241,6 +259,14 @@ TABLE.update(
     macx_encoder_backward=(_I, _ENC + (_V, _V, _V, _Z, _V, _Z, _V, _V, _P(MacxEncGrads), _V)))
 TABLE.update(macx_encoder_forward_w=_masked(TABLE["macx_encoder_forward"]),
              macx_encoder_backward_w=_masked(TABLE["macx_encoder_backward"]))
+# ---- question encoder, every cell
+# (macx_encoder_*_w's argument lists on the rnn structs: unit._FusedCall drives both)
+_RNN = (_P(MacxRnnShapes), _F, _F, _U, _P(MacxRnnParams))
+TABLE.update(
+    macx_rnn_encoder_saved_floats=(_Z, (_P(MacxRnnShapes),)),
+    macx_rnn_encoder_ws_floats=(_Z, (_P(MacxRnnShapes),)),
+    macx_rnn_encoder_forward_w=(_I, _RNN + (_V, _V, _V, _V, _V, _Z, _V, _V)),
+    macx_rnn_encoder_backward_w=(_I, _RNN + (_V, _V, _V, _Z, _V, _Z, _V, _V, _P(MacxRnnGrads), _V, _V)))
 # ---- optimizer step
 TABLE.update(
     macx_adam_ema_step=(_I, (_Z, _V, _V, _V, _V, _V, _F, _F, _F, _F, _I, _F, _F, _V, _V, _V)),

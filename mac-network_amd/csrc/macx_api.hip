@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/macx.h"
 #include "macx_common.hip.h"
 #include "macx_gemm.hip.h"
@@ -18,6 +20,7 @@
 #include "macx_chain_api.hip.h"
 #include "macx_wgrad_h2.hip.h"
 #include "macx_small.hip.h"
+#include "macx_rnn.hip.h"
 #include "macx_ops.hip.h"
 #include "macx_conv.hip.h"
 #include "macx_kb_gather.hip.h"
@@ -3092,64 +3095,324 @@ int macx_conv2d_wgrad(const macx_conv_shapes* s, const float* x, const float* dy
 // =================================================================================================
 // question encoder (model.py:208-307; ops.biRNNLayer ops.py:859-911): SURVEY 8f row 4
 // =================================================================================================
+// One implementation for every cell and direction count (macx_rnn_encoder_*); macx_encoder_* is its (LSTM, 2) case.  Per direction
+// a position's columns are one row of width GT that holds the cell's matrices side by side: the LSTM's [i | j | f | o] (4h), the
+// RNN's h, the GRU's gates [r | u] and candidate [c] (3h).  Zx, the kept per-step values, dG and dZ all have that row.
 namespace {
 inline int pad128(int n) { return (n + 127) & ~127; }
+struct RnnGeom {
+  int cell, dirs, nmat, GT;
+  int col[2], w[2];        // matrix m: columns [col, col + w) of the row; its kernel is [E + h, w]
+};
+RnnGeom rnn_geom(const macx_rnn_shapes* s) {
+  RnnGeom g;
+  memset(&g, 0, sizeof(g));
+  g.cell = s->cell; g.dirs = s->dirs; g.nmat = 1;
+  if (s->cell == MACX_RNN_LSTM) g.w[0] = 4 * s->h;
+  else if (s->cell == MACX_RNN_GRU) { g.nmat = 2; g.w[0] = 2 * s->h; g.col[1] = 2 * s->h; g.w[1] = s->h; }
+  else g.w[0] = s->h;
+  g.GT = g.col[g.nmat - 1] + g.w[g.nmat - 1];
+  return g;
+}
+inline const float* rnn_kernel(const macx_rnn_params* P, int dir, int m) {
+  return m ? (dir ? P->bw_candidate_kernel : P->fw_candidate_kernel) : (dir ? P->bw_kernel : P->fw_kernel);
+}
+inline const float* rnn_bias(const macx_rnn_params* P, int dir, int m) {
+  return m ? (dir ? P->bw_candidate_bias : P->fw_candidate_bias) : (dir ? P->bw_bias : P->fw_bias);
+}
+inline float* rnn_dkernel(const macx_rnn_grads* P, int dir, int m) {
+  return m ? (dir ? P->bw_candidate_kernel : P->fw_candidate_kernel) : (dir ? P->bw_kernel : P->fw_kernel);
+}
+inline float* rnn_dbias(const macx_rnn_grads* P, int dir, int m) {
+  return m ? (dir ? P->bw_candidate_bias : P->fw_candidate_bias) : (dir ? P->bw_bias : P->fw_bias);
+}
 struct EncLayout {
-  size_t wx_p, wh_p;     // packed [2][Ep x 4h], [2][h x 4h]
+  size_t wx_p;           // packed [dirs][Ep x GT]: matrix m's [Ep x w] pack at Ep * col
+  size_t wh_p[2];        // packed [dirs][h x w] per matrix
   size_t Xp;             // [B*S][Ep]  dropped embedded words (columns E..Ep-1 zero)
-  size_t Zx;             // [2][B*S][4h]
-  size_t hs, cs;         // [2][S+1][B][h]
-  size_t gates;          // [2][S][B][4h]
+  size_t Zx;             // [dirs][B*S][GT]
+  size_t hs, cs;         // [dirs][S+1][B][h]  (cs: LSTM)
+  size_t gates;          // [dirs][S][B][GT]   (LSTM: the gates; GRU: r | u | c)
+  size_t rh;             // [dirs][S][B][h]    (GRU: r * h_prev)
   size_t total;
 };
-EncLayout make_enc(const macx_enc_shapes* s) {
+EncLayout make_enc(const macx_rnn_shapes* s) {
   EncLayout L;
   memset(&L, 0, sizeof(L));
   size_t off = 0;
   auto take = [&](size_t n) { size_t r = off; off += al4(n); return r; };
-  const size_t B = s->B, S = s->S, h = s->h, Ep = pad128(s->E), G = 4 * h;
-  L.wx_p = take(2 * Ep * G); L.wh_p = take(2 * h * G);
-  L.Xp = take(B * S * Ep); L.Zx = take(2 * B * S * G);
-  L.hs = take(2 * (S + 1) * B * h); L.cs = take(2 * (S + 1) * B * h);
-  L.gates = take(2 * S * B * G);
+  const RnnGeom g = rnn_geom(s);
+  const size_t B = s->B, S = s->S, h = s->h, Ep = pad128(s->E), G = g.GT, D = s->dirs;
+  L.wx_p = take(D * Ep * G);
+  for (int m = 0; m < g.nmat; ++m) L.wh_p[m] = take(D * h * g.w[m]);
+  L.Xp = take(B * S * Ep); L.Zx = take(D * B * S * G);
+  L.hs = take(D * (S + 1) * B * h);
+  if (s->cell == MACX_RNN_LSTM) L.cs = take(D * (S + 1) * B * h);
+  if (s->cell != MACX_RNN_BASIC) L.gates = take(D * S * B * G);
+  if (s->cell == MACX_RNN_GRU) L.rh = take(D * S * B * h);
   L.total = off;
   return L;
 }
 struct EncBwdLayout {
-  size_t wxT_p, whT_p, dG, dZ, dh, dc, dh_pass, dc2, dXp, tmpW, slab, dq, total;
+  size_t wxT_p, whT_p[2], dG, dZ, dh, dc, dh_pass, dc2, drh, dXp, tmpW, slab, dq, total;
 };
-EncBwdLayout make_enc_bwd(const macx_enc_shapes* s) {
+EncBwdLayout make_enc_bwd(const macx_rnn_shapes* s) {
   EncBwdLayout L;
   memset(&L, 0, sizeof(L));
   size_t off = 0;
   auto take = [&](size_t n) { size_t r = off; off += al4(n); return r; };
-  const size_t B = s->B, S = s->S, h = s->h, Ep = pad128(s->E), G = 4 * h;
-  L.wxT_p = take(2 * G * Ep); L.whT_p = take(2 * G * h);
-  L.dG = take(2 * S * B * G); L.dZ = take(2 * B * S * G);
-  L.dh = take(2 * B * h); L.dc = take(2 * B * h); L.dh_pass = take(2 * B * h); L.dc2 = take(2 * B * h);   // dh_pass: the second dh buffer
-  L.dXp = take(B * S * Ep); L.tmpW = take(Ep * G);
-  // split-reduction slabs of the two kernel-gradient contractions (input block [Ep, 4h], recurrent block [h, 4h]): the larger
+  const RnnGeom g = rnn_geom(s);
+  const size_t B = s->B, S = s->S, h = s->h, Ep = pad128(s->E), G = g.GT, D = s->dirs;
+  L.wxT_p = take(D * G * Ep);
+  for (int m = 0; m < g.nmat; ++m) L.whT_p[m] = take(D * g.w[m] * h);
+  L.dG = take(D * S * B * G); L.dZ = take(D * B * S * G);
+  L.dh = take(D * B * h); L.dh_pass = take(D * B * h);                           // dh_pass: the second dh buffer
+  if (s->cell == MACX_RNN_LSTM) { L.dc = take(D * B * h); L.dc2 = take(D * B * h); }
+  if (s->cell == MACX_RNN_GRU) L.drh = take(D * B * h);
+  L.dXp = take(B * S * Ep); L.tmpW = take(Ep * (size_t)g.w[0]);
+  // split-reduction slabs of the kernel-gradient contractions (input block [Ep, w], recurrent block [h, w]): the largest
   {
-    const size_t in_blk = (size_t)wgrad_splits((int)(B * S), (int)Ep, (int)G) * Ep * G;
-    const size_t rec_blk = (size_t)wgrad_splits((int)(B * S), (int)h, (int)G) * h * G;
-    L.slab = take(in_blk > rec_blk ? in_blk : rec_blk);
+    size_t slab = 0;
+    for (int m = 0; m < g.nmat; ++m) {
+      const size_t in_blk = (size_t)wgrad_splits((int)(B * S), (int)Ep, g.w[m]) * Ep * g.w[m];
+      const size_t rec_blk = (size_t)wgrad_splits((int)(B * S), (int)h, g.w[m]) * h * g.w[m];
+      slab = std::max(slab, std::max(in_blk, rec_blk));
+    }
+    L.slab = take(slab);
   }
-  L.dq = take(B * 2 * h);
+  L.dq = take(B * D * h);
   L.total = off;
   return L;
 }
 constexpr size_t ENC_LDS_MAX = 160 * 1024;      // LDS of one CU (gfx950)
-int enc_check(const macx_enc_shapes* s) {
+int rnn_check(const macx_rnn_shapes* s) {
   if (!s || s->B < 1 || s->S < 1 || s->V < 1 || s->E < 1 || s->h < 128 || s->h % 128) return MACX_EINVAL;
-  // the backward step keeps the gate gradients of 16 questions x 4h columns in LDS: past one CU's 160 KB (h > 512) the
+  if (s->cell < MACX_RNN_BASIC || s->cell > MACX_RNN_LSTM || s->dirs < 1 || s->dirs > 2) return MACX_EINVAL;
+  // the LSTM's backward step keeps the gate gradients of 16 questions x 4h columns in LDS: past one CU's 160 KB (h > 512) the
   // forward pass would run and only the backward launch fail, so the shape is refused before anything is sized or launched
+  // (one bound for every cell: the GRU's and the RNN's tiles are smaller)
   if (lstm_step_bwd_lds(s->h) > ENC_LDS_MAX) return MACX_EUNSUPPORTED;
   return MACX_OK;
 }
+// a NULL pointer among those the cell and the direction count need (parameters; with Gr, their gradients as well)
+bool rnn_lacks(const macx_rnn_params* P, const macx_rnn_grads* Gr, bool grads, const macx_rnn_shapes* s) {
+  if (!P || !P->emb || (grads && (!Gr || !Gr->emb))) return true;
+  for (int dir = 0; dir < s->dirs; ++dir)
+    for (int m = 0; m < (s->cell == MACX_RNN_GRU ? 2 : 1); ++m) {
+      if (!rnn_kernel(P, dir, m) || !rnn_bias(P, dir, m)) return true;
+      if (grads && (!rnn_dkernel(Gr, dir, m) || !rnn_dbias(Gr, dir, m))) return true;
+    }
+  return false;
+}
+
+int rnn_forward(const macx_rnn_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params* P,
+                const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved, size_t saved_floats,
+                const uint32_t* mask_word, void* stream) {
+  CKI(rnn_check(s));
+  if (!P || !questions || !lengths || !words || !vecQ || !saved) return MACX_EINVAL;
+  const EncLayout L = make_enc(s);
+  if (saved_floats < L.total) return MACX_ESMALL;
+  hipStream_t st = (hipStream_t)stream;
+  const RnnGeom g = rnn_geom(s);
+  const int B = s->B, S = s->S, E = s->E, h = s->h, Ep = pad128(E), G = g.GT, D = s->dirs;
+  const size_t Bh = (size_t)B * h;
+  Packer pk;
+  for (int dir = 0; dir < D; ++dir)
+    for (int m = 0; m < g.nmat; ++m) {
+      const float* K = rnn_kernel(P, dir, m);      // [E + h, w]: rows [0,E) input, [E,E+h) recurrent
+      const int w = g.w[m];
+      pk.add(K, w, 1, Ep, w, saved + L.wx_p + (size_t)dir * Ep * G + (size_t)Ep * g.col[m], E, w);
+      pk.add(K + (size_t)E * w, w, 1, h, w, saved + L.wh_p[m] + (size_t)dir * h * w);
+    }
+  CK(pk.run(st));
+  hipLaunchKernelGGL(embed_gather_kernel, dim3(512), dim3(256), 0, st, questions, P->emb, B * S, E, Ep, (uint32_t)s->b0 * (uint32_t)S,
+                     make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), saved + L.Xp);
+  CK(hipGetLastError());
+  // input projections of every position, Zx = X Wx + b: the cell bias is added here once per position, so the per-step
+  // recurrent product needs none and all directions go in one launch (the bias vectors are separate tensors)
+  for (int dir = 0; dir < D; ++dir)
+    for (int m = 0; m < g.nmat; ++m) {
+      LinP l = lin_basic(saved + L.Xp, Ep, Ep, B * S, saved + L.wx_p + (size_t)dir * Ep * G + (size_t)Ep * g.col[m], rnn_bias(P, dir, m), g.w[m],
+                         MACX_ACT_NON, saved + L.Zx + (size_t)dir * B * S * G + g.col[m], G);
+      CK(small_linear_launch(l, 1, st));
+    }
+  CK(dev_zero(saved + L.hs, D * (size_t)(S + 1) * Bh * sizeof(float), st));
+  if (s->cell == MACX_RNN_LSTM) CK(dev_zero(saved + L.cs, D * (size_t)(S + 1) * Bh * sizeof(float), st));
+  CK(dev_zero(words, (size_t)B * S * D * h * sizeof(float), st));
+  const dim3 grid(h / 16, (B + 15) / 16, D);
+  for (int tau = 0; tau < S; ++tau) {
+    // R = h_prev Wh and the cell, all directions, one launch per time step (the GRU: gates, then candidate)
+    if (s->cell == MACX_RNN_LSTM) {
+      LstmStepP c;
+      c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.len = lengths;
+      c.Wh = saved + L.wh_p[0]; c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.cs = saved + L.cs; c.gates = saved + L.gates; c.out = words;
+      hipLaunchKernelGGL(lstm_step_kernel, grid, dim3(256), 0, st, c);
+    } else {
+      RnnStepP c;
+      c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.GT = G; c.len = lengths;
+      c.Wh = saved + L.wh_p[0]; c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.out = words;
+      c.kept = s->cell == MACX_RNN_GRU ? saved + L.gates : nullptr;
+      c.rh = s->cell == MACX_RNN_GRU ? saved + L.rh : nullptr;
+      if (s->cell == MACX_RNN_GRU) {
+        hipLaunchKernelGGL(rnn_step_kernel<RNN_GRU_GATES>, grid, dim3(256), 0, st, c);
+        CK(hipGetLastError());
+        c.Wh = saved + L.wh_p[1];
+        hipLaunchKernelGGL(rnn_step_kernel<RNN_GRU_CAND>, grid, dim3(256), 0, st, c);
+      } else {
+        hipLaunchKernelGGL(rnn_step_kernel<RNN_BASIC>, grid, dim3(256), 0, st, c);
+      }
+    }
+    CK(hipGetLastError());
+  }
+  // vecQuestions = dropout(concat of the directions' final h)   (ops.py:905-906, model.py:292)
+  for (int dir = 0; dir < D; ++dir)
+    CK(dev_copy2d(vecQ + dir * h, (size_t)D * h * sizeof(float), saved + L.hs + ((size_t)dir * (S + 1) + S) * Bh,
+                        (size_t)h * sizeof(float), (size_t)h * sizeof(float), B, st));
+  hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)vecQ, B, D * h, (uint32_t)s->b0,
+                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), vecQ);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+int rnn_backward(const macx_rnn_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params* P,
+                 const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats, float* ws,
+                 size_t ws_floats, const float* d_words, const float* d_vecQ, const macx_rnn_grads* Gr,
+                 const uint32_t* mask_word, void* stream) {
+  CKI(rnn_check(s));
+  if (!P || !questions || !lengths || !saved || !ws || !d_words || !d_vecQ || !Gr) return MACX_EINVAL;
+  const EncLayout L = make_enc(s);
+  const EncBwdLayout W = make_enc_bwd(s);
+  if (saved_floats < L.total || ws_floats < W.total) return MACX_ESMALL;
+  hipStream_t st = (hipStream_t)stream;
+  const RnnGeom g = rnn_geom(s);
+  const int B = s->B, S = s->S, E = s->E, h = s->h, Ep = pad128(E), G = g.GT, D = s->dirs;
+  const size_t Bh = (size_t)B * h;
+  Packer pk;
+  for (int dir = 0; dir < D; ++dir)
+    for (int m = 0; m < g.nmat; ++m) {
+      const float* K = rnn_kernel(P, dir, m);
+      const int w = g.w[m];
+      // Wx^T: [w] -> [Ep], columns >= E zero; the matrices' packs stack along k into one [GT] -> [Ep] weight per direction
+      pk.add(K, 1, w, w, Ep, ws + W.wxT_p + (size_t)dir * G * Ep + (size_t)g.col[m] * Ep, w, E);
+      pk.add(K + (size_t)E * w, 1, w, w, h, ws + W.whT_p[m] + (size_t)dir * w * h);   // Wh^T: [w] -> [h]
+    }
+  CK(pk.run(st));
+  CK(dev_zero(ws + W.dZ, D * (size_t)B * S * G * sizeof(float), st));
+  if (s->cell == MACX_RNN_LSTM) CK(dev_zero(ws + W.dc, D * Bh * sizeof(float), st));
+  // d(final states) = d_vecQ through the question dropout, split per direction
+  hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, d_vecQ, B, D * h, (uint32_t)s->b0,
+                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), ws + W.dq);
+  for (int dir = 0; dir < D; ++dir)
+    CK(dev_copy2d(ws + W.dh + (size_t)dir * Bh, (size_t)h * sizeof(float), ws + W.dq + dir * h, (size_t)D * h * sizeof(float),
+                        (size_t)h * sizeof(float), B, st));
+  {
+    const dim3 grid(h / 16, (B + 15) / 16, D);
+    // the running dh / dc alternate between two buffers (a workgroup reads what its neighbours would otherwise overwrite)
+    float* dhb[2] = {ws + W.dh, ws + W.dh_pass};
+    float* dcb[2] = {ws + W.dc, ws + W.dc2};
+    const size_t lds = s->cell == MACX_RNN_LSTM ? lstm_step_bwd_lds(h) : rnn_step_bwd_lds(h, 1), lds2 = rnn_step_bwd_lds(h, 2);
+    if (s->cell == MACX_RNN_LSTM) CK(lds_attr_once(reinterpret_cast<const void*>(lstm_step_bwd_kernel), lds));
+    if (s->cell == MACX_RNN_BASIC) CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_BASIC>), lds));
+    if (s->cell == MACX_RNN_GRU) {
+      CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_GRU_CAND>), lds));
+      CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_GRU_GATES>), lds2));
+    }
+    int cur = 0;
+    for (int tau = S - 1; tau >= 0; --tau, cur ^= 1) {
+      if (s->cell == MACX_RNN_LSTM) {
+        LstmStepBwdP c;
+        c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.len = lengths;
+        c.WhT = ws + W.whT_p[0]; c.cs = saved + L.cs; c.gates = saved + L.gates; c.dout = d_words;
+        c.dh_in = dhb[cur]; c.dc_in = dcb[cur]; c.dh_out = dhb[cur ^ 1]; c.dc_out = dcb[cur ^ 1];
+        c.dG = ws + W.dG; c.dZ = ws + W.dZ;
+        hipLaunchKernelGGL(lstm_step_bwd_kernel, grid, dim3(LSB_THREADS), lds, st, c);
+      } else {
+        RnnStepBwdP c;
+        c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.GT = G; c.len = lengths;
+        c.hs = saved + L.hs; c.dout = d_words; c.dh_in = dhb[cur]; c.dh_out = dhb[cur ^ 1]; c.dG = ws + W.dG; c.dZ = ws + W.dZ;
+        c.kept = s->cell == MACX_RNN_GRU ? saved + L.gates : nullptr;
+        c.drh = s->cell == MACX_RNN_GRU ? ws + W.drh : nullptr;
+        if (s->cell == MACX_RNN_GRU) {
+          // d(r h) of all units first: the gates' backward needs it across the workgroups' unit split
+          c.WT = ws + W.whT_p[1];
+          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_GRU_CAND>, grid, dim3(RSB_THREADS), lds, st, c);
+          CK(hipGetLastError());
+          c.WT = ws + W.whT_p[0];
+          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_GRU_GATES>, grid, dim3(RSB_THREADS), lds2, st, c);
+        } else {
+          c.WT = ws + W.whT_p[0];
+          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_BASIC>, grid, dim3(RSB_THREADS), lds, st, c);
+        }
+      }
+      CK(hipGetLastError());
+    }
+  }
+  for (int dir = 0; dir < D; ++dir)
+    for (int m = 0; m < g.nmat; ++m) {
+      float* dK = rnn_dkernel(Gr, dir, m);
+      const int w = g.w[m];
+      const float* dZm = ws + W.dZ + (size_t)dir * B * S * G + g.col[m];
+      const float* dGm = ws + W.dG + (size_t)dir * S * B * G + g.col[m];
+      // input block of the kernel: X^T dZ (rows [0,E) of the padded product)
+      CKI(wgrad_impl(saved + L.Xp, Ep, dZm, G, B * S, Ep, w, ws + W.tmpW, ws + W.slab, st));
+      CK(dev_copy(dK, ws + W.tmpW, (size_t)E * w * sizeof(float), st));
+      // recurrent block: sum_tau h_prev(tau)^T dG_tau (the GRU's candidate: (r h_prev)^T)  -- one contraction over S*B rows
+      const float* A = m ? saved + L.rh + (size_t)dir * S * Bh : saved + L.hs + (size_t)dir * (S + 1) * Bh;
+      CKI(wgrad_impl(A, h, dGm, G, S * B, h, w, dK + (size_t)E * w, ws + W.slab, st));
+      CK(rowsum(dGm, S * B, w, G, rnn_dbias(Gr, dir, m), st));
+    }
+  // d(embedded words) = [dZ_fw | dZ_bw] [Wx_fw^T ; Wx_bw^T], then through the input dropout into the embedding rows
+  {
+    LinP l = lin_basic(ws + W.dZ, G, G, B * S, ws + W.wxT_p, nullptr, Ep, MACX_ACT_NON, ws + W.dXp, Ep);
+    if (D == 2) {
+      l.seg[1] = LinSeg{ws + W.dZ + (size_t)B * S * G, G, G, 0};
+      l.Ktot = 2 * G;
+    }
+    CK(small_linear_launch(l, 1, st));
+  }
+  hipLaunchKernelGGL(embed_grad_kernel, dim3(s->V, (E + 1023) / 1024), dim3(256), 0, st, questions, (const float*)(ws + W.dXp), B * S, E, Ep,
+                     (uint32_t)s->b0 * (uint32_t)S, make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), Gr->emb);
+  CK(hipGetLastError());
+  return MACX_OK;
+}
+
+// macx_encoder_* is the bidirectional LSTM of the general implementation: the launches, their order and arguments of before
+inline macx_rnn_shapes enc_as_rnn(const macx_enc_shapes* s) {
+  return macx_rnn_shapes{s->B, s->S, s->V, s->E, s->h, s->b0, MACX_RNN_LSTM, 2};
+}
 }  // namespace
 
-size_t macx_encoder_saved_floats(const macx_enc_shapes* s) { return enc_check(s) ? 0 : make_enc(s).total; }
-size_t macx_encoder_ws_floats(const macx_enc_shapes* s) { return enc_check(s) ? 0 : make_enc_bwd(s).total; }
+size_t macx_rnn_encoder_saved_floats(const macx_rnn_shapes* s) { return rnn_check(s) ? 0 : make_enc(s).total; }
+size_t macx_rnn_encoder_ws_floats(const macx_rnn_shapes* s) { return rnn_check(s) ? 0 : make_enc_bwd(s).total; }
+
+int macx_rnn_encoder_forward_w(const macx_rnn_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params* P,
+                               const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved,
+                               size_t saved_floats, const uint32_t* mask_word, void* stream) {
+  CKI(rnn_check(s));
+  if (rnn_lacks(P, nullptr, false, s)) return MACX_EINVAL;
+  return rnn_forward(s, keep_input, keep_question, seed, P, questions, lengths, words, vecQ, saved, saved_floats, mask_word, stream);
+}
+
+int macx_rnn_encoder_backward_w(const macx_rnn_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_rnn_params* P,
+                                const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats, float* ws,
+                                size_t ws_floats, const float* d_words, const float* d_vecQ, const macx_rnn_grads* Gr,
+                                const uint32_t* mask_word, void* stream) {
+  CKI(rnn_check(s));
+  if (rnn_lacks(P, Gr, true, s)) return MACX_EINVAL;
+  return rnn_backward(s, keep_input, keep_question, seed, P, questions, lengths, saved, saved_floats, ws, ws_floats, d_words, d_vecQ, Gr,
+                      mask_word, stream);
+}
+
+size_t macx_encoder_saved_floats(const macx_enc_shapes* s) {
+  if (!s) return 0;
+  const macx_rnn_shapes r = enc_as_rnn(s);
+  return macx_rnn_encoder_saved_floats(&r);
+}
+size_t macx_encoder_ws_floats(const macx_enc_shapes* s) {
+  if (!s) return 0;
+  const macx_rnn_shapes r = enc_as_rnn(s);
+  return macx_rnn_encoder_ws_floats(&r);
+}
 
 int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
                          const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved,
@@ -3160,49 +3423,12 @@ int macx_encoder_forward(const macx_enc_shapes* s, float keep_input, float keep_
 int macx_encoder_forward_w(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
                            const int32_t* questions, const int32_t* lengths, float* words, float* vecQ, float* saved,
                            size_t saved_floats, const uint32_t* mask_word, void* stream) {
-  CKI(enc_check(s));
-  if (!P || !questions || !lengths || !words || !vecQ || !saved) return MACX_EINVAL;
-  const EncLayout L = make_enc(s);
-  if (saved_floats < L.total) return MACX_ESMALL;
-  hipStream_t st = (hipStream_t)stream;
-  const int B = s->B, S = s->S, E = s->E, h = s->h, Ep = pad128(E), G = 4 * h;
-  const size_t Bh = (size_t)B * h;
-  Packer pk;
-  for (int dir = 0; dir < 2; ++dir) {
-    const float* K = dir ? P->bw_kernel : P->fw_kernel;      // [E + h, 4h]: rows [0,E) input, [E,E+h) recurrent
-    pk.add(K, G, 1, Ep, G, saved + L.wx_p + (size_t)dir * Ep * G, E, G);
-    pk.add(K + (size_t)E * G, G, 1, h, G, saved + L.wh_p + (size_t)dir * h * G);
-  }
-  CK(pk.run(st));
-  hipLaunchKernelGGL(embed_gather_kernel, dim3(512), dim3(256), 0, st, questions, P->emb, B * S, E, Ep, (uint32_t)s->b0 * (uint32_t)S,
-                     make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), saved + L.Xp);
-  CK(hipGetLastError());
-  // input projections of every position, Zx = X Wx + b: the cell bias is added here once per position, so the per-step
-  // recurrent linear needs none and both directions go in one launch (the two bias vectors are separate tensors)
-  for (int dir = 0; dir < 2; ++dir) {
-    LinP l = lin_basic(saved + L.Xp, Ep, Ep, B * S, saved + L.wx_p + (size_t)dir * Ep * G, dir ? P->bw_bias : P->fw_bias, G, MACX_ACT_NON,
-                       saved + L.Zx + (size_t)dir * B * S * G, G);
-    CK(small_linear_launch(l, 1, st));
-  }
-  CK(dev_zero(saved + L.hs, 2 * (size_t)(S + 1) * Bh * sizeof(float), st));
-  CK(dev_zero(saved + L.cs, 2 * (size_t)(S + 1) * Bh * sizeof(float), st));
-  CK(dev_zero(words, (size_t)B * S * 2 * h * sizeof(float), st));
-  for (int tau = 0; tau < S; ++tau) {
-    // R = h_prev Wh and the cell, both directions, one launch per time step
-    LstmStepP c;
-    c.B = B; c.S = S; c.h = h; c.tau = tau; c.len = lengths;
-    c.Wh = saved + L.wh_p; c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.cs = saved + L.cs; c.gates = saved + L.gates; c.out = words;
-    hipLaunchKernelGGL(lstm_step_kernel, dim3(h / 16, (B + 15) / 16, 2), dim3(256), 0, st, c);
-    CK(hipGetLastError());
-  }
-  // vecQuestions = dropout(concat([h_fw_final, h_bw_final]))   (ops.py:905-906, model.py:292)
-  for (int dir = 0; dir < 2; ++dir)
-    CK(dev_copy2d(vecQ + dir * h, (size_t)2 * h * sizeof(float), saved + L.hs + ((size_t)dir * (S + 1) + S) * Bh,
-                        (size_t)h * sizeof(float), (size_t)h * sizeof(float), B, st));
-  hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, (const float*)vecQ, B, 2 * h, (uint32_t)s->b0,
-                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), vecQ);
-  CK(hipGetLastError());
-  return MACX_OK;
+  if (!s) return MACX_EINVAL;
+  const macx_rnn_shapes r = enc_as_rnn(s);
+  CKI(rnn_check(&r));
+  if (!P) return MACX_EINVAL;
+  const macx_rnn_params RP = {P->emb, P->fw_kernel, P->fw_bias, P->bw_kernel, P->bw_bias, nullptr, nullptr, nullptr, nullptr};
+  return rnn_forward(&r, keep_input, keep_question, seed, &RP, questions, lengths, words, vecQ, saved, saved_floats, mask_word, stream);
 }
 
 int macx_encoder_backward(const macx_enc_shapes* s, float keep_input, float keep_question, uint32_t seed, const macx_enc_params* P,
@@ -3216,67 +3442,14 @@ int macx_encoder_backward_w(const macx_enc_shapes* s, float keep_input, float ke
                             const int32_t* questions, const int32_t* lengths, const float* saved, size_t saved_floats, float* ws,
                             size_t ws_floats, const float* d_words, const float* d_vecQ, const macx_enc_grads* Gr,
                             const uint32_t* mask_word, void* stream) {
-  CKI(enc_check(s));
-  if (!P || !questions || !lengths || !saved || !ws || !d_words || !d_vecQ || !Gr) return MACX_EINVAL;
-  const EncLayout L = make_enc(s);
-  const EncBwdLayout W = make_enc_bwd(s);
-  if (saved_floats < L.total || ws_floats < W.total) return MACX_ESMALL;
-  hipStream_t st = (hipStream_t)stream;
-  const int B = s->B, S = s->S, E = s->E, h = s->h, Ep = pad128(E), G = 4 * h;
-  const size_t Bh = (size_t)B * h;
-  Packer pk;
-  for (int dir = 0; dir < 2; ++dir) {
-    const float* K = dir ? P->bw_kernel : P->fw_kernel;
-    pk.add(K, 1, G, G, Ep, ws + W.wxT_p + (size_t)dir * G * Ep, G, E);           // Wx^T: [4h] -> [Ep], columns >= E zero
-    pk.add(K + (size_t)E * G, 1, G, G, h, ws + W.whT_p + (size_t)dir * G * h);   // Wh^T: [4h] -> [h]
-  }
-  CK(pk.run(st));
-  CK(dev_zero(ws + W.dZ, 2 * (size_t)B * S * G * sizeof(float), st));
-  CK(dev_zero(ws + W.dc, 2 * Bh * sizeof(float), st));
-  // d(final states) = d_vecQ through the question dropout, split per direction
-  hipLaunchKernelGGL(drop2_kernel, dim3(64), dim3(256), 0, st, d_vecQ, B, 2 * h, (uint32_t)s->b0,
-                     make_drop(keep_question, seed, SITE_QUESTION, 0, mask_word), no_drop(), ws + W.dq);
-  for (int dir = 0; dir < 2; ++dir)
-    CK(dev_copy2d(ws + W.dh + (size_t)dir * Bh, (size_t)h * sizeof(float), ws + W.dq + dir * h, (size_t)2 * h * sizeof(float),
-                        (size_t)h * sizeof(float), B, st));
-  {
-    const size_t lds = lstm_step_bwd_lds(h);
-    CK(lds_attr_once(reinterpret_cast<const void*>(lstm_step_bwd_kernel), lds));
-    // the running dh / dc alternate between two buffers (a workgroup reads what its neighbours would otherwise overwrite)
-    float* dhb[2] = {ws + W.dh, ws + W.dh_pass};
-    float* dcb[2] = {ws + W.dc, ws + W.dc2};
-    int cur = 0;
-    for (int tau = S - 1; tau >= 0; --tau, cur ^= 1) {
-      LstmStepBwdP c;
-      c.B = B; c.S = S; c.h = h; c.tau = tau; c.len = lengths;
-      c.WhT = ws + W.whT_p; c.cs = saved + L.cs; c.gates = saved + L.gates; c.dout = d_words;
-      c.dh_in = dhb[cur]; c.dc_in = dcb[cur]; c.dh_out = dhb[cur ^ 1]; c.dc_out = dcb[cur ^ 1];
-      c.dG = ws + W.dG; c.dZ = ws + W.dZ;
-      hipLaunchKernelGGL(lstm_step_bwd_kernel, dim3(h / 16, (B + 15) / 16, 2), dim3(LSB_THREADS), lds, st, c);
-      CK(hipGetLastError());
-    }
-  }
-  for (int dir = 0; dir < 2; ++dir) {
-    float* dK = dir ? Gr->bw_kernel : Gr->fw_kernel;
-    // input block of the kernel: X^T dZ (rows [0,E) of the padded product)
-    CKI(wgrad_impl(saved + L.Xp, Ep, ws + W.dZ + (size_t)dir * B * S * G, G, B * S, Ep, G, ws + W.tmpW, ws + W.slab, st));
-    CK(dev_copy(dK, ws + W.tmpW, (size_t)E * G * sizeof(float), st));
-    // recurrent block: sum_tau h_prev(tau)^T dG_tau  -- one contraction over S*B rows
-    CKI(wgrad_impl(saved + L.hs + (size_t)dir * (S + 1) * Bh, h, ws + W.dG + (size_t)dir * S * B * G, G, S * B, h, G,
-                   dK + (size_t)E * G, ws + W.slab, st));
-    CK(rowsum(ws + W.dG + (size_t)dir * S * B * G, S * B, G, G, dir ? Gr->bw_bias : Gr->fw_bias, st));
-  }
-  // d(embedded words) = [dZ_fw | dZ_bw] [Wx_fw^T ; Wx_bw^T], then through the input dropout into the embedding rows
-  {
-    LinP l = lin_basic(ws + W.dZ, G, G, B * S, ws + W.wxT_p, nullptr, Ep, MACX_ACT_NON, ws + W.dXp, Ep);
-    l.seg[1] = LinSeg{ws + W.dZ + (size_t)B * S * G, G, G, 0};
-    l.Ktot = 2 * G;
-    CK(small_linear_launch(l, 1, st));
-  }
-  hipLaunchKernelGGL(embed_grad_kernel, dim3(s->V, (E + 1023) / 1024), dim3(256), 0, st, questions, (const float*)(ws + W.dXp), B * S, E, Ep,
-                     (uint32_t)s->b0 * (uint32_t)S, make_drop(keep_input, seed, SITE_ENC_INPUT, 0, mask_word), Gr->emb);
-  CK(hipGetLastError());
-  return MACX_OK;
+  if (!s) return MACX_EINVAL;
+  const macx_rnn_shapes r = enc_as_rnn(s);
+  CKI(rnn_check(&r));
+  if (!P || !Gr) return MACX_EINVAL;
+  const macx_rnn_params RP = {P->emb, P->fw_kernel, P->fw_bias, P->bw_kernel, P->bw_bias, nullptr, nullptr, nullptr, nullptr};
+  const macx_rnn_grads RG = {Gr->emb, Gr->fw_kernel, Gr->fw_bias, Gr->bw_kernel, Gr->bw_bias, nullptr, nullptr, nullptr, nullptr};
+  return rnn_backward(&r, keep_input, keep_question, seed, &RP, questions, lengths, saved, saved_floats, ws, ws_floats, d_words, d_vecQ, &RG,
+                      mask_word, stream);
 }
 
 // =================================================================================================

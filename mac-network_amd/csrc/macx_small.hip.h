@@ -1061,16 +1061,16 @@ __global__ void embed_gather_kernel(const int32_t* __restrict__ idx, const float
 // replaces (small_linear + lstm_cell_kernel) were ~6 us each of pure latency, 100 dependent pairs per forward pass.
 // A workgroup owns 16 questions x 16 hidden units of one direction and therefore all four gates of its units: four waves
 // split the reduction over h, an LDS combine in fixed order, then one (question, unit) per thread.
-// Grid (h / 16, ceil(B / 16), 2).
+// Grid (h / 16, ceil(B / 16), dirs).
 // ---------------------------------------------------------------------------------------------
 struct LstmStepP {
-  int B, S, h, tau;
+  int B, S, h, tau, dirs;  // dirs: 1 (forward only: grid z = 1) | 2
   const int32_t* len;      // [B]
   const float* Wh;         // [2] packed [h/16][4][4h][4] (pack format 0)
   const float* Zx;         // [2][B*S][4h]  x Wx + b  (all positions)
   float* hs; float* cs;    // [2][S+1][B][h]
   float* gates;            // [2][S][B][4h]
-  float* out;              // [B][S][2h]
+  float* out;              // [B][S][dirs h]
 };
 __global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepP p) {
   __shared__ float red[4][4][16][17];
@@ -1143,7 +1143,7 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepP p) {
     go = 1.0f / (1.0f + expf(-(R[3] + z3)));
     cn = cp * gf + gi * gj;
     hn = tanhf(cn) * go;
-    p.out[((size_t)b * p.S + pos) * 2 * h + dir * h + u] = hn;
+    p.out[((size_t)b * p.S + pos) * p.dirs * h + dir * h + u] = hn;
   }
   p.hs[s1] = hn;
   p.cs[s1] = cn;
@@ -1156,12 +1156,12 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepP p) {
 // 16 units from the LDS tile.  The running dh / dc are double-buffered by the parity of tau (a workgroup reads what its
 // neighbours would otherwise be overwriting); the workgroup with blockIdx.x == 0 writes dc, dG and dZ.
 struct LstmStepBwdP {
-  int B, S, h, tau;
+  int B, S, h, tau, dirs;
   const int32_t* len;
   const float* WhT;        // [2] packed [4h/16][4][h][4] (pack format 0 of Wh^T)
   const float* cs;         // [2][S+1][B][h]
   const float* gates;      // [2][S][B][4h]
-  const float* dout;       // [B][S][2h]
+  const float* dout;       // [B][S][dirs h]
   const float* dh_in; const float* dc_in;     // [2][B][h] running state gradients after step tau + 1
   float* dh_out; float* dc_out;               // ... after this step
   float* dG;               // [2][S][B][4h]
@@ -1209,7 +1209,7 @@ __global__ __launch_bounds__(LSB_THREADS) void lstm_step_bwd_kernel(LstmStepBwdP
         const size_t r = (size_t)b * h + u;
         const float cp = p.cs[(size_t)(dir * (p.S + 1) + p.tau) * Bh + r];
         const float cn = p.cs[(size_t)(dir * (p.S + 1) + p.tau + 1) * Bh + r];
-        dh += p.dout[((size_t)b * p.S + pos) * 2 * h + dir * h + u];
+        dh += p.dout[((size_t)b * p.S + pos) * p.dirs * h + dir * h + u];
         const float tc = tanhf(cn);
         dO = dh * tc * go * (1.0f - go);
         const float dct = dc + dh * go * (1.0f - tc * tc);

@@ -6,6 +6,8 @@ questionCntxWords [B,S,encDim], vecQuestions = dropout(concat(final h_fw, h_bw),
 
     enc = QuestionEncoder(config, vocab=90).to(device)
     questionCntxWords, vecQuestions = enc(questions, lengths, train=True, seed=step)
+
+RecurrentQuestionEncoder is the same unit for encType RNN | GRU | LSTM in one direction or two (macx_rnn_encoder_*), opt-in.
 """
 import torch
 
@@ -112,6 +114,129 @@ class QuestionEncoder(unit.FusedUnit):
 
     def _param_grads(self, grads):
         return [grads[0] if self.emb.requires_grad else None] + grads[1:]
+
+
+RNN_CELLS = {"RNN": ("basic_rnn_cell", 1), "GRU": ("gru_cell", 2), "LSTM": ("basic_lstm_cell", 4)}   # scope, width of `kernel` / h
+
+
+def _check_recurrent(config):
+    """What RecurrentQuestionEncoder refuses, in the order the reference meets it: its own exceptions first (model.py:286, then
+    the cell's first call, then the second layer's variables), then the option sets this class leaves to the other two."""
+    g = lambda n, dflt: getattr(config, n, dflt)
+    if g("encVariationalDropout", False):
+        raise KeyError("stateInput")                  # model.py:286 reads a dropout that model.py:80-90 never creates
+    enc_type, bi = g("encType", "LSTM"), bool(g("encBi", False))
+    if enc_type in ("MiGRU", "MiLSTM"):
+        # ops.createCell hands every cell activation = activations.get(None, None); mi_gru_cell.py:57 / mi_lstm_cell.py:68 call it
+        raise TypeError("'NoneType' object is not callable")
+    if enc_type not in RNN_CELLS:
+        raise KeyError(enc_type)                      # ops.py:770 cells[cellType] (argparse admits the five above)
+    if g("encNumLayers", 1) > 1:
+        first = {"RNN": "kernel", "GRU": "gates/kernel", "LSTM": "kernel"}[enc_type]
+        raise ValueError("Variable encoder/%s/%s%s/%s already exists, disallowed. Did you mean to set reuse=True in VarScope?"
+                         % ("birnnLayer/bidirectional_rnn" if bi else "rnnLayer/rnn", "fw/" if bi else "", RNN_CELLS[enc_type][0], first))
+    if g("encProj", False) or g("encDim", 512) != g("ctrlDim", 512):
+        raise UnsupportedOptions("encoder: the output projections (encProj / encDim != ctrlDim) are missing from the recurrent "
+                                 "encoder's fused path; the LSTM has them on GenericQuestionEncoder")
+    if g("ansEmbMod", "NON") == "SHARED":
+        raise UnsupportedOptions("encoder: embeddings shared with the answers (ansEmbMod SHARED) are missing from the recurrent "
+                                 "encoder's fused path")
+    enc = int(g("encDim", 512))
+    if (bi and enc % 2) or (enc // 2 if bi else enc) % 128:
+        raise UnsupportedOptions("encoder: the recurrent kernels need a multiple of 128 units per direction (encDim%s = %s); the "
+                                 "LSTM runs other widths on GenericQuestionEncoder" % ("/2" if bi else "", "%g" % (enc / 2 if bi else enc)))
+    if (enc // 2 if bi else enc) > FUSED_H_MAX:
+        raise UnsupportedOptions("encoder: the recurrent kernels hold 16 questions' gate gradients in LDS, which fits up to %d units "
+                                 "per direction (macx_rnn_shapes, include/macx.h)" % FUSED_H_MAX)
+
+
+class RecurrentQuestionEncoder(unit.FusedUnit):
+    """qEmbeddingsOp + encoder (model.py:207-219, 279-307 -> ops.RNNLayer, ops.py:798-952) for every cell ops.createCell builds
+    with an activation -- encType RNN (BasicRNNCell), GRU (GRUCell), LSTM (BasicLSTMCell) -- in one direction (no --encBi:
+    tf.nn.dynamic_rnn, h = encDim) or two (h = encDim/2), on fused kernels: macx_rnn_encoder_forward_w / _backward_w, one launch
+    per time step and pass (the GRU two).  QuestionEncoder's interface; (LSTM, --encBi) returns QuestionEncoder's bits.
+    Variables under the reference's names: encoder/rnnLayer/rnn/<cell>/... or encoder/birnnLayer/bidirectional_rnn/{fw,bw}/<cell>/...
+    with <cell> = basic_rnn_cell/{kernel,bias} | gru_cell/{gates,candidate}/{kernel,bias} | basic_lstm_cell/{kernel,bias}; kernels
+    glorot-uniform over the whole matrix, biases zero, the GRU gates' bias one (TF 1.x).
+    Opt-in (MACNet(..., encoder="recurrent")): QuestionEncoder(config) builds what it built before.  MiGRU / MiLSTM,
+    encVariationalDropout and encNumLayers > 1 raise what the reference raises; the output projections, shared answer
+    embeddings and widths off the 128 granule are UnsupportedOptions."""
+    ABI = "rnn_encoder"
+    SHAPES = _lib.MacxRnnShapes
+    check_fused = staticmethod(_check_recurrent)
+    SIZE_ERROR = "encoder: the width per direction must be a multiple of 128, at most %d" % FUSED_H_MAX
+
+    def __new__(cls, *args, **kw):
+        return torch.nn.Module.__new__(cls)               # (no generic twin to fall back to: a refused option set raises)
+
+    def __init__(self, config, vocab, embInit=None, generator=None):
+        torch.nn.Module.__init__(self)
+        g = lambda n, dflt: getattr(config, n, dflt)
+        _check_recurrent(config)
+        self.cell, self.bi = g("encType", "LSTM"), bool(g("encBi", False))
+        self.dirs = 2 if self.bi else 1
+        self.vocab, self.E, self.h = int(vocab), int(g("wrdEmbDim", 300)), int(g("encDim", 512)) // self.dirs
+        self.keep_in, self.keep_q = float(g("encInputDropout", 0.85)), float(g("qDropout", 0.92))
+        E, h = self.E, self.h
+        if embInit is None:
+            emb = torch.randn((self.vocab, E), generator=generator, dtype=torch.float64)
+        else:
+            emb = torch.as_tensor(embInit, dtype=torch.float64)
+            if tuple(emb.shape) != (self.vocab, E):
+                raise ValueError("embInit must be [%d, %d]" % (self.vocab, E))
+        self.emb = torch.nn.Parameter(emb.float(), requires_grad=not g("wrdEmbFixed", False))
+        scope, k = RNN_CELLS[self.cell]
+        fields, names = ["emb"], {"emb": "qEmbeddings/emb"}
+        for d in ("fw", "bw")[:self.dirs]:
+            base = "encoder/%s/%s" % ("birnnLayer/bidirectional_rnn/" + d if self.bi else "rnnLayer/rnn", scope)
+            # TF's creation order: the GRU's gates before its candidate; glorot_uniform over the whole [in + n, k n] matrix
+            for part, prefix, width, bias in _cell_matrices(self.cell, k):
+                kern = unit.xavier_uniform((E + h, width * h), E + h + width * h, generator)
+                for f, t in (("%s_%skernel" % (d, prefix), kern), ("%s_%sbias" % (d, prefix), torch.full((width * h,), bias))):
+                    self.register_parameter(f, torch.nn.Parameter(t))
+                    fields.append(f)
+                    names[f] = "%s/%s%s" % (base, part, f.rsplit("_", 1)[1])
+        self.FIELDS, self.REF_NAMES = tuple(fields), names
+
+    embed, _param_grads = QuestionEncoder.embed, QuestionEncoder._param_grads
+
+    def _struct(self, cls, ptrs):
+        return cls(**dict(zip(self.FIELDS, ptrs)))        # (the pointers this cell does not have stay NULL)
+
+    def PARAMS(self, *ptrs):
+        return self._struct(_lib.MacxRnnParams, ptrs)
+
+    def GRADS(self, *ptrs):
+        return self._struct(_lib.MacxRnnGrads, ptrs)
+
+    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
+        """QuestionEncoder.forward's arguments -> (questionCntxWords [B,S,dirs h], vecQuestions [B,dirs h])"""
+        unit.require_device(questions, "the question encoder")
+        questions = questions.to(torch.int32).contiguous()
+        lengths = lengths.to(device=questions.device, dtype=torch.int32).contiguous()
+        check_questions(questions, lengths, self.vocab, check_ids)
+        B, S = questions.shape
+        sh = self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=int(b0), cell=_lib.RNN_CELL[self.cell], dirs=self.dirs)
+        keeps = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
+        return self._call(sh, keeps, seed, train, mask_word, questions, lengths)
+
+    def _outputs(self, sh, inputs):
+        dev = inputs[0].device
+        words = torch.empty(sh.B, sh.S, sh.dirs * sh.h, dtype=torch.float32, device=dev)
+        vecQ = torch.empty(sh.B, sh.dirs * sh.h, dtype=torch.float32, device=dev)
+        return (words, vecQ), inputs
+
+    def _backward(self, sh, X, d_outs):
+        shapes = ((sh.B, sh.S, sh.dirs * sh.h), (sh.B, sh.dirs * sh.h))
+        d = tuple(torch.zeros(s, dtype=torch.float32, device=X[0].device) if g is None else g.contiguous() for s, g in zip(shapes, d_outs))
+        return d, (), (None, None)
+
+
+def _cell_matrices(cell, k):
+    """(scope part, field prefix, width / h, bias initial value) of a cell's matrices in TF's creation order"""
+    if cell == "GRU":
+        return (("gates/", "", 2, 1.0), ("candidate/", "candidate_", 1, 0.0))
+    return (("", "", k, 0.0),)
 
 
 class GenericQuestionEncoder(generic.ParamsUnit, torch.nn.Module):

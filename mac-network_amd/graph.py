@@ -719,7 +719,7 @@ class CapturedDPTrainStep(_Captured, _CellInputs, _MaskWord, TwoPhaseStep):
 def _require_fused_tower(net, who):
     """the tower's captured classes take a model.MACNet whose four modules are the fused ones (UnsupportedOptions otherwise), on
     the HIP device (RuntimeError otherwise); returns the device"""
-    from .encoder import QuestionEncoder
+    from .encoder import QuestionEncoder, RecurrentQuestionEncoder
     from .output import OutputClassifier
     from .stem import Stem
     want = (("enc", QuestionEncoder), ("stem", Stem), ("cell", MACCellParams), ("out", OutputClassifier))
@@ -727,7 +727,7 @@ def _require_fused_tower(net, who):
         mod = getattr(net, name, None)
         if mod is None:
             raise TypeError("%s takes a macx.MACNet (question encoder, stem, cell, output unit); this net has no .%s" % (who, name))
-        if not isinstance(mod, cls):
+        if not isinstance(mod, cls) and not (name == "enc" and isinstance(mod, RecurrentQuestionEncoder)):
             raise UnsupportedOptions("%s: net.%s is a %s; only a tower of the fused modules (%s) is captured -- the generic "
                                      "one-kernel-per-op modules are out of its scope" % (who, name, type(mod).__name__,
                                                                                         ", ".join(c.__name__ for _, c in want)))

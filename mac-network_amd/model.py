@@ -11,7 +11,7 @@ stem.out_hw cells, e.g. 7 x 7 for --stemStrideSizes 2 1).  Out of this graph sta
 import torch
 
 from .cell import MACCell
-from .encoder import QuestionEncoder
+from .encoder import QuestionEncoder, RecurrentQuestionEncoder
 from .options import UnsupportedOptions, freeze, fresh_seed, get
 from .output import OutputClassifier, answer_loss_and_pred
 from .params import MACCellParams
@@ -125,11 +125,21 @@ class MACNetCore(torch.nn.Module):
 
 
 class MACNet(MACNetCore):
-    """MACnet.build's tower body (model.py:781-813): embeddingsOp -> encoder -> stem -> MACnetwork -> outputOp/classifier."""
+    """MACnet.build's tower body (model.py:781-813): embeddingsOp -> encoder -> stem -> MACnetwork -> outputOp/classifier.
+    encoder: None -- QuestionEncoder(config) (the fused bidirectional LSTM, GenericQuestionEncoder for the other LSTM option sets);
+    "recurrent" -- a RecurrentQuestionEncoder (encType RNN | GRU | LSTM, one direction or two, fused); or a module instance with
+    QuestionEncoder's interface, taken as it is."""
 
-    def __init__(self, config, vocab, H=14, W=14, imageInDim=1024, answerWordsNum=28, embInit=None, generator=None):
+    def __init__(self, config, vocab, H=14, W=14, imageInDim=1024, answerWordsNum=28, embInit=None, generator=None, encoder=None):
         super().__init__(config, H=H, W=W, imageInDim=imageInDim, answerWordsNum=answerWordsNum, generator=generator)
-        self.enc = QuestionEncoder(config, vocab, embInit=embInit, generator=generator)
+        if encoder is None:
+            self.enc = QuestionEncoder(config, vocab, embInit=embInit, generator=generator)
+        elif encoder == "recurrent":
+            self.enc = RecurrentQuestionEncoder(config, vocab, embInit=embInit, generator=generator)
+        elif isinstance(encoder, torch.nn.Module):
+            self.enc = encoder
+        else:
+            raise ValueError('encoder must be None, "recurrent" or a module (got %r)' % (encoder,))
 
     def tensors(self):
         return self.enc.tensors() + super().tensors()

@@ -2,7 +2,9 @@
 validators, the fused-or-generic construction, the reference-name dictionaries, and the ONE autograd node around a unit's pair
 of `_w` ABI calls (include/macx.h).  A leaf: it imports _lib and options only.
 
-A unit declares, as class attributes: FIELDS (its _lib.*_FIELDS) and REF_NAMES, ABI ("stem" | "encoder" | "output": the exports
+A unit declares, as class attributes: FIELDS (its _lib.*_FIELDS) and REF_NAMES, ABI ("stem" | "encoder" | "output" |
+"rnn_encoder" -- encoder.RecurrentQuestionEncoder, whose FIELDS / REF_NAMES / PARAMS / GRADS depend on the cell and so belong to the
+instance: the exports
 macx_<ABI>_saved_floats / _ws_floats / _forward_w / _backward_w), SHAPES / PARAMS / GRADS (its three ctypes structs), GENERIC (the
 class built for the option sets check_fused refuses), check_fused and SIZE_ERROR (the ValueError text of a `saved` size of 0).
 Its forward() validates, builds the shapes struct and hands over to self._call; two hooks say what differs between the units:
