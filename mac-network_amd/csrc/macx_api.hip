@@ -3191,7 +3191,7 @@ int rnn_check(const macx_rnn_shapes* s) {
   // the LSTM's backward step keeps the gate gradients of 16 questions x 4h columns in LDS: past one CU's 160 KB (h > 512) the
   // forward pass would run and only the backward launch fail, so the shape is refused before anything is sized or launched
   // (one bound for every cell: the GRU's and the RNN's tiles are smaller)
-  if (lstm_step_bwd_lds(s->h) > ENC_LDS_MAX) return MACX_EUNSUPPORTED;
+  if (rnn_step_bwd_lds(s->h, 4) > ENC_LDS_MAX) return MACX_EUNSUPPORTED;
   return MACX_OK;
 }
 // a NULL pointer among those the cell and the direction count need (parameters; with Gr, their gradients as well)
@@ -3240,29 +3240,21 @@ int rnn_forward(const macx_rnn_shapes* s, float keep_input, float keep_question,
   if (s->cell == MACX_RNN_LSTM) CK(dev_zero(saved + L.cs, D * (size_t)(S + 1) * Bh * sizeof(float), st));
   CK(dev_zero(words, (size_t)B * S * D * h * sizeof(float), st));
   const dim3 grid(h / 16, (B + 15) / 16, D);
+  const RnnSteps steps = rnn_steps(s->cell);
+  RnnStepP c;
+  c.B = B; c.S = S; c.h = h; c.dirs = D; c.GT = G; c.len = lengths;
+  c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.out = words;
+  c.kept = s->cell != MACX_RNN_BASIC ? saved + L.gates : nullptr;
+  c.rh = s->cell == MACX_RNN_GRU ? saved + L.rh : nullptr;
+  c.cs = s->cell == MACX_RNN_LSTM ? saved + L.cs : nullptr;
   for (int tau = 0; tau < S; ++tau) {
     // R = h_prev Wh and the cell, all directions, one launch per time step (the GRU: gates, then candidate)
-    if (s->cell == MACX_RNN_LSTM) {
-      LstmStepP c;
-      c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.len = lengths;
-      c.Wh = saved + L.wh_p[0]; c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.cs = saved + L.cs; c.gates = saved + L.gates; c.out = words;
-      hipLaunchKernelGGL(lstm_step_kernel, grid, dim3(256), 0, st, c);
-    } else {
-      RnnStepP c;
-      c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.GT = G; c.len = lengths;
-      c.Wh = saved + L.wh_p[0]; c.Zx = saved + L.Zx; c.hs = saved + L.hs; c.out = words;
-      c.kept = s->cell == MACX_RNN_GRU ? saved + L.gates : nullptr;
-      c.rh = s->cell == MACX_RNN_GRU ? saved + L.rh : nullptr;
-      if (s->cell == MACX_RNN_GRU) {
-        hipLaunchKernelGGL(rnn_step_kernel<RNN_GRU_GATES>, grid, dim3(256), 0, st, c);
-        CK(hipGetLastError());
-        c.Wh = saved + L.wh_p[1];
-        hipLaunchKernelGGL(rnn_step_kernel<RNN_GRU_CAND>, grid, dim3(256), 0, st, c);
-      } else {
-        hipLaunchKernelGGL(rnn_step_kernel<RNN_BASIC>, grid, dim3(256), 0, st, c);
-      }
+    c.tau = tau;
+    for (int k = 0; k < steps.n; ++k) {
+      c.Wh = saved + L.wh_p[steps.l[k].mat];
+      hipLaunchKernelGGL(steps.l[k].fwd, grid, dim3(256), 0, st, c);
+      CK(hipGetLastError());
     }
-    CK(hipGetLastError());
   }
   // vecQuestions = dropout(concat of the directions' final h)   (ops.py:905-906, model.py:292)
   for (int dir = 0; dir < D; ++dir)
@@ -3307,44 +3299,30 @@ int rnn_backward(const macx_rnn_shapes* s, float keep_input, float keep_question
                         (size_t)h * sizeof(float), B, st));
   {
     const dim3 grid(h / 16, (B + 15) / 16, D);
+    const RnnSteps steps = rnn_steps(s->cell);
+    for (int k = 0; k < steps.n; ++k)
+      CK(lds_attr_once(reinterpret_cast<const void*>(steps.l[k].bwd), rnn_step_bwd_lds(h, steps.l[k].gates)));
     // the running dh / dc alternate between two buffers (a workgroup reads what its neighbours would otherwise overwrite)
     float* dhb[2] = {ws + W.dh, ws + W.dh_pass};
     float* dcb[2] = {ws + W.dc, ws + W.dc2};
-    const size_t lds = s->cell == MACX_RNN_LSTM ? lstm_step_bwd_lds(h) : rnn_step_bwd_lds(h, 1), lds2 = rnn_step_bwd_lds(h, 2);
-    if (s->cell == MACX_RNN_LSTM) CK(lds_attr_once(reinterpret_cast<const void*>(lstm_step_bwd_kernel), lds));
-    if (s->cell == MACX_RNN_BASIC) CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_BASIC>), lds));
-    if (s->cell == MACX_RNN_GRU) {
-      CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_GRU_CAND>), lds));
-      CK(lds_attr_once(reinterpret_cast<const void*>(rnn_step_bwd_kernel<RNN_GRU_GATES>), lds2));
-    }
+    const bool lstm = s->cell == MACX_RNN_LSTM;
+    RnnStepBwdP c;
+    c.B = B; c.S = S; c.h = h; c.dirs = D; c.GT = G; c.len = lengths;
+    c.hs = saved + L.hs; c.dout = d_words; c.dG = ws + W.dG; c.dZ = ws + W.dZ;
+    c.kept = s->cell != MACX_RNN_BASIC ? saved + L.gates : nullptr;
+    c.drh = s->cell == MACX_RNN_GRU ? ws + W.drh : nullptr;
+    c.cs = lstm ? saved + L.cs : nullptr;
     int cur = 0;
     for (int tau = S - 1; tau >= 0; --tau, cur ^= 1) {
-      if (s->cell == MACX_RNN_LSTM) {
-        LstmStepBwdP c;
-        c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.len = lengths;
-        c.WhT = ws + W.whT_p[0]; c.cs = saved + L.cs; c.gates = saved + L.gates; c.dout = d_words;
-        c.dh_in = dhb[cur]; c.dc_in = dcb[cur]; c.dh_out = dhb[cur ^ 1]; c.dc_out = dcb[cur ^ 1];
-        c.dG = ws + W.dG; c.dZ = ws + W.dZ;
-        hipLaunchKernelGGL(lstm_step_bwd_kernel, grid, dim3(LSB_THREADS), lds, st, c);
-      } else {
-        RnnStepBwdP c;
-        c.B = B; c.S = S; c.h = h; c.tau = tau; c.dirs = D; c.GT = G; c.len = lengths;
-        c.hs = saved + L.hs; c.dout = d_words; c.dh_in = dhb[cur]; c.dh_out = dhb[cur ^ 1]; c.dG = ws + W.dG; c.dZ = ws + W.dZ;
-        c.kept = s->cell == MACX_RNN_GRU ? saved + L.gates : nullptr;
-        c.drh = s->cell == MACX_RNN_GRU ? ws + W.drh : nullptr;
-        if (s->cell == MACX_RNN_GRU) {
-          // d(r h) of all units first: the gates' backward needs it across the workgroups' unit split
-          c.WT = ws + W.whT_p[1];
-          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_GRU_CAND>, grid, dim3(RSB_THREADS), lds, st, c);
-          CK(hipGetLastError());
-          c.WT = ws + W.whT_p[0];
-          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_GRU_GATES>, grid, dim3(RSB_THREADS), lds2, st, c);
-        } else {
-          c.WT = ws + W.whT_p[0];
-          hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_BASIC>, grid, dim3(RSB_THREADS), lds, st, c);
-        }
+      c.tau = tau;
+      c.dh_in = dhb[cur]; c.dh_out = dhb[cur ^ 1];
+      c.dc_in = lstm ? dcb[cur] : nullptr; c.dc_out = lstm ? dcb[cur ^ 1] : nullptr;
+      // last to first: the GRU's d(r h) of all units before its gates' backward, which needs it across the workgroups' unit split
+      for (int k = steps.n - 1; k >= 0; --k) {
+        c.WT = ws + W.whT_p[steps.l[k].mat];
+        hipLaunchKernelGGL(steps.l[k].bwd, grid, dim3(RSB_THREADS), rnn_step_bwd_lds(h, steps.l[k].gates), st, c);
+        CK(hipGetLastError());
       }
-      CK(hipGetLastError());
     }
   }
   for (int dir = 0; dir < D; ++dir)

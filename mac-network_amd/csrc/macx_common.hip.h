@@ -17,7 +17,7 @@ namespace macx {
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) and size: the attribute is per-device state, so
 // the cache is keyed by both (a process that drives several GPUs from one thread each must not skip the call on the second
 // device), and it is guarded for concurrent callers.  The cache holds the LARGEST size set so far: a kernel whose dynamic LDS
-// grows with the shape (lstm_step_bwd_kernel: with h) raises the attribute when a larger request arrives and never lowers it;
+// grows with the shape (rnn_step_bwd_kernel: with h) raises the attribute when a larger request arrives and never lowers it;
 // a caller with one constant size sets it once.
 inline hipError_t lds_attr_once(const void* fn, size_t bytes) {
   static std::mutex mu;

@@ -1032,283 +1032,7 @@ __global__ __launch_bounds__(256) void pad_mul_actgrad_kernel(const float* __res
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// question encoder (model.py:208-307, ops.py:749-911): embedding lookup + bidirectional
-// BasicLSTMCell(h) under tf.nn.bidirectional_dynamic_rnn semantics (per-question lengths: the state
-// is carried through and the output is zero past the end; the backward direction runs over the
-// length-reversed question).
-// ---------------------------------------------------------------------------------------------
-// x[b][s][0:E] = dropout(embeddings[idx]) with embeddings = concat([zeros(1,E), emb]) (model.py:217); columns E..Ep-1 = 0
-__global__ void embed_gather_kernel(const int32_t* __restrict__ idx, const float* __restrict__ emb, int rows, int E, int Ep, uint32_t row0,
-                                    DropSpec ds, float* x) {
-  ds = drop_resolve(ds);
-  const size_t total = (size_t)rows * Ep;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / Ep;
-    const int c = (int)(i - r * Ep);
-    float v = 0.f;
-    if (c < E) {
-      const int t = idx[r];
-      if (t > 0) v = emb[(size_t)(t - 1) * E + c];
-      v = drop_apply(v, (uint32_t)((row0 + r) * E + c), ds);
-    }
-    x[i] = v;
-  }
-}
-// BasicLSTMCell (TF1): gates i, j, f, o ; c' = c * sigmoid(f + 1) + sigmoid(i) * tanh(j) ; h' = tanh(c') * sigmoid(o)
-// ---------------------------------------------------------------------------------------------
-// One LSTM time step of both directions in ONE launch: R = h_prev Wh on fp32 MFMA, then the cell.  The two launches this
-// replaces (small_linear + lstm_cell_kernel) were ~6 us each of pure latency, 100 dependent pairs per forward pass.
-// A workgroup owns 16 questions x 16 hidden units of one direction and therefore all four gates of its units: four waves
-// split the reduction over h, an LDS combine in fixed order, then one (question, unit) per thread.
-// Grid (h / 16, ceil(B / 16), dirs).
-// ---------------------------------------------------------------------------------------------
-struct LstmStepP {
-  int B, S, h, tau, dirs;  // dirs: 1 (forward only: grid z = 1) | 2
-  const int32_t* len;      // [B]
-  const float* Wh;         // [2] packed [h/16][4][4h][4] (pack format 0)
-  const float* Zx;         // [2][B*S][4h]  x Wx + b  (all positions)
-  float* hs; float* cs;    // [2][S+1][B][h]
-  float* gates;            // [2][S][B][4h]
-  float* out;              // [B][S][dirs h]
-};
-__global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepP p) {
-  __shared__ float red[4][4][16][17];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  const int u0 = blockIdx.x * 16, r0 = blockIdx.y * 16, dir = blockIdx.z;
-  const int h = p.h, G = 4 * h;
-  const size_t Bh = (size_t)p.B * h;
-  const float* hp = p.hs + (size_t)(dir * (p.S + 1) + p.tau) * Bh;
-  const float* Wd = p.Wh + (size_t)dir * h * G;
-  const int rowc = min(r0 + li, p.B - 1);
-  f32x4 acc[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nQ = h >> 4;
-  constexpr int PF = 4;                     // k groups in flight per wave (h = 256: the wave's whole share)
-  // what the cell needs behind the product -- this thread's (question, unit): length, previous state, the input projection's
-  // four gate columns -- is requested BEFORE the product, so that its round trip does not start behind the barrier
-  const int crow = tid >> 4, cuu = tid & 15;
-  const int cb = min(r0 + crow, p.B - 1), cu = u0 + cuu;
-  const int cL = min(max(p.len[cb], 0), p.S);      // never index past the padded question (host validates too)
-  const int cpos = dir == 0 ? p.tau : max(cL - 1 - p.tau, 0);
-  const size_t cs0 = (size_t)(dir * (p.S + 1) + p.tau) * Bh + (size_t)cb * h + cu;
-  const float hpv_pre = p.hs[cs0], cp_pre = p.cs[cs0];
-  const float* Zpre = p.Zx + ((size_t)dir * p.B * p.S + (size_t)cb * p.S + cpos) * G;
-  const float z0 = Zpre[cu], z1 = Zpre[h + cu], z2 = Zpre[2 * h + cu], z3 = Zpre[3 * h + cu];
-  for (int Q0 = wave; Q0 < nQ; Q0 += 4 * PF) {
-    f32x4 af[PF], bf[PF][4];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int Q = min(Q0 + 4 * u, nQ - 1);
-      af[u] = *reinterpret_cast<const f32x4*>(hp + (size_t)rowc * h + Q * 16 + lg * 4);
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        bf[u][g] = *reinterpret_cast<const f32x4*>(Wd + ((size_t)(Q * 4 + lg) * G + g * h + u0 + li) * 4);
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-      if (Q0 + 4 * u < nQ) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][e], bf[u][g][e], acc[g], 0, 0, 0);
-      }
-  }
-  // accumulator map: unit = lane & 15, question = (lane >> 4) * 4 + e
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) red[wave][g][lg * 4 + e][li] = acc[g][e];
-  __syncthreads();
-  const int row = tid >> 4, uu = tid & 15;
-  const int b = r0 + row, u = u0 + uu;
-  if (b >= p.B) return;
-  float R[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) R[g] = ((red[0][g][row][uu] + red[1][g][row][uu]) + red[2][g][row][uu]) + red[3][g][row][uu];
-  const int L = cL;
-  const bool active = p.tau < L;
-  const int pos = cpos;
-  const size_t s0 = cs0, s1 = s0 + Bh;
-  const float hpv = hpv_pre, cp = cp_pre;
-  float hn = hpv, cn = cp;
-  float gi = 0.f, gj = 0.f, gf = 0.f, go = 0.f;
-  if (active) {
-    gi = 1.0f / (1.0f + expf(-(R[0] + z0)));
-    gj = tanhf(R[1] + z1);
-    gf = 1.0f / (1.0f + expf(-(R[2] + z2 + 1.0f)));
-    go = 1.0f / (1.0f + expf(-(R[3] + z3)));
-    cn = cp * gf + gi * gj;
-    hn = tanhf(cn) * go;
-    p.out[((size_t)b * p.S + pos) * p.dirs * h + dir * h + u] = hn;
-  }
-  p.hs[s1] = hn;
-  p.cs[s1] = cn;
-  float* gp = p.gates + ((size_t)(dir * p.S + p.tau) * p.B + b) * G;
-  gp[u] = gi; gp[h + u] = gj; gp[2 * h + u] = gf; gp[3 * h + u] = go;
-}
-
-// The backward step likewise: gate gradients of the workgroup's 16 questions (all 4h columns, recomputed by each of the h / 16
-// workgroups that share the questions -- elementwise work, cheaper than a launch), then dh_prev = dG Wh^T for the workgroup's
-// 16 units from the LDS tile.  The running dh / dc are double-buffered by the parity of tau (a workgroup reads what its
-// neighbours would otherwise be overwriting); the workgroup with blockIdx.x == 0 writes dc, dG and dZ.
-struct LstmStepBwdP {
-  int B, S, h, tau, dirs;
-  const int32_t* len;
-  const float* WhT;        // [2] packed [4h/16][4][h][4] (pack format 0 of Wh^T)
-  const float* cs;         // [2][S+1][B][h]
-  const float* gates;      // [2][S][B][4h]
-  const float* dout;       // [B][S][dirs h]
-  const float* dh_in; const float* dc_in;     // [2][B][h] running state gradients after step tau + 1
-  float* dh_out; float* dc_out;               // ... after this step
-  float* dG;               // [2][S][B][4h]
-  float* dZ;               // [2][B*S][4h] (zero-initialised)
-};
-constexpr int LSB_THREADS = 1024;      // 16 waves: the elementwise part is h / 64 (question, unit) pairs per thread, the product 4 k groups per wave at h = 256
-__global__ __launch_bounds__(LSB_THREADS) void lstm_step_bwd_kernel(LstmStepBwdP p) {
-  extern __shared__ __attribute__((aligned(16))) float lsm[];
-  const int h = p.h, G = 4 * h;
-  float* sG = lsm;                          // [16][G + 4] gate gradients of the workgroup's questions
-  float* sPass = sG + 16 * (G + 4);         // [16][16] dh that bypasses the recurrent product (questions that have ended)
-  float* red = sPass + 256;                 // [16 waves][16][17]
-  const int ldg = G + 4;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  const int u0 = blockIdx.x * 16, r0 = blockIdx.y * 16, dir = blockIdx.z;
-  const size_t Bh = (size_t)p.B * h;
-  // the recurrent weights of this wave's k groups first: their L2 round trip runs under the cell's backward instead of
-  // behind the barrier (the launch is latency, 100 of them in a row)
-  const float* Wd = p.WhT + (size_t)dir * G * h;
-  const int nQ = G >> 4;
-  constexpr int PF = 4, NW = LSB_THREADS / 64;
-  f32x4 bf0[PF];
-#pragma unroll
-  for (int u = 0; u < PF; ++u) bf0[u] = *reinterpret_cast<const f32x4*>(Wd + ((size_t)(min(wave + NW * u, nQ - 1) * 4 + lg) * h + u0 + li) * 4);
-  // ---- the cell's backward for 16 questions x h units.  Every workgroup of a question block computes all of it (its
-  //      product needs all 4h gate gradients) and WRITES the columns of its own 16 units: dc, dG, dZ
-#pragma unroll 4
-  for (int it = tid; it < 16 * h; it += LSB_THREADS) {
-    const int row = it / h, u = it - row * h;
-    const int b = r0 + row;
-    float di = 0.f, dj = 0.f, df = 0.f, dO = 0.f, pass = 0.f, dc = 0.f;
-    if (b < p.B) {
-      const size_t i = (size_t)dir * Bh + (size_t)b * h + u;
-      const int L = min(max(p.len[b], 0), p.S);
-      const bool active = p.tau < L;
-      const int pos = dir == 0 ? p.tau : L - 1 - p.tau;
-      float dh = p.dh_in[i];
-      dc = p.dc_in[i];
-      pass = dh;
-      if (active) {
-        const float* ga = p.gates + ((size_t)(dir * p.S + p.tau) * p.B + b) * G;
-        const float gi = ga[u], gj = ga[h + u], gf = ga[2 * h + u], go = ga[3 * h + u];
-        const size_t r = (size_t)b * h + u;
-        const float cp = p.cs[(size_t)(dir * (p.S + 1) + p.tau) * Bh + r];
-        const float cn = p.cs[(size_t)(dir * (p.S + 1) + p.tau + 1) * Bh + r];
-        dh += p.dout[((size_t)b * p.S + pos) * p.dirs * h + dir * h + u];
-        const float tc = tanhf(cn);
-        dO = dh * tc * go * (1.0f - go);
-        const float dct = dc + dh * go * (1.0f - tc * tc);
-        di = dct * gj * gi * (1.0f - gi);
-        dj = dct * gi * (1.0f - gj * gj);
-        df = dct * cp * gf * (1.0f - gf);
-        dc = dct * gf;
-        pass = 0.f;
-        if (u >= u0 && u < u0 + 16) {
-          float* z = p.dZ + ((size_t)dir * p.B * p.S + (size_t)b * p.S + pos) * G;
-          z[u] = di; z[h + u] = dj; z[2 * h + u] = df; z[3 * h + u] = dO;
-        }
-      }
-      if (u >= u0 && u < u0 + 16) {
-        float* g = p.dG + ((size_t)(dir * p.S + p.tau) * p.B + b) * G;
-        g[u] = di; g[h + u] = dj; g[2 * h + u] = df; g[3 * h + u] = dO;
-        p.dc_out[i] = dc;
-      }
-    }
-    float* sg = sG + row * ldg;
-    sg[u] = di; sg[h + u] = dj; sg[2 * h + u] = df; sg[3 * h + u] = dO;
-    if (u >= u0 && u < u0 + 16) sPass[row * 16 + (u - u0)] = pass;
-  }
-  __syncthreads();
-  // ---- dh_prev[16 questions][16 units] = dG[16][4h] WhT[4h][units]
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int Q0 = wave; Q0 < nQ; Q0 += NW * PF) {
-    f32x4 af[PF], bf[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int Q = min(Q0 + NW * u, nQ - 1);
-      af[u] = *reinterpret_cast<const f32x4*>(sG + li * ldg + Q * 16 + lg * 4);
-      bf[u] = Q0 == wave ? bf0[u] : *reinterpret_cast<const f32x4*>(Wd + ((size_t)(Q * 4 + lg) * h + u0 + li) * 4);
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-      if (Q0 + NW * u < nQ) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][e], bf[u][e], acc, 0, 0, 0);
-      }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[(wave * 16 + lg * 4 + e) * 17 + li] = acc[e];
-  __syncthreads();
-  if (tid >= 256) return;
-  const int row = tid >> 4, uu = tid & 15;
-  const int b = r0 + row;
-  if (b >= p.B) return;
-  float v = red[row * 17 + uu];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) v += red[(w * 16 + row) * 17 + uu];        // fixed order
-  p.dh_out[(size_t)dir * Bh + (size_t)b * h + u0 + uu] = v + sPass[row * 16 + uu];
-}
-inline size_t lstm_step_bwd_lds(int h) { return ((size_t)16 * (4 * h + 4) + 256 + (LSB_THREADS / 64) * 16 * 17) * sizeof(float); }
-
-// d emb[v-1][c] = sum over tokens == v of dropmask * dx[r][c]   (one workgroup per vocabulary row: no atomics).
-// The rows that hold token v are found 256 at a time by all threads (ballot + ordered compaction into LDS), then summed in
-// ascending row order: the scan is rows / 256 short passes instead of `rows` sequential compares per thread.
-__global__ __launch_bounds__(256) void embed_grad_kernel(const int32_t* __restrict__ idx, const float* __restrict__ dx, int rows, int E, int Ep,
-                                                        uint32_t row0, DropSpec ds, float* demb) {
-  ds = drop_resolve(ds);
-  __shared__ int list[256];
-  __shared__ int wcount[4];
-  const int v = blockIdx.x + 1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  constexpr int CMAX = 4;                           // columns per thread held in registers: blockIdx.y selects a chunk of 1024 columns
-  const int c0 = blockIdx.y * 1024;
-  float acc[CMAX];
-#pragma unroll
-  for (int k = 0; k < CMAX; ++k) acc[k] = 0.f;
-  for (int r0 = 0; r0 < rows; r0 += 256) {
-    const int r = r0 + tid;
-    const bool m = r < rows && idx[r] == v;
-    const unsigned long long mask = __ballot(m);
-    const int before = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[wave] = __popcll(mask);
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { base += w < wave ? wcount[w] : 0; total += wcount[w]; }
-    if (m) list[base + before] = r;
-    __syncthreads();
-    for (int k = 0; k < total; ++k) {                // ascending rows
-      const int rr = list[k];
-#pragma unroll
-      for (int j = 0; j < CMAX; ++j) {
-        const int c = c0 + tid + 256 * j;
-        if (c < E) acc[j] += drop_apply(dx[(size_t)rr * Ep + c], (uint32_t)((row0 + rr) * E + c), ds);
-      }
-    }
-    __syncthreads();                                 // list / wcount are rewritten by the next pass
-  }
-#pragma unroll
-  for (int j = 0; j < CMAX; ++j) {
-    const int c = c0 + tid + 256 * j;
-    if (c < E) demb[(size_t)(v - 1) * E + c] = acc[j];
-  }
-}
-
+// the output unit's bias over [rows][n]
 __global__ void add_bias_kernel(const float* __restrict__ bias, int rows, int n, float* x) {
   const int t = rows * n;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < t; i += gridDim.x * blockDim.x) x[i] += bias[i % n];

@@ -52,7 +52,84 @@ def check_questions(questions, lengths, vocab, check_ids):
             raise ValueError("question length outside [0, %d]" % questions.shape[1])
 
 
-class QuestionEncoder(unit.FusedUnit):
+RNN_CELLS = {"RNN": ("basic_rnn_cell", 1), "GRU": ("gru_cell", 2), "LSTM": ("basic_lstm_cell", 4)}   # scope, width of `kernel` / h
+
+
+def _cell_matrices(cell, k):
+    """(scope part, field prefix, width / h, bias initial value) of a cell's matrices in TF's creation order"""
+    if cell == "GRU":
+        return (("gates/", "", 2, 1.0), ("candidate/", "candidate_", 1, 0.0))
+    return (("", "", k, 0.0),)
+
+
+class _FusedRecurrentEncoder(unit.FusedUnit):
+    """The body QuestionEncoder and RecurrentQuestionEncoder share: the embedding, a cell's matrices per direction under the
+    reference's names, and the one pair of ABI calls around them.  A class built on it names its ABI and says, in _shapes, how its
+    shapes struct is filled (MacxEncShapes has no cell / dirs fields)."""
+
+    def _declare(self, config, vocab, embInit, generator, cell, bi):
+        """emb, then per direction the cell's matrices: registered, and drawn from the generator, in that order (a bias draws
+        nothing).  Returns the fields in ABI order and their reference names."""
+        g = lambda n, dflt: getattr(config, n, dflt)
+        self.cell, self.bi, self.dirs = cell, bi, 2 if bi else 1
+        self.vocab, self.E, self.h = int(vocab), int(g("wrdEmbDim", 300)), int(g("encDim", 512)) // self.dirs
+        self.keep_in, self.keep_q = float(g("encInputDropout", 0.85)), float(g("qDropout", 0.92))
+        E, h = self.E, self.h
+        if embInit is None:
+            emb = torch.randn((self.vocab, E), generator=generator, dtype=torch.float64)
+        else:
+            emb = torch.as_tensor(embInit, dtype=torch.float64)
+            if tuple(emb.shape) != (self.vocab, E):
+                raise ValueError("embInit must be [%d, %d]" % (self.vocab, E))
+        self.emb = torch.nn.Parameter(emb.float(), requires_grad=not g("wrdEmbFixed", False))
+        scope, k = RNN_CELLS[cell]
+        fields, names = ["emb"], {"emb": "qEmbeddings/emb"}
+        for d in ("fw", "bw")[:self.dirs]:
+            base = "encoder/%s/%s" % ("birnnLayer/bidirectional_rnn/" + d if bi else "rnnLayer/rnn", scope)
+            # TF's creation order: the GRU's gates before its candidate; glorot_uniform over the whole [in + n, k n] matrix
+            for part, prefix, width, bias in _cell_matrices(cell, k):
+                kern = unit.xavier_uniform((E + h, width * h), E + h + width * h, generator)
+                for f, t in (("%s_%skernel" % (d, prefix), kern), ("%s_%sbias" % (d, prefix), torch.full((width * h,), bias))):
+                    self.register_parameter(f, torch.nn.Parameter(t))
+                    fields.append(f)
+                    names[f] = "%s/%s%s" % (base, part, f.rsplit("_", 1)[1])
+        return tuple(fields), names
+
+    def embed(self, questions):
+        """embeddingsOp's `questionWords` (model.py:207-219, 783): the embedded question words [B,S,wrdEmbDim] WITHOUT the encoder's
+        input dropout -- what the cell attends over when --controlContextual is off (mac_cell.py:570)."""
+        B, S = questions.shape
+        return generic._Embed.apply(questions, self.emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
+
+    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
+        """questions [B,S] int32 (0 = pad), lengths [B] int32 -> (questionCntxWords [B,S,dirs h], vecQuestions [B,dirs h]).
+        mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's): XORed into the keys of the input
+        and the question dropout when the kernels run, so that one captured graph draws fresh masks per replay."""
+        unit.require_device(questions, "the question encoder")
+        questions = questions.to(torch.int32).contiguous()
+        lengths = lengths.to(device=questions.device, dtype=torch.int32).contiguous()
+        check_questions(questions, lengths, self.vocab, check_ids)
+        B, S = questions.shape
+        keeps = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
+        return self._call(self._shapes(B, S, int(b0)), keeps, seed, train, mask_word, questions, lengths)
+
+    def _outputs(self, sh, inputs):
+        dev = inputs[0].device
+        words = torch.empty(sh.B, sh.S, self.dirs * sh.h, dtype=torch.float32, device=dev)
+        vecQ = torch.empty(sh.B, self.dirs * sh.h, dtype=torch.float32, device=dev)
+        return (words, vecQ), inputs
+
+    def _backward(self, sh, X, d_outs):
+        # an output nothing was computed from has no gradient: the kernels read zeros there
+        shapes = ((sh.B, sh.S, self.dirs * sh.h), (sh.B, self.dirs * sh.h))
+        d = tuple(torch.zeros(s, dtype=torch.float32, device=X[0].device) if g is None else g.contiguous() for s, g in zip(shapes, d_outs))
+        return d, (), (None, None)
+
+    def _param_grads(self, grads):
+        return [grads[0] if self.emb.requires_grad else None] + grads[1:]
+
+
+class QuestionEncoder(_FusedRecurrentEncoder):
     """Mirrors `MACnet.embeddingsOp` + `MACnet.encoder` for the configuration every flag file uses
     (encType LSTM, --encBi, encNumLayers 1, encDim == ctrlDim so no projections) on the fused kernels.  Constructing it for
     another LSTM configuration -- no --encBi (the parser's default), --encProj, encDim != ctrlDim -- returns a
@@ -64,59 +141,11 @@ class QuestionEncoder(unit.FusedUnit):
 
     def __init__(self, config, vocab, embInit=None, generator=None):
         super().__init__()
-        g = lambda n, dflt: getattr(config, n, dflt)
         _check_fused(config)
-        self.vocab, self.E, self.h = int(vocab), int(g("wrdEmbDim", 300)), int(g("encDim", 512)) // 2
-        self.keep_in, self.keep_q = float(g("encInputDropout", 0.85)), float(g("qDropout", 0.92))
-        E, h = self.E, self.h
-        if embInit is None:
-            emb = torch.randn((self.vocab, E), generator=generator, dtype=torch.float64)
-        else:
-            emb = torch.as_tensor(embInit, dtype=torch.float64)
-            if tuple(emb.shape) != (self.vocab, E):
-                raise ValueError("embInit must be [%d, %d]" % (self.vocab, E))
-        self.emb = torch.nn.Parameter(emb.float(), requires_grad=not g("wrdEmbFixed", False))
-        for d in ("fw", "bw"):
-            k = unit.xavier_uniform((E + h, 4 * h), E + h + 4 * h, generator)      # glorot_uniform over [E+h, 4h]
-            self.register_parameter(d + "_kernel", torch.nn.Parameter(k))
-            self.register_parameter(d + "_bias", torch.nn.Parameter(torch.zeros(4 * h)))
+        self._declare(config, vocab, embInit, generator, "LSTM", True)
 
-    def embed(self, questions):
-        """embeddingsOp's `questionWords` (model.py:207-219, 783): the embedded question words [B,S,wrdEmbDim] WITHOUT the encoder's
-        input dropout -- what the cell attends over when --controlContextual is off (mac_cell.py:570)."""
-        B, S = questions.shape
-        return generic._Embed.apply(questions, self.emb, self.E, 1.0, 0, 0).reshape(B, S, self.E)
-
-    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
-        """questions [B,S] int32 (0 = pad), lengths [B] int32 -> (questionCntxWords [B,S,2h], vecQuestions [B,2h]).
-        mask_word: None, or the run's mask word (1-element int32 device tensor, as MACCell's): XORed into the keys of the input
-        and the question dropout when the kernels run, so that one captured graph draws fresh masks per replay."""
-        unit.require_device(questions, "the question encoder")
-        questions = questions.to(torch.int32).contiguous()
-        lengths = lengths.to(device=questions.device, dtype=torch.int32).contiguous()
-        check_questions(questions, lengths, self.vocab, check_ids)
-        B, S = questions.shape
-        sh = self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=int(b0))
-        keeps = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
-        return self._call(sh, keeps, seed, train, mask_word, questions, lengths)
-
-    def _outputs(self, sh, inputs):
-        dev = inputs[0].device
-        words = torch.empty(sh.B, sh.S, 2 * sh.h, dtype=torch.float32, device=dev)
-        vecQ = torch.empty(sh.B, 2 * sh.h, dtype=torch.float32, device=dev)
-        return (words, vecQ), inputs
-
-    def _backward(self, sh, X, d_outs):
-        # an output nothing was computed from has no gradient: the kernels read zeros there
-        shapes = ((sh.B, sh.S, 2 * sh.h), (sh.B, 2 * sh.h))
-        d = tuple(torch.zeros(s, dtype=torch.float32, device=X[0].device) if g is None else g.contiguous() for s, g in zip(shapes, d_outs))
-        return d, (), (None, None)
-
-    def _param_grads(self, grads):
-        return [grads[0] if self.emb.requires_grad else None] + grads[1:]
-
-
-RNN_CELLS = {"RNN": ("basic_rnn_cell", 1), "GRU": ("gru_cell", 2), "LSTM": ("basic_lstm_cell", 4)}   # scope, width of `kernel` / h
+    def _shapes(self, B, S, b0):
+        return self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=b0)
 
 
 def _check_recurrent(config):
@@ -150,7 +179,7 @@ def _check_recurrent(config):
                                  "per direction (macx_rnn_shapes, include/macx.h)" % FUSED_H_MAX)
 
 
-class RecurrentQuestionEncoder(unit.FusedUnit):
+class RecurrentQuestionEncoder(_FusedRecurrentEncoder):
     """qEmbeddingsOp + encoder (model.py:207-219, 279-307 -> ops.RNNLayer, ops.py:798-952) for every cell ops.createCell builds
     with an activation -- encType RNN (BasicRNNCell), GRU (GRUCell), LSTM (BasicLSTMCell) -- in one direction (no --encBi:
     tf.nn.dynamic_rnn, h = encDim) or two (h = encDim/2), on fused kernels: macx_rnn_encoder_forward_w / _backward_w, one launch
@@ -170,35 +199,10 @@ class RecurrentQuestionEncoder(unit.FusedUnit):
         return torch.nn.Module.__new__(cls)               # (no generic twin to fall back to: a refused option set raises)
 
     def __init__(self, config, vocab, embInit=None, generator=None):
-        torch.nn.Module.__init__(self)
-        g = lambda n, dflt: getattr(config, n, dflt)
+        super().__init__()
         _check_recurrent(config)
-        self.cell, self.bi = g("encType", "LSTM"), bool(g("encBi", False))
-        self.dirs = 2 if self.bi else 1
-        self.vocab, self.E, self.h = int(vocab), int(g("wrdEmbDim", 300)), int(g("encDim", 512)) // self.dirs
-        self.keep_in, self.keep_q = float(g("encInputDropout", 0.85)), float(g("qDropout", 0.92))
-        E, h = self.E, self.h
-        if embInit is None:
-            emb = torch.randn((self.vocab, E), generator=generator, dtype=torch.float64)
-        else:
-            emb = torch.as_tensor(embInit, dtype=torch.float64)
-            if tuple(emb.shape) != (self.vocab, E):
-                raise ValueError("embInit must be [%d, %d]" % (self.vocab, E))
-        self.emb = torch.nn.Parameter(emb.float(), requires_grad=not g("wrdEmbFixed", False))
-        scope, k = RNN_CELLS[self.cell]
-        fields, names = ["emb"], {"emb": "qEmbeddings/emb"}
-        for d in ("fw", "bw")[:self.dirs]:
-            base = "encoder/%s/%s" % ("birnnLayer/bidirectional_rnn/" + d if self.bi else "rnnLayer/rnn", scope)
-            # TF's creation order: the GRU's gates before its candidate; glorot_uniform over the whole [in + n, k n] matrix
-            for part, prefix, width, bias in _cell_matrices(self.cell, k):
-                kern = unit.xavier_uniform((E + h, width * h), E + h + width * h, generator)
-                for f, t in (("%s_%skernel" % (d, prefix), kern), ("%s_%sbias" % (d, prefix), torch.full((width * h,), bias))):
-                    self.register_parameter(f, torch.nn.Parameter(t))
-                    fields.append(f)
-                    names[f] = "%s/%s%s" % (base, part, f.rsplit("_", 1)[1])
-        self.FIELDS, self.REF_NAMES = tuple(fields), names
-
-    embed, _param_grads = QuestionEncoder.embed, QuestionEncoder._param_grads
+        self.FIELDS, self.REF_NAMES = self._declare(config, vocab, embInit, generator, getattr(config, "encType", "LSTM"),
+                                                    bool(getattr(config, "encBi", False)))
 
     def _struct(self, cls, ptrs):
         return cls(**dict(zip(self.FIELDS, ptrs)))        # (the pointers this cell does not have stay NULL)
@@ -209,34 +213,8 @@ class RecurrentQuestionEncoder(unit.FusedUnit):
     def GRADS(self, *ptrs):
         return self._struct(_lib.MacxRnnGrads, ptrs)
 
-    def forward(self, questions, lengths, train=False, seed=None, b0=0, check_ids=True, mask_word=None):
-        """QuestionEncoder.forward's arguments -> (questionCntxWords [B,S,dirs h], vecQuestions [B,dirs h])"""
-        unit.require_device(questions, "the question encoder")
-        questions = questions.to(torch.int32).contiguous()
-        lengths = lengths.to(device=questions.device, dtype=torch.int32).contiguous()
-        check_questions(questions, lengths, self.vocab, check_ids)
-        B, S = questions.shape
-        sh = self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=int(b0), cell=_lib.RNN_CELL[self.cell], dirs=self.dirs)
-        keeps = (self.keep_in, self.keep_q) if train else (1.0, 1.0)
-        return self._call(sh, keeps, seed, train, mask_word, questions, lengths)
-
-    def _outputs(self, sh, inputs):
-        dev = inputs[0].device
-        words = torch.empty(sh.B, sh.S, sh.dirs * sh.h, dtype=torch.float32, device=dev)
-        vecQ = torch.empty(sh.B, sh.dirs * sh.h, dtype=torch.float32, device=dev)
-        return (words, vecQ), inputs
-
-    def _backward(self, sh, X, d_outs):
-        shapes = ((sh.B, sh.S, sh.dirs * sh.h), (sh.B, sh.dirs * sh.h))
-        d = tuple(torch.zeros(s, dtype=torch.float32, device=X[0].device) if g is None else g.contiguous() for s, g in zip(shapes, d_outs))
-        return d, (), (None, None)
-
-
-def _cell_matrices(cell, k):
-    """(scope part, field prefix, width / h, bias initial value) of a cell's matrices in TF's creation order"""
-    if cell == "GRU":
-        return (("gates/", "", 2, 1.0), ("candidate/", "candidate_", 1, 0.0))
-    return (("", "", k, 0.0),)
+    def _shapes(self, B, S, b0):
+        return self.SHAPES(B=B, S=S, V=self.vocab, E=self.E, h=self.h, b0=b0, cell=_lib.RNN_CELL[self.cell], dirs=self.dirs)
 
 
 class GenericQuestionEncoder(generic.ParamsUnit, torch.nn.Module):

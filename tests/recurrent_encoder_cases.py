@@ -1,5 +1,5 @@
-"""The recurrent question encoder (rnn_step_kernel<MODE> / rnn_step_bwd_kernel<MODE> of mac-network_amd/csrc/macx_rnn.hip.h, the two LSTM
-step kernels of macx_small.hip.h, and the host sequence rnn_forward / rnn_backward of macx_api.hip) at its block, width and length
+"""The recurrent question encoder (rnn_step_kernel<MODE> / rnn_step_bwd_kernel<MODE> of mac-network_amd/csrc/macx_rnn.hip.h, every cell's
+step, and the host sequence rnn_forward / rnn_backward of macx_api.hip) at its block, width and length
 edges: case table, data, reference, metrics, log.  No device, and nothing of the product is imported here (the callers hand `macx` in).
 
 Shared by tests/test_gpu_recurrent_encoder_edges.py (the kernels) and tests/test_recurrent_encoder_cases_host.py (CPU: the metrics

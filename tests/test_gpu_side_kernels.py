@@ -1,7 +1,7 @@
 """-m gpu: the kernels AROUND the cell past their first block and first pass -- what bench.py's model-level number and
 CapturedTowerTrainStep run at B = 64 and no other test holds against a reference:
 
-* the question encoder's step kernels (lstm_step_kernel / lstm_step_bwd_kernel) against the fp64 oracle over 1 - 4 question blocks
+* the question encoder's step kernels (rnn_step_kernel<RNN_LSTM> / rnn_step_bwd_kernel<RNN_LSTM>) against the fp64 oracle over 1 - 4 question blocks
   (a workgroup owns 16 questions), ragged last blocks, questions of length 0, and the widths h = 384 / 512 at which the K loops
   take a second pass (forward: 16 k-groups per pass of h / 16; backward: 64 of h / 4, the later ones loaded from global memory);
 * macx_adam_ema_step per element (p, m, v, ema and the norm) against a numpy fp64 evaluation of the header's formulas, over the

@@ -241,37 +241,49 @@ def test_the_grid_rules_still_read_as_restated():
     rnn = flat(open(os.path.join(CSRC, "macx_rnn.hip.h")).read())
     small = flat(open(os.path.join(CSRC, "macx_small.hip.h")).read())
     api = flat(open(os.path.join(CSRC, "macx_api.hip")).read())
-    lstm = small[small.index("struct LstmStepP {"): small.index("inline size_t lstm_step_bwd_lds(int h)") + 200]
-    for text, n in ((rnn, 2), (lstm, 2)):
-        assert text.count("const int u0 = blockIdx.x * 16, r0 = blockIdx.y * 16, dir = blockIdx.z;") == n
-        assert text.count("const int rowc = min(r0 + li, p.B - 1);") == 1
-        # forward: four waves, PF groups each per pass
-        assert text.count("constexpr int PF = 4;") == 1 and text.count("const int nQ = h >> 4;") == 1
-        assert text.count("for (int Q0 = wave; Q0 < nQ; Q0 += 4 * PF) {") == 1
-        assert text.count("const int Q = min(Q0 + 4 * u, nQ - 1);") == 1 and text.count("if (Q0 + 4 * u < nQ) {") == 1
-        # backward: NW waves, PF groups each per pass
-        assert text.count("const int nQ = G >> 4;") == 1 and text.count("for (int Q0 = wave; Q0 < nQ; Q0 += NW * PF) {") == 1
-        assert text.count("const int Q = min(Q0 + NW * u, nQ - 1);") == 1 and text.count("if (Q0 + NW * u < nQ) {") == 1
-        # the clamp of a length
-        assert text.count("const int cL = min(max(p.len[cb], 0), p.S);") == 1 and text.count("const int L = min(max(p.len[b], 0), p.S);") == 1
-        assert text.count("const int cpos = dir == 0 ? p.tau : max(cL - 1 - p.tau, 0);") == 1
-        assert text.count("const int pos = dir == 0 ? p.tau : L - 1 - p.tau;") == 1
+    # one template pair for every cell: each rule stands once per kernel, in the encoder's header and nowhere else
+    once = ("const int rowc = min(r0 + li, p.B - 1);",
+            # forward: four waves, PF groups each per pass
+            "constexpr int PF = 4;", "const int nQ = h >> 4;", "for (int Q0 = wave; Q0 < nQ; Q0 += 4 * PF) {",
+            "const int Q = min(Q0 + 4 * u, nQ - 1);", "if (Q0 + 4 * u < nQ) {",
+            # backward: NW waves, PF groups each per pass
+            "const int nQ = G >> 4;", "for (int Q0 = wave; Q0 < nQ; Q0 += NW * PF) {",
+            "const int Q = min(Q0 + NW * u, nQ - 1);", "if (Q0 + NW * u < nQ) {",
+            # the clamp of a length
+            "const int cL = min(max(p.len[cb], 0), p.S);", "const int L = min(max(p.len[b], 0), p.S);",
+            "const int cpos = dir == 0 ? p.tau : max(cL - 1 - p.tau, 0);", "const int pos = dir == 0 ? p.tau : L - 1 - p.tau;")
+    twice = ("const int u0 = blockIdx.x * 16, r0 = blockIdx.y * 16, dir = blockIdx.z;", "const int h = p.h, G = NG * h, GT = p.GT;",
+             "constexpr int NG = rnn_mode_gates(MODE);")
+    for rule in once:
+        assert rnn.count(rule) == 1 and small.count(rule) == 0, rule
+    for rule in twice:
+        assert rnn.count(rule) == 2 and small.count(rule) == 0, rule
+    assert rnn.count("template <int MODE> __global__") == 2 and rnn.count("__global__") == 4        # (and the two embedding kernels)
     assert "constexpr int RSB_THREADS = %d;" % rc.RSB_THREADS in rnn and "constexpr int PF = %d, NW = RSB_THREADS / 64;" % rc.PF in rnn
-    assert "constexpr int LSB_THREADS = %d;" % rc.RSB_THREADS in small and "constexpr int PF = %d, NW = LSB_THREADS / 64;" % rc.PF in lstm
-    assert "constexpr int rnn_mode_gates(int mode) { return mode == RNN_GRU_GATES ? 2 : 1; }" in rnn and "const int h = p.h, G = 4 * h;" in lstm
+    assert "enum { RNN_BASIC = 0, RNN_GRU_GATES = 1, RNN_GRU_CAND = 2, RNN_LSTM = 3 };" in rnn
+    assert "constexpr int rnn_mode_gates(int mode) { return mode == RNN_LSTM ? 4 : mode == RNN_GRU_GATES ? 2 : 1; }" in rnn
+    assert rc.NG == {"RNN": (1,), "GRU": (1, 2), "LSTM": (4,)}
     assert ("inline size_t rnn_step_bwd_lds(int h, int gates) { return ((size_t)16 * (gates * h + 4) + 256 + (RSB_THREADS / 64) * 16 * 17) "
-            "* sizeof(float); }") in rnn
-    assert "inline size_t lstm_step_bwd_lds(int h) { return ((size_t)16 * (4 * h + 4) + 256 + (LSB_THREADS / 64) * 16 * 17) * sizeof(float); }" in small
+            "* sizeof(float); }") in rnn and (rnn + small + api).count("_step_bwd_lds(int h") == 1
     assert "hp = MODE == RNN_GRU_CAND ? p.rh + (size_t)(dir * p.S + p.tau) * Bh : p.hs + (size_t)(dir * (p.S + 1) + p.tau) * Bh;" in rnn
-    # the host sequence: one grid for every launch, the dh pair toggled once per step, the LDS request of each MODE
+    # which instantiations a cell launches, in the forward pass's order; an instantiation's gate count is its MODE's
+    assert ("template <int MODE> constexpr RnnLaunch rnn_launch(int mat) { return {rnn_step_kernel<MODE>, rnn_step_bwd_kernel<MODE>, mat, "
+            "rnn_mode_gates(MODE)}; }") in rnn
+    assert "case MACX_RNN_GRU: return {2, {rnn_launch<RNN_GRU_GATES>(0), rnn_launch<RNN_GRU_CAND>(1)}};" in rnn
+    assert "case MACX_RNN_LSTM: return {1, {rnn_launch<RNN_LSTM>(0), {}}};" in rnn and "default: return {1, {rnn_launch<RNN_BASIC>(0), {}}};" in rnn
+    # the host sequence: one grid for every launch, the dh pair toggled once per step, the LDS request of each MODE from the one formula
     seq = api[api.index("int rnn_forward(const macx_rnn_shapes* s"): api.index("inline macx_rnn_shapes enc_as_rnn(")]
     assert seq.count("const dim3 grid(h / 16, (B + 15) / 16, D);") == 2
     assert seq.count("for (int tau = S - 1; tau >= 0; --tau, cur ^= 1) {") == 1 and seq.count("for (int tau = 0; tau < S; ++tau) {") == 1
-    assert seq.count("c.dh_in = dhb[cur]; c.dh_out = dhb[cur ^ 1];") == 1 and "c.dh_in = dhb[cur]; c.dc_in = dcb[cur]; c.dh_out = dhb[cur ^ 1];" in seq
-    assert "lds = s->cell == MACX_RNN_LSTM ? lstm_step_bwd_lds(h) : rnn_step_bwd_lds(h, 1), lds2 = rnn_step_bwd_lds(h, 2);" in seq
-    assert "hipLaunchKernelGGL(rnn_step_bwd_kernel<RNN_GRU_GATES>, grid, dim3(RSB_THREADS), lds2, st, c);" in seq
+    assert seq.count("c.dh_in = dhb[cur]; c.dh_out = dhb[cur ^ 1];") == 1
+    assert seq.count("c.dc_in = lstm ? dcb[cur] : nullptr; c.dc_out = lstm ? dcb[cur ^ 1] : nullptr;") == 1
+    assert seq.count("hipLaunchKernelGGL(") - seq.count("hipLaunchKernelGGL(drop2_kernel") - seq.count("hipLaunchKernelGGL(embed_") == 2
+    assert "for (int k = 0; k < steps.n; ++k) { c.Wh = saved + L.wh_p[steps.l[k].mat]; hipLaunchKernelGGL(steps.l[k].fwd, grid, dim3(256), 0, st, c);" in seq
+    assert ("for (int k = steps.n - 1; k >= 0; --k) { c.WT = ws + W.whT_p[steps.l[k].mat]; hipLaunchKernelGGL(steps.l[k].bwd, grid, "
+            "dim3(RSB_THREADS), rnn_step_bwd_lds(h, steps.l[k].gates), st, c);") in seq
+    assert "CK(lds_attr_once(reinterpret_cast<const void*>(steps.l[k].bwd), rnn_step_bwd_lds(h, steps.l[k].gates)));" in seq
     assert "if (!s || s->B < 1 || s->S < 1 || s->V < 1 || s->E < 1 || s->h < 128 || s->h % 128) return MACX_EINVAL;" in api
-    assert "constexpr size_t ENC_LDS_MAX = 160 * 1024;" in api
+    assert "constexpr size_t ENC_LDS_MAX = 160 * 1024;" in api and "if (rnn_step_bwd_lds(s->h, 4) > ENC_LDS_MAX) return MACX_EUNSUPPORTED;" in api
 
 
 # ---- sizing, homogeneity -----------------------------------------------------------------------------------------------------

@@ -21,9 +21,9 @@ from test_gpu_side_kernels import OPT_KINDS, OPT_SIZES, opt_bounds, opt_case, op
 def test_encoder_sizing_refuses_widths_past_the_lds(macx):
     L = macx._lib.lib()
     sh = lambda h: C.byref(macx._lib.MacxEncShapes(B=2, S=3, V=9, E=20, h=h, b0=0))
-    for h in (128, 256, 384, 512):                        # lstm_step_bwd_lds(512) = 149,760 B <= 163,840 B
+    for h in (128, 256, 384, 512):                        # rnn_step_bwd_lds(512, 4) = 149,760 B <= 163,840 B
         assert L.macx_encoder_saved_floats(sh(h)) > 0 and L.macx_encoder_ws_floats(sh(h)) > 0, h
-    for h in (640, 768, 1024):                            # lstm_step_bwd_lds(640) = 182,528 B
+    for h in (640, 768, 1024):                            # rnn_step_bwd_lds(640, 4) = 182,528 B
         assert L.macx_encoder_saved_floats(sh(h)) == 0 and L.macx_encoder_ws_floats(sh(h)) == 0, h
     for h in (0, 64, 192, 520):                           # not a multiple of 128: refused as before
         assert L.macx_encoder_saved_floats(sh(h)) == 0 and L.macx_encoder_ws_floats(sh(h)) == 0, h
