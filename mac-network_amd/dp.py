@@ -214,6 +214,87 @@ class TwoPhaseStep:
         return b.allreduce_(self.shard, self.global_batch)      # late bucket (or the one bucket), join; releases the flat buffer
 
 
+def shard_count(n, lo, hi):
+    """Of the n live questions of a short global batch -- global slots 0 .. n-1 are live, the slots are dealt by tower_slice -- the
+    rank that holds slots [lo, hi) has clamp(n - lo, 0, hi - lo), at the front of its shard."""
+    return max(0, min(int(n) - int(lo), int(hi) - int(lo)))
+
+
+def live_weight_sum(weights, out):
+    """out[0] <- the sum in fp64 of the live weights of a [B] float32 tensor: live means w > 0, everything else counts 0, as
+    macx_answer_loss_weighted defines it.  `out` is a 1-element float64 tensor; kernels only (capturable), no host read."""
+    live = torch.where(weights > 0, weights, torch.zeros_like(weights))
+    return torch.sum(live.to(torch.float64), dim=0, keepdim=True, out=out)
+
+
+def shard_factor(w_local, w_global):
+    """W_r / W_g as a 1-element float64 tensor, exactly 0 where W_g == 0 (no division by zero: the quotient is taken over 1 there) and
+    exactly 1 where the two are equal: what a rank's locally normalised weighted mean is multiplied by so that the ranks' terms SUM to
+    the weighted mean over the global batch.  Torch ops on 1-element tensors, read when they run."""
+    some = w_global > 0
+    return torch.where(some, w_local / torch.where(some, w_global, torch.ones_like(w_global)), torch.zeros_like(w_global))
+
+
+def reduce_totals(totals, group=None):
+    """The dict output.AnswerTotals.read() returns, for the whole job: ONE sum all-reduce of the three doubles of every rank's `totals`
+    (loss, accuracy and weight are then those of all the questions the ranks scored).  A collective: every rank of the group calls it,
+    once per epoch; it synchronises.  The rank's own totals are left as they are.  One process: totals.read()."""
+    t = totals.tensor.clone()
+    if _world(group) > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    loss, hit, w = t.tolist()
+    return dict(loss=loss / w if w > 0 else 0.0, accuracy=hit / w if w > 0 else 0.0, weight=w)
+
+
+class TowerExchangeStep:
+    """The host side of a data-parallel step of the WHOLE tower that is cut at its collectives, not inside its backward pass:
+
+        [ part Q: W_r, the sum of the shard's live weights ]   [ sum all-reduce of that one double: W_g ]      weighted steps only
+          part A: forward, loss, backward, gather into the flat buffer      sum all-reduce of the flat buffer
+          part B: the optimizer step on the reduced buffer
+
+    What the parts ARE is the subclass's business, as with TwoPhaseStep: the sequence is made for parts that are captured HIP graphs
+    (two or three replays and one or two collectives per step in the place of every launch of the eager step; torch.distributed calls
+    cannot sit inside a graph, and the tower's backward pass is an autograd pass that cannot be cut in two as the cell's library
+    calls can).  No such subclass ships yet: tests/test_dp_tower_exchange_gloo.py drives this class with stand-in parts on CPU.
+    Every rank issues the same collectives in the same order whatever its parts do -- a rank whose shard is all dead, or whose
+    parts fell back to eager launches, stays in lock step.  One process: no collective at all.
+
+    Weighted steps (w_local / w_global given: 1-element float64 tensors): part Q writes W_r into BOTH, the all-reduce turns w_global
+    into W_g, and part A trains on  ce_r * factor()  with ce_r the rank's own weighted mean -- so the plain SUM of the ranks' gradients
+    is the gradient of the weighted mean over the global batch, the buffer is not rescaled, and a rank without a live question
+    contributes zeros.  Unweighted steps scale by shard / global inside part A, as GradBucket._reduce_all does in front of its all-reduce."""
+
+    def __init__(self, flat_grad, group=None, w_local=None, w_global=None):
+        self.flat_grad, self.group = flat_grad, group
+        self.w_local, self.w_global = w_local, w_global
+
+    def run_part_q(self):          # w_local, w_global <- the shard's live weight (live_weight_sum)
+        raise NotImplementedError
+
+    def run_part_a(self):          # forward .. the gathered (unweighted: scaled) flat gradient buffer
+        raise NotImplementedError
+
+    def run_part_b(self):          # the optimizer step on the reduced buffer
+        raise NotImplementedError
+
+    def factor(self):
+        """shard_factor of the step's two sums (1-element float64)"""
+        return shard_factor(self.w_local, self.w_global)
+
+    def exchange_step(self):
+        world = _world(self.group)
+        if self.w_global is not None:
+            self.run_part_q()
+            if world > 1:
+                dist.all_reduce(self.w_global, op=dist.ReduceOp.SUM, group=self.group)
+        self.run_part_a()
+        if world > 1:
+            dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM, group=self.group)
+        self.run_part_b()
+        return self.flat_grad
+
+
 class TowerBuckets(_TwoBuckets):
     """Data parallelism for the WHOLE tower the reference builds per GPU (model.py:775-826: embeddings, question encoder, stem,
     MAC cell, output unit + classifier -- 57 MB of fp32 gradients at p = 12), two buckets over ONE flat buffer:
