@@ -66,7 +66,7 @@ struct ModeScope {
 inline bool h2_mode() { return gemm_split_mode() == 2; }      // (the fused cell asks its CellRoute instead)
 inline size_t wsize(size_t K, size_t n) { return K * n * 3 / 2; }     // covers format 1 (3/2) and format 3 (1 + the exponent)
 inline hipError_t wgrad_any(const TnP& t, hipStream_t st) {
-  return (gemm_split_mode() && !(kb_gemm_dbg() & 128)) ? wgrad6_launch(t, st) : wgrad_tn_launch<A_PLAIN>(t, st);   // dbg 128: f32 TN kernel
+  return (gemm_split_mode() && !(kb_gemm_dbg() & 128)) ? wgrad_bf16x3_launch(t, st) : wgrad_tn_launch<A_PLAIN>(t, st);   // dbg 128: f32 TN kernel
 }
 // fp32-operand GEMM (stem convolutions, unit entry points, and the cell in modes 0 / 1); in h2 mode the fp32-operand
 // callers that remain (the stem's implicit GEMM) run on the split-bf16 kernel, whose weight format they pack (1)
@@ -784,9 +784,9 @@ struct SmallWgradBatch {
   float* slab; size_t slab_stride;
   SmallWgradBatch(float* slab_, size_t stride) : slab(slab_), slab_stride(stride) { memset(&L, 0, sizeof(L)); memset(&S, 0, sizeof(S)); }
   int add(const float* A, int lda, const float* G, int ldg, int M, int Kd, int Jd, float* out, hipStream_t st) {
-    const bool ok = gemm_split_mode() && !(kb_gemm_dbg() & 128) && n < 8 && (jw == 0 || jw == wgrad6_jw(Jd));
+    const bool ok = gemm_split_mode() && !(kb_gemm_dbg() & 128) && n < 8 && (jw == 0 || jw == wgrad_split_jw(Jd));
     if (!ok) return wgrad_impl(A, lda, G, ldg, M, Kd, Jd, out, slab + (size_t)7 * slab_stride, st);
-    jw = wgrad6_jw(Jd);
+    jw = wgrad_split_jw(Jd);
     TnP& t = L.d[n];
     t.M = M; t.Kd = Kd; t.Jd = Jd;
     t.nsplit = wgrad_splits(M, Kd, Jd);
@@ -907,7 +907,7 @@ int ctrl_inputs_bwd(bool unshared, int act, int B, int d, int p, const float* ve
       t.M = B; t.Kd = d; t.Jd = d; t.nsplit = 1; t.rows_per_split = rows_per_split(B, 1);
       t.A = ctrl_t; t.lda = d; t.a_mod = B; t.G = dcI; t.ldg = d;
       t.part = GP->qInputU_W; t.nz = p; t.zG = Bd; t.zpart = dd;
-      CK(wgrad6_launch(t, st));
+      CK(wgrad_bf16x3_launch(t, st));
     } else if (GP->qInputU_W) {
       for (int i = 0; i < p; ++i) CKI(wgrad_impl(ctrl_t, d, dcI + (size_t)i * Bd, d, B, d, d, GP->qInputU_W + (size_t)i * dd, x.slab, st));
     }
@@ -2888,7 +2888,7 @@ int conv_wgrad(const macx_stem_shapes* s, const StemGeo& geo, const float* Apad,
   t.magic_w = (uint32_t)(((1ull << 32) + s->W - 1) / s->W);
   t.part = (ns == 1) ? out : slab;
   t.a_maxabs = a_max; t.g_maxabs = g_max;
-  if (a_max && g_max) CK(wgrad3h_launch(t, st));      // three fp16 terms (macx_gemm3h.hip.h)
+  if (a_max && g_max) CK(wgrad_fp16x2_launch(t, st));      // three fp16 terms (macx_wgrad6.hip.h)
   else CK(wgrad_any(t, st));
   if (ns > 1) CK(slab_reduce_launch(slab, ns, (size_t)t.Kd * t.Jd, out, 0, st));
   return 0;

@@ -13,7 +13,6 @@
 // B_PLAIN weights only (the per-question weight mixing of the read unit has its own kernels).
 #pragma once
 #include "macx_gemm6.hip.h"
-#include "macx_gemm_tn.hip.h"
 #include "macx_h2.hip.h"
 
 namespace macx {
@@ -465,207 +464,6 @@ inline hipError_t kb_gemm3h_launch(const GemmP& p, hipStream_t st) {
     case 7: return kb_gemm3h_launch_rt<7, AP, BP, EP, COLSUM>(p, st);
     default: return kb_gemm3h_launch_rt<13, AP, BP, EP, COLSUM>(p, st);
   }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// The weight-gradient contraction of macx_wgrad6.hip.h (C[k][j] = sum_m A[m][k] G[m][j], both operands fp32 row-major over
-// m, producer waves transpose and split in registers, consumer waves multiply) on the same three fp16 terms: two planes per
-// operand, one exponent per operand tensor (TnP::a_maxabs / g_maxabs).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int W3_GS = 128 * 16 + 32;       // bytes between m-groups of a plane
-constexpr int W3_PLANE = 4 * W3_GS;
-constexpr int W3_OPER = 2 * W3_PLANE;
-constexpr int W3_STAGE = 2 * W3_OPER;
-
-// JW = j-width of the output tile in units of 128 columns.  JW = 2 (128 x 256 tiles, consumer wave tile 64 x 128) doubles
-// the MFMA work per barrier and reads the A operand half as often; used whenever Jd is a multiple of 256.
-template <int JW>
-constexpr int w3_stage_bytes() { return W3_OPER + 2 * 4 * (JW * 128 * 16 + 32); }
-
-template <bool CONV, int JW>
-__global__ __launch_bounds__(512) void wgrad3h_kernel(TnP p) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* lds = reinterpret_cast<char*>(smem);
-  constexpr int JT = JW * T_TILE;                   // output tile width
-  constexpr int GG = JW * 128 * 16 + 32;            // bytes between m-groups of a G plane
-  constexpr int GPL = 4 * GG;                       // G plane
-  constexpr int STAGE = W3_OPER + 2 * GPL;
-
-  const int ntj = p.Jd / JT;
-  const int ntk = p.Kd / T_TILE;
-  const int ntile = ntj * ntk;
-  const int nblk = gridDim.x;
-  int v = blockIdx.x;
-  if ((nblk & 7) == 0) v = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
-  const int split = v / ntile;
-  const int tile = v % ntile;
-  const int tk = tile / ntj, tj = tile % ntj;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m_begin = split * p.rows_per_split;
-  const int m_end = min(p.M, m_begin + p.rows_per_split);
-  const int nchunk = (m_end - m_begin + 31) >> 5;
-  const int nloop = (nchunk + 2) / 3 * 3;          // whole groups of three stages; the extra ones multiply zeros
-  // one power-of-two unit per operand tensor (macx_gemm3h.hip.h): from the largest magnitudes an absmax pass left on the device
-  const int eA = h2_exponent(*p.a_maxabs), eG = h2_exponent(*p.g_maxabs);
-  const float a_scale = h2_pow2(eA), g_scale = h2_pow2(eG);
-  const float unscale = h2_unscale(eA, eG);
-
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  typedef float gvec __attribute__((ext_vector_type(2 * JW)));     // a lane's columns of one G row
-
-  if (wave < 4) {
-    // ================= producer waves: global -> registers -> fp16 hi/lo split -> LDS planes =================
-    // wave w stages m-group w (8 rows) of BOTH operands; every row address is wave-uniform (scalar ALU), the lane
-    // contributes its columns (2 of A, 2 JW of G).  Three register sets keep the loads of stages c+1..c+3 in flight.
-    int conv_shift = 0, a_col0 = tk * T_TILE;
-    if (CONV) {
-      const int per = p.conv_cin / T_TILE;
-      const int tap = tk / per;
-      conv_shift = (tap / 3 - 1) * p.conv_wp + (tap - (tap / 3) * 3 - 1);
-      a_col0 = (tk - tap * per) * T_TILE;
-    }
-    const int mg = wave;
-    const float* baseA = p.A + a_col0 + 2 * lane;
-    const float* baseG = p.G + (size_t)blockIdx.y * p.zG + tj * JT + 2 * JW * lane;
-    int amod_row = (m_begin + mg * 8) % p.a_mod;   // A row of reduction row m is m % a_mod, kept incrementally
-    f32x2_t ra[3][8];
-    gvec rg[3][8];
-    auto load = [&](auto slot_c, int ch) __attribute__((always_inline)) {
-      constexpr int SL = decltype(slot_c)::value;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int m = m_begin + ch * 32 + mg * 8 + r;
-        const int mc = min(m, p.M - 1);        // rows past the end are zeroed when the stage is split, not here
-        int arow;
-        if (CONV) {
-          const int img = (int)__umulhi((uint32_t)mc, p.magic_n);
-          const int n = mc - img * p.conv_n;
-          const int yy = (int)__umulhi((uint32_t)n, p.magic_w);
-          arow = img * p.conv_np + (yy + 1) * p.conv_wp + (n - yy * p.conv_w) + 1 + conv_shift;
-        } else {
-          arow = amod_row + r;
-          while (arow >= p.a_mod) arow -= p.a_mod;     // a_mod may be smaller than a stage (tiny [B,d]-sized contractions)
-        }
-        ra[SL][r] = *reinterpret_cast<const f32x2_t*>(baseA + (size_t)arow * p.lda);
-        rg[SL][r] = *reinterpret_cast<const gvec*>(baseG + (size_t)mc * p.ldg);
-      }
-      amod_row += 32;
-      while (amod_row >= p.a_mod) amod_row -= p.a_mod;
-    };
-    auto store = [&](auto slot_c, int ch) __attribute__((always_inline)) {
-      constexpr int SL = decltype(slot_c)::value;
-      const int mrow = m_begin + ch * 32 + mg * 8;
-      char* dA = lds + (ch & 1) * STAGE + mg * W3_GS + (2 * lane) * 16;
-      char* dG = lds + (ch & 1) * STAGE + W3_OPER + mg * GG + (2 * JW * lane) * 16;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        float x[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? ra[SL][r][c] * a_scale : 0.f;
-        u32x4 s0, s1;
-        h2_split8(x, s0, s1);
-        *reinterpret_cast<u32x4*>(dA + c * 16) = s0;
-        *reinterpret_cast<u32x4*>(dA + W3_PLANE + c * 16) = s1;
-      }
-#pragma unroll
-      for (int c = 0; c < 2 * JW; ++c) {
-        float x[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? rg[SL][r][c] * g_scale : 0.f;
-        u32x4 s0, s1;
-        h2_split8(x, s0, s1);
-        *reinterpret_cast<u32x4*>(dG + c * 16) = s0;
-        *reinterpret_cast<u32x4*>(dG + GPL + c * 16) = s1;
-      }
-    };
-    // straight-line pipeline: no conditional loads (a branch around a load drains vmcnt at the join)
-    load(S0{}, 0);
-    load(S1{}, 1);
-    load(S2{}, 2);
-    store(S0{}, 0);
-    __syncthreads();
-#pragma unroll 1
-    for (int ch = 0; ch < nloop; ch += 3) {
-      load(S0{}, ch + 3); store(S1{}, ch + 1); __syncthreads();
-      load(S1{}, ch + 4); store(S2{}, ch + 2); __syncthreads();
-      load(S2{}, ch + 5); store(S0{}, ch + 3); __syncthreads();
-    }
-  } else {
-    // ================= consumer waves: LDS fragments -> MFMA; wave tile 64 x (64 JW) = 4 x (4 JW) MFMA tiles =================
-    const int cw = wave - 4;
-    const int wr = cw >> 1, wc = cw & 1;
-    constexpr int NC = 4 * JW;
-    f32x4 acc[4][NC];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-      const char* sa = lds + buf * STAGE + (lane >> 4) * W3_GS + (wr * 64 + (lane & 15)) * 16;
-      const char* sg = lds + buf * STAGE + W3_OPER + (lane >> 4) * GG + (wc * 64 * JW + (lane & 15)) * 16;
-      u32x4 af[2][4];
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) af[pl][t] = *reinterpret_cast<const u32x4*>(sa + pl * W3_PLANE + t * 256);
-      // G plane by plane (smallest terms first): G_lo x A_hi ; G_hi x {A_lo, A_hi}
-#pragma unroll
-      for (int bp = 1; bp >= 0; --bp) {
-        u32x4 gf[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) gf[c] = *reinterpret_cast<const u32x4*>(sg + bp * GPL + c * 256);
-#pragma unroll
-        for (int ap = 1 - bp; ap >= 0; --ap)
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[t][c] = mfma_f16(af[ap][t], gf[c], acc[t][c]);
-      }
-    };
-    __syncthreads();
-#pragma unroll 1
-    for (int ch = 0; ch < nloop; ++ch) {
-      compute(ch & 1);
-      __syncthreads();
-    }
-    // 16x16 accumulator map: col = lane & 15 (j), row = (lane >> 4) * 4 + reg (k)
-    float* out = p.part + (size_t)blockIdx.y * p.zpart + (size_t)split * p.Kd * p.Jd;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int k = tk * T_TILE + wr * 64 + t * 16 + (lane >> 4) * 4 + e;
-          const int j = tj * JT + wc * 64 * JW + c * 16 + (lane & 15);
-          out[(size_t)k * p.Jd + j] = acc[t][c][e] * unscale;
-        }
-  }
-}
-
-inline int wgrad3h_jw(int Jd) { return (Jd % 256 == 0) ? 2 : 1; }
-
-template <bool CONV, int JW>
-inline hipError_t wgrad3h_launch_t(const TnP& p, hipStream_t st) {
-  auto kern = wgrad3h_kernel<CONV, JW>;
-  constexpr size_t lds = 2 * w3_stage_bytes<JW>();
-  {
-    hipError_t e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);   // per (kernel, device)
-    if (e != hipSuccess) return e;
-  }
-  const int grid = (p.Kd / T_TILE) * (p.Jd / (JW * T_TILE)) * p.nsplit;
-  hipLaunchKernelGGL(kern, dim3(grid, p.nz > 1 ? p.nz : 1), dim3(512), lds, st, p);
-  return hipGetLastError();
-}
-
-inline hipError_t wgrad3h_launch(const TnP& p, hipStream_t st) {
-  if (wgrad3h_jw(p.Jd) == 2) return p.conv_taps ? wgrad3h_launch_t<true, 2>(p, st) : wgrad3h_launch_t<false, 2>(p, st);
-  return p.conv_taps ? wgrad3h_launch_t<true, 1>(p, st) : wgrad3h_launch_t<false, 1>(p, st);
 }
 
 }  // namespace macx

@@ -1,7 +1,10 @@
 // macx_wgrad6.hip.h -- the weight-gradient contractions  C[k][j] = sum_m A[m][k] * G[m][j]  (macx_gemm_tn.hip.h) on the
-// bf16 matrix pipe with fp32-class numerics: the same exact 3-way bf16 operand split and six MFMA terms as
-// macx_gemm6.hip.h.  Both operands are row-major over the reduction index m, and v_mfma_f32_16x16x32_bf16 wants 8
-// consecutive m per lane, so the transpose happens in registers while staging: a thread loads an 8 (m) x 2 (columns)
+// low-precision matrix pipes with fp32-class numerics, in two operand formats (the FMT argument of everything below):
+//   WgBf16x3: the exact 3-way bf16 operand split and six MFMA terms of macx_gemm6.hip.h;
+//   WgFp16x2: the fp16 hi/lo split and three MFMA terms of macx_gemm3h.hip.h, with one power-of-two unit per operand tensor
+//     (TnP::a_maxabs / g_maxabs): operands are scaled on load, accumulators unscaled on store.
+// Both operands are row-major over the reduction index m, and the 16x16x32 MFMAs want 8 consecutive m per lane, so the
+// transpose happens in registers while staging: a thread loads an 8 (m) x 2 (columns)
 // block (eight 8-byte loads, 512 B contiguous per row across a wave), splits the 16 values and writes, per column and
 // plane, one 16-byte slot [m-group][column] -- conflict-free b128 stores, and fragments are conflict-free b128 reads.
 //   workgroup: 128 x 128 output tile, 8 waves SPECIALISED: waves 0-3 produce (load, split, LDS store of stage c+1) while
@@ -12,27 +15,49 @@
 #pragma once
 #include "macx_gemm6.hip.h"
 #include "macx_gemm_tn.hip.h"
+#include "macx_h2.hip.h"
 
 namespace macx {
 
-constexpr int W6_GS = 128 * 16 + 32;       // bytes between m-groups of a plane
-constexpr int W6_PLANE = 4 * W6_GS;
-constexpr int W6_OPER = 3 * W6_PLANE;
-constexpr int W6_STAGE = 2 * W6_OPER;
+// operand formats: planes per operand, the 8-value split into one 16-byte slot per plane, the MFMA of two slots
+struct WgBf16x3 {
+  static constexpr int PLANES = 3;
+  static constexpr bool SCALED = false;
+  static __device__ __forceinline__ void split(const float* x, u32x4* s) { split8(x, s[0], s[1], s[2]); }
+  static __device__ __forceinline__ f32x4 mfma(const u32x4 a, const u32x4 b, f32x4 c) { return mfma_bf16(a, b, c); }
+};
+struct WgFp16x2 {
+  static constexpr int PLANES = 2;
+  static constexpr bool SCALED = true;          // one exponent per operand tensor
+  static __device__ __forceinline__ void split(const float* x, u32x4* s) { h2_split8(x, s[0], s[1]); }
+  static __device__ __forceinline__ f32x4 mfma(const u32x4 a, const u32x4 b, f32x4 c) { return mfma_f16(a, b, c); }
+};
+
+// LDS layout of one stage: the A operand's planes, then the G operand's
+template <typename FMT, int JW>
+struct WgLayout {
+  static constexpr int GS = 128 * 16 + 32;          // bytes between m-groups of an A plane
+  static constexpr int PLANE = 4 * GS;
+  static constexpr int OPER = FMT::PLANES * PLANE;
+  static constexpr int GG = JW * 128 * 16 + 32;     // bytes between m-groups of a G plane
+  static constexpr int GPL = 4 * GG;                // G plane
+  static constexpr int STAGE = OPER + FMT::PLANES * GPL;
+};
+constexpr int W6_GS = WgLayout<WgBf16x3, 1>::GS;         // sb6_wgrad_kernel: both operands 128 columns wide
+constexpr int W6_PLANE = WgLayout<WgBf16x3, 1>::PLANE;
+constexpr int W6_OPER = WgLayout<WgBf16x3, 1>::OPER;
+constexpr int W6_STAGE = WgLayout<WgBf16x3, 1>::STAGE;
 
 // JW = j-width of the output tile in units of 128 columns.  JW = 2 (128 x 256 tiles, consumer wave tile 64 x 128) doubles
 // the MFMA work per barrier and reads the A operand half as often; used whenever Jd is a multiple of 256.
-template <int JW>
-constexpr int w6_stage_bytes() { return W6_OPER + 3 * 4 * (JW * 128 * 16 + 32); }
-
-template <bool CONV, int JW>
-__device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const int bid, const int nblk) {
+template <typename FMT, bool CONV, int JW>
+__device__ __forceinline__ void wgrad_split_body(const TnP& p, const int zidx, const int bid, const int nblk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
+  using L = WgLayout<FMT, JW>;
+  constexpr int PLANES = FMT::PLANES;
   constexpr int JT = JW * T_TILE;                   // output tile width
-  constexpr int GG = JW * 128 * 16 + 32;            // bytes between m-groups of a G plane
-  constexpr int GPL = 4 * GG;                       // G plane
-  constexpr int STAGE = W6_OPER + 3 * GPL;
+  constexpr int GS = L::GS, PLANE = L::PLANE, OPER = L::OPER, GG = L::GG, GPL = L::GPL, STAGE = L::STAGE;
 
   const int ntj = p.Jd / JT;
   const int ntk = p.Kd / T_TILE;
@@ -49,6 +74,17 @@ __device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const 
   const int m_end = min(p.M, m_begin + p.rows_per_split);
   const int nchunk = (m_end - m_begin + 31) >> 5;
   const int nloop = (nchunk + 2) / 3 * 3;          // whole groups of three stages; the extra ones multiply zeros
+  // fp16 only: one power-of-two unit per operand tensor (macx_gemm3h.hip.h), from the largest magnitudes an absmax pass left on the device
+  [[maybe_unused]] float a_scale = 1.f, g_scale = 1.f, unscale = 1.f;
+  if constexpr (FMT::SCALED) {
+    const int eA = h2_exponent(*p.a_maxabs), eG = h2_exponent(*p.g_maxabs);
+    a_scale = h2_pow2(eA), g_scale = h2_pow2(eG);
+    unscale = h2_unscale(eA, eG);
+  }
+  auto scaled = [](float v, float s) __attribute__((always_inline)) {      // the bf16 format has no multiply at all
+    if constexpr (FMT::SCALED) return v * s;
+    else return v;
+  };
 
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
@@ -56,7 +92,7 @@ __device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const 
   typedef float gvec __attribute__((ext_vector_type(2 * JW)));     // a lane's columns of one G row
 
   if (wave < 4) {
-    // ================= producer waves: global -> registers -> exact bf16 split -> LDS planes =================
+    // ================= producer waves: global -> registers -> split into planes -> LDS =================
     // wave w stages m-group w (8 rows) of BOTH operands; every row address is wave-uniform (scalar ALU), the lane
     // contributes its columns (2 of A, 2 JW of G).  Three register sets keep the loads of stages c+1..c+3 in flight.
     int conv_shift = 0, a_col0 = tk * T_TILE;
@@ -97,29 +133,27 @@ __device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const 
     auto store = [&](auto slot_c, int ch) __attribute__((always_inline)) {
       constexpr int SL = decltype(slot_c)::value;
       const int mrow = m_begin + ch * 32 + mg * 8;
-      char* dA = lds + (ch & 1) * STAGE + mg * W6_GS + (2 * lane) * 16;
-      char* dG = lds + (ch & 1) * STAGE + W6_OPER + mg * GG + (2 * JW * lane) * 16;
+      char* dA = lds + (ch & 1) * STAGE + mg * GS + (2 * lane) * 16;
+      char* dG = lds + (ch & 1) * STAGE + OPER + mg * GG + (2 * JW * lane) * 16;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         float x[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? ra[SL][r][c] : 0.f;
-        u32x4 s0, s1, s2;
-        split8(x, s0, s1, s2);
-        *reinterpret_cast<u32x4*>(dA + c * 16) = s0;
-        *reinterpret_cast<u32x4*>(dA + W6_PLANE + c * 16) = s1;
-        *reinterpret_cast<u32x4*>(dA + 2 * W6_PLANE + c * 16) = s2;
+        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? scaled(ra[SL][r][c], a_scale) : 0.f;
+        u32x4 s[PLANES];
+        FMT::split(x, s);
+#pragma unroll
+        for (int pl = 0; pl < PLANES; ++pl) *reinterpret_cast<u32x4*>(dA + pl * PLANE + c * 16) = s[pl];
       }
 #pragma unroll
       for (int c = 0; c < 2 * JW; ++c) {
         float x[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? rg[SL][r][c] : 0.f;
-        u32x4 s0, s1, s2;
-        split8(x, s0, s1, s2);
-        *reinterpret_cast<u32x4*>(dG + c * 16) = s0;
-        *reinterpret_cast<u32x4*>(dG + GPL + c * 16) = s1;
-        *reinterpret_cast<u32x4*>(dG + 2 * GPL + c * 16) = s2;
+        for (int r = 0; r < 8; ++r) x[r] = (mrow + r < m_end) ? scaled(rg[SL][r][c], g_scale) : 0.f;
+        u32x4 s[PLANES];
+        FMT::split(x, s);
+#pragma unroll
+        for (int pl = 0; pl < PLANES; ++pl) *reinterpret_cast<u32x4*>(dG + pl * GPL + c * 16) = s[pl];
       }
     };
     // straight-line pipeline: no conditional loads (a branch around a load drains vmcnt at the join)
@@ -145,25 +179,25 @@ __device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const 
 #pragma unroll
       for (int c = 0; c < NC; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto compute = [&](int buf) __attribute__((always_inline)) {
-      const char* sa = lds + buf * STAGE + (lane >> 4) * W6_GS + (wr * 64 + (lane & 15)) * 16;
-      const char* sg = lds + buf * STAGE + W6_OPER + (lane >> 4) * GG + (wc * 64 * JW + (lane & 15)) * 16;
-      u32x4 af[3][4];
+      const char* sa = lds + buf * STAGE + (lane >> 4) * GS + (wr * 64 + (lane & 15)) * 16;
+      const char* sg = lds + buf * STAGE + OPER + (lane >> 4) * GG + (wc * 64 * JW + (lane & 15)) * 16;
+      u32x4 af[PLANES][4];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
+      for (int pl = 0; pl < PLANES; ++pl)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) af[pl][t] = *reinterpret_cast<const u32x4*>(sa + pl * W6_PLANE + t * 256);
-      // G plane by plane (smallest terms first): G2 x A0 ; G1 x {A1, A0} ; G0 x {A2, A1, A0}
+        for (int t = 0; t < 4; ++t) af[pl][t] = *reinterpret_cast<const u32x4*>(sa + pl * PLANE + t * 256);
+      // G plane by plane (smallest terms first).  bf16: G2 x A0 ; G1 x {A1, A0} ; G0 x {A2, A1, A0}.  fp16: G_lo x A_hi ; G_hi x {A_lo, A_hi}
 #pragma unroll
-      for (int bp = 2; bp >= 0; --bp) {
+      for (int bp = PLANES - 1; bp >= 0; --bp) {
         u32x4 gf[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) gf[c] = *reinterpret_cast<const u32x4*>(sg + bp * GPL + c * 256);
 #pragma unroll
-        for (int ap = 2 - bp; ap >= 0; --ap)
+        for (int ap = PLANES - 1 - bp; ap >= 0; --ap)
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int c = 0; c < NC; ++c) acc[t][c] = mfma_bf16(af[ap][t], gf[c], acc[t][c]);
+            for (int c = 0; c < NC; ++c) acc[t][c] = FMT::mfma(af[ap][t], gf[c], acc[t][c]);
       }
     };
     __syncthreads();
@@ -182,13 +216,13 @@ __device__ __forceinline__ void wgrad6_body(const TnP& p, const int zidx, const 
         for (int e = 0; e < 4; ++e) {
           const int k = tk * T_TILE + wr * 64 + t * 16 + (lane >> 4) * 4 + e;
           const int j = tj * JT + wc * 64 * JW + c * 16 + (lane & 15);
-          out[(size_t)k * p.Jd + j] = acc[t][c][e];
+          out[(size_t)k * p.Jd + j] = scaled(acc[t][c][e], unscale);
         }
   }
 }
 
-template <bool CONV, int JW>
-__global__ __launch_bounds__(512) void wgrad6_kernel(TnP p) { wgrad6_body<CONV, JW>(p, blockIdx.y, blockIdx.x, gridDim.x); }
+template <typename FMT, bool CONV, int JW>
+__global__ __launch_bounds__(512) void wgrad_split_kernel(TnP p) { wgrad_split_body<FMT, CONV, JW>(p, blockIdx.y, blockIdx.x, gridDim.x); }
 
 // several independent contractions of the same tile geometry in ONE launch (the [B,d]-sized linears' weight gradients at the end
 // of a backward pass: 768 reduction rows each, a launch of their own was 17 us of latency + a slab reduction): blockIdx.y
@@ -198,15 +232,15 @@ template <int JW>
 __global__ __launch_bounds__(512) void wgrad6_list_kernel(TnList L) {
   const int n = L.nblk[blockIdx.y];
   if ((int)blockIdx.x >= n) return;
-  wgrad6_body<false, JW>(L.d[blockIdx.y], 0, blockIdx.x, n);
+  wgrad_split_body<WgBf16x3, false, JW>(L.d[blockIdx.y], 0, blockIdx.x, n);
 }
 
-inline int wgrad6_jw(int Jd) { return (Jd % 256 == 0) ? 2 : 1; }
+inline int wgrad_split_jw(int Jd) { return (Jd % 256 == 0) ? 2 : 1; }
 
-template <bool CONV, int JW>
-inline hipError_t wgrad6_launch_t(const TnP& p, hipStream_t st) {
-  auto kern = wgrad6_kernel<CONV, JW>;
-  constexpr size_t lds = 2 * w6_stage_bytes<JW>();
+template <typename FMT, bool CONV, int JW>
+inline hipError_t wgrad_split_launch_t(const TnP& p, hipStream_t st) {
+  auto kern = wgrad_split_kernel<FMT, CONV, JW>;
+  constexpr size_t lds = 2 * WgLayout<FMT, JW>::STAGE;
   {
     hipError_t e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);   // per (kernel, device)
     if (e != hipSuccess) return e;
@@ -219,7 +253,7 @@ inline hipError_t wgrad6_launch_t(const TnP& p, hipStream_t st) {
 template <int JW>
 inline hipError_t wgrad6_list_launch_t(const TnList& L, int count, hipStream_t st) {
   auto kern = wgrad6_list_kernel<JW>;
-  constexpr size_t lds = 2 * w6_stage_bytes<JW>();
+  constexpr size_t lds = 2 * WgLayout<WgBf16x3, JW>::STAGE;
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(kern), lds);
   if (e != hipSuccess) return e;
   int gx = 1;
@@ -227,9 +261,15 @@ inline hipError_t wgrad6_list_launch_t(const TnList& L, int count, hipStream_t s
   hipLaunchKernelGGL(kern, dim3(gx, count), dim3(512), lds, st, L);
   return hipGetLastError();
 }
-inline hipError_t wgrad6_launch(const TnP& p, hipStream_t st) {
-  if (wgrad6_jw(p.Jd) == 2) return p.conv_taps ? wgrad6_launch_t<true, 2>(p, st) : wgrad6_launch_t<false, 2>(p, st);
-  return p.conv_taps ? wgrad6_launch_t<true, 1>(p, st) : wgrad6_launch_t<false, 1>(p, st);
+inline hipError_t wgrad_bf16x3_launch(const TnP& p, hipStream_t st) {
+  if (wgrad_split_jw(p.Jd) == 2)
+    return p.conv_taps ? wgrad_split_launch_t<WgBf16x3, true, 2>(p, st) : wgrad_split_launch_t<WgBf16x3, false, 2>(p, st);
+  return p.conv_taps ? wgrad_split_launch_t<WgBf16x3, true, 1>(p, st) : wgrad_split_launch_t<WgBf16x3, false, 1>(p, st);
+}
+// the fp16 format only ever runs the stem convolutions' kernel gradients (conv_wgrad): no plain instantiation
+inline hipError_t wgrad_fp16x2_launch(const TnP& p, hipStream_t st) {
+  if (!p.conv_taps) return hipErrorInvalidValue;
+  return wgrad_split_jw(p.Jd) == 2 ? wgrad_split_launch_t<WgFp16x2, true, 2>(p, st) : wgrad_split_launch_t<WgFp16x2, true, 1>(p, st);
 }
 
 // ---------------------------------------------------------------------------------------------

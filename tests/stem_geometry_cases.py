@@ -3,7 +3,7 @@
 Shared by tests/test_gpu_stem_geometry.py (the kernels, three families) and tests/test_stem_geometry_host.py (CPU: the table's claims
 against a restatement of the launch rules, the inputs' fairness under the finer metrics, the magic division's refusal bound).
 
-Routes (mac-network_amd/csrc/macx_api.hip, macx_gemm.hip.h, macx_gemm3h.hip.h), restated below in Python:
+Routes (mac-network_amd/csrc/macx_api.hip, macx_gemm.hip.h, macx_gemm3h.hip.h, macx_wgrad6.hip.h), restated below in Python:
   * forward of layer 0 / layer 1 and backward-data are three GEMM launches [B N, 9 cin] x [9 cin, nout] with (cin, nout) =
     (Cin, Cmid), (Cmid, Cout), (Cout, Cmid).  In the H2 family a launch with nout == 512 and cin % 256 == 0 runs on
     kb_conv_chain_kernel (64 rows of the FLATTENED [B N] axis per workgroup); every other launch, and every launch of families 1 / 0,

@@ -5,7 +5,7 @@ Cross-entropy hands every question a gradient of its own magnitude, attention ha
 exact zeros.  The H2 family (two fp16 planes + power-of-two block exponents) is where scale decides: the per-row exponents of
 read_att_bwd_h2_kernel and the chain kernels, the row minima of h2_emin_list_kernel / h2_emin_final, the per-question minima of
 sb_h2_kernel / sb_h2w_kernel, the fp16 row factor pk_pow2_f16(da + dg) (0 below 2^-24), the clamps H2_E_MIN/MAX and H2_WE_LO/HI,
-and the one exponent per tensor of the stem's kb_gemm3h_kernel / wgrad3h_kernel.  Every route with exponent logic of its own runs
+and the one exponent per tensor of the stem's kb_gemm3h_kernel / wgrad_split_kernel<WgFp16x2>.  Every route with exponent logic of its own runs
 here against the fp64 oracle with
 
   * input gradients (d_kb, d_words, d_vq) PER QUESTION, no absolute floor, exact zeros where the reference has them;
@@ -198,7 +198,7 @@ def test_stem_forward_per_image_scales(macx, dev):
 
 
 def test_stem_backward_per_image_scales(macx, dev):
-    """d_out at 2^{0, -10, -20} per image under one exponent per tensor (kb_gemm3h_kernel backward-data, wgrad3h_kernel): the four
+    """d_out at 2^{0, -10, -20} per image under one exponent per tensor (kb_gemm3h_kernel backward-data, wgrad_split_kernel<WgFp16x2>): the four
     parameter gradients with the scaled floor (unit 1).  The fused stem returns no image gradient (image features are inputs), so
     the per-image figure of the backward-data product cannot be observed from outside; it enters kernel0's gradient."""
     got, r64, r32 = run_stem(macx, dev, dout_scales=gsc.STEM_BWD_SCALES)

@@ -5,7 +5,7 @@ test_stem_geometry_host.py, which also shows that fp32 arithmetic on the same da
   * per-image route: N = 2 ... 1024 on 16-, 32-, 64-, 112- and 208-row workgroups with one to 32 row blocks per image, ragged last tiles
     of one row, single-row images (six all-halo taps: exactly zero kernel gradients), kernel gradients in 1 ... 16 slabs with the cut
     inside an image, on 128 x 128 and 128 x 256 tiles; in the H2 family a last slab that starts AT row M (32 x 9 x 9) and one that starts
-    204 rows PAST it (21 x 14 x 14): wgrad3h_kernel's producer and consumer loops make no pass (nloop = 0 / -3: one barrier on each
+    204 rows PAST it (21 x 14 x 14): wgrad_split_kernel<WgFp16x2>'s producer and consumer loops make no pass (nloop = 0 / -3: one barrier on each
     side, every load clamped to row M - 1), the accumulators are stored as the exact zeros slab_reduce adds;
   * kb_conv_chain_kernel (H2 family, 64 rows of the flattened [B N] axis): M = 2, 63, 64, 65, image boundaries inside a tile, ragged last
     tiles; with Cout = 256 layer 1 leaves the chain while backward-data stays; E_MUL_DACT without keep bits (keep = 1).

@@ -54,7 +54,7 @@ def test_case_takes_the_route_its_row_names(case):
 
 
 def _c_nchunk(m_begin, m_end):
-    """wgrad3h_kernel / wgrad6_kernel: nchunk = (m_end - m_begin + 31) >> 5 (arithmetic shift), nloop = (nchunk + 2) / 3 * 3 (C division)"""
+    """wgrad_split_body (both operand formats): nchunk = (m_end - m_begin + 31) >> 5 (arithmetic shift), nloop = (nchunk + 2) / 3 * 3 (C division)"""
     nchunk = (m_end - m_begin + 31) >> 5
     q = abs(nchunk + 2) // 3 * (1 if nchunk + 2 >= 0 else -1)
     return nchunk, q * 3
