@@ -15,8 +15,8 @@ from .features import FeatureStore                  # noqa: F401
 from .questions import EpochOrder, QuestionStore    # noqa: F401
 from .records import EvalRecords                    # noqa: F401
 from .model import MACNet, MACNetCore               # noqa: F401
-from .graph import (CapturedDPTrainStep, CapturedForward, CapturedTowerForward, CapturedTowerTrainStep,   # noqa: F401
-                    CapturedTrainStep)
+from .graph import (CapturedDPTowerTrainStep, CapturedDPTrainStep, CapturedForward, CapturedTowerForward,   # noqa: F401
+                    CapturedTowerTrainStep, CapturedTrainStep)
 
 __all__ = ["MACCell", "MACCellTuple", "MACCellParams", "OutputClassifier", "GenericOutputClassifier", "UnsupportedOptions", "freeze",
            "HandoffTimeout"]

@@ -256,7 +256,8 @@ class TowerExchangeStep:
     What the parts ARE is the subclass's business, as with TwoPhaseStep: the sequence is made for parts that are captured HIP graphs
     (two or three replays and one or two collectives per step in the place of every launch of the eager step; torch.distributed calls
     cannot sit inside a graph, and the tower's backward pass is an autograd pass that cannot be cut in two as the cell's library
-    calls can).  No such subclass ships yet: tests/test_dp_tower_exchange_gloo.py drives this class with stand-in parts on CPU.
+    calls can).  graph.CapturedDPTowerTrainStep is that subclass (existing kernels replayed, none added);
+    tests/test_dp_tower_exchange_gloo.py drives this class with stand-in parts on CPU.
     Every rank issues the same collectives in the same order whatever its parts do -- a rank whose shard is all dead, or whose
     parts fell back to eager launches, stays in lock step.  One process: no collective at all.
 
@@ -323,11 +324,17 @@ class TowerBuckets(_TwoBuckets):
     zeroed (an unflushed table gathers nothing): a buffer allocated under the capture would sit in a block of the graph's
     pool that an earlier temporary of the same graph has given back, and that temporary's kernels write it again on every
     replay -- behind the upload, in front of the gather.  Two spares per captured step (reserve_tables() adds more).
+
+    exchange=False: the bucket gathers and the STEP exchanges (TowerExchangeStep; graph.CapturedDPTowerTrainStep captures the
+    gather inside its part A, where a collective must never be issued).  The phase-1 hook then starts nothing, whatever the world
+    size, and gather_(shard, global_batch) is allreduce_ without its collectives: gather, flat *= shard / global, publish.  One
+    gather, so one spare table per captured step.  exchange=True, the default, is the class as it always was.
     """
 
-    def __init__(self, net, group=None, fused_gather=False):
+    def __init__(self, net, group=None, fused_gather=False, exchange=True):
         self.net = net
         self.fused_gather = bool(fused_gather)
+        self.exchange = bool(exchange)
         self._tables = {}                    # (lo, hi) -> [host rows, device table]: the eager gathers
         self._captured_tables = []           # [host rows, device table, uploaded]: one per gather issued under a capture
         self._spare_tables = []              # device tables for gathers issued under a capture (see the class docstring)
@@ -399,6 +406,8 @@ class TowerBuckets(_TwoBuckets):
         return self._gather_fused(lo, hi) if self.fused_gather else super()._gather(lo, hi)
 
     def _phase1(self, flat):
+        if not self.exchange:
+            return                                    # the step owns the collectives (gather_): none is ever started from here
         if flat.data_ptr() != self.flat.data_ptr() + 4 * self.cell_lo:
             return                                    # this backward pass got a buffer of its own: everything goes late
         if any(t.grad is None for t in self._tensors[:self.n_out]):
@@ -416,3 +425,16 @@ class TowerBuckets(_TwoBuckets):
             self._gather(0, n)
         self._gather(n, len(self._tensors))
         return self._finish(w) if early_done else self._reduce_all(w, self.group)
+
+    def gather_(self, shard_size, global_size):
+        """exchange=False: what allreduce_ does around its collectives and nothing else -- every gradient into `flat` (fused: one
+        macx_gather_flat launch), flat *= shard / global where that is not 1.0 (the same mul_, in the same place in front of the
+        reduce, as _reduce_all and _start_early), the .grad views published and the cell's buffer released.  The caller reduces `flat`."""
+        if self.exchange:
+            raise RuntimeError("gather_() belongs to a bucket built with exchange=False; this one exchanges from its phase-1 hook and "
+                               "in allreduce_()")
+        w = float(shard_size) / float(global_size)
+        self._gather(0, len(self._tensors))
+        if w != 1.0:
+            self.flat.mul_(w)
+        return self._publish()

@@ -42,7 +42,7 @@ every class here has `.check()` (raises macx.HandoffTimeout; SYNCHRONISES), `.re
 `check_every=k`: with k > 0 every k-th replay() / step() ends in a check(); the default 0 adds nothing to a replay.  The reset is
 never part of a graph -- the status survives replays until the caller clears it.
 
-Five classes, one protocol, written once in `_Captured`: warm up on a side stream and capture (`_capture`), compare replays with
+Six classes, one protocol, written once in `_Captured`: warm up on a side stream and capture (`_capture`), compare replays with
 the eager run and fall back (`_self_check`, `_eager_on_captured`, `_compare_replays`), report the status.  A class adds its static
 inputs (`_CellInputs`, `_TowerInputs`; the training classes' mask word: `_MaskWord`), `_eager()` -- its launches on the current
 stream -- and `_issue()`, which publishes what they return: the body of the capture and the eager fallback of `replay()`.
@@ -57,13 +57,15 @@ Per-question answer weights and partial batches (the tower's two classes): `Capt
 kernel runs, a weighted-mean loss, optional running totals (output.AnswerTotals) -- and their load() takes n <= B questions: the slots
 behind them become copies of slot 0 with weight 0 (`_pad_slots`, `_TowerInputs._load_inputs`).  Built without, the classes issue the
 launches of before and refuse a batch of any other size than B.  The cell-level classes are out of this: their caller owns d_memory.
+Over several processes the weighted mean needs the weights summed over the ranks: `CapturedDPTowerTrainStep(weights=True)`, the tower's
+step cut at its collectives (dp.TowerExchangeStep) into two or three graphs that replay the eager step's launches.
 """
 import warnings
 
 import torch
 
 from .cell import MACCell, MACCellTuple, _Run
-from .dp import TwoPhaseStep
+from .dp import TowerExchangeStep, TwoPhaseStep, live_weight_sum
 from .options import UnsupportedOptions, get
 from .params import MACCellParams
 # (encoder, output and stem are imported where the tower's classes use them, not here.  No cycle: `from macx.graph import mix32`,
@@ -147,14 +149,15 @@ class _Captured:
                 t.grad = g
         return want
 
-    def _compare_replays(self, replays, written, want, before=None):
+    def _compare_replays(self, replays, written, want, before=None, replay=None):
         """`replays` replays (before() in front of each): written() is the (label, tensor) list of what the graph wrote, `want` the
-        eager run's clones of the same; (replay, label) of everything that differed goes to `verify_report`"""
+        eager run's clones of the same; (replay, label) of everything that differed goes to `verify_report`.  replay: what a class
+        of several graphs replays in the place of self.graph"""
         self.verify_report = []
         for r in range(replays):
             if before is not None:
                 before()
-            self.graph.replay()
+            (replay or self.graph.replay)()
             for (label, t), w in zip(written(), want):
                 if not torch.equal(t, w):
                     self.verify_report.append((r, label))
@@ -1350,6 +1353,19 @@ class CapturedTowerForward(_Captured, _TowerInputs):
         return self.replay()
 
 
+def _check_step_bucket(who, net, opt, bucket):
+    """what the tower's training steps require of their bucket and optimizer"""
+    if not getattr(bucket, "fused_gather", False):
+        raise ValueError("%s needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
+                         "nodes, which graph replay does not keep in stream order" % who)
+    if bucket.net is not net:
+        raise ValueError("the bucket was built over another net")
+    own = bucket.tensors()
+    if len(opt.params) != len(own) or any(a is not b for a, b in zip(opt.params, own)) or opt.flat.numel() != bucket.flat.numel():
+        raise ValueError("the optimizer must be built over bucket.tensors() (FlatAdamEMA(bucket.tensors(), ...)): it steps on "
+                         "bucket.flat as it is")
+
+
 class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     """One whole training step of a macx.MACNet replayed from ONE captured HIP graph: forward (train-mode dropout), mean CE loss,
     backward, the gather of every gradient into the tower's flat buffer, global-norm clip + Adam + EMA.
@@ -1370,8 +1386,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     The graph holds exactly what the eager step issues: net(..., train=True, check_ids=False, mask_word=...), loss_and_pred,
     bucket.begin_step / allreduce_(B, B) for this one process (macx_gather_flat: one launch per gather, its table uploaded after
     the capture) and opt.step(flat_grad=bucket.flat, device_lr=True).  Data parallelism over several processes is not captured
-    here (CapturedDPTrainStep is the cell-level route).  `opt` must be built over bucket.tensors(), `bucket` with
-    fused_gather=True.
+    here: CapturedDPTowerTrainStep cuts this step at its collectives (CapturedDPTrainStep is the cell-level route).  `opt` must be
+    built over bucket.tensors(), `bucket` with fused_gather=True.
 
     images=G / kb_lengths=True / image_lengths=True: CapturedTowerForward's (load() takes image_index / kb_lengths / image_lengths
     accordingly).  With images=G the stem runs once per image and the gather and its backward (macx_kb_gather[_l] / _bwd[_l]) are
@@ -1421,7 +1437,8 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
     read with one synchronisation per epoch (totals.read()); construction leaves it cleared.
     The self-check draws weights too (one 0, one fraction, the rest ones).  Built without weights the class issues the launches it
     always issued and refuses n != B.  Out of scope: several processes (with global_batch != B the weighted mean would need W summed over
-    the ranks: a bucket that spans more than one process is refused with weights=True), the cell-level classes (their caller owns
+    the ranks: a bucket that spans more than one process is refused with weights=True -- CapturedDPTowerTrainStep(weights=True) is
+    the class that sums it), the cell-level classes (their caller owns
     d_memory), S and N other than the capture's, and towers with generic modules (capture stays refused as it is; the eager
     net.loss_and_pred(logits, answers, weights=) works for them, because it only sees logits)."""
 
@@ -1437,15 +1454,7 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
             raise ValueError("CapturedTowerTrainStep(weights=True): the bucket spans more than one process; the weighted mean over a "
                              "global batch needs the weights summed over the ranks, which the step does not do")
         dev = _require_fused_tower(net, "CapturedTowerTrainStep")
-        if not getattr(bucket, "fused_gather", False):
-            raise ValueError("CapturedTowerTrainStep needs TowerBuckets(net, fused_gather=True): per-tensor copy_ gathers become memcpy "
-                             "nodes, which graph replay does not keep in stream order")
-        if bucket.net is not net:
-            raise ValueError("the bucket was built over another net")
-        own = bucket.tensors()
-        if len(opt.params) != len(own) or any(a is not b for a, b in zip(opt.params, own)) or opt.flat.numel() != bucket.flat.numel():
-            raise ValueError("the optimizer must be built over bucket.tensors() (FlatAdamEMA(bucket.tensors(), ...)): it steps on "
-                             "bucket.flat as it is")
+        _check_step_bucket("CapturedTowerTrainStep", net, opt, bucket)
         self.net, self.opt, self.bucket, self.seed = net, opt, bucket, int(seed)
         self.check_every = int(check_every)
         self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths,
@@ -1595,5 +1604,247 @@ class CapturedTowerTrainStep(_Captured, _TowerInputs, _MaskWord):
             self.graph.replay()
         else:
             self._issue()
+        self._count_replay()
+        return self.loss
+
+
+class CapturedDPTowerTrainStep(_Captured, _TowerInputs, _MaskWord, TowerExchangeStep):
+    """One DATA-PARALLEL training step of a whole macx.MACNet as two or three graph replays with the collectives between them
+    (dp.TowerExchangeStep's sequence; this class supplies the parts):
+
+        [ graph Q: W_r, the shard's live weight, into w_local and w_global ]   [ sum all-reduce of that one double ]   weights=True only
+          graph A: forward, loss, backward, the gather into the flat buffer      sum all-reduce of the flat buffer
+          graph B: global-norm clip + Adam + EMA on the reduced buffer
+
+    No kernel is new: the graphs replay the launches the eager data-parallel step issues (about 200 per rank), and the weighted
+    arithmetic is dp.py's torch ops on 1-element device tensors.  What the class buys is the host: a shard of 8 questions is bound
+    by the launch rate, not by the GPU.  Nothing here has been measured on more than one GPU (profiles/tower_dp_ab.txt is one
+    process).  One process: no collective at all, and with B == global_batch the bits of CapturedTowerTrainStep.
+
+        bucket = macx.dp.TowerBuckets(net, fused_gather=True, exchange=False)       # the step owns the collectives
+        opt = macx.optim.FlatAdamEMA(bucket.tensors(), lr=1e-4)
+        lo, hi = macx.dp.tower_slice(64, rank, world)
+        step = macx.CapturedDPTowerTrainStep(net, opt, bucket, B=hi - lo, S=50, global_batch=64, b0=lo, seed=1234)
+        step.load(images[lo:hi], questions[lo:hi], lengths[lo:hi], answers[lo:hi])
+        step.step(iteration=it)              # step.loss, .ce, .logits, .pred, .norm; every rank holds the same parameters
+
+    Part A runs net(..., train=True, seed=seed, b0=b0, check_ids=False, mask_word=...) -- b0 is the shard's first global slot, so the
+    ranks draw the masks of the full batch -- then net.loss_and_pred, backward and bucket.gather_.  Unweighted it trains on the
+    shard's mean and gather_(B, global_batch) scales the buffer by B / global_batch in front of the reduce, as GradBucket does.
+    Part B is opt.step(flat_grad=bucket.flat, device_lr=True); opt.advance() and the mask word are step()'s, outside the graphs.  A
+    guarded optimizer decides on the reduced buffer, so every rank decides alike.
+
+    After a step: `loss` is this rank's TERM of the global mean (the ranks' terms sum to it: ce * B / global_batch, or weighted
+    ce * W_r / W_g), `ce` the shard's own (weighted) mean, `logits`, `pred`, `norm` (of the reduced gradient, the same on every
+    rank), `n`, and with totals= this rank's `totals` (dp.reduce_totals sums them, once per epoch).
+
+    weights=True: per-question answer weights and short global batches.  Graph Q writes W_r with kernels into both sums, the
+    all-reduce makes w_global W_g, and part A trains on ce * factor() -- the fp64 quotient W_r / W_g cast to fp32 on the device -- and
+    calls gather_(1, 1): the factor carries the weight, the buffer is not rescaled.  load() then takes the shard's
+    n_r = dp.shard_count(n, lo, hi) <= B questions (CapturedTowerTrainStep.load's padding rule); a shard without a live question
+    calls load_dead() and still steps: its buffer is all +0 in front of the reduce, its loss +0, and it issues the same collectives.
+
+    Warm-up, capture and verify=True are local -- construction issues no collective.  The self-check runs Q, A, B back to back with
+    w_global = w_local (graph Q writes both) and compares replays with the eager parts over loss, ce, logits, pred, norm, the flat
+    gradient, parameters, m, v, ema, guard and totals, each time from the same restored state; a rank whose replays differ falls back
+    to the eager parts (`captured` False, a RuntimeWarning) and keeps issuing the same collectives.  capture=False builds that
+    eager-parts step directly.  All graphs share one pool.
+
+    images=G / kb_lengths=True / image_lengths=True / features=store / totals= / check_every=: CapturedTowerTrainStep's, per rank.
+    Refused: att_loss= / aux_loss= (their p * B normaliser needs a rule for shards) and questions=store (its gather writes the
+    weights, so it would have to move in front of graph Q)."""
+    _loaded = False
+    # the optimizer's state around warm-up and verification, and the cleared .grad tensors: the one-process step's
+    _buffers, _state, _restore = CapturedTowerTrainStep._buffers, CapturedTowerTrainStep._state, CapturedTowerTrainStep._restore
+    _clear_grads = CapturedTowerTrainStep._clear_grads
+
+    def __init__(self, net, opt, bucket, B, S, H=14, W=14, imageInDim=1024, global_batch=None, b0=0, group=None, seed=0, warmup=2,
+                 capture=True, verify=True, check_every=0, images=None, kb_lengths=False, image_lengths=False, att_loss=None, aux_loss=None,
+                 weights=False, totals=None, features=None, questions=None):
+        who = "CapturedDPTowerTrainStep"
+        for name, given in (("att_loss", att_loss), ("aux_loss", aux_loss)):
+            if given is not None:
+                raise ValueError("%s takes no %s: the auxiliary loss is normalised by p * B, and which B a shard of a global batch "
+                                 "divides by is not settled; CapturedTowerTrainStep takes it in one process" % (who, name))
+        if questions is not None:
+            raise ValueError("%s takes no questions= store: its gather writes the weights, so it would have to move in front of the "
+                             "graph that sums them (part Q); load() the shard's questions" % who)
+        self._check_options(net, who, images, kb_lengths, image_lengths, train=True)
+        self._check_totals(who, weights, totals)
+        global_batch = int(B if global_batch is None else global_batch)
+        if not (1 <= int(B) and 0 <= int(b0) and int(b0) + int(B) <= global_batch):
+            raise ValueError("%s: the shard holds the global slots [b0, b0 + B) = [%d, %d) of a global batch of %d"
+                             % (who, int(b0), int(b0) + int(B), global_batch))
+        dev = _require_fused_tower(net, who)
+        _check_step_bucket(who, net, opt, bucket)
+        if getattr(bucket, "exchange", True):
+            raise ValueError("%s needs TowerBuckets(net, fused_gather=True, exchange=False): the step issues the collectives between "
+                             "its graphs, and a bucket that exchanges from the cell's phase-1 hook would issue one inside part A" % who)
+        self.net, self.opt, self.bucket = net, opt, bucket
+        self.seed, self.b0, self.global_batch = int(seed), int(b0), global_batch
+        self.check_every = int(check_every)
+        self._alloc_inputs(net, B, S, H, W, imageInDim, dev, images=images, kb_lengths=kb_lengths, image_lengths=image_lengths,
+                           features=features)
+        self.answers = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        sums = [None, None]
+        if weights:
+            self._alloc_weights(dev, totals)
+            sums = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(2)]      # W_r and W_g: before the capture (DESIGN 8)
+        self._alloc_mask_word(dev)
+        TowerExchangeStep.__init__(self, bucket.flat, group if group is not None else bucket.group, *sums)
+        self.shard_weight = float(self.B) / float(global_batch)
+        self.norm = opt.norm
+        state = self._state()
+        bodies = ([self._part_q] if weights else []) + [self._part_a, self._part_b]
+        self.graphs = {body: torch.cuda.CUDAGraph() for body in bodies} if capture else {}
+        graphs = [(self.graphs[body], body) for body in bodies if capture]
+
+        def warm():
+            opt.advance()
+            self._eager_parts()
+        self._capture(dev, warmup, warm, graphs, before=self._clear_grads)
+        try:
+            if capture:
+                self._self_check(verify, state)
+        finally:
+            self._reset_weights()                           # warm-up and verification scored their inputs
+        self._restore(state)                                # ... and trained on them: undo
+
+    def _after_capture(self):
+        self.bucket.flush_tables()                          # the gather's table, which a capture can only point at (dp.TowerBuckets)
+        _Captured._after_capture(self)
+
+    # ---- the parts: their launches on the current stream (the bodies of the captures and the eager fallback)
+    def _part_q(self):
+        """both sums with kernels (out=): a copy_ from one to the other would be a memcpy node (dp.TowerBuckets)"""
+        live_weight_sum(self.weights, self.w_local)
+        live_weight_sum(self.weights, self.w_global)
+
+    def _eager_a(self):
+        """part A's launches on the current stream: (loss term, ce, logits, pred)"""
+        self._clear_grads()
+        net = self.net
+        logits = net(self._net_images(), self.questions, self.lengths, train=True, seed=self.seed, b0=self.b0, check_ids=False,
+                     mask_word=self.mask_word, **self._net_arguments())
+        self.cell = net.last_cell                           # (status(): the latest run's buffers)
+        ce, pred = net.loss_and_pred(logits, self.answers, **self._loss_arguments())
+        if self.w_global is not None:
+            loss = ce * self.factor().to(torch.float32).reshape(ce.shape)
+            loss.backward()
+            self.bucket.gather_(1, 1)                       # the factor carries the weight: the buffer is not rescaled
+            term = loss.detach()
+        else:
+            ce.backward()
+            self.bucket.gather_(self.B, self.global_batch)
+            term = ce.detach() if self.shard_weight == 1.0 else ce.detach() * self.shard_weight
+        return term, ce.detach(), logits.detach(), pred
+
+    def _part_a(self):
+        """... published: the body of graph A and of the eager fallback (the self-check's reference run publishes nothing, so the
+        attributes stay the tensors the graph writes)"""
+        self.loss, self.ce, self.logits, self.pred = self._eager_a()
+
+    def _part_b(self):
+        self.opt.step(flat_grad=self.bucket.flat, device_lr=True)
+
+    def _eager_parts(self, part_a=None):
+        """Q, A, B back to back without a collective: graph Q has written W_r into w_global as well, so the factor is 1 (or 0).
+        Returns what part_a (default: _part_a) returns."""
+        if self.w_global is not None:
+            self._part_q()
+        out = (part_a or self._part_a)()
+        self._part_b()
+        return out
+
+    def _run_part(self, body):
+        if self.captured:
+            self.graphs[body].replay()
+        else:
+            body()
+
+    def run_part_q(self):
+        self._run_part(self._part_q)
+
+    def run_part_a(self):
+        self._run_part(self._part_a)
+
+    def run_part_b(self):
+        self._run_part(self._part_b)
+
+    def _local_step(self):
+        """_eager_parts through run_part_*: what the self-check replays"""
+        if self.w_global is not None:
+            self.run_part_q()
+        self.run_part_a()
+        self.run_part_b()
+
+    # ---- the self-check
+    def _written(self, outputs=None):
+        """(label, tensor) of what a step writes; outputs: part A's four of another run than the published one"""
+        o = self.opt
+        named = list(zip(("loss", "ce", "logits", "pred"), outputs or (self.loss, self.ce, self.logits, self.pred)))
+        named += [("norm", o.norm), ("flat_grad", self.bucket.flat), ("params", o.flat), ("m", o.m), ("v", o.v), ("ema", o.ema),
+                  ("guard", getattr(o, "guard", None)), ("totals", None if self.totals is None else self.totals.tensor),
+                  ("w_local", self.w_local), ("w_global", self.w_global)]
+        return [(name, t) for name, t in named if t is not None]
+
+    def _replays_match_eager(self, state, replays=3):
+        g = torch.Generator().manual_seed(20240523)
+        (images, q, lengths, ans), ids = self._random_images(g, self.net.out.answers)
+        self._load_inputs(images, q, lengths, False, *self._random_groups(g), **ids)
+        self.answers.copy_(ans)
+        self._draw_weights()
+        self.set_mask_word(0x5bd1e995)                      # a non-trivial word: the check covers the device-read path as well
+
+        def from_state():                                   # the eager parts and every replay start from the same state
+            self._restore(state)
+            self.opt.advance()
+            if self.totals is not None:
+                self.totals.reset()
+
+        def reference():
+            return [t.clone() for _, t in self._written(self._eager_parts(self._eager_a))]
+        from_state()
+        want = self._eager_on_captured(self.bucket.tensors(), reference)
+        return self._compare_replays(replays, self._written, want, before=from_state, replay=self._local_step)
+
+    # ---- batches
+    def load(self, images, questions, lengths, answers, check_ids=True, image_index=None, kb_lengths=None, image_lengths=None,
+             weights=None, image_ids=None):
+        """CapturedTowerTrainStep.load on this rank's shard: B questions, or in a class built with weights=True the shard's
+        n_r = dp.shard_count(n, lo, hi) questions with 1 <= n_r <= B (n_r == 0: load_dead()).  Returns n_r."""
+        n = CapturedTowerTrainStep.load(self, images, questions, lengths, answers, check_ids, image_index, kb_lengths, image_lengths,
+                                        weights=weights, image_ids=image_ids)
+        self._loaded = True
+        return n
+
+    def load_dead(self):
+        """A shard without a live question (weights=True): every weight 0.  The per-question inputs stay what the last load() left;
+        if there never was one they become ONE valid placeholder -- word id 1, length 1, answer 0, zero image features or image id 0
+        -- because a dead row must stay finite: its gradient row is +0, but 0 * NaN in a weight-gradient contraction is NaN."""
+        if self.weights is None:
+            raise TypeError("%s.load_dead() belongs to a class built with weights=True" % type(self).__name__)
+        with torch.no_grad():
+            if not self._loaded:
+                self.questions.zero_()
+                self.questions[:, 0] = 1
+                self.lengths.fill_(1)
+                self.answers.zero_()
+                for t in (self.images, self.image_ids, self.image_index):
+                    if t is not None:
+                        t.zero_()
+                for t in (self.kb_lengths, self.image_lengths):
+                    if t is not None:
+                        t.fill_(self.N)
+            self.weights.zero_()
+        self.n = 0
+        return 0
+
+    def step(self, iteration=None):
+        """one data-parallel step: the mask word (iteration: None keeps it, an int draws the masks of mix32(iteration)),
+        opt.advance(), the parts and collectives of dp.TowerExchangeStep.exchange_step().  Returns this rank's loss term."""
+        self._set_iteration(iteration)
+        self.opt.advance()
+        self.exchange_step()
         self._count_replay()
         return self.loss
